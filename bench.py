@@ -4,6 +4,11 @@
 Contract (see the task statement): `python bench.py --gpus N --steps K --warmup W`; for N > 1 it
 is launched by torch.distributed.run with one rank per GPU.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps of the headline leg and the
+line (`ms_per_step` = wall time of the timed region / K).  `--dump-outputs DIR` then writes what the last step left
+(dump_outputs).  Everything else -- the second leg, device-side validation, the PMC passes, the CPU baseline, the
+end-to-end and side legs, the box calibration -- runs only with `--full`.
+
 Headline leg ("im", the line's top-level fields).  A "step" = one launch of the sweep kernel:
 `--sweeps-per-step` calls of Optimizer::update (include/tnco/optimize/infinite_memory/
 optimizer.hpp:90-221 of the reference) on EVERY replica resident on the GPU.  The beta schedule is
@@ -26,10 +31,10 @@ fraction; the contract's algorithmic bytes (no caching credit: the 
 7 masks of a move in registers from one level to the next) are kept as `frac_algorithmic`, and
 `frac_compulsory` prices the traffic the kernel as built cannot avoid.
 
-`roofline.traffic` and the request counts are measured in THIS run: after the timed legs, rank 0
-(N = 1 only) re-runs the same command under `rocprofv3 --pmc` as child processes, one pass per
-counter group, and reads the counters of the timed launches (`--pmc 0` skips it; a file under
-profiles/ is used only if it was written for the same library version and workload).
+With `--full`, `roofline.traffic` and the request counts are measured in THIS run: after the timed
+legs, rank 0 (N = 1 only) re-runs the same command under `rocprofv3 --pmc` as child processes, one
+pass per counter group, and reads the counters of the timed launches (`--pmc 0` skips it; a file
+under profiles/ is used only if it was written for the same library version and workload).
 """
 from __future__ import annotations
 
@@ -317,7 +322,7 @@ def pmc_passes(args, lib_version):
                 "--replicas", str(args.replicas), "--graph-seed", str(args.graph_seed), "--init", args.init,
                 "--workload", args.workload, "--fw-max-width", str(args.fw_max_width),
                 "--fw-update-slices", str(args.fw_update_slices), "--fw-depth", str(args.fw_depth),
-                "--fw-layout", args.fw_layout, "--cpu-sample", "0", "--pmc", "0", "--e2e", "0", "--no-validate"]
+                "--fw-layout", args.fw_layout, "--cpu-sample", "0", "--pmc", "0", "--e2e", "0", "--no-validate", "--full"]
     vals = {}  # (kernel short name, counter) -> per-dispatch values in dispatch order
     names = {}  # kernel short name -> the kernels' names in the trace
     t0 = time.perf_counter()
@@ -553,6 +558,28 @@ def calibration(local_rank):
         return {"error": f"{type(e).__name__}: {e}"}
 
 
+def dump_outputs(opt, best, out_dir, budget=64 << 20):
+    """What a caller of the timed path holds after its last step, as float64 DIR/<name>.npy: every replica's current and
+    best cost, the best over all ranks, and of a fixed seeded sample of replicas the current and best trees (links
+    [k, 3, N]) and, finite width, their slices (one 0/1 per index) -- `budget` bytes at most."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    tot, mn = opt.costs()
+    arrays = {"total_cost": tot, "min_total_cost": mn, "best_cost": np.array([best])}
+    per_replica = 8 * (1 + 2 * 3 * opt.n_nodes + (2 * opt.n_inds if opt.finite_width else 0))
+    k = max(0, min(opt.n_replicas, 256, (budget - 8 * sum(a.size for a in arrays.values())) // per_replica))
+    ids = np.sort(np.random.default_rng(0).choice(opt.n_replicas, size=k, replace=False))
+    arrays["sample_replicas"] = ids
+    arrays["sample_links"] = opt.trees(ids, which_min=False, contraction=False)[0]
+    arrays["sample_min_links"] = opt.trees(ids, which_min=True, contraction=False)[0]
+    if opt.finite_width:
+        bits = lambda m: np.unpackbits(m.view(np.uint8), axis=1, bitorder="little")[:, :opt.n_inds]  # noqa: E731
+        sl, msl = opt.slices_many(ids)
+        arrays["sample_slices"], arrays["sample_min_slices"] = bits(sl), bits(msl)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", np.asarray(a, np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -566,7 +593,7 @@ def main() -> None:
                     help="initial trees: the reference's recipe (Random(seed).shuffle + opt_einsum greedy, restated, drawn "
                          "on the GPU) or the build's random-Kruskal generator (the line of round 1)")
     ap.add_argument("--workload", choices=("both", "im", "fw"), default="both",
-                    help="im: the headline leg only; fw: the finite-width leg as the headline; both: im + 'fw' object")
+                    help="im: the headline leg only; fw: the finite-width leg as the headline; both: im + 'fw' object (with --full)")
     ap.add_argument("--fw-max-width", type=float, default=32.0)
     ap.add_argument("--fw-layout", choices=("supremacy", "alternating"), default="supremacy",
                     help="coupler patterns of the Sycamore-53 network: the supremacy experiment's (A, B one orientation on alternate "
@@ -586,7 +613,14 @@ def main() -> None:
     ap.add_argument("--extras", default="c2,hyper,dims,small_batch,wide",
                     help="informational side legs of the line (N = 1; with --e2e 1): any of c2, hyper, dims, small_batch, wide; '' = none")
     ap.add_argument("--calibrate", type=int, default=1, help="1: measure this box's random-request rates in this process (`calibration`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the 'fw' object of --workload both, --validate, --pmc, "
+                         "--cpu-sample, --e2e / --extras and --calibrate (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline leg's last step left as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if not args.full:  # (a plain run: the headline leg and nothing its figure does not need)
+        args.validate, args.pmc, args.cpu_sample, args.e2e, args.calibrate = False, 0, 0, 0, 0
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -662,11 +696,15 @@ def main() -> None:
             torch.cuda.synchronize()
 
     legs = {"both": ("im", "fw"), "im": ("im",), "fw": ("fw",)}[args.workload]
+    if not args.full:
+        legs = legs[:1]
     results, objs = {}, {}
     calib = calibration(local_rank) if (args.calibrate and rank == 0 and world == 1) else None
     for kind in legs:
         leg = Leg(kind, args, rank, world, local_rank, grouped)
         res = leg.run(barrier, dist)
+        if args.dump_outputs and rank == 0 and kind == legs[0]:
+            dump_outputs(leg.opt, res["best"], args.dump_outputs)
         # after the timed region: is_valid(atol) of EVERY replica, recomputed on the device from the trees alone
         # (ContractionTree::is_valid + both caches against a from-scratch rebuild, infinite_memory/optimizer.hpp:223-251)
         # -- the line certifies the work it counted: every rank validates its own replicas, the counts are summed
@@ -708,7 +746,7 @@ def main() -> None:
                 pmc["workload_key"] = key
                 if args.pmc_out:
                     Path(args.pmc_out).write_text(json.dumps(pmc, indent=1) + "\n")
-        if pmc is None and world == 1:
+        if args.full and pmc is None and world == 1:
             pmc = pmc_from_file(lib_version, key)
             if pmc is not None:
                 pmc_note = "profiles/pmc_traffic.json (same library and workload)"

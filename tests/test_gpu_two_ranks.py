@@ -83,7 +83,7 @@ def test_bench_line_of_a_two_rank_launch():
     env = dict(os.environ, TNCO_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--replicas", "2048", "--sweeps-per-step", "20", "--pmc", "0", "--cpu-sample", "0"]
+           "--warmup", "1", "--replicas", "2048", "--sweeps-per-step", "20", "--pmc", "0", "--cpu-sample", "0", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=540, env=env, cwd=str(ROOT))
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -109,7 +109,7 @@ def test_bench_line_of_a_two_rank_launch_over_the_socket_transport():
     env = dict(os.environ, TNCO_BENCH_SHARE_GPU="sockets", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--replicas", "2048", "--sweeps-per-step", "20", "--pmc", "0", "--cpu-sample", "0"]
+           "--warmup", "1", "--replicas", "2048", "--sweeps-per-step", "20", "--pmc", "0", "--cpu-sample", "0", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=540, env=env, cwd=str(ROOT))
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -152,7 +152,7 @@ def test_bench_line_through_rccl_group_of_one():
     import json
     import subprocess
     tail = [str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--replicas", "2048",
-            "--sweeps-per-step", "20", "--pmc", "0", "--cpu-sample", "0"]
+            "--sweeps-per-step", "20", "--pmc", "0", "--cpu-sample", "0", "--full"]
     lines = []
     for extra in ({"TNCO_BENCH_FORCE_GROUP": "1", "MASTER_PORT": str(_free_port())},
                   {"TNCO_BENCH_FORCE_GROUP": "1", "MASTER_PORT": str(_free_port()), "TNCO_BENCH_COMM": "torch"}, {}):

@@ -12,9 +12,9 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-python3 "$ROOT/bench.py" "$@" --pmc-out "$OUT/pmc_traffic.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 "$ROOT/bench.py" --full "$@" --pmc-out "$OUT/pmc_traffic.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench rc $?"; tail -c 600 "$OUT/bench.err"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- python3 "$ROOT/bench.py" "$@" --pmc 0 --cpu-sample 0 > "$OUT/trace.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- python3 "$ROOT/bench.py" --full "$@" --pmc 0 --cpu-sample 0 > "$OUT/trace.log" 2>&1
 echo "trace rc $?"
 find "$OUT/trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;
 head -8 "$OUT/kernel_stats.csv"
