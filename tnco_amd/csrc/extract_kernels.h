@@ -90,7 +90,8 @@ static __global__ __launch_bounds__(256) void gather_costs_kernel(const Params P
   if (r >= P.R) return;
   if (mn) mn[r] = P.rs[r].min_cost;
   if (total)
-    total[r] = reinterpret_cast<const NodeRec*>(P.blocks + r * P.RB + (int64_t)(P.n - 2) * P.BS)->partial;
+    total[r] = P.cpl ? P.rs[r].total  // (child-partial layout: the root's partial cost is kept with the replica)
+                     : reinterpret_cast<const NodeRec*>(P.blocks + r * P.RB + (int64_t)(P.n - 2) * P.BS)->partial;
 }
 
 // slices / min_slices of k replicas: out[q][0..W) <- src[ids[q]][which][0..W)

@@ -16,6 +16,11 @@
 //     so one move touches ONE line per node it reads or writes (512-leaf TN: W = 12, BS = 128 B
 //     = exactly one 128-B line).  HBM here is bound by the number of random line activations,
 //     not by bytes.
+//     Child-partial layout (Params::cpl: no hyper-indices, the power-of-two cost model, infinite memory):
+//       [ left right parent pad | partial(left) | partial(right) | legs: W words ]
+//     a leaf child's slot holds 0, the root's own partial cost is ReplicaState::total, and the contraction cost is not
+//     stored: it is pow2_cost(log2d * popc(legs(left) | legs(right))).  A move then reads ONE line: the parent of A
+//     holds A's legs, so legs(C) = legs(parent(A)) ^ legs(A), and the partial cost of C (sa_sweep.h).
 //   leaf parents: int32[n] (a leaf has no children, no cost, and its legs never change: the leg
 //     masks of the leaves are one table shared by all replicas).
 //   mt19937 state: 624 words.  best tree: checkpoint links + a log of rotations (below).
@@ -37,8 +42,9 @@ constexpr int LPS = TNCO_LPS;
 
 struct __attribute__((aligned(32))) NodeRec {
   int32_t left, right, parent, pad;
-  double ccost;    // CostCache::contraction_cost
-  double partial;  // CostCache::partial_cost
+  // (child-partial layout, Params::cpl: the partial costs of the left / right child in their place)
+  union { double ccost; double pleft; };     // CostCache::contraction_cost
+  union { double partial; double pright; };  // CostCache::partial_cost
 };
 struct __attribute__((aligned(16))) Links {
   int32_t left, right, parent, pad;
@@ -53,7 +59,8 @@ struct __attribute__((aligned(128))) ReplicaState {
   int32_t jinvalid;               // rotation log overflowed: next improvement takes a full copy
   unsigned long long n_randpick;  // moves whose (D, E) order was drawn at random
   // min_ctree == checkpoint (minlinks) + rotations jlog[0, jmin) ; jlog holds jtail entries
-  uint32_t jmin, jtail, pad0, pad2;
+  uint32_t jmin, jtail;
+  double total;  // child-partial layout: CostCache::partial_cost of the root (the tree's total cost)
   unsigned long long n_fullcopy;
   unsigned long long pad1[5];
 };
@@ -103,6 +110,10 @@ struct Params {
   int32_t disable_shared;
   const uint64_t* dimclass;  // [n_dimclass][L*K] mode 3: legs whose dimension is 2^(j+1), j = 0..n_dimclass-1
   int32_t n_dimclass;
+  // 1: the node headers hold the partial costs of the children (child-partial layout, above): a handle without
+  // hyper-indices, of the power-of-two cost model, infinite memory -- the sweep kernels that run it are those with
+  // HYPER, GENERIC and FW all false
+  int32_t cpl;
 };
 
 // K words of a leg mask held by one lane.
@@ -282,6 +293,25 @@ struct View {
   __device__ __forceinline__ int left(int x) const { return x < n ? -1 : hdr(x)->left; }
   __device__ __forceinline__ int right(int x) const { return x < n ? -1 : hdr(x)->right; }
 };
+
+// Child-partial layout (Params::cpl), read by one lane outside the sweep kernel (the LDS-resident kernels, sa_small.h):
+// the contraction cost of internal node p with children l, rr as pow2_cost's exponent, and the own partial cost of node p
+// -- its parent's slot for it, the replica's total at the root.  blk: the replica's blocks (unified layout); lk: words per
+// row of the leaf table.
+__device__ inline int cpl_cost_exp(const Params& P, const uint8_t* blk, int lk, int l, int rr) {
+  auto legs = [&](int x) -> const uint64_t* {
+    return x < P.n ? P.leafmask + (int64_t)x * lk : reinterpret_cast<const uint64_t*>(blk + (int64_t)(x - P.n) * P.BS + 32);
+  };
+  const uint64_t *a = legs(l), *b = legs(rr);
+  int pc = 0;
+  for (int w = 0; w < P.W; ++w) pc += __popcll(a[w] | b[w]);
+  return P.log2d * pc;
+}
+__device__ inline double cpl_partial(const Params& P, const uint8_t* blk, int64_t r, int p, int parent) {
+  if (parent < 0) return P.rs[r].total;
+  const NodeRec* h = reinterpret_cast<const NodeRec*>(blk + (int64_t)(parent - P.n) * P.BS);
+  return h->left == p ? h->pleft : h->pright;
+}
 
 // ---------------------------------------------------------------------------
 // group reductions
@@ -606,7 +636,7 @@ __global__ __launch_bounds__(256) void build_kernel(const Params P, const BuildA
 #pragma unroll
     for (int k = 0; k < K; ++k) csl.w[k] = a.cost_slices[r * a.cost_slices_stride + v.widx(k)];
   }
-  double sum = 0.0;
+  double sum = 0.0, tot = 0.0;
   // validity (ctree.hpp:101-152), hyper cache, cost caches of one internal node whose children are done
   auto finish_node = [&](int p, int l, int rr, const M& ia, const M& ib, const M& ip) {
     const M uni = mor<K>(ia, ib);
@@ -614,9 +644,19 @@ __global__ __launch_bounds__(256) void build_kernel(const Params P, const BuildA
     if (gany<LOG2L>(mnonzero<K>(mor<K>(mandn<K>(mxor<K>(ia, ib), ip), mandn<K>(ip, uni))))) status = status ? status : 11;
     v.set_hyper(p, mand<K>(ip, mand<K>(ia, ib)));
     const double c = generic_cost<LOG2L, K>(P, mor<K>(uni, csl), lig, gbase);
-    const double part = rnd_cost(rnd_cost(c + v.partial(l), P.f32) + v.partial(rr), P.f32);  // utils.hpp:54
-    sum = rnd_cost(sum + c, P.f32);                                                          // utils.hpp:112
-    if (lane0) { v.hdr(p)->ccost = c; v.hdr(p)->partial = part; }
+    // (child-partial layout: the children's partial costs are in p's own header, put there when they were done)
+    const double pl = P.cpl ? v.hdr(p)->pleft : v.partial(l), pr = P.cpl ? v.hdr(p)->pright : v.partial(rr);
+    const double part = rnd_cost(rnd_cost(c + pl, P.f32) + pr, P.f32);  // utils.hpp:54
+    sum = rnd_cost(sum + c, P.f32);                                     // utils.hpp:112
+    if (p == N - 1) tot = part;
+    if (lane0) {
+      if (!P.cpl) {
+        v.hdr(p)->ccost = c; v.hdr(p)->partial = part;
+      } else if (p != N - 1) {  // (the root's: out_total)
+        NodeRec* h = v.hdr(v.hdr(p)->parent);
+        if (h->left == p) h->pleft = part; else h->pright = part;
+      }
+    }
   };
   // Without hyper-indices and with legs derived from the links, a node's legs, checks and costs need nothing but its
   // children's: everything is done when the traverse LEAVES the node -- one pass of dependent round trips over the
@@ -719,7 +759,7 @@ __global__ __launch_bounds__(256) void build_kernel(const Params P, const BuildA
     }
   }
   if (lane0) {
-    a.out_total[q] = v.hdr(N - 1)->partial;
+    a.out_total[q] = P.cpl ? tot : v.hdr(N - 1)->partial;
     a.out_sum[q] = sum;
     a.out_status[q] = status;
   }
@@ -751,7 +791,7 @@ __global__ __launch_bounds__(256) void compare_kernel(const Params P, const Buil
     if (ref.parent(i) != cur.parent(i)) bad = bad ? bad : 2;
     if (i >= n) {
       const NodeRec x = *ref.hdr(i), y = *cur.hdr(i);
-      if (!logclose(x.ccost, y.ccost)) bad = bad ? bad : 31;
+      if (!logclose(x.ccost, y.ccost)) bad = bad ? bad : (P.cpl ? 32 : 31);  // (child-partial layout: pleft, pright)
       if (!logclose(x.partial, y.partial)) bad = bad ? bad : 32;
       if (x.left != y.left || x.right != y.right) bad = bad ? bad : 2;
       if (cur.parent(y.left) != i || cur.parent(y.right) != i) bad = bad ? bad : 8;
@@ -760,6 +800,7 @@ __global__ __launch_bounds__(256) void compare_kernel(const Params P, const Buil
   for (int p = n; p < N; ++p) {
     if (mdiffer<K>(ref.mask(p), cur.mask(p))) bad = bad ? bad : 34;
   }
+  if (P.cpl && !logclose(a.out_total[q], P.rs[r].total)) bad = bad ? bad : 32;  // (the root's partial cost)
   const uint32_t anybad = gsum<LOG2L>((uint32_t)(bad != 0));
   if (lig == 0) out_bad[q] = anybad ? (bad ? bad : 99) : 0;
 }

@@ -529,8 +529,11 @@ __global__ __launch_bounds__(TPB) void sa_small_kernel(const Params P, const dou
   for (int i = lig0; i < ni; i += L) {
     const NodeRec* q = reinterpret_cast<const NodeRec*>(blk + (int64_t)i * P.BS);
     const uint64_t* lg = reinterpret_cast<const uint64_t*>(blk + (int64_t)i * P.BS + 32);
-    st.set_head(i, SmallStore<NI>::pack(q->left, q->right, q->parent, small_exp_of(q->ccost)));
-    st.rec[i].partial = q->partial;
+    const NodeRec h = *q;
+    // (child-partial layout: the cost from the children's legs, the partial cost from the parent's record)
+    const double cc = P.cpl ? pow2_cost(cpl_cost_exp(P, blk, L, h.left, h.right), 0) : h.ccost;
+    st.set_head(i, SmallStore<NI>::pack(h.left, h.right, h.parent, small_exp_of(cc)));
+    st.rec[i].partial = P.cpl ? cpl_partial(P, blk, r, i + n, h.parent) : h.partial;
     st.rec[i].legs[0] = lg[0];
     st.rec[i].legs[1] = P.W > 1 ? lg[1] : 0ull;
   }
@@ -543,8 +546,14 @@ __global__ __launch_bounds__(TPB) void sa_small_kernel(const Params P, const dou
     o.left = SmallStore<NI>::left_of(hd); o.right = SmallStore<NI>::right_of(hd);
     o.parent = SmallStore<NI>::parent_of(hd);
     o.pad = 0;
-    o.ccost = pow2_cost((int)SmallStore<NI>::exp_of(hd), 0);
-    o.partial = st.rec[i].partial;
+    if (P.cpl) {
+      o.pleft = o.left < n ? 0.0 : st.rec[o.left - n].partial;
+      o.pright = o.right < n ? 0.0 : st.rec[o.right - n].partial;
+      if (o.parent < 0) P.rs[r].total = st.rec[i].partial;
+    } else {
+      o.ccost = pow2_cost((int)SmallStore<NI>::exp_of(hd), 0);
+      o.partial = st.rec[i].partial;
+    }
     *reinterpret_cast<NodeRec*>(blk + (int64_t)i * P.BS) = o;
     uint64_t* lg = reinterpret_cast<uint64_t*>(blk + (int64_t)i * P.BS + 32);
     lg[0] = st.rec[i].legs[0];
@@ -585,8 +594,11 @@ __global__ __launch_bounds__(SMALL_TPB) void sa_lds_kernel(const Params P, const
   for (int i = lig0; i < ni; i += L) {
     const NodeRec* q = reinterpret_cast<const NodeRec*>(blk + (int64_t)i * P.BS);
     const uint64_t* lg = reinterpret_cast<const uint64_t*>(blk + (int64_t)i * P.BS + 32);
-    st.set_head(i, WideStore<K>::pack(q->left, q->right, q->parent, small_exp_of(q->ccost)));
-    st.part[i] = q->partial;
+    const NodeRec h = *q;
+    // (child-partial layout: as in sa_small_kernel)
+    const double cc = P.cpl ? pow2_cost(cpl_cost_exp(P, blk, L * K, h.left, h.right), 0) : h.ccost;
+    st.set_head(i, WideStore<K>::pack(h.left, h.right, h.parent, small_exp_of(cc)));
+    st.part[i] = P.cpl ? cpl_partial(P, blk, r, i + n, h.parent) : h.partial;
     for (int w = 0; w < 4 * K; ++w) st.leg[i * (4 * K) + w] = w < W ? lg[w] : 0ull;
   }
   for (int i = lig0; i < n; i += L) st.lpar[i] = (uint16_t)lp[(int64_t)i * LPS];
@@ -597,8 +609,14 @@ __global__ __launch_bounds__(SMALL_TPB) void sa_lds_kernel(const Params P, const
     o.left = WideStore<K>::left_of(hd); o.right = WideStore<K>::right_of(hd);
     o.parent = WideStore<K>::parent_of(hd);
     o.pad = 0;
-    o.ccost = pow2_cost((int)WideStore<K>::exp_of(hd), 0);
-    o.partial = st.part[i];
+    if (P.cpl) {
+      o.pleft = o.left < n ? 0.0 : st.part[o.left - n];
+      o.pright = o.right < n ? 0.0 : st.part[o.right - n];
+      if (o.parent < 0) P.rs[r].total = st.part[i];
+    } else {
+      o.ccost = pow2_cost((int)WideStore<K>::exp_of(hd), 0);
+      o.partial = st.part[i];
+    }
     *reinterpret_cast<NodeRec*>(blk + (int64_t)i * P.BS) = o;
     uint64_t* lg = reinterpret_cast<uint64_t*>(blk + (int64_t)i * P.BS + 32);
     for (int w = 0; w < W; ++w) lg[w] = st.leg[i * (4 * K) + w];

@@ -414,6 +414,11 @@ __device__ __forceinline__ void sa_run_body(
   // without hyper-indices -- one line per node at <= 12 mask words (round 5; rounds 1-4 stored W more words per node
   // and read + wrote them with every move).
   constexpr bool HYD = HYPER;
+  // Child-partial layout (sa_kernels.h, Params::cpl): the handles of the plain instantiations.  A node's header holds the
+  // partial costs of its children, so a move reads ONE line, parent(A): its header (the next A's links, the partial cost
+  // of the next C) and its legs (legs(C) = legs(parent(A)) ^ legs(A)); the contraction cost of A is derived from the legs.
+  // The root's partial cost is ReplicaState::total, carried in S.total from one sweep to the next.
+  constexpr bool CP = !HYPER && !GENERIC && !FW;
   v.init(P, P.blocks + r * P.RB, nullptr, lig);
   auto lpar = [&]() -> int32_t* { return P.lpar + r * (int64_t)n * LPS; };
   lds_cold& cold = *((lds_cold*)coldbuf + gib);
@@ -480,6 +485,11 @@ __device__ __forceinline__ void sa_run_body(
   auto& S = *[&]() {
     if constexpr (LEAN) return scal_lds; else return &scal_regs;
   }();
+  if constexpr (CP) {
+    double t0 = P.rs[r].total;
+    TNCO_LANDED(t0);  // (consumed here: a load still in flight at the loop's entry would be waited for inside it)
+    S.total = t0;
+  }
   if constexpr (LEAN) {
     S.total = 0; S.beta = 0; S.pP = 0; S.pO = 0; S.pC = 0; S.raC = 0; S.rnC = 0;
     S.raL = -1; S.raR = -1; S.raP = -1; S.rnL = -1; S.rnR = -1; S.rnP = -1; S.raW = 0; S.rnW = 0; S.n_moves = 0; S.n_acc = 0;
@@ -504,11 +514,17 @@ __device__ __forceinline__ void sa_run_body(
   // (B's record is written from the carried B, A, bl, br, ccB, partB, wB themselves: the B <- A shift follows the stores)
   int stC = 0, stE = 0;
   [[maybe_unused]] double stW64 = 0;
+  [[maybe_unused]] double stQ0 = 0, stQ1 = 0;  // (child-partial layout: the slots of B's record)
   int x_al = 0, x_ar = 0, x_aP = -1;
   double x_ccA = 0, x_partA = 0, x_pCcur = 0;
   int gL = -1, gR = -1, gP = -1;
   [[maybe_unused]] int gW = 0;
   double gC = 0;
+  [[maybe_unused]] double gQ1 = 0;  // (child-partial layout: gC, gQ1 = the partial costs of the left / right child)
+  // (child-partial layout: the links as ONE register tuple, so that the dwordx4 load lands in place -- three registers of
+  //  their own each made the compiler copy them out of the load's destination, a wait right behind the load)
+  typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+  [[maybe_unused]] i32x4 gLRP = (i32x4)(-1);
   M gM = mzero<K>(), gH = mzero<K>();
   uint32_t gXlo = 0, gXhi = 0;
 
@@ -530,6 +546,10 @@ __device__ __forceinline__ void sa_run_body(
       did_end = true;
       // (finite width, a launch that ends in a re-slicing sweep: fw_reslice_kernel closes that sweep)
       const bool close_sweep = !FW || tail_last != 0 || step != nsteps32 - 1;
+      if constexpr (CP) {  // (the root's record: the partial costs of its children by role)
+        stQ0 = pl ? S.pP : S.pO;
+        stQ1 = pl ? S.pO : S.pP;
+      }
       if (close_sweep && partB < cold.min_cost) {
         if constexpr (FW) impr_any = true;  // min_slices := slices, once, at the end of the kernel
         if (lane0) {
@@ -541,7 +561,7 @@ __device__ __forceinline__ void sa_run_body(
           // root header of this sweep is still in registers: write it first.
           if (lane0) {
             NodeRec o;
-            o.left = bl; o.right = br; o.parent = -1; o.pad = 0; o.ccost = ccB; o.partial = partB;
+            o.left = bl; o.right = br; o.parent = -1; o.pad = 0; o.ccost = CP ? stQ0 : ccB; o.partial = CP ? stQ1 : partB;
             *v.hdr(B) = o;
           }
           v.lpar = lpar();
@@ -572,6 +592,7 @@ __device__ __forceinline__ void sa_run_body(
         }
         improved = true;  // cold.jmin = jtail: in the store phase (nothing may read jtail's register here)
       }
+      if constexpr (CP) S.total = partB;  // (the next sweep's total: optimizer.hpp:112)
       ++step;
       state = (step >= nsteps32) ? -1 : S_BEGIN;
     }
@@ -593,7 +614,14 @@ __device__ __forceinline__ void sa_run_body(
       xa = reinterpret_cast<const uint32_t*>(lpar() + (int64_t)x_al * LPS);
     } else if (state == S_GOT_B) {
       hN = B;
-      xa = reinterpret_cast<const uint32_t*>(&v.hdr(B)->partial);
+      if constexpr (CP) x1 = B;  // (B's whole line: the legs of the leaf's sibling are legs(B) ^ legs(leaf))
+      else xa = reinterpret_cast<const uint32_t*>(&v.hdr(B)->partial);
+    } else if (CP && state == S_GOT_HB) {
+      xa = reinterpret_cast<const uint32_t*>(betas + step);
+      if (A >= 0) {  // A's whole line
+        hN = A;
+        x1 = A;
+      }
     } else if (state == S_GOT_HB) {
       x1 = pl ? br : bl;  // the leaf's sibling
       hN = A;
@@ -607,7 +635,12 @@ __device__ __forceinline__ void sa_run_body(
         x1 = (S.raL == B) ? S.raR : S.raL;  // C, the sibling of B (A's header landed with the leaf's sibling)
       }
     } else if (state == S_MOVE) {
-      if (S.raP >= 0) {
+      if constexpr (CP) {
+        if (S.raP >= 0) {  // the whole line of A's parent: the next A
+          hN = S.raP;
+          x1 = S.raP;
+        }
+      } else if (S.raP >= 0) {
         x1 = (S.rnL == A) ? S.rnR : S.rnL;  // the sibling of A: C of the next move
         hN = S.rnP;
         yN = S.raP;
@@ -619,13 +652,17 @@ __device__ __forceinline__ void sa_run_body(
     // Nothing below reads these registers before the landing fence.
     if (hN >= 0) {
       const NodeRec* q = v.hdr(hN);
-      gL = q->left; gR = q->right; gP = q->parent; gC = q->ccost;
+      if constexpr (CP) gLRP = *reinterpret_cast<const i32x4*>(q);
+      else { gL = q->left; gR = q->right; gP = q->parent; }
+      gC = q->ccost;
       if constexpr (FW) gW = q->pad;
+      if constexpr (CP) gQ1 = q->pright;
     }
     double gMp = 0;
     if (x1 >= 0) {
       v.mask_stage_into(gM, x1);
-      if (x1 >= n) gMp = v.hdr(x1)->partial;
+      if constexpr (!CP)
+        if (x1 >= n) gMp = v.hdr(x1)->partial;
     }
     if (xa != nullptr) {
       gXlo = xa[0];
@@ -764,6 +801,10 @@ __device__ __forceinline__ void sa_run_body(
         mBnow = HYD ? hB : mxor<K>(mP, mO);
         mX = mC;
       }
+      if constexpr (CP) {  // B's record: D is child0 when pick0, the other child (E, or C after the swap) has pEcur
+        stQ0 = pick0 ? pD : pEcur;
+        stQ1 = pick0 ? pEcur : pD;
+      }
       // :185-188
       partB = rnd_cost(rnd_cost(pD + pEcur, f32) + ccB, f32);
       const double partA = rnd_cost(rnd_cost(partB + pCcur, f32) + ccA, f32);
@@ -779,6 +820,7 @@ __device__ __forceinline__ void sa_run_body(
     // Everything requested above is needed before the first store below: vmcnt is in order, so
     // waiting for these loads later would also wait for the stores.
     TNCO_LANDED(gL); TNCO_LANDED(gR); TNCO_LANDED(gP); TNCO_LANDED(gC);
+    if constexpr (CP) { TNCO_LANDED(gQ1); TNCO_LANDED(gLRP); }
     if constexpr (FW) TNCO_LANDED(gW);
     TNCO_LANDED(gMp); TNCO_LANDED(gXlo); TNCO_LANDED(gXhi);
 #pragma unroll
@@ -817,7 +859,8 @@ __device__ __forceinline__ void sa_run_body(
     if (did_move || did_end) {
       if (lane0) {
         NodeRec o;
-        o.left = bl; o.right = br; o.parent = A; o.pad = FW ? wB : 0; o.ccost = ccB; o.partial = partB;  // (END: A == -1)
+        o.left = bl; o.right = br; o.parent = A; o.pad = FW ? wB : 0;  // (END: A == -1)
+        if constexpr (CP) { o.pleft = stQ0; o.pright = stQ1; } else { o.ccost = ccB; o.partial = partB; }
         *v.hdr(B) = o;
         if constexpr (FW) {
           if (did_move && acc && !F.width_f32) F.width64[(int64_t)rng.r32 * N + B] = stW64;
@@ -838,7 +881,36 @@ __device__ __forceinline__ void sa_run_body(
     TNCO_PROF_ACC;
 
     // ======================= what landed goes where ==========================
-    if (did_move) {
+    // (child-partial layout: A's line landed -- its links, the partial cost of its child that is not B, its legs; with
+    //  the legs of B = mP ^ mO: legs(C) and the contraction cost of A, popc(legs(B) | legs(C)) = popc(legs(B) | legs(A)))
+    if constexpr (CP) { gL = gLRP.x; gR = gLRP.y; gP = gLRP.z; }
+    auto land_A = [&]() {
+      S.raL = gL; S.raR = gR; S.raP = gP;
+      const M mB = mxor<K>(mP, mO);
+      mC = mxor<K>(gM, mB);
+      S.pC = (gL == B) ? gQ1 : gC;
+      S.raC = pow2_cost(log2d * (int)gsum<LOG2L>(mpopc<K>(mor<K>(mB, gM))), 0);
+    };
+    if (CP && did_move) {
+      // :191  B <- A
+      S.pP = partB; S.pO = x_pCcur;
+      B = A; bl = x_al; br = x_ar; ccB = x_ccA; partB = x_partA;
+      A = x_aP;
+      if (A >= 0) land_A();
+      state = (A < 0) ? S_END : S_MOVE;
+    } else if (CP && state == S_GOT_B) {
+      bl = gL; br = gR; A = gP;
+      pl = gL == x_al;  // the leaf is B's left child
+      mO = mxor<K>(gM, mP);
+      S.pO = pl ? gQ1 : gC;
+      partB = S.total;  // (B is the root when the walk has no move: its partial cost is the total; a move recomputes it)
+      ccB = pow2_cost(log2d * (int)gsum<LOG2L>(mpopc<K>(mor<K>(mP, mO))), 0);
+      state = S_GOT_HB;
+    } else if (CP && state == S_GOT_HB) {
+      S.beta = __hiloint2double((int)gXhi, (int)gXlo);
+      if (A >= 0) land_A();
+      state = (A < 0) ? S_END : S_MOVE;
+    } else if (did_move) {
       // :191  B <- A, carrying what is already known about A's children
       S.pP = partB; S.pO = x_pCcur;
       B = A; bl = x_al; br = x_ar; ccB = x_ccA; partB = x_partA;
@@ -852,7 +924,7 @@ __device__ __forceinline__ void sa_run_body(
       state = (A < 0) ? S_END : S_MOVE;
     } else if (state == S_BEGIN) {
       B = (int)gXlo;
-      mP = gM; S.pP = gMp;  // (the leaf: the path child of the first move; its partial cost is the zero gMp starts from)
+      mP = gM; S.pP = CP ? 0.0 : gMp;  // (the leaf: the path child of the first move; its partial cost is the zero gMp starts from)
       state = S_GOT_B;
     } else if (state == S_GOT_B) {
       bl = gL; br = gR; A = gP; ccB = gC;
@@ -894,6 +966,7 @@ __device__ __forceinline__ void sa_run_body(
   rng.finish(mti, mtw);
   if (lane0) {
     ReplicaState* rs = P.rs + r;
+    if constexpr (CP) rs->total = S.total;
     rs->jmin = cold.jmin; rs->jtail = jtail;
     rs->jinvalid = jinvalid ? 1 : 0;
     rs->n_fullcopy += cold.n_full;

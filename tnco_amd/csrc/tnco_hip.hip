@@ -245,7 +245,7 @@ __global__ void finish_init_kernel(Params P, const double* sum, const double* to
     rs->min_cost = sum[r];
     rs->init_total = total[r];
     rs->n_moves = 0; rs->n_accepted = 0; rs->n_improved = 0; rs->n_randpick = 0; rs->n_fullcopy = 0;
-    rs->status = 0; rs->jinvalid = 0; rs->jmin = 0; rs->jtail = 0; rs->pad0 = 0; rs->pad2 = 0;
+    rs->status = 0; rs->jinvalid = 0; rs->jmin = 0; rs->jtail = 0; rs->total = total[r];
   }
 }
 
@@ -617,6 +617,7 @@ int tnco_hip_create(const tnco_hip_desc* d, tnco_hip_handle* out) {
     P.WOFF = ((n - 1) * 32 + 127) / 128 * 128;
     P.RB = ((int64_t)P.WOFF + (int64_t)(n - 1) * P.WS + 127) / 128 * 128;
   }
+  P.cpl = !fw && !h->hyper && !h->generic;  // (child-partial layout: sa_kernels.h)
   P.f32 = f32; P.disable_shared = d->disable_shared_inds ? 1 : 0;
   P.cost_mode = uniform ? (pow2u ? 0 : 1) : 2;
   if (!uniform) {  // per-index dims, all powers of two: exponent classes only, no leg loop
@@ -1578,11 +1579,39 @@ int tnco_hip_get_caches(tnco_hip_handle h, int64_t r, double* ccost, double* par
   std::vector<uint8_t> blk((size_t)h->block_bytes());
   HIP_TRY(hipMemcpy(blk.data(), h->P.blocks + r * h->block_bytes(), blk.size(), hipMemcpyDeviceToHost));
   if (hyper) std::memset(hyper, 0, (size_t)N * W * 8);
-  for (int i = 0; i < N; ++i) {
+  auto node = [&](int x) {
     NodeRec hd{};
-    if (i >= n) std::memcpy(&hd, blk.data() + (size_t)(i - n) * BS, sizeof(hd));
-    if (ccost) ccost[i] = i < n ? 0.0 : hd.ccost;
-    if (partial) partial[i] = i < n ? 0.0 : hd.partial;
+    if (x >= n) std::memcpy(&hd, blk.data() + (size_t)(x - n) * BS, sizeof(hd));
+    return hd;
+  };
+  double root_total = 0.0;
+  if (h->P.cpl) {
+    ReplicaState rs;
+    HIP_TRY(hipMemcpy(&rs, h->P.rs + r, sizeof(rs), hipMemcpyDeviceToHost));
+    root_total = rs.total;
+  }
+  for (int i = 0; i < N; ++i) {
+    const NodeRec hd = node(i);
+    if (i >= n && h->P.cpl) {
+      // child-partial layout: the contraction cost from the legs of the children, the partial cost from the parent's slot
+      if (ccost) {
+        auto legs = [&](int x) -> const uint64_t* {
+          return x < n ? h->leafmask_w.data() + (size_t)x * W
+                       : reinterpret_cast<const uint64_t*>(blk.data() + ((int64_t)h->P.WOFF + (int64_t)(x - n) * h->P.WS));
+        };
+        const uint64_t *l0 = legs(hd.left), *l1 = legs(hd.right);
+        int64_t pc = 0;
+        for (int w = 0; w < W; ++w) pc += __builtin_popcountll(l0[w] | l1[w]);
+        ccost[i] = std::ldexp(1.0, (int)std::min<int64_t>(pc * h->P.log2d, 1024));  // pow2_cost: 2^e, inf beyond 1023
+      }
+      if (partial) {
+        const NodeRec ph = node(hd.parent);
+        partial[i] = hd.parent < 0 ? root_total : (ph.left == i ? ph.pleft : ph.pright);
+      }
+    } else {
+      if (ccost) ccost[i] = i < n ? 0.0 : hd.ccost;
+      if (partial) partial[i] = i < n ? 0.0 : hd.partial;
+    }
     if (hyper && h->hyper && i >= n) {
       {  // HyperCache (infinite_memory/utils.hpp:82-91): legs(p) & legs(c0) & legs(c1), from the stored legs
         auto legs = [&](int x) -> const uint64_t* {
