@@ -354,6 +354,53 @@ int tnco_hip_comm_allgather(tnco_hip_comm c, const void* send, void* recv, uint6
 int tnco_hip_comm_barrier(tnco_hip_comm c);
 const char* tnco_hip_comm_last_error(void);
 
+/*
+ * Sliced pairwise contraction of arrays along a linear path (tnco/utils/tn.py:906 `contract(..., arrays=...)`, with
+ * the slices of a finite-width result).  The plan is built by tnco_amd/contraction.py and handed over as flat int64
+ * tables; tnco_hip_contract_run runs every slice assignment of [slice_start, slice_stop) and every step of the path in
+ * one call, on one stream, and sums the assignments in that order (bit-reproducible).
+ *
+ * Kinds of an operand or destination: 0 a leaf (ref: leaf number), 1 the arena (ref: element offset), 2 the output
+ * (the block of the current assignment).  Tables, row-major, max_axes = 32:
+ *   leaf_sl [n_leaves][1 + 2 max_axes]  number of sliced axes, their slice positions, their element strides;
+ *   perms   [n_perms][8 + 2 max_axes]   src kind, src ref, dst kind, dst ref, ndim, numel, group, 0, dims, src strides
+ *                                      (group -1: gathered at the start of an assignment, one launch for all; k: before
+ *                                      step k; rows sorted by group);
+ *   steps   [n_steps][16]              A kind, ref, stride m, stride k; B kind, ref, stride k, stride n; C kind, ref;
+ *                                      H, M, N, K; 0, 0.  Z[h][m][n] = sum_k A[h][m][k] B[h][k][n], operands dense per
+ *                                      batch (A strides (K, 1) or (1, M), B (N, 1) or (1, K)), C dense [h][m][n].
+ * The output buffer is [block slices][the rest]: block_slices lists the slice positions whose value selects a block.
+ */
+typedef struct tnco_hip_contract_s* tnco_hip_contract;
+typedef struct tnco_hip_contract_desc {
+  int32_t dtype;            /* 0 float32, 1 float64, 2 complex64, 3 complex128 (interleaved) */
+  int32_t device;
+  int64_t max_axes;         /* must be 32 */
+  int64_t n_leaves;
+  const int64_t* leaf_numel;
+  const int64_t* leaf_sl;
+  int64_t n_perms;
+  const int64_t* perms;
+  int64_t n_steps;
+  const int64_t* steps;
+  int64_t arena_elems;
+  int64_t out_numel;        /* the whole output, every block */
+  int64_t n_slice_dims;
+  const int64_t* slice_dims;  /* the first one the most significant digit of an assignment number */
+  int64_t n_block;
+  const int64_t* block_slices;
+  int64_t slice_start;
+  int64_t slice_stop;
+} tnco_hip_contract_desc;
+/* validates the plan, allocates leaves + arena + output on the device (ERUNTIME when they exceed its free memory) */
+int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract* out);
+/* leaves: host pointers in the leaves' order (C-contiguous, dtype of the plan); out: host, out_numel elements */
+int tnco_hip_contract_run(tnco_hip_contract h, const void* const* leaves, void* out);
+/* stats[4]: multiply-adds launched by the last run, its kernel launches, device bytes reserved, device time of the
+ * last run's kernels in ns (events around the slice loop: leaf copies in and the result copy out excluded) */
+int tnco_hip_contract_stats(tnco_hip_contract h, int64_t* stats);
+void tnco_hip_contract_destroy(tnco_hip_contract h);
+
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */
 int tnco_hip_device_name(int device, char* buf, int cap);
 int tnco_hip_device_count(void);

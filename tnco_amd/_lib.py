@@ -51,6 +51,29 @@ class Desc(C.Structure):
     ]
 
 
+class ContractDesc(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32),
+        ("device", C.c_int32),
+        ("max_axes", C.c_int64),
+        ("n_leaves", C.c_int64),
+        ("leaf_numel", C.c_void_p),
+        ("leaf_sl", C.c_void_p),
+        ("n_perms", C.c_int64),
+        ("perms", C.c_void_p),
+        ("n_steps", C.c_int64),
+        ("steps", C.c_void_p),
+        ("arena_elems", C.c_int64),
+        ("out_numel", C.c_int64),
+        ("n_slice_dims", C.c_int64),
+        ("slice_dims", C.c_void_p),
+        ("n_block", C.c_int64),
+        ("block_slices", C.c_void_p),
+        ("slice_start", C.c_int64),
+        ("slice_stop", C.c_int64),
+    ]
+
+
 EXPORTS = [
     "tnco_hip_create", "tnco_hip_run", "tnco_hip_run_fw", "tnco_hip_get_slices", "tnco_hip_get_slices_many", "tnco_hip_diag_reslice_info", "tnco_hip_diag_fw_stats", "tnco_hip_sync", "tnco_hip_get_costs", "tnco_hip_get_tree",
     "tnco_hip_get_caches", "tnco_hip_validate", "tnco_hip_get_prng", "tnco_hip_set_prng", "tnco_hip_get_prng_many", "tnco_hip_set_prng_many",
@@ -60,6 +83,7 @@ EXPORTS = [
     "tnco_hip_greedy_trees_device", "tnco_hip_diag_greedy_device_supported", "tnco_hip_diag_greedy_device_redone", "tnco_hip_greedy_device_release", "tnco_hip_copy_to_host", "tnco_hip_diag_greedy_cost_key",
     "tnco_hip_comm_unique_id", "tnco_hip_comm_init", "tnco_hip_comm_destroy", "tnco_hip_comm_allreduce_min", "tnco_hip_comm_allgather",
     "tnco_hip_comm_barrier", "tnco_hip_comm_last_error",
+    "tnco_hip_contract_create", "tnco_hip_contract_run", "tnco_hip_contract_stats", "tnco_hip_contract_destroy",
     "tnco_hip_device_name", "tnco_hip_device_count", "tnco_hip_last_error", "tnco_hip_version",
 ]
 
@@ -157,6 +181,11 @@ def load() -> C.CDLL:
     L.tnco_hip_comm_allgather.argtypes = [vp, vp, vp, C.c_uint64]
     L.tnco_hip_comm_barrier.argtypes = [vp]
     L.tnco_hip_comm_last_error.restype = C.c_char_p
+    L.tnco_hip_contract_create.argtypes = [C.POINTER(ContractDesc), C.POINTER(vp)]
+    L.tnco_hip_contract_run.argtypes = [vp, vp, vp]
+    L.tnco_hip_contract_stats.argtypes = [vp, vp]
+    L.tnco_hip_contract_destroy.argtypes = [vp]
+    L.tnco_hip_contract_destroy.restype = None
     L.tnco_hip_device_name.argtypes = [C.c_int, vp, C.c_int]
     L.tnco_hip_device_count.restype = C.c_int
     L.tnco_hip_last_error.restype = C.c_char_p

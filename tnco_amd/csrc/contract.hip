@@ -1,0 +1,532 @@
+// contract.hip -- sliced pairwise contraction of arrays (include/tnco_hip.h, tnco_hip_contract_*).
+// The plan comes from tnco_amd/contraction.py as flat tables; here: its validation, device memory, and the slice loop
+// x step loop on one stream.  Kernels, each templated over float / double / complex<float> / complex<double>:
+//   ct_gather_kernel       strided gather with a per-assignment base offset: slicing + permuting of every leaf of an
+//                          assignment in one launch (one row of the table per grid row), permutes of intermediates;
+//   ct_gemm_tiled_kernel   C[h] = beta C[h] + A[h] B[h] through LDS, 64 x 64 tiles, 4 x 4 per lane: M, N, K large;
+//   ct_gemm_stream_kernel  one lane per output element: skinny steps (K or N small, outer products), memory-bound;
+//   ct_gemm_dot_kernel     one block per output element, K split over the block: few outputs, long K.
+// No atomics: every sum runs in one fixed order, so a run is bit-reproducible.
+#include "../../include/tnco_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace tnco {
+int set_error(int code, const std::string& msg);
+}
+
+namespace {
+
+constexpr int CT_MAX_AXES = 32;
+constexpr int PERM_W = 8 + 2 * CT_MAX_AXES;
+constexpr int STEP_W = 16;
+constexpr int LEAF_SL_W = 1 + 2 * CT_MAX_AXES;
+constexpr int64_t K_LEAF = 0, K_ARENA = 1, K_OUT = 2;
+
+int fail(int code, const std::string& msg) { return tnco::set_error(code, msg); }
+
+#define CT_TRY(expr)                                                                                   \
+  do {                                                                                                 \
+    hipError_t e_ = (expr);                                                                            \
+    if (e_ != hipSuccess) return fail(TNCO_HIP_ERUNTIME, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+template <class R>
+struct cplx {
+  R re, im;
+};
+
+// multiply-add and zero of each element type (a complex MAC: 4 real FMAs)
+__device__ inline float ct_zero(float*) { return 0.f; }
+__device__ inline double ct_zero(double*) { return 0.0; }
+template <class R>
+__device__ inline cplx<R> ct_zero(cplx<R>*) { return cplx<R>{R(0), R(0)}; }
+__device__ inline float ct_mac(float c, float a, float b) { return fmaf(a, b, c); }
+__device__ inline double ct_mac(double c, double a, double b) { return fma(a, b, c); }
+template <class R>
+__device__ inline cplx<R> ct_mac(cplx<R> c, cplx<R> a, cplx<R> b) {
+  c.re = fma(a.re, b.re, c.re);
+  c.re = fma(-a.im, b.im, c.re);
+  c.im = fma(a.re, b.im, c.im);
+  c.im = fma(a.im, b.re, c.im);
+  return c;
+}
+__device__ inline float ct_add(float a, float b) { return a + b; }
+__device__ inline double ct_add(double a, double b) { return a + b; }
+template <class R>
+__device__ inline cplx<R> ct_add(cplx<R> a, cplx<R> b) { return cplx<R>{a.re + b.re, a.im + b.im}; }
+template <class T>
+__device__ inline T ct_zero() { return ct_zero((T*)nullptr); }
+
+struct GatherArgs {
+  const int64_t* rows;         // the rows of this launch
+  const int64_t* leaf_sl;      // [n_leaves][LEAF_SL_W]
+  const int64_t* slice_place;  // place value of every slice position
+  const int64_t* slice_dims;
+  const void* const* leaves;
+  void* arena;
+  void* out;
+  int64_t sid;      // the assignment
+  int64_t out_off;  // its block of the output
+};
+
+template <class T>
+__global__ __launch_bounds__(256) void ct_gather_kernel(GatherArgs g) {
+  const int64_t* row = g.rows + (int64_t)blockIdx.y * PERM_W;
+  const int64_t numel = row[5];
+  const int nd = (int)row[4];
+  const T* src;
+  int64_t base = 0;
+  if (row[0] == K_LEAF) {
+    const int64_t* ls = g.leaf_sl + row[1] * LEAF_SL_W;
+    for (int j = 0; j < (int)ls[0]; ++j) {
+      const int64_t s = ls[1 + j];
+      base += ((g.sid / g.slice_place[s]) % g.slice_dims[s]) * ls[1 + CT_MAX_AXES + j];
+    }
+    src = (const T*)g.leaves[row[1]];
+  } else {
+    src = (const T*)g.arena + row[1];
+  }
+  T* dst = row[2] == K_ARENA ? (T*)g.arena + row[3] : (T*)g.out + g.out_off;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (int64_t)gridDim.x * blockDim.x) {
+    int64_t rem = e, off = base;
+    for (int k = nd - 1; k >= 0; --k) {
+      const int64_t d = row[8 + k], q = rem / d;
+      off += (rem - q * d) * row[8 + CT_MAX_AXES + k];
+      rem = q;
+    }
+    dst[e] = src[off];
+  }
+}
+
+template <class T>
+struct GemmArgs {
+  const T* A;
+  const T* B;
+  T* C;
+  int64_t a_m, a_k, b_k, b_n;  // strides inside a batch; batches are dense: M K, K N, M N
+  int64_t H, M, N, K;
+  int beta;  // 1: C += A B, 0: C = A B
+};
+
+constexpr int TB = 64, TK = 16;
+
+// AK: A contiguous along k (A[h][m][k]), else along m; BN: B contiguous along n (B[h][k][n]), else along k
+template <class T, bool AK, bool BN>
+__global__ __launch_bounds__(256) void ct_gemm_tiled_kernel(GemmArgs<T> p) {
+  __shared__ T As[TK][TB + 1];
+  __shared__ T Bs[TK][TB + 1];
+  const int tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
+  const int64_t tm = (p.M + TB - 1) / TB, tn = (p.N + TB - 1) / TB;
+  for (int64_t t = blockIdx.x; t < p.H * tm * tn; t += gridDim.x) {
+    const int64_t h = t / (tm * tn), m0 = (t / tn % tm) * TB, n0 = t % tn * TB;
+    const T* A = p.A + h * p.M * p.K;
+    const T* B = p.B + h * p.K * p.N;
+    T acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = ct_zero<T>();
+    for (int64_t k0 = 0; k0 < p.K; k0 += TK) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int e = tid + 256 * i;
+        const int ak = AK ? e % TK : e / TB, am = AK ? e / TK : e % TB;
+        const int64_t m = m0 + am, k = k0 + ak;
+        As[ak][am] = (m < p.M && k < p.K) ? A[m * p.a_m + k * p.a_k] : ct_zero<T>();
+        const int bk = BN ? e / TB : e % TK, bn = BN ? e % TB : e / TK;
+        const int64_t n = n0 + bn, k2 = k0 + bk;
+        Bs[bk][bn] = (n < p.N && k2 < p.K) ? B[k2 * p.b_k + n * p.b_n] : ct_zero<T>();
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int kk = 0; kk < TK; ++kk) {
+        T a[4], b[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = As[kk][ty + 16 * i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[j] = Bs[kk][tx + 16 * j];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = ct_mac(acc[i][j], a[i], b[j]);
+      }
+      __syncthreads();
+    }
+    T* Cb = p.C + h * p.M * p.N;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t m = m0 + ty + 16 * i, n = n0 + tx + 16 * j;
+        if (m < p.M && n < p.N) {
+          T* c = Cb + m * p.N + n;
+          *c = p.beta ? ct_add(*c, acc[i][j]) : acc[i][j];
+        }
+      }
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void ct_gemm_stream_kernel(GemmArgs<T> p) {
+  const int64_t total = p.H * p.M * p.N;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t n = e % p.N, r = e / p.N, m = r % p.M, h = r / p.M;
+    const T* a = p.A + h * p.M * p.K + m * p.a_m;
+    const T* b = p.B + h * p.K * p.N + n * p.b_n;
+    T acc = ct_zero<T>();
+    for (int64_t k = 0; k < p.K; ++k) acc = ct_mac(acc, a[k * p.a_k], b[k * p.b_k]);
+    p.C[e] = p.beta ? ct_add(p.C[e], acc) : acc;
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void ct_gemm_dot_kernel(GemmArgs<T> p) {
+  __shared__ T part[256];
+  const int tid = threadIdx.x;
+  const int64_t total = p.H * p.M * p.N;
+  for (int64_t e = blockIdx.x; e < total; e += gridDim.x) {
+    const int64_t n = e % p.N, r = e / p.N, m = r % p.M, h = r / p.M;
+    const T* a = p.A + h * p.M * p.K + m * p.a_m;
+    const T* b = p.B + h * p.K * p.N + n * p.b_n;
+    T acc = ct_zero<T>();
+    for (int64_t k = tid; k < p.K; k += 256) acc = ct_mac(acc, a[k * p.a_k], b[k * p.b_k]);
+    part[tid] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (tid < w) part[tid] = ct_add(part[tid], part[tid + w]);
+      __syncthreads();
+    }
+    if (tid == 0) p.C[e] = p.beta ? ct_add(p.C[e], part[0]) : part[0];
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+struct tnco_hip_contract_s {
+  int device = 0, dtype = 0;
+  size_t elem = 4;
+  std::vector<int64_t> leaf_numel, leaf_off, leaf_sl, perms, steps, slice_dims, place, block;
+  std::vector<int64_t> group_first, group_count, group_max;  // perm rows of group g at index g + 1
+  int64_t arena_elems = 0, out_numel = 0, block_numel = 1, n_blocks = 1, start = 0, stop = 1;
+  char* d_leaves = nullptr;  // every leaf, back to back
+  void* d_arena = nullptr;
+  void* d_out = nullptr;
+  int64_t* d_tables = nullptr;  // perms | leaf_sl | place | slice_dims
+  void** d_leaf_ptrs = nullptr;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};  // around the kernels of a run
+  int64_t macs = 0, launches = 0, bytes = 0, device_ns = 0;
+};
+
+namespace {
+
+int64_t leaf_slice_offset(const tnco_hip_contract_s* c, int64_t leaf, int64_t sid) {
+  const int64_t* ls = &c->leaf_sl[leaf * LEAF_SL_W];
+  int64_t off = 0;
+  for (int j = 0; j < (int)ls[0]; ++j) {
+    const int64_t s = ls[1 + j];
+    off += (sid / c->place[s]) % c->slice_dims[s] * ls[1 + CT_MAX_AXES + j];
+  }
+  return off;
+}
+
+int64_t leaf_slice_reach(const tnco_hip_contract_s* c, int64_t leaf) {  // the largest offset an assignment gives
+  const int64_t* ls = &c->leaf_sl[leaf * LEAF_SL_W];
+  int64_t off = 0;
+  for (int j = 0; j < (int)ls[0]; ++j) off += (c->slice_dims[ls[1 + j]] - 1) * ls[1 + CT_MAX_AXES + j];
+  return off;
+}
+
+const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
+  const int64_t L = d->n_leaves, P = d->n_perms, S = d->n_steps;
+  if (d->dtype < 0 || d->dtype > 3) return "'dtype' is not valid.";
+  if (d->max_axes != CT_MAX_AXES) return "'max_axes' must be 32.";
+  if (L < 0 || P < 0 || S < 0 || d->n_slice_dims < 0 || d->n_block < 0 || d->arena_elems < 0 || d->out_numel < 1)
+    return "negative sizes.";
+  if ((L && (!d->leaf_numel || !d->leaf_sl)) || (P && !d->perms) || (S && !d->steps) ||
+      (d->n_slice_dims && !d->slice_dims) || (d->n_block && !d->block_slices))
+    return "null table.";
+  c->leaf_numel.assign(d->leaf_numel, d->leaf_numel + L);
+  c->leaf_sl.assign(d->leaf_sl, d->leaf_sl + L * LEAF_SL_W);
+  c->perms.assign(d->perms, d->perms + P * PERM_W);
+  c->steps.assign(d->steps, d->steps + S * STEP_W);
+  c->slice_dims.assign(d->slice_dims, d->slice_dims + d->n_slice_dims);
+  c->block.assign(d->block_slices, d->block_slices + d->n_block);
+  const int64_t NS = d->n_slice_dims;
+  c->place.assign(NS, 1);
+  int64_t n_slices = 1;
+  for (int64_t s = NS - 1; s >= 0; --s) {
+    if (c->slice_dims[s] < 1) return "slice dimensions must be positive.";
+    c->place[s] = n_slices;
+    if (n_slices > (INT64_MAX >> 2) / c->slice_dims[s]) return "too many slice assignments.";
+    n_slices *= c->slice_dims[s];
+  }
+  if (!(0 <= d->slice_start && d->slice_start < d->slice_stop && d->slice_stop <= n_slices)) return "'slice_range' is not valid.";
+  c->start = d->slice_start, c->stop = d->slice_stop;
+  std::vector<char> seen(NS, 0);
+  for (int64_t b : c->block) {
+    if (b < 0 || b >= NS || seen[b]) return "'block_slices' is not valid.";
+    seen[b] = 1;
+    c->n_blocks *= c->slice_dims[b];
+  }
+  if (d->out_numel % c->n_blocks) return "'out_numel' is not a whole number of blocks.";
+  c->out_numel = d->out_numel, c->block_numel = d->out_numel / c->n_blocks, c->arena_elems = d->arena_elems;
+  c->leaf_off.assign(L + 1, 0);
+  for (int64_t t = 0; t < L; ++t) {
+    const int64_t* ls = &c->leaf_sl[t * LEAF_SL_W];
+    if (c->leaf_numel[t] < 1 || ls[0] < 0 || ls[0] > CT_MAX_AXES) return "leaf table is not valid.";
+    for (int j = 0; j < (int)ls[0]; ++j)
+      if (ls[1 + j] < 0 || ls[1 + j] >= NS || ls[1 + CT_MAX_AXES + j] < 0) return "leaf table is not valid.";
+    if (leaf_slice_reach(c, t) >= c->leaf_numel[t]) return "leaf slices reach beyond the leaf.";
+    c->leaf_off[t + 1] = c->leaf_off[t] + ((c->leaf_numel[t] + 63) / 64) * 64;
+  }
+  // permutes: sizes, reach of the source, room at the destination; rows sorted by group
+  c->group_first.assign(S + 1, 0), c->group_count.assign(S + 1, 0), c->group_max.assign(S + 1, 0);
+  int64_t prev_group = -1;
+  for (int64_t r = 0; r < P; ++r) {
+    const int64_t* row = &c->perms[r * PERM_W];
+    const int64_t nd = row[4], numel = row[5], g = row[6];
+    if (nd < 0 || nd > CT_MAX_AXES || g < -1 || g >= S || g < prev_group) return "permute table is not valid.";
+    if (g != prev_group || r == 0) c->group_first[g + 1] = r;
+    prev_group = g;
+    c->group_count[g + 1] += 1, c->group_max[g + 1] = std::max(c->group_max[g + 1], numel);
+    int64_t prod = 1, reach = 0;
+    for (int k = 0; k < nd; ++k) {
+      if (row[8 + k] < 1 || row[8 + CT_MAX_AXES + k] < 0) return "permute table is not valid.";
+      prod *= row[8 + k];
+      reach += (row[8 + k] - 1) * row[8 + CT_MAX_AXES + k];
+    }
+    if (prod != numel) return "permute table is not valid.";
+    if (row[0] == K_LEAF) {
+      if (row[1] < 0 || row[1] >= L || reach + leaf_slice_reach(c, row[1]) >= c->leaf_numel[row[1]]) return "permute source out of range.";
+    } else if (row[0] == K_ARENA) {
+      if (row[1] < 0 || row[1] + reach >= c->arena_elems) return "permute source out of range.";
+    } else {
+      return "permute table is not valid.";
+    }
+    if (row[2] == K_ARENA) {
+      if (row[3] < 0 || row[3] + numel > c->arena_elems) return "permute destination out of range.";
+      if (row[0] == K_ARENA && row[1] < row[3] + numel && row[3] < row[1] + reach + 1) return "permute in place.";
+    } else if (row[2] != K_OUT || numel != c->block_numel || S != 0) {
+      return "permute table is not valid.";
+    }
+  }
+  if (S == 0 && !(P == 1 && c->perms[2] == K_OUT)) return "a path without steps needs one copy to the output.";
+  for (int64_t k = 0; k < S; ++k) {
+    const int64_t* st = &c->steps[k * STEP_W];
+    const int64_t H = st[10], M = st[11], N = st[12], K = st[13];
+    if (H < 1 || M < 1 || N < 1 || K < 1) return "step sizes must be positive.";
+    if (!((st[2] == K && st[3] == 1) || (st[2] == 1 && st[3] == M))) return "A strides are not valid.";
+    if (!((st[6] == N && st[7] == 1) || (st[6] == 1 && st[7] == K))) return "B strides are not valid.";
+    int64_t lo[2], hi[2];
+    for (int side = 0; side < 2; ++side) {
+      const int64_t kind = st[4 * side], ref = st[4 * side + 1], n = H * K * (side ? N : M);
+      if (kind == K_LEAF) {
+        if (ref < 0 || ref >= L || n + leaf_slice_reach(c, ref) > c->leaf_numel[ref]) return "step operand out of range.";
+        lo[side] = hi[side] = -1;
+      } else if (kind == K_ARENA) {
+        if (ref < 0 || ref + n > c->arena_elems) return "step operand out of range.";
+        lo[side] = ref, hi[side] = ref + n;
+      } else {
+        return "step operand kind is not valid.";
+      }
+    }
+    const int64_t nc = H * M * N;
+    if (st[8] == K_OUT) {
+      if (k != S - 1 || nc != c->block_numel) return "only the last step writes the output, one block.";
+    } else if (st[8] == K_ARENA && k != S - 1) {
+      if (st[9] < 0 || st[9] + nc > c->arena_elems) return "step result out of range.";
+      for (int side = 0; side < 2; ++side)
+        if (lo[side] >= 0 && st[9] < hi[side] && lo[side] < st[9] + nc) return "step result overlaps an operand.";
+    } else {
+      return "the last step must write the output.";
+    }
+  }
+  return nullptr;
+}
+
+template <class T>
+int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t out_off) {
+  const int64_t n = c->group_count[group + 1];
+  if (!n) return TNCO_HIP_OK;
+  const int64_t P = (int64_t)c->perms.size() / PERM_W;
+  GatherArgs g;
+  g.rows = c->d_tables + c->group_first[group + 1] * PERM_W;
+  g.leaf_sl = c->d_tables + P * PERM_W;
+  g.slice_place = g.leaf_sl + c->leaf_sl.size();
+  g.slice_dims = g.slice_place + c->place.size();
+  g.leaves = (const void* const*)c->d_leaf_ptrs;
+  g.arena = c->d_arena, g.out = c->d_out, g.sid = sid, g.out_off = out_off;
+  const int64_t blocks = std::min<int64_t>((c->group_max[group + 1] + 255) / 256, 2048);
+  hipLaunchKernelGGL(ct_gather_kernel<T>, dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, c->stream, g);
+  CT_TRY(hipGetLastError());
+  c->launches += 1;
+  return TNCO_HIP_OK;
+}
+
+template <class T>
+int launch_gemm(tnco_hip_contract_s* c, const GemmArgs<T>& p) {
+  const bool ak = p.a_k == 1, bn = p.b_n == 1;
+  const int64_t outs = p.H * p.M * p.N;
+  if (p.M >= 64 && p.N >= 64 && p.K > 32) {  // tiled: every operand element reused 64 times from LDS
+    const int64_t tiles = p.H * ((p.M + TB - 1) / TB) * ((p.N + TB - 1) / TB);
+    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20));
+    if (ak && bn) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, true, true>), grid, dim3(256), 0, c->stream, p);
+    else if (ak) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, true, false>), grid, dim3(256), 0, c->stream, p);
+    else if (bn) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, false, true>), grid, dim3(256), 0, c->stream, p);
+    else hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, false, false>), grid, dim3(256), 0, c->stream, p);
+  } else if (p.K >= 512 && outs <= 8192) {  // few outputs, long sums: K split over a block
+    hipLaunchKernelGGL(ct_gemm_dot_kernel<T>, dim3((unsigned)outs), dim3(256), 0, c->stream, p);
+  } else {
+    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16));
+    hipLaunchKernelGGL(ct_gemm_stream_kernel<T>, grid, dim3(256), 0, c->stream, p);
+  }
+  CT_TRY(hipGetLastError());
+  c->launches += 1;
+  c->macs += p.H * p.M * p.N * p.K;
+  return TNCO_HIP_OK;
+}
+
+template <class T>
+int run_impl(tnco_hip_contract_s* c) {
+  std::vector<char> visited(c->n_blocks, 0);
+  const int64_t S = (int64_t)c->steps.size() / STEP_W;
+  T* arena = (T*)c->d_arena;
+  T* out = (T*)c->d_out;
+  for (int64_t sid = c->start; sid < c->stop; ++sid) {
+    int64_t blk = 0;
+    for (int64_t b : c->block) blk = blk * c->slice_dims[b] + (sid / c->place[b]) % c->slice_dims[b];
+    const int beta = visited[blk];
+    visited[blk] = 1;
+    const int64_t out_off = blk * c->block_numel;
+    int rc = launch_gathers<T>(c, -1, sid, out_off);
+    if (rc) return rc;
+    for (int64_t k = 0; k < S; ++k) {
+      if ((rc = launch_gathers<T>(c, k, sid, out_off))) return rc;
+      const int64_t* st = &c->steps[k * STEP_W];
+      const T* opnd[2];
+      for (int side = 0; side < 2; ++side) {
+        const int64_t kind = st[4 * side], ref = st[4 * side + 1];
+        opnd[side] = kind == K_LEAF ? (const T*)(c->d_leaves + c->leaf_off[ref] * c->elem) + leaf_slice_offset(c, ref, sid)
+                                    : arena + ref;
+      }
+      GemmArgs<T> p;
+      p.A = opnd[0], p.B = opnd[1];
+      p.C = st[8] == K_OUT ? out + out_off : arena + st[9];
+      p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
+      p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
+      p.beta = st[8] == K_OUT ? beta : 0;
+      if ((rc = launch_gemm<T>(c, p))) return rc;
+    }
+  }
+  return TNCO_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract* out) {
+  if (!d || !out) return fail(TNCO_HIP_EINVAL, "null argument.");
+  *out = nullptr;
+  auto* c = new tnco_hip_contract_s();
+  if (const char* e = validate(c, d)) {
+    delete c;
+    return fail(TNCO_HIP_EINVAL, e);
+  }
+  static const size_t elem[4] = {4, 8, 8, 16};
+  c->dtype = d->dtype, c->elem = elem[d->dtype], c->device = d->device;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || d->device < 0 || d->device >= ndev) {
+    delete c;
+    return fail(TNCO_HIP_EINVAL, "'device' is not valid.");
+  }
+  const size_t n_tab = c->perms.size() + c->leaf_sl.size() + c->place.size() + c->slice_dims.size();
+  const size_t leaves = (size_t)c->leaf_off.back() * c->elem;
+  const size_t arena = (size_t)std::max<int64_t>(c->arena_elems, 1) * c->elem, outb = (size_t)c->out_numel * c->elem;
+  const size_t ptrs = std::max<size_t>(c->leaf_numel.size(), 1) * sizeof(void*);
+  c->bytes = (int64_t)(leaves + arena + outb + n_tab * 8 + ptrs);
+  auto bail = [&](int code, const std::string& msg) {
+    tnco_hip_contract_destroy(c);
+    return fail(code, msg);
+  };
+  if (hipSetDevice(d->device) != hipSuccess) return bail(TNCO_HIP_ERUNTIME, "hipSetDevice failed.");
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return bail(TNCO_HIP_ERUNTIME, "hipMemGetInfo failed.");
+  if ((size_t)c->bytes > free_b)
+    return bail(TNCO_HIP_ERUNTIME, "the contraction needs " + std::to_string(c->bytes) + " bytes of device memory, " +
+                                       std::to_string(free_b) + " are free.");
+  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreate(&c->ev[0]) != hipSuccess || hipEventCreate(&c->ev[1]) != hipSuccess ||
+      hipMalloc((void**)&c->d_leaves, std::max<size_t>(leaves, 64)) != hipSuccess ||
+      hipMalloc(&c->d_arena, arena) != hipSuccess || hipMalloc(&c->d_out, outb) != hipSuccess ||
+      hipMalloc((void**)&c->d_tables, std::max<size_t>(n_tab, 1) * 8) != hipSuccess ||
+      hipMalloc((void**)&c->d_leaf_ptrs, ptrs) != hipSuccess)
+    return bail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+  std::vector<int64_t> tab;
+  tab.reserve(n_tab);
+  for (auto* v : {&c->perms, &c->leaf_sl, &c->place, &c->slice_dims}) tab.insert(tab.end(), v->begin(), v->end());
+  std::vector<void*> lp(c->leaf_numel.size());
+  for (size_t t = 0; t < lp.size(); ++t) lp[t] = c->d_leaves + c->leaf_off[t] * c->elem;
+  // on the handle's own stream: a plain hipMemcpy from pageable memory may return before its DMA lands, and the
+  // non-blocking stream of the kernels would not wait for it
+  if ((n_tab && hipMemcpyAsync(c->d_tables, tab.data(), n_tab * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+      (!lp.empty() && hipMemcpyAsync(c->d_leaf_ptrs, lp.data(), lp.size() * sizeof(void*), hipMemcpyHostToDevice,
+                                     c->stream) != hipSuccess) ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return bail(TNCO_HIP_ERUNTIME, "copy of the plan failed.");
+  *out = c;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* out) {
+  if (!c || !out || (!leaves && !c->leaf_numel.empty())) return fail(TNCO_HIP_EINVAL, "null argument.");
+  CT_TRY(hipSetDevice(c->device));
+  for (size_t t = 0; t < c->leaf_numel.size(); ++t) {
+    if (!leaves[t]) return fail(TNCO_HIP_EINVAL, "null leaf.");
+    CT_TRY(hipMemcpyAsync(c->d_leaves + c->leaf_off[t] * c->elem, leaves[t], (size_t)c->leaf_numel[t] * c->elem,
+                          hipMemcpyHostToDevice, c->stream));
+  }
+  CT_TRY(hipMemsetAsync(c->d_out, 0, (size_t)c->out_numel * c->elem, c->stream));
+  c->macs = c->launches = 0;
+  CT_TRY(hipEventRecord(c->ev[0], c->stream));
+  int rc = c->dtype == 0 ? run_impl<float>(c)
+           : c->dtype == 1 ? run_impl<double>(c)
+           : c->dtype == 2 ? run_impl<cplx<float>>(c)
+                           : run_impl<cplx<double>>(c);
+  if (rc) return rc;
+  CT_TRY(hipEventRecord(c->ev[1], c->stream));
+  CT_TRY(hipMemcpyAsync(out, c->d_out, (size_t)c->out_numel * c->elem, hipMemcpyDeviceToHost, c->stream));
+  CT_TRY(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  CT_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+  c->device_ns = (int64_t)((double)ms * 1e6);
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_stats(tnco_hip_contract c, int64_t* stats) {
+  if (!c || !stats) return fail(TNCO_HIP_EINVAL, "null argument.");
+  stats[0] = c->macs, stats[1] = c->launches, stats[2] = c->bytes, stats[3] = c->device_ns;
+  return TNCO_HIP_OK;
+}
+
+void tnco_hip_contract_destroy(tnco_hip_contract c) {
+  if (!c) return;
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  for (void* p : {(void*)c->d_leaves, c->d_arena, c->d_out, (void*)c->d_tables, (void*)c->d_leaf_ptrs})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t e : c->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
+  delete c;
+}
+
+}  // extern "C"

@@ -65,6 +65,11 @@ struct TempBufs {
 
 }  // namespace
 
+namespace tnco {
+// the status + message of a failing call in another translation unit (contract.hip), read by tnco_hip_last_error
+int set_error(int code, const std::string& msg) { return fail(code, msg); }
+}  // namespace tnco
+
 namespace {
 
 // (LOG2L, K) for W mask words
