@@ -399,6 +399,13 @@ int tnco_hip_contract_run(tnco_hip_contract h, const void* const* leaves, void* 
 /* stats[4]: multiply-adds launched by the last run, its kernel launches, device bytes reserved, device time of the
  * last run's kernels in ns (events around the slice loop: leaf copies in and the result copy out excluded) */
 int tnco_hip_contract_stats(tnco_hip_contract h, int64_t* stats);
+/* counts[TNCO_HIP_CONTRACT_N_KERNELS]: the last run's launches per kernel path; their sum is stats[1].  Order:
+ *   0 gather (slices + permutes);
+ *   1..4 tiled GEMM by operand layout: 1 A [k][m], B [n][k];  2 A [k][m], B [k][n];  3 A [m][k], B [n][k];
+ *        4 A [m][k], B [k][n]  (slot 1 + 2 (A contiguous along k) + (B contiguous along n));
+ *   5 dot (K split over a block);  6 stream (one lane per output element). */
+#define TNCO_HIP_CONTRACT_N_KERNELS 7
+int tnco_hip_contract_kernel_launches(tnco_hip_contract h, int64_t* counts);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

@@ -1,6 +1,7 @@
 """The contraction engine's plan (tnco_amd/contraction.py), without a GPU: axes against the index-only contract, MACs
 against the cost models, every refusal before any device use, the tables replayed by a numpy interpreter of the
-device's semantics, and the code objects of the new kernels."""
+device's semantics, the code objects of the new kernels, and the plan side of the kernels' edge cases
+(tests/contract_cases.py)."""
 import math
 import sys
 from decimal import Decimal
@@ -9,6 +10,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from tests import contract_cases as cc
 from tnco_amd import contraction as ctr
 from tnco_amd import synthetic as syn
 from tnco_amd.app import tn as tnmod
@@ -329,3 +331,47 @@ def test_permutes_of_one_launch_do_not_overlap(seed):
         for a0, a1 in dst:
             assert all(a1 <= b0 or b1 <= a0 for b0, b1 in src), (g, dst, src)
         assert all(a1 <= b0 or b1 <= a0 for i, (a0, a1) in enumerate(dst) for b0, b1 in dst[i + 1:])
+
+
+@pytest.mark.parametrize("case", cc.CASES, ids=lambda c: c.name)
+def test_kernel_edge_cases_plan_as_designed(case):
+    """Every case of the kernels' GPU tests gives the one step it was designed for -- sizes, operand forms, permutes --
+    so that a planner change that reroutes a case shows where there is no GPU; and the interpreter of the tables agrees
+    with a plain einsum on it."""
+    p = ctr.plan([(0, 1)], case.ts, case.shapes(), case.output, slices=case.slices)
+    (op,) = p.ops
+    got = {k: op[k] for k in ("H", "M", "N", "K", "form_a", "form_b")}
+    assert dict(got, perms=len(p.perms)) == case.ops
+    assert p.n_slices == case.n_slices() and p.slice_inds == case.slices
+    assert p.macs == case.n_slices() * op["H"] * op["M"] * op["N"] * op["K"]
+    held = [x for x in case.slices if x in p.inds]
+    assert p.block_inds == tuple(held)
+    assert case.kt == op["K"] * math.prod(case.dims[x] for x in case.slices if x not in p.inds)
+    # the dtype rule: without a list of its own a case runs every type up to KT_SINGLE products per element and
+    # the double types beyond; a list of its own may add single types to a long sum, never drop one from a short one
+    # except where memory says so (the 4100 x 4100 outer product runs in the two real types)
+    if not case.dtypes:
+        assert case.run_dtypes() == (cc.ALL if case.kt <= cc.KT_SINGLE else cc.DOUBLES)
+    else:
+        assert case.run_dtypes() == case.dtypes
+        assert set(cc.DOUBLES) <= set(case.dtypes) or p.out_numel > 1 << 24
+    assert sum(case.kernels.values()) == case.n_slices() * (1 + (case.ops["perms"] > 0))
+    if p.out_numel <= 1 << 20:
+        arrays = _arrays(case.ts, case.dims, np.float64, 2)
+        sym = {x: k for k, x in enumerate(dict.fromkeys(x for xs in case.ts for x in xs))}
+        ref = np.einsum(arrays[0], [sym[x] for x in case.ts[0]], arrays[1], [sym[x] for x in case.ts[1]],
+                        [sym[x] for x in p.inds], optimize=True)
+        np.testing.assert_allclose(_interpret(p, arrays), ref, rtol=1e-10, atol=1e-13)
+
+
+def test_kernel_edge_cases_reach_every_kernel_path_in_every_dtype():
+    """The seven launch-count slots -- the gather, the four tiled layouts, dot, stream -- are each expected non-zero
+    by at least one case per dtype; the GPU tests assert those expectations against the device's counts."""
+    assert len(ctr.KERNEL_PATHS) == 7 and len(set(ctr.KERNEL_PATHS)) == 7
+    for dtype in cc.ALL:
+        reached = {name for c in cc.CASES if dtype in c.run_dtypes() for name, n in c.kernels.items() if n > 0}
+        assert reached == set(ctr.KERNEL_PATHS), (np.dtype(dtype).name, set(ctr.KERNEL_PATHS) - reached)
+    assert set(cc.NORMAL_FILL) <= set(cc.BY_NAME)
+    pairs = {(c.ops["form_a"], c.ops["form_b"], c.ops["M"], c.ops["N"], c.ops["K"]) for c in cc.CASES
+             if next(iter(c.kernels)).startswith("tiled") and c.ops["H"] == 1 and not c.slices}
+    assert len(pairs) >= 12

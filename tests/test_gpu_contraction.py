@@ -106,11 +106,16 @@ def test_dtypes_on_a_hyper_network(ctr, dtype):
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64, np.complex64, np.complex128])
-@pytest.mark.parametrize("layout", [(("i", "k"), ("k", "j")), (("k", "i"), ("k", "j")), (("i", "k"), ("j", "k"))])
+@pytest.mark.parametrize("layout", [(("i", "k"), ("k", "j")), (("k", "i"), ("k", "j")), (("i", "k"), ("j", "k")),
+                                    (("k", "i"), ("j", "k"))])
 def test_large_square_step_takes_the_tiled_gemm(ctr, dtype, layout):
     dims = dict(i=530, k=515, j=512)
     arrays = _arrays(layout, dims, dtype, 2)
     r = ctr.contract([(0, 1)], layout, arrays)
+    letter = dict(i="m", j="n", k="k")  # (the kernel path is named by the memory order of A, then of B)
+    tiled = "tiled_" + "".join(letter[c] for c in layout[0]) + "_" + "".join(letter[c] for c in layout[1])
+    assert dict(zip(ctr.KERNEL_PATHS, r.kernel_launches)) == {name: int(name == tiled) for name in ctr.KERNEL_PATHS}
+    assert r.launches == 1
     ref = np.einsum(arrays[0].astype(np.complex128), [ord(c) - 97 for c in layout[0]],
                     arrays[1].astype(np.complex128), [ord(c) - 97 for c in layout[1]], [8, 9])
     assert r.inds == ("i", "j") and r.macs == 530 * 515 * 512

@@ -83,7 +83,8 @@ EXPORTS = [
     "tnco_hip_greedy_trees_device", "tnco_hip_diag_greedy_device_supported", "tnco_hip_diag_greedy_device_redone", "tnco_hip_greedy_device_release", "tnco_hip_copy_to_host", "tnco_hip_diag_greedy_cost_key",
     "tnco_hip_comm_unique_id", "tnco_hip_comm_init", "tnco_hip_comm_destroy", "tnco_hip_comm_allreduce_min", "tnco_hip_comm_allgather",
     "tnco_hip_comm_barrier", "tnco_hip_comm_last_error",
-    "tnco_hip_contract_create", "tnco_hip_contract_run", "tnco_hip_contract_stats", "tnco_hip_contract_destroy",
+    "tnco_hip_contract_create", "tnco_hip_contract_run", "tnco_hip_contract_stats", "tnco_hip_contract_kernel_launches",
+    "tnco_hip_contract_destroy",
     "tnco_hip_device_name", "tnco_hip_device_count", "tnco_hip_last_error", "tnco_hip_version",
 ]
 
@@ -184,6 +185,7 @@ def load() -> C.CDLL:
     L.tnco_hip_contract_create.argtypes = [C.POINTER(ContractDesc), C.POINTER(vp)]
     L.tnco_hip_contract_run.argtypes = [vp, vp, vp]
     L.tnco_hip_contract_stats.argtypes = [vp, vp]
+    L.tnco_hip_contract_kernel_launches.argtypes = [vp, vp]
     L.tnco_hip_contract_destroy.argtypes = [vp]
     L.tnco_hip_contract_destroy.restype = None
     L.tnco_hip_device_name.argtypes = [C.c_int, vp, C.c_int]

@@ -24,7 +24,7 @@ import numpy as np
 
 from .app import tn as tnmod
 
-__all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES"]
+__all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -34,6 +34,9 @@ LEAF, ARENA, OUT = 0, 1, 2
 PERM_W = 8 + 2 * MAX_AXES
 STEP_W = 16
 LEAF_SL_W = 1 + 2 * MAX_AXES
+# the kernel paths of csrc/contract.hip in the order tnco_hip_contract_kernel_launches counts them; a tiled name gives
+# the memory order of A, then of B (mk_kn: A [m][k], B [k][n])
+KERNEL_PATHS = ("gather", "tiled_km_nk", "tiled_km_kn", "tiled_mk_nk", "tiled_mk_kn", "dot", "stream")
 ALIGN = 64  # arena offsets in elements: 64 x (4..16 B) keeps every buffer 256-byte aligned
 
 
@@ -47,6 +50,7 @@ class ContractionResult:
     launches: int = 0  # kernel launches
     device_s: float = 0.0  # device time of the kernels (copies in and out excluded)
     fuse_macs: int = 0  # contract_results: multiply-adds of the fuse stage (not part of `macs`)
+    kernel_launches: tuple = (0,) * len(KERNEL_PATHS)  # `launches` per kernel path, in KERNEL_PATHS order
 
 
 @dataclass
@@ -365,7 +369,12 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
                               _sub_output(ts_inds, leaves, out), device=device))
     assert [tuple(r.inds) for r in parts] == [tuple(f) for f in final]
     return ContractionResult([r.inds for r in parts], [r.array for r in parts], sum(r.macs for r in parts), 1,
-                             max(r.peak_device_bytes for r in parts), sum(r.launches for r in parts))
+                             max(r.peak_device_bytes for r in parts), sum(r.launches for r in parts),
+                             kernel_launches=_add_counts(*(r.kernel_launches for r in parts)))
+
+
+def _add_counts(*counts) -> tuple:
+    return tuple(sum(c) for c in zip(*counts))
 
 
 def _run(p: Plan, arrays, device) -> ContractionResult:
@@ -395,6 +404,8 @@ def _run(p: Plan, arrays, device) -> ContractionResult:
         _lib.check(L.tnco_hip_contract_run(h, ptrs, staging.ctypes.data_as(C.c_void_p)))
         stats = np.zeros(4, np.int64)
         _lib.check(L.tnco_hip_contract_stats(h, stats.ctypes.data_as(C.c_void_p)))
+        by_kernel = np.zeros(len(KERNEL_PATHS), np.int64)
+        _lib.check(L.tnco_hip_contract_kernel_launches(h, by_kernel.ctypes.data_as(C.c_void_p)))
     finally:
         L.tnco_hip_contract_destroy(h)
     # the output buffer holds [block axes][the others]; the result's own axis order is a view of it
@@ -403,7 +414,7 @@ def _run(p: Plan, arrays, device) -> ContractionResult:
     array = staging.reshape(tuple(p.shape[p.inds.index(x)] for x in held))
     array = array.transpose([held.index(x) for x in p.inds]).copy(order="C")  # (0-d stays 0-d)
     return ContractionResult(p.inds, array, int(stats[0]), p.slice_range[1] - p.slice_range[0], int(stats[2]),
-                             int(stats[1]), float(stats[3]) * 1e-9)
+                             int(stats[1]), float(stats[3]) * 1e-9, kernel_launches=tuple(int(v) for v in by_kernel))
 
 
 def contract_results(tn0, arrays, tn, result, *, device=None) -> ContractionResult:
@@ -435,10 +446,11 @@ def contract_results(tn0, arrays, tn, result, *, device=None) -> ContractionResu
         r = contract(result.path, tn.ts_inds, arrays, tn.output_inds, slices=getattr(result, "slices", ()),
                      device=device)
         return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
-                                 fuse_macs)
+                                 fuse_macs, r.kernel_launches)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
     ts, n = [tuple(x) for x in tn.ts_inds], len(tn.ts_inds)
     done, results, macs, n_slices, peak, launches, device_s = set(), [], 0, 0, 0, 0, 0.0
+    by_kernel = (0,) * len(KERNEL_PATHS)
     n_comp_steps = 0
     for q, cut in zip(result.disconnected_paths, result.disconnected_slices):
         if not q:
@@ -451,6 +463,7 @@ def contract_results(tn0, arrays, tn, result, *, device=None) -> ContractionResu
         results.append(r)
         macs, n_slices, launches = macs + r.macs, n_slices + r.n_slices, launches + r.launches
         peak, device_s = max(peak, r.peak_device_bytes), device_s + r.device_s
+        by_kernel = _add_counts(by_kernel, r.kernel_launches)
     state_inds = [ts[t] for t in range(n) if t not in done] + [tuple(r.inds) for r in results]
     state_arrays = [arrays[t] for t in range(n) if t not in done] + [r.array for r in results]
     expect = tnmod.contract(_check_path(result.path[:n_comp_steps], n), ts, tn.output_inds)[0]
@@ -462,7 +475,8 @@ def contract_results(tn0, arrays, tn, result, *, device=None) -> ContractionResu
                      device=device)
         macs, launches, peak = macs + r.macs, launches + r.launches, max(peak, r.peak_device_bytes)
         device_s += r.device_s
+        by_kernel = _add_counts(by_kernel, r.kernel_launches)
         inds, array = r.inds, r.array
     else:
         inds, array = (state_inds[0], state_arrays[0]) if len(state_inds) == 1 else (state_inds, state_arrays)
-    return ContractionResult(inds, array, macs, n_slices, peak, launches, device_s, fuse_macs)
+    return ContractionResult(inds, array, macs, n_slices, peak, launches, device_s, fuse_macs, by_kernel)

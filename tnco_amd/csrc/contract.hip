@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <iterator>
 #include <string>
 #include <vector>
 
@@ -224,6 +225,7 @@ struct tnco_hip_contract_s {
   hipStream_t stream = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};  // around the kernels of a run
   int64_t macs = 0, launches = 0, bytes = 0, device_ns = 0;
+  int64_t by_kernel[TNCO_HIP_CONTRACT_N_KERNELS] = {};  // launches of the last run per kernel path (tnco_hip.h)
 };
 
 namespace {
@@ -369,6 +371,7 @@ int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t o
   hipLaunchKernelGGL(ct_gather_kernel<T>, dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, c->stream, g);
   CT_TRY(hipGetLastError());
   c->launches += 1;
+  c->by_kernel[0] += 1;
   return TNCO_HIP_OK;
 }
 
@@ -376,6 +379,7 @@ template <class T>
 int launch_gemm(tnco_hip_contract_s* c, const GemmArgs<T>& p) {
   const bool ak = p.a_k == 1, bn = p.b_n == 1;
   const int64_t outs = p.H * p.M * p.N;
+  int path;  // slot of tnco_hip_contract_kernel_launches
   if (p.M >= 64 && p.N >= 64 && p.K > 32) {  // tiled: every operand element reused 64 times from LDS
     const int64_t tiles = p.H * ((p.M + TB - 1) / TB) * ((p.N + TB - 1) / TB);
     const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20));
@@ -383,14 +387,18 @@ int launch_gemm(tnco_hip_contract_s* c, const GemmArgs<T>& p) {
     else if (ak) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, true, false>), grid, dim3(256), 0, c->stream, p);
     else if (bn) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, false, true>), grid, dim3(256), 0, c->stream, p);
     else hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, false, false>), grid, dim3(256), 0, c->stream, p);
+    path = 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0);
   } else if (p.K >= 512 && outs <= 8192) {  // few outputs, long sums: K split over a block
     hipLaunchKernelGGL(ct_gemm_dot_kernel<T>, dim3((unsigned)outs), dim3(256), 0, c->stream, p);
+    path = 5;
   } else {
     const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16));
     hipLaunchKernelGGL(ct_gemm_stream_kernel<T>, grid, dim3(256), 0, c->stream, p);
+    path = 6;
   }
   CT_TRY(hipGetLastError());
   c->launches += 1;
+  c->by_kernel[path] += 1;
   c->macs += p.H * p.M * p.N * p.K;
   return TNCO_HIP_OK;
 }
@@ -497,6 +505,7 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
   }
   CT_TRY(hipMemsetAsync(c->d_out, 0, (size_t)c->out_numel * c->elem, c->stream));
   c->macs = c->launches = 0;
+  std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
   CT_TRY(hipEventRecord(c->ev[0], c->stream));
   int rc = c->dtype == 0 ? run_impl<float>(c)
            : c->dtype == 1 ? run_impl<double>(c)
@@ -515,6 +524,12 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
 int tnco_hip_contract_stats(tnco_hip_contract c, int64_t* stats) {
   if (!c || !stats) return fail(TNCO_HIP_EINVAL, "null argument.");
   stats[0] = c->macs, stats[1] = c->launches, stats[2] = c->bytes, stats[3] = c->device_ns;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_kernel_launches(tnco_hip_contract c, int64_t* counts) {
+  if (!c || !counts) return fail(TNCO_HIP_EINVAL, "null argument.");
+  std::copy(std::begin(c->by_kernel), std::end(c->by_kernel), counts);
   return TNCO_HIP_OK;
 }
 
