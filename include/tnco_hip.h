@@ -370,6 +370,17 @@ const char* tnco_hip_comm_last_error(void);
  *                                      H, M, N, K; 0, 0.  Z[h][m][n] = sum_k A[h][m][k] B[h][k][n], operands dense per
  *                                      batch (A strides (K, 1) or (1, M), B (N, 1) or (1, K)), C dense [h][m][n].
  * The output buffer is [block slices][the rest]: block_slices lists the slice positions whose value selects a block.
+ *
+ * Row axes (projections of sparse indices): a tensor that holds sparse indices carries one outermost axis, a row per
+ * distinct projection of those indices; the permute table sees it as an ordinary axis.  Two more tables say how the
+ * rows of a step's operands meet:
+ *   row_steps [n_steps][5]             R, rows of A, map of A, rows of B, map of B.  The result has R rows and
+ *                                      Z[r][h][m][n] = sum_k A[a_map[r]][h][m][k] B[b_map[r]][h][k][n]; a map is an
+ *                                      offset into row_maps (R entries, each below the operand's row count) or -1: the
+ *                                      operand then has R rows, read in place, or one row, read for every r.
+ *                                      Operands are dense [rows][h] batches, C dense [r][h][m][n].
+ *   row_maps  [n_row_maps] int32       the pool of the maps.
+ * row_steps == NULL (and n_row_maps == 0): no step has a row axis; a row of (1, 1, -1, 1, -1) says the same of one step.
  */
 typedef struct tnco_hip_contract_s* tnco_hip_contract;
 typedef struct tnco_hip_contract_desc {
@@ -391,6 +402,9 @@ typedef struct tnco_hip_contract_desc {
   const int64_t* block_slices;
   int64_t slice_start;
   int64_t slice_stop;
+  const int64_t* row_steps;  /* NULL: no row axes */
+  int64_t n_row_maps;
+  const int32_t* row_maps;
 } tnco_hip_contract_desc;
 /* validates the plan, allocates leaves + arena + output on the device (ERUNTIME when they exceed its free memory) */
 int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract* out);
@@ -399,13 +413,19 @@ int tnco_hip_contract_run(tnco_hip_contract h, const void* const* leaves, void* 
 /* stats[4]: multiply-adds launched by the last run, its kernel launches, device bytes reserved, device time of the
  * last run's kernels in ns (events around the slice loop: leaf copies in and the result copy out excluded) */
 int tnco_hip_contract_stats(tnco_hip_contract h, int64_t* stats);
-/* counts[TNCO_HIP_CONTRACT_N_KERNELS]: the last run's launches per kernel path; their sum is stats[1].  Order:
+/* counts[TNCO_HIP_CONTRACT_N_KERNELS]: the last run's launches per kernel path; with the row-mapped paths below their sum
+ * is stats[1].  Order:
  *   0 gather (slices + permutes);
  *   1..4 tiled GEMM by operand layout: 1 A [k][m], B [n][k];  2 A [k][m], B [k][n];  3 A [m][k], B [n][k];
  *        4 A [m][k], B [k][n]  (slot 1 + 2 (A contiguous along k) + (B contiguous along n));
  *   5 dot (K split over a block);  6 stream (one lane per output element). */
 #define TNCO_HIP_CONTRACT_N_KERNELS 7
 int tnco_hip_contract_kernel_launches(tnco_hip_contract h, int64_t* counts);
+/* counts[TNCO_HIP_CONTRACT_N_ROW_KERNELS]: the last run's launches of the row-mapped GEMM paths (steps with a row axis);
+ * stats[1] is the sum of these and of the seven above.  Order: 0 rows_tiled (any operand layout), 1 rows_dot,
+ * 2 rows_stream. */
+#define TNCO_HIP_CONTRACT_N_ROW_KERNELS 3
+int tnco_hip_contract_row_launches(tnco_hip_contract h, int64_t* counts);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

@@ -13,6 +13,13 @@ summed over, assignment after assignment in one fixed order on the device, so a 
 The plan -- per-step layouts, which operand needs a permute, buffer liveness in one device arena -- is built here and
 has no GPU dependency; `libtnco_hip.so` (csrc/contract.hip) gets it as flat int64 tables and runs the slice loop and
 the step loop in one call (`tnco_hip_contract_run`).
+
+Projections: with `sparse_inds` (output indices) and `projs`, an integer array [P, len(sparse_inds)], the result is the
+dense result taken at those P assignments of the sparse indices: axes ("proj",) + the other axes, out[p] =
+Z[sparse_inds = projs[p]].  A tensor that holds the subset T of the sparse indices is stored as [rows][its other
+axes], a row per distinct row of projs[:, T] (numpy.unique(axis=0) order, columns in sparse_inds order): at most
+min(prod dims(T), P) rows, the factor of the sparse cost model.  A step Z = X Y has T_z = T_x | T_y, and two int32 maps
+give the rows of X and of Y that each row of Z restricts to; the leaves are restricted to their rows on the host.
 """
 from __future__ import annotations
 
@@ -24,7 +31,8 @@ import numpy as np
 
 from .app import tn as tnmod
 
-__all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS"]
+__all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
+           "ROW_KERNEL_PATHS"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -37,6 +45,10 @@ LEAF_SL_W = 1 + 2 * MAX_AXES
 # the kernel paths of csrc/contract.hip in the order tnco_hip_contract_kernel_launches counts them; a tiled name gives
 # the memory order of A, then of B (mk_kn: A [m][k], B [k][n])
 KERNEL_PATHS = ("gather", "tiled_km_nk", "tiled_km_kn", "tiled_mk_nk", "tiled_mk_kn", "dot", "stream")
+# the row-mapped GEMM paths (steps with a row axis) in the order tnco_hip_contract_row_launches counts them
+ROW_KERNEL_PATHS = ("rows_tiled", "rows_dot", "rows_stream")
+ROW_W = 5  # row_steps: R, rows of A, map of A, rows of B, map of B (a map: offset into row_maps, -1 none)
+PROJ = "proj"  # the first axis of a projected result
 ALIGN = 64  # arena offsets in elements: 64 x (4..16 B) keeps every buffer 256-byte aligned
 
 
@@ -50,7 +62,8 @@ class ContractionResult:
     launches: int = 0  # kernel launches
     device_s: float = 0.0  # device time of the kernels (copies in and out excluded)
     fuse_macs: int = 0  # contract_results: multiply-adds of the fuse stage (not part of `macs`)
-    kernel_launches: tuple = (0,) * len(KERNEL_PATHS)  # `launches` per kernel path, in KERNEL_PATHS order
+    kernel_launches: tuple = (0,) * len(KERNEL_PATHS)  # launches per kernel path, in KERNEL_PATHS order
+    row_kernel_launches: tuple = (0, 0, 0)  # ... per row-mapped path, in ROW_KERNEL_PATHS order; `launches` is both
 
 
 @dataclass
@@ -71,6 +84,12 @@ class Plan:
     macs_per_slice: int
     slice_range: tuple = (0, 1)
     ops: list = field(default_factory=list)  # readable copy of the step decisions (tests, tools)
+    # projections (None / empty without `projs`)
+    sparse_inds: tuple = ()
+    row_steps: np.ndarray = None  # [n_steps, ROW_W]
+    row_maps: np.ndarray = None  # int32 pool of the maps
+    leaf_rows: tuple = ()  # per leaf: None, or (axes of its sparse indices, their values [rows, len(axes)])
+    out_rows: tuple = None  # (rows of the final tensor, row of it for each of the P projections)
 
     @property
     def n_slices(self) -> int:
@@ -84,7 +103,8 @@ class Plan:
     def peak_device_bytes(self) -> int:
         item = self.dtype.itemsize
         tables = 8 * (self.leaf_sl.size + self.perms.size + 2 * self.leaf_numel.size)
-        return item * (int(self.leaf_numel.sum()) + self.arena_elems + self.out_numel) + tables
+        maps = 0 if self.row_maps is None else 4 * self.row_maps.size + 8 * self.row_steps.size
+        return item * (int(self.leaf_numel.sum()) + self.arena_elems + self.out_numel) + tables + maps
 
 
 class _Arena:
@@ -169,9 +189,55 @@ class _Live:
         self.inds, self.kind, self.ref, self.leaf = tuple(inds), kind, ref, leaf
 
 
-def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64) -> Plan:
+class _RowAxis:
+    """The row axis of the tensors that hold the sparse indices of columns `cols` of projs: an index like any other
+    to the permutes and the arena, always outermost."""
+
+    def __init__(self, cols):
+        self.cols = tuple(cols)
+
+    def __eq__(self, other):
+        return isinstance(other, _RowAxis) and other.cols == self.cols
+
+    def __hash__(self):
+        return hash(("rows", self.cols))
+
+    def __repr__(self):
+        return f"rows{self.cols}"
+
+
+def _check_projs(sparse_inds, projs, dims, ts_inds, out_inds, sl):
+    sparse = tuple(sparse_inds)
+    held = {x for xs in ts_inds for x in xs}
+    if len(set(sparse)) != len(sparse) or not set(sparse) <= held:
+        raise ValueError("'sparse_inds' has indices not in 'ts_inds'.")
+    if not set(sparse) <= set(out_inds):
+        raise ValueError("'sparse_inds' must be output indices.")
+    if set(sparse) & sl:
+        raise NotImplementedError("a sliced index that is also sparse is not supported.")
+    projs = np.asarray(projs)
+    if projs.dtype.kind not in "iu":
+        raise TypeError("'projs' must be an array of integers.")
+    if projs.ndim != 2 or projs.shape[1] != len(sparse) or projs.shape[0] < 1:
+        raise ValueError("'projs' must have shape [P, len(sparse_inds)], P >= 1.")
+    projs = projs.astype(np.int64)
+    if (projs < 0).any() or (projs >= np.array([dims[x] for x in sparse], np.int64).reshape(1, -1)).any():
+        raise ValueError("'projs' has values beyond the dimensions of 'sparse_inds'.")
+    return sparse, projs
+
+
+def _unique_rows(table):
+    """numpy.unique(axis=0) of an int64 [n, c] table, and the row of it that each of the n rows is; c == 0: one row."""
+    if table.shape[1] == 0:
+        return table[:1], np.zeros(len(table), np.int64)
+    rows, inverse = np.unique(table, axis=0, return_inverse=True)
+    return rows, inverse.reshape(-1)
+
+
+def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
+         sparse_inds=(), projs=None) -> Plan:
     """The device plan of one contraction along a path that leaves one tensor (no GPU).
-    `shapes`: the leaves' shapes, in ts_inds order."""
+    `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`: see the module docstring."""
     ts_inds = [tuple(xs) for xs in ts_inds]
     shapes = [tuple(int(d) for d in s) for s in shapes]
     dims = _dims_of(ts_inds, shapes)
@@ -181,6 +247,39 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         raise ValueError("plan() needs a path that leaves one tensor.")
     final = tuple(final[0])
     sl = frozenset(slices)
+    if projs is None and tuple(sparse_inds):
+        raise ValueError("'sparse_inds' need 'projs'.")
+    rows_of, leaf_rows, row_steps, row_maps = {}, (), None, None  # _RowAxis -> its table of values [rows, len(cols)]
+    if projs is not None:
+        sparse, projs = _check_projs(sparse_inds, projs, dims, ts_inds, out_inds, sl)
+        col = {x: j for j, x in enumerate(sparse)}
+
+        def row_axis(xs):  # of a tensor that holds the indices xs, None when none of them is sparse
+            cols = tuple(sorted(col[x] for x in xs if x in col))
+            if not cols:
+                return None
+            ax = _RowAxis(cols)
+            if ax not in rows_of:
+                rows_of[ax] = _unique_rows(projs[:, cols])[0]
+                dims[ax] = len(rows_of[ax])
+            return ax
+
+        # a leaf is restricted to its rows on the host: [rows][its other axes], sliced ones included
+        leaf_rows = []
+        for t, (xs, shape) in enumerate(zip(ts_inds, shapes)):
+            ax = row_axis(xs)
+            if ax is None:
+                leaf_rows.append(None)
+                continue
+            leaf_rows.append((tuple(xs.index(sparse[j]) for j in ax.cols), rows_of[ax]))
+            kept = [k for k, x in enumerate(xs) if x not in col]
+            ts_inds[t] = (ax,) + tuple(xs[k] for k in kept)
+            shapes[t] = (dims[ax],) + tuple(shape[k] for k in kept)
+        leaf_rows = tuple(leaf_rows)
+        full_final = final
+        ax = row_axis(final)
+        final = (() if ax is None else (ax,)) + tuple(x for x in final if x not in col)
+        row_steps, row_maps = [], []
     every = list(dict.fromkeys(x for xs in ts_inds for x in xs))
     if not sl <= set(every):
         raise ValueError("'slices' has indices not in 'ts_inds'.")
@@ -241,24 +340,31 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         ops.append(dict(copy=live[0].inds))
     for k, (a, b) in enumerate(steps):
         B, A = live.pop(b), live.pop(a)
-        shared = frozenset(A.inds) & frozenset(B.inds)
+        # row axes stay outermost and out of the roles: h, m, n, k are computed over the other indices
+        ra = tuple(x for x in A.inds[:1] if isinstance(x, _RowAxis))
+        rb = tuple(x for x in B.inds[:1] if isinstance(x, _RowAxis))
+        rz = (_RowAxis(sorted(set(ra[0].cols if ra else ()) | set(rb[0].cols if rb else ()))),) if ra or rb else ()
+        if rz and rz[0] not in rows_of:
+            rows_of[rz[0]] = _unique_rows(projs[:, rz[0].cols])[0]
+            dims[rz[0]] = len(rows_of[rz[0]])
+        shared = frozenset(A.inds[len(ra):]) & frozenset(B.inds[len(rb):])
         stay = frozenset(x for x in shared if left[x] > 1) | (keep & shared)
         for x in shared:
             left[x] -= 1
         h = tuple(x for x in A.inds if x in stay)
-        xs = tuple(x for x in A.inds if x not in shared)
-        ys = tuple(y for y in B.inds if y not in shared)
+        xs = tuple(x for x in A.inds[len(ra):] if x not in shared)
+        ys = tuple(y for y in B.inds[len(rb):] if y not in shared)
         s = shared - stay
         best = None
         for s_order in dict.fromkeys((tuple(q for q in A.inds if q in s), tuple(q for q in B.inds if q in s))):
-            fa = [f for f in (0, 1) if A.kind is not None and _fits(A.inds, h, xs, s_order, f == 1)]
-            fb = [f for f in (0, 1) if B.kind is not None and _fits(B.inds, h, ys, s_order, f == 0)]
+            fa = [f for f in (0, 1) if A.kind is not None and _fits(A.inds, ra + h, xs, s_order, f == 1)]
+            fb = [f for f in (0, 1) if B.kind is not None and _fits(B.inds, rb + h, ys, s_order, f == 0)]
             moved = (0 if fa else size(A.inds)) + (0 if fb else size(B.inds))
             if best is None or moved < best[0]:
                 best = (moved, s_order, fa[0] if fa else None, fb[0] if fb else None)
         _, s_order, form_a, form_b = best
         moved_from = []  # (the permutes of one step run in one launch: their sources are released after both)
-        for T, form, target in ((A, form_a, h + xs + s_order), (B, form_b, h + s_order + ys)):
+        for T, form, target in ((A, form_a, ra + h + xs + s_order), (B, form_b, rb + h + s_order + ys)):
             if form is None:
                 ref = permute(T, target, -1 if T.leaf is not None else k)
                 if T.kind == ARENA:
@@ -268,11 +374,36 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         form_a = 0 if form_a is None else form_a
         form_b = 0 if form_b is None else form_b
         H, M, N, K = size(h), size(xs), size(ys), size(s_order)
-        z = h + xs + ys
+        z = rz + h + xs + ys
         c_kind, c_ref = (OUT, 0) if k == len(steps) - 1 else (ARENA, new_buf(size(z)))
+        op = dict(h=h, x=xs, y=ys, s=s_order, form_a=form_a, form_b=form_b, H=H, M=M, N=N, K=K)
+        if projs is not None:
+            R = size(rz)
+            if ra == rz and not rb and H == 1 and form_a == 0:
+                # only the first operand has rows, stored [r][m][k]: a plain GEMM with R M rows
+                M, R = R * M, 1
+                row_steps.append([1, 1, -1, 1, -1])
+                op.update(M=M, R=1, folded=True, a_map=None, b_map=None)
+            else:
+                maps = []
+                for r in (ra, rb):
+                    if not r or r == rz:  # one row for every r / the rows of the result, in place
+                        maps.append(None)
+                        continue
+                    sub = rows_of[rz[0]][:, [rz[0].cols.index(c) for c in r[0].cols]]
+                    both, where = _unique_rows(np.concatenate([rows_of[r[0]], sub]))
+                    assert len(both) == len(rows_of[r[0]])  # (every row of the result restricts to a row it has)
+                    maps.append(where[len(both):].astype(np.int32))
+                at = []
+                for m in maps:
+                    at.append(-1 if m is None else sum(len(q) for q in row_maps))
+                    if m is not None:
+                        row_maps.append(m)
+                row_steps.append([R, size(ra), at[0], size(rb), at[1]])
+                op.update(R=R, folded=False, a_map=maps[0], b_map=maps[1])
         rows.append([A.kind, A.ref, *((K, 1) if form_a == 0 else (1, M)),
                      B.kind, B.ref, *((N, 1) if form_b == 0 else (1, K)), c_kind, c_ref, H, M, N, K, 0, 0])
-        ops.append(dict(h=h, x=xs, y=ys, s=s_order, form_a=form_a, form_b=form_b, H=H, M=M, N=N, K=K))
+        ops.append(op)
         for T in (A, B):
             if T.kind == ARENA:
                 events.append(("free", T.ref))
@@ -297,10 +428,25 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     perm_tab = perm_tab[np.argsort(perm_tab[:, 6], kind="stable")]  # slice-start gathers (group -1) first
     step_tab = np.array(rows, np.int64).reshape(-1, STEP_W)
     macs = int(sum(int(r[10]) * int(r[11]) * int(r[12]) * int(r[13]) for r in rows))
-    return Plan(dtype=np.dtype(dtype), inds=final, shape=tuple(dims[x] for x in final), slice_inds=slice_inds,
-                slice_dims=slice_dims, block_inds=tuple(x for x in slice_inds if x in final), leaf_numel=leaf_numel,
-                leaf_sl=leaf_sl, perms=perm_tab, steps=step_tab, arena_elems=arena.peak, out_numel=size(final),
-                macs_per_slice=macs, slice_range=(lo, hi), ops=ops)
+    p = Plan(dtype=np.dtype(dtype), inds=final, shape=tuple(dims[x] for x in final), slice_inds=slice_inds,
+             slice_dims=slice_dims, block_inds=tuple(x for x in slice_inds if x in final), leaf_numel=leaf_numel,
+             leaf_sl=leaf_sl, perms=perm_tab, steps=step_tab, arena_elems=arena.peak, out_numel=size(final),
+             macs_per_slice=macs, slice_range=(lo, hi), ops=ops)
+    if projs is None:
+        return p
+    # the device holds the distinct rows of the final tensor; the result has one per projection, duplicates included
+    p.sparse_inds, p.leaf_rows = sparse, leaf_rows
+    p.row_steps = np.array(row_steps, np.int64).reshape(-1, ROW_W)
+    p.row_maps = np.concatenate(row_maps + [np.zeros(0, np.int32)]).astype(np.int32)
+    p.macs_per_slice = int(sum(int(w[0]) * int(r[10]) * int(r[11]) * int(r[12]) * int(r[13])
+                               for w, r in zip(row_steps, rows)))
+    rest = tuple(x for x in full_final if x not in col)
+    if sparse:
+        p.out_rows = (dims[final[0]], _unique_rows(projs)[1])
+    else:
+        p.out_rows = (1, np.zeros(len(projs), np.int64))
+    p.inds, p.shape = (PROJ,) + rest, (len(projs),) + tuple(dims[x] for x in rest)
+    return p
 
 
 def check_memory(p: Plan, free_bytes: int) -> None:
@@ -345,9 +491,11 @@ def _sub_output(ts_inds, leaves, output) -> frozenset:
     return frozenset(output) & inside | (inside & outside)
 
 
-def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=None, device=None) -> ContractionResult:
+def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=None, device=None,
+             sparse_inds=(), projs=None) -> ContractionResult:
     """Contract `arrays` (numpy, in ts_inds order) along the linear `path` on the GPU; see the module docstring.
-    A path that leaves several tensors gives lists in `inds` / `array` (the sliced form needs one tensor)."""
+    A path that leaves several tensors gives lists in `inds` / `array` (the sliced and the projected form need one
+    tensor)."""
     ts_inds = [tuple(xs) for xs in ts_inds]
     arrays = [np.asarray(a) for a in arrays]
     dims = _dims_of(ts_inds, [a.shape for a in arrays])
@@ -355,10 +503,13 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     steps = _check_path(path, len(ts_inds))
     final, out = tnmod.contract(steps, ts_inds, output_inds, dims)
     if len(final) == 1:
-        p = plan(steps, ts_inds, [a.shape for a in arrays], out, slices=slices, slice_range=slice_range, dtype=dtype)
+        p = plan(steps, ts_inds, [a.shape for a in arrays], out, slices=slices, slice_range=slice_range, dtype=dtype,
+                 sparse_inds=sparse_inds, projs=projs)
         return _run(p, arrays, device)
     if slices:
         raise NotImplementedError("slices need a path that leaves one tensor.")
+    if projs is not None or tuple(sparse_inds):
+        raise NotImplementedError("projections need a path that leaves one tensor.")
     parts = []
     for leaves, sub in _split(steps, len(ts_inds)):
         if not sub:
@@ -370,7 +521,8 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     assert [tuple(r.inds) for r in parts] == [tuple(f) for f in final]
     return ContractionResult([r.inds for r in parts], [r.array for r in parts], sum(r.macs for r in parts), 1,
                              max(r.peak_device_bytes for r in parts), sum(r.launches for r in parts),
-                             kernel_launches=_add_counts(*(r.kernel_launches for r in parts)))
+                             kernel_launches=_add_counts(*(r.kernel_launches for r in parts)),
+                             row_kernel_launches=_add_counts(*(r.row_kernel_launches for r in parts)))
 
 
 def _add_counts(*counts) -> tuple:
@@ -382,6 +534,10 @@ def _run(p: Plan, arrays, device) -> ContractionResult:
     L = _lib.load()
     device = parallel.local_device() if device is None else int(device)
     leaves = [np.ascontiguousarray(a, dtype=p.dtype) for a in arrays]
+    for t, rows in enumerate(p.leaf_rows):
+        if rows is not None:  # [rows][the other axes]: the leaf at the distinct projections of its sparse indices
+            axes, values = rows
+            leaves[t] = np.ascontiguousarray(np.moveaxis(leaves[t], axes, range(len(axes)))[tuple(values.T)])
     i64p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     keep = dict(leaf_numel=np.ascontiguousarray(p.leaf_numel), leaf_sl=np.ascontiguousarray(p.leaf_sl),
                 perms=np.ascontiguousarray(p.perms), steps=np.ascontiguousarray(p.steps),
@@ -396,6 +552,9 @@ def _run(p: Plan, arrays, device) -> ContractionResult:
     d.n_slice_dims, d.slice_dims = len(p.slice_dims), i64p(keep["slice_dims"])
     d.n_block, d.block_slices = len(p.block_inds), i64p(keep["block"])
     d.slice_start, d.slice_stop = p.slice_range
+    if p.row_steps is not None:
+        keep.update(row_steps=np.ascontiguousarray(p.row_steps), row_maps=np.ascontiguousarray(p.row_maps))
+        d.row_steps, d.n_row_maps, d.row_maps = i64p(keep["row_steps"]), p.row_maps.size, i64p(keep["row_maps"])
     h = C.c_void_p()
     _lib.check(L.tnco_hip_contract_create(C.byref(d), C.byref(h)))
     try:
@@ -406,26 +565,56 @@ def _run(p: Plan, arrays, device) -> ContractionResult:
         _lib.check(L.tnco_hip_contract_stats(h, stats.ctypes.data_as(C.c_void_p)))
         by_kernel = np.zeros(len(KERNEL_PATHS), np.int64)
         _lib.check(L.tnco_hip_contract_kernel_launches(h, by_kernel.ctypes.data_as(C.c_void_p)))
+        by_row_kernel = np.zeros(len(ROW_KERNEL_PATHS), np.int64)
+        _lib.check(L.tnco_hip_contract_row_launches(h, by_row_kernel.ctypes.data_as(C.c_void_p)))
     finally:
         L.tnco_hip_contract_destroy(h)
-    # the output buffer holds [block axes][the others]; the result's own axis order is a view of it
-    rest = tuple(x for x in p.inds if x not in set(p.slice_inds))
-    held = p.block_inds + rest
-    array = staging.reshape(tuple(p.shape[p.inds.index(x)] for x in held))
-    array = array.transpose([held.index(x) for x in p.inds]).copy(order="C")  # (0-d stays 0-d)
+    array = _host_layout(p, staging)
     return ContractionResult(p.inds, array, int(stats[0]), p.slice_range[1] - p.slice_range[0], int(stats[2]),
-                             int(stats[1]), float(stats[3]) * 1e-9, kernel_launches=tuple(int(v) for v in by_kernel))
+                             int(stats[1]), float(stats[3]) * 1e-9, kernel_launches=tuple(int(v) for v in by_kernel),
+                             row_kernel_launches=tuple(int(v) for v in by_row_kernel))
 
 
-def contract_results(tn0, arrays, tn, result, *, device=None) -> ContractionResult:
+def _host_layout(p: Plan, staging) -> np.ndarray:
+    """The output buffer, [block axes][the others] (with projections: [block axes][rows of the final tensor][the
+    others]), in the result's own axis order; the distinct rows expanded to the P projections with one take."""
+    if p.out_rows is None:
+        rest = tuple(x for x in p.inds if x not in set(p.slice_inds))
+        held = p.block_inds + rest
+        array = staging.reshape(tuple(p.shape[p.inds.index(x)] for x in held))
+        return array.transpose([held.index(x) for x in p.inds]).copy(order="C")  # (0-d stays 0-d)
+    n_rows, row_of_proj = p.out_rows
+    named = p.inds[1:]  # (position 0 is the projection axis)
+    rest = tuple(x for x in named if x not in set(p.slice_inds))
+    held = p.block_inds + (None,) + rest
+    array = staging.reshape(tuple(n_rows if x is None else p.shape[1 + named.index(x)] for x in held))
+    array = array.transpose([held.index(None)] + [held.index(x) for x in named])
+    return array.take(row_of_proj, axis=0)
+
+
+def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse_inds=None) -> ContractionResult:
     """Run a result of `Optimizer.optimize` over the arrays of the network as given.
 
     tn0: the network before pre-fusing (`load_tn(obj, fuse=None)`); arrays: in tn0.tensors order, or {name: array}
     by the tensors' `name` tag; tn, result: what `optimize` returned.  The fuse stage (tn.tags['fuse_path']) runs
     unsliced, its multiply-adds go to `fuse_macs`; then `result.path` with `result.slices`, every connected component
-    of a finite-width result sliced by its own set (`disconnected_slices`)."""
-    if tn0.sparse_inds or tn.sparse_inds:
-        raise NotImplementedError("sparse indices (n_projs) have no array meaning here.")
+    of a finite-width result sliced by its own set (`disconnected_slices`).
+
+    A network with sparse indices needs `projs`, [P, number of sparse indices]: the result is then taken at those
+    assignments of the sparse indices (axes ("proj",) + the others).  The columns are the sparse indices in
+    `sorted(tn.sparse_inds, key=str)` order, or in the order of `sparse_inds` when that is given."""
+    if (tn0.sparse_inds or tn.sparse_inds) and projs is None:
+        raise NotImplementedError("sparse indices (n_projs) have an array meaning only at given projections: "
+                                  "pass projs=, an integer array [P, number of sparse indices].")
+    if projs is not None:
+        if sparse_inds is None:
+            sparse_inds = sorted(tn.sparse_inds, key=str)
+        if set(sparse_inds) != set(tn.sparse_inds) or set(tn0.sparse_inds) != set(tn.sparse_inds):
+            raise ValueError("'sparse_inds' are not the sparse indices of the network.")
+        if tn.tags.get("fuse_path") or len([q for q in getattr(result, "disconnected_paths", ()) if q]) > 1:
+            raise NotImplementedError("projections need one connected network that was not pre-fused.")
+    elif sparse_inds is not None:
+        raise ValueError("'sparse_inds' need 'projs'.")
     if isinstance(arrays, dict):
         try:
             arrays = [arrays[t.tags["name"]] for t in tn0.tensors]
@@ -444,9 +633,9 @@ def contract_results(tn0, arrays, tn, result, *, device=None) -> ContractionResu
     comp_paths = [list(q) for q in getattr(result, "disconnected_paths", ()) if q]
     if len(comp_paths) <= 1:  # one component to contract: the path with its slices, in one call
         r = contract(result.path, tn.ts_inds, arrays, tn.output_inds, slices=getattr(result, "slices", ()),
-                     device=device)
+                     device=device, sparse_inds=sparse_inds or (), projs=projs)
         return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
-                                 fuse_macs, r.kernel_launches)
+                                 fuse_macs, r.kernel_launches, r.row_kernel_launches)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
     ts, n = [tuple(x) for x in tn.ts_inds], len(tn.ts_inds)
     done, results, macs, n_slices, peak, launches, device_s = set(), [], 0, 0, 0, 0, 0.0

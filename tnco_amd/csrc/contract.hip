@@ -5,7 +5,11 @@
 //                          assignment in one launch (one row of the table per grid row), permutes of intermediates;
 //   ct_gemm_tiled_kernel   C[h] = beta C[h] + A[h] B[h] through LDS, 64 x 64 tiles, 4 x 4 per lane: M, N, K large;
 //   ct_gemm_stream_kernel  one lane per output element: skinny steps (K or N small, outer products), memory-bound;
-//   ct_gemm_dot_kernel     one block per output element, K split over the block: few outputs, long K.
+//   ct_gemm_dot_kernel     one block per output element, K split over the block: few outputs, long K;
+//   ct_rows_tiled_kernel, ct_rows_stream_kernel, ct_rows_dot_kernel
+//                          the same three with a row axis outermost (the distinct projections of the sparse indices a
+//                          tensor holds): Z[r][h] = X[a_map[r]][h] Y[b_map[r]][h], the operand rows taken through int32
+//                          maps (tnco_hip.h, row_steps).  Steps without a row axis do not come here.
 // No atomics: every sum runs in one fixed order, so a run is bit-reproducible.
 #include "../../include/tnco_hip.h"
 
@@ -28,6 +32,7 @@ constexpr int CT_MAX_AXES = 32;
 constexpr int PERM_W = 8 + 2 * CT_MAX_AXES;
 constexpr int STEP_W = 16;
 constexpr int LEAF_SL_W = 1 + 2 * CT_MAX_AXES;
+constexpr int ROW_W = 5;  // row_steps: R, rows of A, map of A, rows of B, map of B
 constexpr int64_t K_LEAF = 0, K_ARENA = 1, K_OUT = 2;
 
 int fail(int code, const std::string& msg) { return tnco::set_error(code, msg); }
@@ -209,6 +214,131 @@ __global__ __launch_bounds__(256) void ct_gemm_dot_kernel(GemmArgs<T> p) {
   }
 }
 
+// A step with a row axis: row r of the result reads row a_map[r] of A and row b_map[r] of B.  A null map with a row
+// stride: row r itself; a row stride of 0: the operand has one row, read for every r.
+template <class T>
+struct RowGemmArgs {
+  const T* A;
+  const T* B;
+  T* C;
+  const int32_t* a_map;
+  const int32_t* b_map;
+  int64_t a_row, b_row;        // elements between two rows of A / of B (H M K, H K N, or 0)
+  int64_t a_m, a_k, b_k, b_n;  // strides inside a batch, as in GemmArgs
+  int64_t R, H, M, N, K;
+  int beta;
+};
+
+template <class T>
+__device__ inline const T* ct_row_of(const T* base, const int32_t* map, int64_t stride, int64_t r) {
+  return base + (map ? (int64_t)map[r] : r) * stride;
+}
+
+// the tile loop of ct_gemm_tiled_kernel, batches (r, h): the operand bases go through the maps
+template <class T, bool AK, bool BN>
+__global__ __launch_bounds__(256) void ct_rows_tiled_kernel(RowGemmArgs<T> p) {
+  __shared__ T As[TK][TB + 1];
+  __shared__ T Bs[TK][TB + 1];
+  const int tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
+  const int64_t tm = (p.M + TB - 1) / TB, tn = (p.N + TB - 1) / TB;
+  for (int64_t t = blockIdx.x; t < p.R * p.H * tm * tn; t += gridDim.x) {
+    const int64_t rh = t / (tm * tn), r = rh / p.H, h = rh % p.H, m0 = (t / tn % tm) * TB, n0 = t % tn * TB;
+    const T* A = ct_row_of(p.A, p.a_map, p.a_row, r) + h * p.M * p.K;
+    const T* B = ct_row_of(p.B, p.b_map, p.b_row, r) + h * p.K * p.N;
+    T acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = ct_zero<T>();
+    for (int64_t k0 = 0; k0 < p.K; k0 += TK) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int e = tid + 256 * i;
+        const int ak = AK ? e % TK : e / TB, am = AK ? e / TK : e % TB;
+        const int64_t m = m0 + am, k = k0 + ak;
+        As[ak][am] = (m < p.M && k < p.K) ? A[m * p.a_m + k * p.a_k] : ct_zero<T>();
+        const int bk = BN ? e / TB : e % TK, bn = BN ? e % TB : e / TK;
+        const int64_t n = n0 + bn, k2 = k0 + bk;
+        Bs[bk][bn] = (n < p.N && k2 < p.K) ? B[k2 * p.b_k + n * p.b_n] : ct_zero<T>();
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int kk = 0; kk < TK; ++kk) {
+        T a[4], b[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = As[kk][ty + 16 * i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[j] = Bs[kk][tx + 16 * j];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = ct_mac(acc[i][j], a[i], b[j]);
+      }
+      __syncthreads();
+    }
+    T* Cb = p.C + rh * p.M * p.N;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t m = m0 + ty + 16 * i, n = n0 + tx + 16 * j;
+        if (m < p.M && n < p.N) {
+          T* c = Cb + m * p.N + n;
+          *c = p.beta ? ct_add(*c, acc[i][j]) : acc[i][j];
+        }
+      }
+  }
+}
+
+// One lane per output element (r, h, m, n), n fastest: a wavefront covers consecutive n, then m, of one row, or of
+// adjacent rows when H M N < 64, so the lanes of a row read its two map entries from one address, once, before the k
+// loop, and the result is written in full lines.  I: the integer type of the element arithmetic (uint32_t while the
+// result has fewer than 2^31 elements: three 32-bit divisions per element instead of 64-bit ones).
+template <class T, class I>
+__device__ inline void ct_rows_stream_body(const RowGemmArgs<T>& p) {
+  const I N = (I)p.N, M = (I)p.M, H = (I)p.H, total = (I)(p.R * p.H * p.M * p.N);
+  const I stride = (I)gridDim.x * (I)blockDim.x;
+  const I first = (I)blockIdx.x * (I)blockDim.x + (I)threadIdx.x;
+  const I trips = first < total ? (total - first + stride - 1) / stride : 0;  // (no wrap of e + stride)
+  I e = first;
+  for (I t = 0; t < trips; ++t, e += stride) {
+    const I n = e % N, q = e / N, m = q % M, rh = q / M, h = rh % H, r = rh / H;
+    const T* a = ct_row_of(p.A, p.a_map, p.a_row, (int64_t)r) + (int64_t)h * p.M * p.K + (int64_t)m * p.a_m;
+    const T* b = ct_row_of(p.B, p.b_map, p.b_row, (int64_t)r) + (int64_t)h * p.K * p.N + (int64_t)n * p.b_n;
+    T acc = ct_zero<T>();
+    for (int64_t k = 0; k < p.K; ++k) acc = ct_mac(acc, a[k * p.a_k], b[k * p.b_k]);
+    p.C[e] = p.beta ? ct_add(p.C[e], acc) : acc;
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void ct_rows_stream_kernel(RowGemmArgs<T> p) {
+  if (p.R * p.H * p.M * p.N < (int64_t)1 << 31) ct_rows_stream_body<T, uint32_t>(p);
+  else ct_rows_stream_body<T, uint64_t>(p);
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void ct_rows_dot_kernel(RowGemmArgs<T> p) {
+  __shared__ T part[256];
+  const int tid = threadIdx.x;
+  const int64_t total = p.R * p.H * p.M * p.N;
+  for (int64_t e = blockIdx.x; e < total; e += gridDim.x) {
+    const int64_t n = e % p.N, q = e / p.N, m = q % p.M, rh = q / p.M, h = rh % p.H, r = rh / p.H;
+    const T* a = ct_row_of(p.A, p.a_map, p.a_row, r) + h * p.M * p.K + m * p.a_m;
+    const T* b = ct_row_of(p.B, p.b_map, p.b_row, r) + h * p.K * p.N + n * p.b_n;
+    T acc = ct_zero<T>();
+    for (int64_t k = tid; k < p.K; k += 256) acc = ct_mac(acc, a[k * p.a_k], b[k * p.b_k]);
+    part[tid] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (tid < w) part[tid] = ct_add(part[tid], part[tid + w]);
+      __syncthreads();
+    }
+    if (tid == 0) p.C[e] = p.beta ? ct_add(p.C[e], part[0]) : part[0];
+    __syncthreads();
+  }
+}
+
 }  // namespace
 
 struct tnco_hip_contract_s {
@@ -216,16 +346,20 @@ struct tnco_hip_contract_s {
   size_t elem = 4;
   std::vector<int64_t> leaf_numel, leaf_off, leaf_sl, perms, steps, slice_dims, place, block;
   std::vector<int64_t> group_first, group_count, group_max;  // perm rows of group g at index g + 1
+  std::vector<int64_t> row_steps;  // [n_steps][ROW_W], empty: no step has a row axis
+  std::vector<int32_t> row_maps;
   int64_t arena_elems = 0, out_numel = 0, block_numel = 1, n_blocks = 1, start = 0, stop = 1;
   char* d_leaves = nullptr;  // every leaf, back to back
   void* d_arena = nullptr;
   void* d_out = nullptr;
   int64_t* d_tables = nullptr;  // perms | leaf_sl | place | slice_dims
   void** d_leaf_ptrs = nullptr;
+  int32_t* d_row_maps = nullptr;
   hipStream_t stream = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};  // around the kernels of a run
   int64_t macs = 0, launches = 0, bytes = 0, device_ns = 0;
   int64_t by_kernel[TNCO_HIP_CONTRACT_N_KERNELS] = {};  // launches of the last run per kernel path (tnco_hip.h)
+  int64_t by_row_kernel[TNCO_HIP_CONTRACT_N_ROW_KERNELS] = {};  // the same of the row-mapped paths
 };
 
 namespace {
@@ -256,6 +390,9 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
   if ((L && (!d->leaf_numel || !d->leaf_sl)) || (P && !d->perms) || (S && !d->steps) ||
       (d->n_slice_dims && !d->slice_dims) || (d->n_block && !d->block_slices))
     return "null table.";
+  if (d->n_row_maps < 0 || (d->n_row_maps && (!d->row_maps || !d->row_steps))) return "row-map tables are not valid.";
+  if (d->row_steps) c->row_steps.assign(d->row_steps, d->row_steps + S * ROW_W);
+  if (d->n_row_maps) c->row_maps.assign(d->row_maps, d->row_maps + d->n_row_maps);
   c->leaf_numel.assign(d->leaf_numel, d->leaf_numel + L);
   c->leaf_sl.assign(d->leaf_sl, d->leaf_sl + L * LEAF_SL_W);
   c->perms.assign(d->perms, d->perms + P * PERM_W);
@@ -326,11 +463,27 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
     const int64_t* st = &c->steps[k * STEP_W];
     const int64_t H = st[10], M = st[11], N = st[12], K = st[13];
     if (H < 1 || M < 1 || N < 1 || K < 1) return "step sizes must be positive.";
+    // the row axis: an operand has one row, or the result's rows (no map), or rows of its own reached through a map
+    static const int64_t no_rows[ROW_W] = {1, 1, -1, 1, -1};
+    const int64_t* rw = c->row_steps.empty() ? no_rows : &c->row_steps[k * ROW_W];
+    const int64_t R = rw[0];
+    if (R < 1) return "step row counts must be positive.";
+    for (int side = 0; side < 2; ++side) {
+      const int64_t rows = rw[1 + 2 * side], map = rw[2 + 2 * side];
+      if (rows < 1) return "step row counts must be positive.";
+      if (map == -1) {
+        if (rows != 1 && rows != R) return "an operand without a row map has one row or the result's rows.";
+        continue;
+      }
+      if (map < 0 || map > (int64_t)c->row_maps.size() || R > (int64_t)c->row_maps.size() - map) return "row map out of range.";
+      for (int64_t r = 0; r < R; ++r)
+        if (c->row_maps[map + r] < 0 || c->row_maps[map + r] >= rows) return "row map entry beyond the operand's rows.";
+    }
     if (!((st[2] == K && st[3] == 1) || (st[2] == 1 && st[3] == M))) return "A strides are not valid.";
     if (!((st[6] == N && st[7] == 1) || (st[6] == 1 && st[7] == K))) return "B strides are not valid.";
     int64_t lo[2], hi[2];
     for (int side = 0; side < 2; ++side) {
-      const int64_t kind = st[4 * side], ref = st[4 * side + 1], n = H * K * (side ? N : M);
+      const int64_t kind = st[4 * side], ref = st[4 * side + 1], n = rw[1 + 2 * side] * H * K * (side ? N : M);
       if (kind == K_LEAF) {
         if (ref < 0 || ref >= L || n + leaf_slice_reach(c, ref) > c->leaf_numel[ref]) return "step operand out of range.";
         lo[side] = hi[side] = -1;
@@ -341,7 +494,7 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
         return "step operand kind is not valid.";
       }
     }
-    const int64_t nc = H * M * N;
+    const int64_t nc = R * H * M * N;
     if (st[8] == K_OUT) {
       if (k != S - 1 || nc != c->block_numel) return "only the last step writes the output, one block.";
     } else if (st[8] == K_ARENA && k != S - 1) {
@@ -403,6 +556,35 @@ int launch_gemm(tnco_hip_contract_s* c, const GemmArgs<T>& p) {
   return TNCO_HIP_OK;
 }
 
+// launch_gemm for a step with a row axis: the same shape classes, outputs counted with the rows
+template <class T>
+int launch_rows_gemm(tnco_hip_contract_s* c, const RowGemmArgs<T>& p) {
+  const bool ak = p.a_k == 1, bn = p.b_n == 1;
+  const int64_t outs = p.R * p.H * p.M * p.N;
+  int path;  // slot of tnco_hip_contract_row_launches
+  if (p.M >= 64 && p.N >= 64 && p.K > 32) {
+    const int64_t tiles = p.R * p.H * ((p.M + TB - 1) / TB) * ((p.N + TB - 1) / TB);
+    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20));
+    if (ak && bn) hipLaunchKernelGGL((ct_rows_tiled_kernel<T, true, true>), grid, dim3(256), 0, c->stream, p);
+    else if (ak) hipLaunchKernelGGL((ct_rows_tiled_kernel<T, true, false>), grid, dim3(256), 0, c->stream, p);
+    else if (bn) hipLaunchKernelGGL((ct_rows_tiled_kernel<T, false, true>), grid, dim3(256), 0, c->stream, p);
+    else hipLaunchKernelGGL((ct_rows_tiled_kernel<T, false, false>), grid, dim3(256), 0, c->stream, p);
+    path = 0;
+  } else if (p.K >= 512 && outs <= 8192) {
+    hipLaunchKernelGGL(ct_rows_dot_kernel<T>, dim3((unsigned)outs), dim3(256), 0, c->stream, p);
+    path = 1;
+  } else {
+    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16));
+    hipLaunchKernelGGL(ct_rows_stream_kernel<T>, grid, dim3(256), 0, c->stream, p);
+    path = 2;
+  }
+  CT_TRY(hipGetLastError());
+  c->launches += 1;
+  c->by_row_kernel[path] += 1;
+  c->macs += outs * p.K;
+  return TNCO_HIP_OK;
+}
+
 template <class T>
 int run_impl(tnco_hip_contract_s* c) {
   std::vector<char> visited(c->n_blocks, 0);
@@ -426,9 +608,24 @@ int run_impl(tnco_hip_contract_s* c) {
         opnd[side] = kind == K_LEAF ? (const T*)(c->d_leaves + c->leaf_off[ref] * c->elem) + leaf_slice_offset(c, ref, sid)
                                     : arena + ref;
       }
+      T* dest = st[8] == K_OUT ? out + out_off : arena + st[9];
+      const int64_t* rw = c->row_steps.empty() ? nullptr : &c->row_steps[k * ROW_W];
+      if (rw && (rw[0] > 1 || rw[2] >= 0 || rw[4] >= 0)) {
+        RowGemmArgs<T> p;
+        p.A = opnd[0], p.B = opnd[1], p.C = dest;
+        p.a_map = rw[2] >= 0 ? c->d_row_maps + rw[2] : nullptr;
+        p.b_map = rw[4] >= 0 ? c->d_row_maps + rw[4] : nullptr;
+        p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
+        p.R = rw[0], p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
+        p.a_row = rw[2] < 0 && rw[1] == 1 ? 0 : p.H * p.M * p.K;
+        p.b_row = rw[4] < 0 && rw[3] == 1 ? 0 : p.H * p.K * p.N;
+        p.beta = st[8] == K_OUT ? beta : 0;
+        if ((rc = launch_rows_gemm<T>(c, p))) return rc;
+        continue;
+      }
       GemmArgs<T> p;
       p.A = opnd[0], p.B = opnd[1];
-      p.C = st[8] == K_OUT ? out + out_off : arena + st[9];
+      p.C = dest;
       p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
       p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
       p.beta = st[8] == K_OUT ? beta : 0;
@@ -461,7 +658,8 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
   const size_t leaves = (size_t)c->leaf_off.back() * c->elem;
   const size_t arena = (size_t)std::max<int64_t>(c->arena_elems, 1) * c->elem, outb = (size_t)c->out_numel * c->elem;
   const size_t ptrs = std::max<size_t>(c->leaf_numel.size(), 1) * sizeof(void*);
-  c->bytes = (int64_t)(leaves + arena + outb + n_tab * 8 + ptrs);
+  const size_t maps = c->row_maps.size() * sizeof(int32_t);
+  c->bytes = (int64_t)(leaves + arena + outb + n_tab * 8 + ptrs + maps);
   auto bail = [&](int code, const std::string& msg) {
     tnco_hip_contract_destroy(c);
     return fail(code, msg);
@@ -477,7 +675,8 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
       hipMalloc((void**)&c->d_leaves, std::max<size_t>(leaves, 64)) != hipSuccess ||
       hipMalloc(&c->d_arena, arena) != hipSuccess || hipMalloc(&c->d_out, outb) != hipSuccess ||
       hipMalloc((void**)&c->d_tables, std::max<size_t>(n_tab, 1) * 8) != hipSuccess ||
-      hipMalloc((void**)&c->d_leaf_ptrs, ptrs) != hipSuccess)
+      hipMalloc((void**)&c->d_leaf_ptrs, ptrs) != hipSuccess ||
+      (maps && hipMalloc((void**)&c->d_row_maps, maps) != hipSuccess))
     return bail(TNCO_HIP_ERUNTIME, "device allocation failed.");
   std::vector<int64_t> tab;
   tab.reserve(n_tab);
@@ -489,6 +688,7 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
   if ((n_tab && hipMemcpyAsync(c->d_tables, tab.data(), n_tab * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
       (!lp.empty() && hipMemcpyAsync(c->d_leaf_ptrs, lp.data(), lp.size() * sizeof(void*), hipMemcpyHostToDevice,
                                      c->stream) != hipSuccess) ||
+      (maps && hipMemcpyAsync(c->d_row_maps, c->row_maps.data(), maps, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
       hipStreamSynchronize(c->stream) != hipSuccess)
     return bail(TNCO_HIP_ERUNTIME, "copy of the plan failed.");
   *out = c;
@@ -506,6 +706,7 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
   CT_TRY(hipMemsetAsync(c->d_out, 0, (size_t)c->out_numel * c->elem, c->stream));
   c->macs = c->launches = 0;
   std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
+  std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
   CT_TRY(hipEventRecord(c->ev[0], c->stream));
   int rc = c->dtype == 0 ? run_impl<float>(c)
            : c->dtype == 1 ? run_impl<double>(c)
@@ -533,10 +734,16 @@ int tnco_hip_contract_kernel_launches(tnco_hip_contract c, int64_t* counts) {
   return TNCO_HIP_OK;
 }
 
+int tnco_hip_contract_row_launches(tnco_hip_contract c, int64_t* counts) {
+  if (!c || !counts) return fail(TNCO_HIP_EINVAL, "null argument.");
+  std::copy(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), counts);
+  return TNCO_HIP_OK;
+}
+
 void tnco_hip_contract_destroy(tnco_hip_contract c) {
   if (!c) return;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (void* p : {(void*)c->d_leaves, c->d_arena, c->d_out, (void*)c->d_tables, (void*)c->d_leaf_ptrs})
+  for (void* p : {(void*)c->d_leaves, c->d_arena, c->d_out, (void*)c->d_tables, (void*)c->d_leaf_ptrs, (void*)c->d_row_maps})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);

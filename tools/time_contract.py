@@ -5,7 +5,10 @@ on the same GPU along the same path.
 
 Legs: one large square step per dtype (TFLOP/s: 2 flops per real MAC, 8 per complex MAC); one skinny step (effective
 GB/s: operands read once + result written once, against the ~6.3 TB/s an MI355X streams); a sliced Sycamore-53
-amplitude from the finite-width optimizer (wall time, device time, launches per slice, MACs/s).  Engine figures are its
+amplitude from the finite-width optimizer (wall time, device time, launches per slice, MACs/s); P output bitstrings
+of that circuit in one projected call (`--projs`: the 53 output indices sparse, an infinite-memory path from
+optimize(n_projs=P)) against a loop of plain contract() calls over leaves indexed at one bitstring each, along the same
+path.  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device).
 """
@@ -132,6 +135,64 @@ def sycamore(lines, depth, max_width, max_slices):
     print("\n".join(lines[-4:]), flush=True)
 
 
+def projections(lines, depth, counts, loop_max):
+    """P amplitudes per call.  The network: the circuit without its 53 <x| tensors, the open wires its output and
+    sparse indices.  The largest depth <= `depth` whose unsliced plan fits the free device memory at every P is used."""
+    lines.append("")
+    free = torch.cuda.mem_get_info()[0]
+    rng = np.random.RandomState(3)
+    while True:
+        ts, d, _ = syn.sycamore53_tn(depth=depth)
+        ts, out = [tuple(x) for x in ts[:-53]], [x[0] for x in ts[-53:]]
+        tn0 = tnmod.TensorNetwork([tnmod.Tensor(xs, [d] * len(xs)) for xs in ts], output_inds=out, sparse_inds=out)
+        sparse = sorted(out, key=str)
+        arrays = [_rand(tuple(d for _ in xs), np.complex64, rng) for xs in ts]
+        runs = []
+        for P in counts:
+            tn, res = Optimizer(method="sa", seed=0).optimize(tn0, betas=(0, 50), n_steps=200, n_runs=256, n_projs=P,
+                                                              fuse=None, decompose_hyper_inds=False)
+            projs = rng.randint(0, 2, (P, 53))
+            p = ctr.plan(res[0].path, tn.ts_inds, [a.shape for a in arrays], tn.output_inds, dtype=np.complex64,
+                         sparse_inds=sparse, projs=projs)
+            runs.append((P, res[0], projs, p))
+        need = max(p.peak_device_bytes for *_, p in runs)
+        if need <= 0.9 * free or depth <= 2:
+            break
+        lines.append(f"(depth {depth}: the unsliced plan needs {need} bytes, {free} are free: two cycles fewer)")
+        depth -= 2
+    lines.append(f"## P bitstring amplitudes of Sycamore-53, depth {depth}, complex64, in one projected call: {len(ts)} "
+                 f"tensors, 53 sparse output indices, infinite-memory SA per P (256 runs x 200 sweeps); loop: contract() "
+                 f"per bitstring over leaves indexed at it, same path")
+    for P, r0, projs, p in runs:
+        call = lambda: ctr.contract(r0.path, tn0.ts_inds, arrays, out, sparse_inds=sparse, projs=projs)  # noqa: E731
+        r = call()
+        t_p = min(r.device_s, _engine_time(call, reps=2))
+        # the loop a user writes without projections, on min(P, loop_max) bitstrings, scaled linearly to P
+        n_loop = min(P, loop_max)
+        t_l = macs_l = launches_l = 0
+        worst = 0.0
+        for k in range(n_loop):
+            bits = dict(zip(sparse, projs[k]))
+            fixed = [tuple(x for x in xs if x not in bits) for xs in ts]
+            leaves = [a[tuple(bits[x] if x in bits else slice(None) for x in xs)] for a, xs in zip(arrays, ts)]
+            q = ctr.contract(r0.path, fixed, leaves, ())
+            t_l, macs_l, launches_l = t_l + q.device_s, macs_l + q.macs, launches_l + q.launches
+            got, ref = r.array[k], q.array
+            worst = max(worst, float(abs(got - ref) / max(abs(ref), 1e-30)))
+        scale = P / n_loop
+        stream = [op for op in p.ops if not op["folded"] and (op["R"] > 1 or op["a_map"] is not None
+                                                              or op["b_map"] is not None)]
+        lines.append(f"  P = {P}: cost {r0.cost}, projected call device {t_p:.5f} s, MACs {r.macs}, "
+                     f"{r.macs / t_p / 1e9:.1f} GMAC/s, peak device bytes {r.peak_device_bytes}; launches "
+                     f"{dict(zip(ctr.KERNEL_PATHS, r.kernel_launches))} {dict(zip(ctr.ROW_KERNEL_PATHS, r.row_kernel_launches))}"
+                     f" ({len(stream)} steps with rows, most rows {max(op['R'] for op in p.ops if not op['folded'])})")
+        lines.append(f"    loop of contract(): {n_loop} bitstrings measured, device {t_l:.5f} s, {launches_l} launches, MACs "
+                     f"{macs_l}; scaled x{scale:g} to P{' (scaled)' if scale != 1 else ''}: {t_l * scale:.5f} s; "
+                     f"loop / projected = {t_l * scale / t_p:.1f}x; largest relative difference of an amplitude {worst:.2e}")
+    print("\n".join(lines[-1 - 2 * len(runs):]), flush=True)
+    return runs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=str(ROOT / "profiles" / "contract_timing.txt"))
@@ -139,11 +200,20 @@ def main():
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--max-width", type=float, default=14)
     ap.add_argument("--max-slices", type=int, default=4096)
+    ap.add_argument("--projs", action="store_true", help="only the projections leg, appended to --out")
+    ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
+    ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
+    if a.projs:  # (the other legs' sections stay as they are)
+        projections(lines, a.depth, a.counts, a.loop_max)
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines[1:]) + "\n")
+        return
     square(lines, a.n)
     skinny(lines)
     sycamore(lines, a.depth, a.max_width, a.max_slices)
+    projections(lines, a.depth, a.counts, a.loop_max)
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
