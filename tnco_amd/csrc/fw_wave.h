@@ -120,6 +120,17 @@ __device__ __forceinline__ uint32_t fws_rowscan(uint32_t v) {
   v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
   return v;
 }
+// q = x / dv, rem = x % dv of the parallel shuffle's variates, 2 <= dv <= 129 and x < (dv - 1) dv <= 128 * 129: the
+// quotient through a float reciprocal, one step of correction either way.  Compared with integer division over that
+// whole domain on the card by tests/test_gpu_accept.py (tests/csrc/accept_probe.hip).
+__device__ __forceinline__ void fws_divmod(uint32_t x, uint32_t dv, uint32_t& q_out, uint32_t& rem_out) {
+  uint32_t q = (uint32_t)((float)x * __frcp_rn((float)dv));
+  int rem = (int)x - (int)(q * dv);
+  if (rem < 0) { q -= 1u; rem += (int)dv; }
+  else if (rem >= (int)dv) { q += 1u; rem -= (int)dv; }
+  q_out = q;
+  rem_out = (uint32_t)rem;
+}
 
 // ---------------------------------------------------------------------------------------------
 // fw_wave_kernel: the whole re-slice of a replica in one wavefront.  The headers are read once (J nodes per lane,
@@ -550,14 +561,12 @@ static __global__ __launch_bounds__(64) void fw_wave_kernel(const Params P, cons
           if (__any(rej)) {
             fast = false;
           } else {
-            // x < (i0 + 1) (i0 + 2) <= 128 * 129: the quotient through a float reciprocal, one step of correction either way
+            // x < range = (dv - 1) dv, dv = i0 + 2 <= 129 (lane <= 63, base <= 1): the domain of fws_divmod
             const uint32_t x = (uint32_t)(product >> 32), dv = i0 + 2u;
-            uint32_t q = (uint32_t)((float)x * __frcp_rn((float)dv));
-            int rem = (int)x - (int)(q * dv);
-            if (rem < 0) { q -= 1u; rem += (int)dv; }
-            else if (rem >= (int)dv) { q += 1u; rem -= (int)dv; }
+            uint32_t q, rem;
+            fws_divmod(x, dv, q, rem);
             p0 = q;
-            p1 = (uint32_t)rem;
+            p1 = rem;
             rng.advance((uint32_t)nd);
           }
         }

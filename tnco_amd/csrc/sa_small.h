@@ -75,7 +75,8 @@ constexpr int small_replicas_per_cu(int ni) { return (160 * 1024 / small_lds_byt
 static_assert(small_replicas_per_cu(63) == 64 && small_replicas_per_cu(127) == 32, "LDS budget of the small-tree kernel");
 
 // accept_move (sa_sweep.h: same rule, same filter, same margin, same decision) without its early returns: one branch, taken
-// when some replica of the wavefront needs the double-precision pow.
+// when some replica of the wavefront needs the double-precision pow.  tests/test_gpu_accept.py holds the two to each other
+// and to the exact rule element by element; tests/test_accept_model.py reads the constants of both copies.
 __device__ __forceinline__ bool small_accept(int kind, double beta, double delta, double total, double u) {
   const bool yes = kind == 0 || delta <= 0;        // base.hpp; greedy.hpp / mh.hpp: p = 1
   const bool zero = kind == 1 || total == 0;       // greedy.hpp: p = 0; mh.hpp:55-57
@@ -87,6 +88,7 @@ __device__ __forceinline__ bool small_accept(int kind, double beta, double delta
   const bool ok = uf > 1e-30f && xf < 1e30f && fabsf(lp) < 1e30f && beta >= 0.0;
   const bool sure_yes = ok && lu < lp - margin, sure_no = ok && lu > lp + margin;
   bool acc = yes || (zero ? u <= 0.0 : sure_yes);
+  TNCO_ACCEPT_PATH(yes ? 0 : zero ? 1 : sure_yes ? 2 : sure_no ? 3 : 4);
   if (!yes && !zero && !sure_yes && !sure_no) acc = accept_exact(x, beta, u, 0);
   return acc;
 }

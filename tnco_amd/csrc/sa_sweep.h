@@ -214,6 +214,13 @@ struct Rng {
   }
 };
 
+// Which way a decision of accept_move / small_accept went -- 0 early yes, 1 early zero, 2 filter yes, 3 filter no,
+// 4 the exact pow.  Expands to nothing in the product; the test probe (tests/csrc/accept_probe.hip) defines it
+// before it includes this header.
+#ifndef TNCO_ACCEPT_PATH
+#define TNCO_ACCEPT_PATH(p)
+#endif
+
 // The double-precision pow of the Metropolis rule, kept out of line: it is reached with
 // probability ~1e-5 per uphill move and would otherwise dominate the kernel's register budget.
 __device__ __attribute__((noinline)) bool accept_exact(double x, double beta, double u, int f32) {
@@ -231,21 +238,25 @@ __device__ __attribute__((noinline)) bool accept_exact(double x, double beta, do
 //   lu = log2f((float)u), lx = log2f((float)x), lp = -beta * lx.
 //   * rounding u, x to float: relative 2^-24 each -> |d lu|, |d lx| <= 1.4427 * 6.0e-8 = 8.6e-8
 //     absolute (|d log2 t| = |dt / t| * log2 e), hence up to 8.6e-8 * beta on lp;
-//   * v_log_f32: assumed |err| <= 2e-7 + 1.2e-7 * |result| (1 ulp of the result plus an absolute
-//     floor near 1) -- an assumption about the instruction, not a documented bound;
+//   * v_log_f32: |err| <= 2e-7 + 1.2e-7 * |result| (1 ulp of the result plus an absolute floor near 1).
+//     Measured on gfx950 over every float in [1e-30, 1e30], the filter's whole domain: |err| <= 1.191e-7 *
+//     |result| everywhere, <= 5.96e-8 absolute for t in [0.5, 2) -- the absolute floor is not even touched
+//     (tests/test_gpu_accept.py asserts the bound, profiles/accept_probe.md has the figures);
 //   * (float)beta and the product -beta * lx: relative 2^-24 each.
 //   Sum: |lp_true - lp| + |lu_true - lu| <= (|lp| + |lu|) * 2.4e-7 + beta * 2.9e-7 + 2e-7, bounded
 //   by the margin (|lp| + |lu|) * 2e-6 + beta * 3e-7 + 1e-5 used below.
-// Cross-check: a build with -DTNCO_CHECK_ACCEPT evaluates the exact rule next to every filtered
-// decision and traps on a difference (tools/fuzz_gpu.py and the parity tests run clean with it:
-// profiles/r02_accept_check.txt).
+// Checked by tests/test_gpu_accept.py: this function and small_accept (sa_small.h) against the exact rule in
+// high precision on inputs placed around the margin, at p +- a few ulps and at the guards below; that the
+// margin suffices given the bound on the log: tests/test_accept_model.py.  (A build with -DTNCO_CHECK_ACCEPT
+// evaluates the exact rule next to every filtered decision and traps on a difference: random decisions only,
+// last run in round 2, profiles/r02_accept_check.txt.)
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ bool accept_move(int kind, double beta, double delta, double total, double u,
                                             int f32) {
-  if (kind == 0) return true;             // base.hpp: p = 1, u < 1
-  if (delta <= 0) return true;            // greedy.hpp / mh.hpp: p = 1
-  if (kind == 1) return u <= 0.0;         // greedy.hpp: p = 0
-  if (total == 0) return u <= 0.0;        // mh.hpp:55-57
+  if (kind == 0) { TNCO_ACCEPT_PATH(0); return true; }      // base.hpp: p = 1, u < 1
+  if (delta <= 0) { TNCO_ACCEPT_PATH(0); return true; }     // greedy.hpp / mh.hpp: p = 1
+  if (kind == 1) { TNCO_ACCEPT_PATH(1); return u <= 0.0; }  // greedy.hpp: p = 0
+  if (total == 0) { TNCO_ACCEPT_PATH(1); return u <= 0.0; } // mh.hpp:55-57
   const double x = rnd_cost(1.0 + rnd_cost(delta / total, f32), f32);
   const float uf = (float)u, xf = (float)x, bf = (float)beta;
   const float lu = __log2f(uf), lx = __log2f(xf);
@@ -259,10 +270,11 @@ __device__ __forceinline__ bool accept_move(int kind, double beta, double delta,
       return fast;
     }
 #else
-    if (lu < lp - margin) return true;
-    if (lu > lp + margin) return false;
+    if (lu < lp - margin) { TNCO_ACCEPT_PATH(2); return true; }
+    if (lu > lp + margin) { TNCO_ACCEPT_PATH(3); return false; }
 #endif
   }
+  TNCO_ACCEPT_PATH(4);
   return accept_exact(x, beta, u, f32);
 }
 
