@@ -187,6 +187,44 @@ int tnco_hip_get_caches(tnco_hip_handle h, int64_t replica, double* ccost, doubl
  * of them or -1. */
 int tnco_hip_validate(tnco_hip_handle h, double atol, int64_t* n_bad, int64_t* first_bad);
 
+/* Diagnostics (no reference counterpart; the tests of tnco_hip_validate damage a replica with it and restore it): one
+ * field of one replica is read and, when write != 0, replaced -- from the host (the handle is synchronised, the bytes
+ * are copied; no kernel), at the address the getters above decode.  *previous (may be NULL) receives the value the
+ * field held.  Costs travel as the bits of a double, mask words as they are, node ids and jmin as integers; a cached
+ * width as the bits of a double whatever the width type (a float32 width is converted both ways).
+ *   field                          node            word      value
+ *   PARENT                         any node        -         an INTERNAL node id (n_leaves <= value < N; -1 at the root)
+ *   SWAP_CHILDREN                  internal        -         -  (the left and right link words change places; previous = 0)
+ *   LEGS                           internal        < W       mask word
+ *   CCOST, PARTIAL                 internal        -         cost      (unified and split layouts)
+ *   PARTIAL_LEFT, PARTIAL_RIGHT    internal        -         cost      (child-partial layout)
+ *   TOTAL                          -               -         cost      (child-partial layout: the root's partial cost)
+ *   MIN_COST                       -               -         cost      (min_total_cost)
+ *   JMIN                           -               -         length of the journal prefix that makes the best tree
+ *   SLICES, MIN_SLICES             -               < W       mask word (finite width)
+ *   WIDTH                          internal        -         width     (finite width: the cached width of the node)
+ * EINVAL, and nothing written, for: an index out of range; a field the handle's layout does not store (CCOST / PARTIAL
+ * under child partials, PARTIAL_LEFT / PARTIAL_RIGHT / TOTAL elsewhere, SLICES / MIN_SLICES / WIDTH without max_width);
+ * and every value that would let tnco_hip_validate's kernels walk off a tree -- they trust the child links while they
+ * traverse.  So child links change only by SWAP_CHILDREN (still a binary tree), a parent is an existing internal node,
+ * and JMIN stays within the rotations the journal holds (any prefix of them is a sequence of legal rotations from the
+ * checkpoint: a test lowers it and puts the old value back). */
+#define TNCO_HIP_POKE_PARENT 0
+#define TNCO_HIP_POKE_SWAP_CHILDREN 1
+#define TNCO_HIP_POKE_LEGS 2
+#define TNCO_HIP_POKE_CCOST 3
+#define TNCO_HIP_POKE_PARTIAL 4
+#define TNCO_HIP_POKE_PARTIAL_LEFT 5
+#define TNCO_HIP_POKE_PARTIAL_RIGHT 6
+#define TNCO_HIP_POKE_TOTAL 7
+#define TNCO_HIP_POKE_MIN_COST 8
+#define TNCO_HIP_POKE_JMIN 9
+#define TNCO_HIP_POKE_SLICES 10
+#define TNCO_HIP_POKE_MIN_SLICES 11
+#define TNCO_HIP_POKE_WIDTH 12
+int tnco_hip_diag_poke(tnco_hip_handle h, int64_t replica, int field, int64_t node, int64_t word, int write,
+                       uint64_t value, uint64_t* previous);
+
 /* prng_state property / string-seed constructor (optimize/optimizer.hpp:68-71,
  * 191-195): 624 state words followed by the position, exactly the numbers
  * `oss << std::mt19937` prints. */

@@ -20,6 +20,7 @@ def test_library_exports_every_declared_symbol():
     for name in names:
         assert hasattr(lib, name), f"libtnco_hip.so does not export {name}"
     assert sorted(_lib.EXPORTS) == names
+    assert "tnco_hip_diag_poke" in names
     assert lib.tnco_hip_version().startswith(b"tnco_hip")
 
 
@@ -51,6 +52,7 @@ def test_error_reporting_without_gpu():
     assert lib.tnco_hip_create(None, ctypes.byref(h)) == _lib.EINVAL
     assert b"null" in lib.tnco_hip_last_error()
     assert lib.tnco_hip_sync(None) == _lib.EINVAL
+    assert lib.tnco_hip_diag_poke(None, 0, 0, 0, 0, 0, 0, None) == _lib.EINVAL
     d = _lib.Desc()
     d.n_leaves, d.n_replicas = 1, 1
     assert lib.tnco_hip_create(ctypes.byref(d), ctypes.byref(h)) == _lib.EINVAL

@@ -79,7 +79,7 @@ class ContractDesc(C.Structure):
 
 EXPORTS = [
     "tnco_hip_create", "tnco_hip_run", "tnco_hip_run_fw", "tnco_hip_get_slices", "tnco_hip_get_slices_many", "tnco_hip_diag_reslice_info", "tnco_hip_diag_fw_stats", "tnco_hip_sync", "tnco_hip_get_costs", "tnco_hip_get_tree",
-    "tnco_hip_get_caches", "tnco_hip_validate", "tnco_hip_get_prng", "tnco_hip_set_prng", "tnco_hip_get_prng_many", "tnco_hip_set_prng_many",
+    "tnco_hip_get_caches", "tnco_hip_validate", "tnco_hip_diag_poke", "tnco_hip_get_prng", "tnco_hip_set_prng", "tnco_hip_get_prng_many", "tnco_hip_set_prng_many",
     "tnco_hip_best", "tnco_hip_min_cost_device", "tnco_hip_get_trees", "tnco_hip_linear_paths", "tnco_hip_linear_paths_ssa", "tnco_hip_diag_counters", "tnco_hip_diag_moves", "tnco_hip_diag_full_copies",
     "tnco_hip_diag_kernel_time", "tnco_hip_diag_kernel_times", "tnco_hip_diag_stage_cycles",
     "tnco_hip_diag_launch_groups", "tnco_hip_diag_device_bytes", "tnco_hip_set_stream", "tnco_hip_destroy", "tnco_hip_release_cached", "tnco_hip_diag_cached_bytes", "tnco_hip_random_trees", "tnco_hip_greedy_trees",
@@ -141,6 +141,7 @@ def load() -> C.CDLL:
     L.tnco_hip_get_tree.argtypes = [vp, i64, C.c_int, vp, vp, vp, vp]
     L.tnco_hip_get_caches.argtypes = [vp, i64, vp, vp, vp]
     L.tnco_hip_validate.argtypes = [vp, dbl, C.POINTER(i64), C.POINTER(i64)]
+    L.tnco_hip_diag_poke.argtypes = [vp, i64, C.c_int, i64, i64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
     L.tnco_hip_get_prng.argtypes = [vp, i64, vp]
     L.tnco_hip_set_prng.argtypes = [vp, i64, vp]
     L.tnco_hip_get_prng_many.argtypes = [vp, i64, vp, vp]

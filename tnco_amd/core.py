@@ -420,6 +420,30 @@ class BatchedOptimizer:
     def is_valid(self, atol: float = 1e-5) -> bool:
         return self.validate(atol)[0] == 0
 
+    _POKE_FIELDS = {"parent": 0, "swap_children": 1, "legs": 2, "ccost": 3, "partial": 4, "partial_left": 5,
+                    "partial_right": 6, "total": 7, "min_cost": 8, "jmin": 9, "slices": 10, "min_slices": 11, "width": 12}
+    _POKE_FLOATS = ("ccost", "partial", "partial_left", "partial_right", "total", "min_cost", "width")
+
+    def _poke(self, replica: int, field: str, value=None, *, node: int = 0, word: int = 0):
+        """Diagnostics, for the tests of validate() (tnco_hip_diag_poke): one field of one replica is replaced from the
+        host and its previous value returned (costs and widths as float, the rest as int); value None only reads.
+        "swap_children" takes no value and returns 0.  ValueError, nothing written, for a field the layout does not
+        store and for anything that would take a kernel off the tree (see include/tnco_hip.h)."""
+        code = self._POKE_FIELDS[field]
+        is_float = field in self._POKE_FLOATS
+        write = value is not None or field == "swap_children"
+        raw = 0
+        if value is not None:
+            raw = int(np.float64(value).view(np.uint64)) if is_float else int(value) & 0xFFFFFFFFFFFFFFFF
+        prev = C.c_uint64(0)
+        _lib.check(self._L.tnco_hip_diag_poke(self._h, int(replica), code, int(node), int(word), int(write), raw,
+                                              C.byref(prev)))
+        if is_float:
+            return float(np.uint64(prev.value).view(np.float64))
+        if field in ("parent", "jmin"):
+            return int(np.uint64(prev.value).view(np.int64))
+        return int(prev.value)
+
     def prng_state(self, replica: int) -> np.ndarray:
         out = np.empty(625, np.uint32)
         _lib.check(self._L.tnco_hip_get_prng(self._h, int(replica), _ptr(out)))

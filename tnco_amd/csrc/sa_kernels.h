@@ -788,7 +788,11 @@ __global__ __launch_bounds__(256) void compare_kernel(const Params P, const Buil
     return fabs(log(x) - log(y)) <= atol;
   };
   for (int i = lig; i < N; i += L) {
+    // (validate() builds `ref` from the live links, parent words included: this comparison cannot fire there -- it is for
+    //  a `ref` built from other links; a wrong parent word is found from the parent's side below and at the root)
     if (ref.parent(i) != cur.parent(i)) bad = bad ? bad : 2;
+    // (every other node's parent is checked from its parent's side below; nobody names the root as a child)
+    if (i == N - 1 && cur.parent(i) != -1) bad = bad ? bad : 3;  // tree.hpp:73-76 "Last node should be root."
     if (i >= n) {
       const NodeRec x = *ref.hdr(i), y = *cur.hdr(i);
       if (!logclose(x.ccost, y.ccost)) bad = bad ? bad : (P.cpl ? 32 : 31);  // (child-partial layout: pleft, pright)

@@ -1702,6 +1702,133 @@ int tnco_hip_validate(tnco_hip_handle h, double atol, int64_t* n_bad, int64_t* f
   return TNCO_HIP_OK;
 }
 
+// One field of one replica read and, with `write`, replaced from the host (the tests of tnco_hip_validate).  The
+// addresses are those the getters above decode: node headers BS bytes apart, legs at WOFF + WS per node, leaf parents
+// LPS words apart, slices / min_slices LK words each.  What the validator's kernels walk stays walkable: child links only
+// change places, a parent is an internal node, jmin stays inside the journal -- see the header.
+int tnco_hip_diag_poke(tnco_hip_handle h, int64_t r, int field, int64_t node, int64_t word, int write, uint64_t value,
+                       uint64_t* previous) {
+  if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
+  const Params& P = h->P;
+  const int64_t n = P.n, N = P.N, W = P.W, LK = (int64_t)h->L * h->K;
+  if (r < 0 || r >= P.R) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
+  const bool internal = node >= n && node < N;
+  uint8_t* hdr = internal ? P.blocks + r * P.RB + (node - n) * (int64_t)P.BS : nullptr;
+  ReplicaState* rs = P.rs + r;
+  uint8_t* at = nullptr;  // the field's device address
+  size_t nb = 8;          // ... and its size
+  bool as_float = false;  // a float32 field: `value` / `previous` are the bits of the double of the same value
+  switch (field) {
+    case TNCO_HIP_POKE_PARENT:
+      if (node < 0 || node >= N) return fail(TNCO_HIP_EINVAL, "'node' out of range.");
+      at = internal ? hdr + offsetof(NodeRec, parent) : reinterpret_cast<uint8_t*>(P.lpar + r * n * LPS + node * LPS);
+      nb = 4;
+      // (the root's own null parent is what a test puts back there)
+      if (write && !((int64_t)value >= n && (int64_t)value < N) && !(node == N - 1 && (int64_t)value == -1))
+        return fail(TNCO_HIP_EINVAL, "a parent must be an internal node.");
+      break;
+    case TNCO_HIP_POKE_SWAP_CHILDREN:
+      if (!internal) return fail(TNCO_HIP_EINVAL, "'node' is not an internal node.");
+      at = hdr + offsetof(NodeRec, left);
+      break;
+    case TNCO_HIP_POKE_LEGS:
+      if (!internal) return fail(TNCO_HIP_EINVAL, "'node' is not an internal node.");
+      if (word < 0 || word >= W) return fail(TNCO_HIP_EINVAL, "'word' out of range.");
+      at = P.blocks + r * P.RB + P.WOFF + (node - n) * (int64_t)P.WS + word * 8;
+      break;
+    case TNCO_HIP_POKE_CCOST:
+    case TNCO_HIP_POKE_PARTIAL:
+      if (P.cpl) return fail(TNCO_HIP_EINVAL, "the child-partial layout stores neither 'ccost' nor 'partial' of a node.");
+      if (!internal) return fail(TNCO_HIP_EINVAL, "'node' is not an internal node.");
+      at = hdr + (field == TNCO_HIP_POKE_CCOST ? offsetof(NodeRec, ccost) : offsetof(NodeRec, partial));
+      break;
+    case TNCO_HIP_POKE_PARTIAL_LEFT:
+    case TNCO_HIP_POKE_PARTIAL_RIGHT:
+      if (!P.cpl) return fail(TNCO_HIP_EINVAL, "only the child-partial layout stores the partial costs of a node's children.");
+      if (!internal) return fail(TNCO_HIP_EINVAL, "'node' is not an internal node.");
+      at = hdr + (field == TNCO_HIP_POKE_PARTIAL_LEFT ? offsetof(NodeRec, pleft) : offsetof(NodeRec, pright));
+      break;
+    case TNCO_HIP_POKE_TOTAL:
+      if (!P.cpl) return fail(TNCO_HIP_EINVAL, "only the child-partial layout keeps the root's partial cost in the replica record.");
+      at = reinterpret_cast<uint8_t*>(rs) + offsetof(ReplicaState, total);
+      break;
+    case TNCO_HIP_POKE_MIN_COST:
+      at = reinterpret_cast<uint8_t*>(rs) + offsetof(ReplicaState, min_cost);
+      break;
+    case TNCO_HIP_POKE_JMIN:
+      at = reinterpret_cast<uint8_t*>(rs) + offsetof(ReplicaState, jmin);
+      nb = 4;
+      break;
+    case TNCO_HIP_POKE_SLICES:
+    case TNCO_HIP_POKE_MIN_SLICES:
+      if (!h->fw) return fail(TNCO_HIP_EINVAL, "handle was created without 'max_width'.");
+      if (word < 0 || word >= W) return fail(TNCO_HIP_EINVAL, "'word' out of range.");
+      at = reinterpret_cast<uint8_t*>(h->F.slices + r * 2 * LK + (field == TNCO_HIP_POKE_MIN_SLICES ? LK : 0) + word);
+      break;
+    case TNCO_HIP_POKE_WIDTH:
+      if (!h->fw) return fail(TNCO_HIP_EINVAL, "handle was created without 'max_width'.");
+      if (!internal) return fail(TNCO_HIP_EINVAL, "'node' is not an internal node.");
+      if (h->F.width_f32) {
+        at = hdr + offsetof(NodeRec, pad);
+        nb = 4;
+        as_float = true;
+      } else {
+        at = reinterpret_cast<uint8_t*>(h->F.width64 + r * N + node);
+      }
+      break;
+    default:
+      return fail(TNCO_HIP_EINVAL, "unknown 'field'.");
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(h->sync_all());
+  uint64_t old = 0;
+  if (field == TNCO_HIP_POKE_SWAP_CHILDREN) {
+    if (write) {
+      int32_t lr[2];
+      HIP_TRY(hipMemcpy(lr, at, 8, hipMemcpyDeviceToHost));
+      std::swap(lr[0], lr[1]);
+      HIP_TRY(hipMemcpy(at, lr, 8, hipMemcpyHostToDevice));
+    }
+    if (previous) *previous = 0;
+    return TNCO_HIP_OK;
+  }
+  if (nb == 4) {
+    uint32_t x = 0;
+    HIP_TRY(hipMemcpy(&x, at, 4, hipMemcpyDeviceToHost));
+    if (as_float) {
+      float f;
+      std::memcpy(&f, &x, 4);
+      const double d = (double)f;
+      std::memcpy(&old, &d, 8);
+    } else {
+      old = (uint64_t)(int64_t)(int32_t)x;  // (a parent: -1 at the root)
+    }
+  } else {
+    HIP_TRY(hipMemcpy(&old, at, 8, hipMemcpyDeviceToHost));
+  }
+  if (write) {
+    if (field == TNCO_HIP_POKE_JMIN) {  // every prefix of the journal's jtail entries is a sequence of legal rotations
+      uint32_t jtail = 0;
+      HIP_TRY(hipMemcpy(&jtail, reinterpret_cast<uint8_t*>(rs) + offsetof(ReplicaState, jtail), 4, hipMemcpyDeviceToHost));
+      if (value > (uint64_t)jtail) return fail(TNCO_HIP_EINVAL, "'jmin' beyond the rotations the journal holds.");
+    }
+    if (nb == 4) {
+      uint32_t x = (uint32_t)value;
+      if (as_float) {
+        double d;
+        std::memcpy(&d, &value, 8);
+        const float f = (float)d;
+        std::memcpy(&x, &f, 4);
+      }
+      HIP_TRY(hipMemcpy(at, &x, 4, hipMemcpyHostToDevice));
+    } else {
+      HIP_TRY(hipMemcpy(at, &value, 8, hipMemcpyHostToDevice));
+    }
+  }
+  if (previous) *previous = old;
+  return TNCO_HIP_OK;
+}
+
 int tnco_hip_get_prng(tnco_hip_handle h, int64_t r, uint32_t* out) {
   if (!h || !out) return fail(TNCO_HIP_EINVAL, "null argument.");
   if (r < 0 || r >= h->P.R) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
