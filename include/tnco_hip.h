@@ -419,10 +419,18 @@ const char* tnco_hip_comm_last_error(void);
  *                                      Operands are dense [rows][h] batches, C dense [r][h][m][n].
  *   row_maps  [n_row_maps] int32       the pool of the maps.
  * row_steps == NULL (and n_row_maps == 0): no step has a row axis; a row of (1, 1, -1, 1, -1) says the same of one step.
+ *
+ * Storage mode, dtype codes 4..7: leaves and arena hold 16-bit values, every step sums in float32 and rounds once, to
+ * nearest even, when it stores to the arena; the output is float32 / complex64 (beta and block placement in float32):
+ *   4 float16 -> float32;  5 float16 pairs (re, im) -> complex64;  6 bfloat16 -> float32;  7 bfloat16 pairs -> complex64.
+ * The leaves passed to tnco_hip_contract_run are in storage layout, `out` is float32 / complex64; arena_elems, leaf_numel
+ * and every offset of the tables count storage elements (a pair is one element).  row_steps must be NULL (EINVAL).  No
+ * scaling: a sum beyond the storage type's range is stored as inf.  The launch slots keep their meaning (shape class and
+ * operand layout of the step); the four tiled slots then count launches of the MFMA kernel.
  */
 typedef struct tnco_hip_contract_s* tnco_hip_contract;
 typedef struct tnco_hip_contract_desc {
-  int32_t dtype;            /* 0 float32, 1 float64, 2 complex64, 3 complex128 (interleaved) */
+  int32_t dtype;            /* 0 float32, 1 float64, 2 complex64, 3 complex128 (interleaved); 4..7: storage mode, above */
   int32_t device;
   int64_t max_axes;         /* must be 32 */
   int64_t n_leaves;

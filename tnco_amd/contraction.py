@@ -20,6 +20,12 @@ Z[sparse_inds = projs[p]].  A tensor that holds the subset T of the sparse indic
 axes], a row per distinct row of projs[:, T] (numpy.unique(axis=0) order, columns in sparse_inds order): at most
 min(prod dims(T), P) rows, the factor of the sparse cost model.  A step Z = X Y has T_z = T_x | T_y, and two int32 maps
 give the rows of X and of Y that each row of Z restricts to; the leaves are restricted to their rows on the host.
+
+Storage mode: with `storage="float16"` or `"bfloat16"` (float32 / complex64 arrays only) the leaves are rounded to that
+type on the host, to nearest even, and every intermediate is rounded once when a step stores it; every step sums in
+float32, the big steps on the matrix cores, and the output, the sum over slice assignments included, stays float32 /
+complex64.  Leaves and intermediates take half the device memory.  There is no scaling: an intermediate beyond the
+storage type's range becomes inf or 0.  Projections are not supported with it.
 """
 from __future__ import annotations
 
@@ -32,10 +38,14 @@ import numpy as np
 from .app import tn as tnmod
 
 __all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
-           "ROW_KERNEL_PATHS"]
+           "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
+
+# storage mode: leaves and intermediates in a 16-bit type, sums and the output in float32 / complex64.  The dtype code
+# of include/tnco_hip.h is STORAGES[name] + (1 when complex)
+STORAGES = {"float16": 4, "bfloat16": 6}
 
 # operand / destination kinds and table widths: include/tnco_hip.h (tnco_hip_contract_desc)
 LEAF, ARENA, OUT = 0, 1, 2
@@ -86,6 +96,7 @@ class Plan:
     ops: list = field(default_factory=list)  # readable copy of the step decisions (tests, tools)
     # projections (None / empty without `projs`)
     sparse_inds: tuple = ()
+    storage: str = None  # "float16" / "bfloat16": the type of leaves and arena on the device (dtype: sums, output)
     row_steps: np.ndarray = None  # [n_steps, ROW_W]
     row_maps: np.ndarray = None  # int32 pool of the maps
     leaf_rows: tuple = ()  # per leaf: None, or (axes of its sparse indices, their values [rows, len(axes)])
@@ -102,9 +113,10 @@ class Plan:
     @property
     def peak_device_bytes(self) -> int:
         item = self.dtype.itemsize
+        held = item if self.storage is None else _storage_itemsize(self.dtype)  # of leaves and arena
         tables = 8 * (self.leaf_sl.size + self.perms.size + 2 * self.leaf_numel.size)
         maps = 0 if self.row_maps is None else 4 * self.row_maps.size + 8 * self.row_steps.size
-        return item * (int(self.leaf_numel.sum()) + self.arena_elems + self.out_numel) + tables + maps
+        return held * (int(self.leaf_numel.sum()) + self.arena_elems) + item * self.out_numel + tables + maps
 
 
 class _Arena:
@@ -172,6 +184,65 @@ def _compute_dtype(arrays) -> np.dtype:
     return np.result_type(*arrays) if arrays else np.dtype(np.float64)
 
 
+def _storage_itemsize(dtype) -> int:
+    return 4 if np.dtype(dtype).kind == "c" else 2
+
+
+def _check_storage(storage, dtype, projs=None) -> None:
+    if storage is None:
+        return
+    if storage not in STORAGES:
+        raise ValueError(f"'storage' must be None, {' or '.join(repr(s) for s in STORAGES)}.")
+    if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.complex64)):
+        raise TypeError(f"with 'storage' the compute dtype must be float32 or complex64, not {np.dtype(dtype)}.")
+    if projs is not None:
+        raise NotImplementedError("projections are not supported with 'storage'.")
+
+
+def _bf16_bits(x) -> np.ndarray:
+    """The bfloat16 nearest to each float32 of x, ties to even, as uint16; NaN stays NaN (quiet), what lies beyond the
+    largest bfloat16 becomes inf."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    nan = (u & 0x7FFFFFFF) > 0x7F800000
+    r = (u + 0x7FFF + ((u >> 16) & 1)) >> 16
+    return np.where(nan, (u >> 16) | 0x40, r).astype(np.uint16)
+
+
+def _storage_bits(a, storage, check=True) -> np.ndarray:
+    """A float32 / complex64 array in storage layout: uint16 of the same shape (complex: one more axis of 2, re and
+    im).  ValueError when a finite value is not finite in the storage type; with check=False it becomes inf, as an
+    intermediate does on the device."""
+    a = np.ascontiguousarray(a)
+    parts = a.reshape(-1).view(np.float32).reshape(a.shape + (2,)) if a.dtype.kind == "c" else a.astype(np.float32, copy=False)
+    if storage == "float16":
+        with np.errstate(over="ignore"):
+            half = parts.astype(np.float16)
+        bits, finite = half.view(np.uint16), np.isfinite(half)
+    else:
+        bits = _bf16_bits(parts).reshape(parts.shape)
+        finite = (bits & 0x7F80) != 0x7F80
+    if check and (np.isfinite(parts) & ~finite).any():
+        raise ValueError(f"an array has finite values beyond the range of {storage}.")
+    return bits
+
+
+def round_to_storage(a, storage) -> np.ndarray:
+    """`a` (float32 / complex64) with every part rounded to `storage` as the engine rounds a leaf: same dtype and
+    shape.  ValueError as the engine raises it."""
+    a = np.asarray(a)
+    _check_storage(storage, a.dtype)
+    return _from_storage_bits(_storage_bits(a, storage), storage, a)
+
+
+def _from_storage_bits(bits, storage, like) -> np.ndarray:
+    """The values of _storage_bits, widened: the dtype and shape of `like`."""
+    if storage == "float16":
+        parts = bits.view(np.float16).astype(np.float32)
+    else:
+        parts = (bits.astype(np.uint32) << 16).view(np.float32)
+    return parts.view(np.complex64).reshape(like.shape) if like.dtype.kind == "c" else parts.reshape(like.shape)
+
+
 def _fits(layout, head, rest, s_order, s_first) -> bool:
     """layout == head + s_order + rest (s_first) or head + rest + s_order, `rest` in the layout's own order."""
     body = tuple(layout[len(head):])
@@ -235,9 +306,10 @@ def _unique_rows(table):
 
 
 def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
-         sparse_inds=(), projs=None) -> Plan:
+         sparse_inds=(), projs=None, storage=None) -> Plan:
     """The device plan of one contraction along a path that leaves one tensor (no GPU).
-    `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`: see the module docstring."""
+    `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`: see the module docstring."""
+    _check_storage(storage, dtype, projs)
     ts_inds = [tuple(xs) for xs in ts_inds]
     shapes = [tuple(int(d) for d in s) for s in shapes]
     dims = _dims_of(ts_inds, shapes)
@@ -431,7 +503,7 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     p = Plan(dtype=np.dtype(dtype), inds=final, shape=tuple(dims[x] for x in final), slice_inds=slice_inds,
              slice_dims=slice_dims, block_inds=tuple(x for x in slice_inds if x in final), leaf_numel=leaf_numel,
              leaf_sl=leaf_sl, perms=perm_tab, steps=step_tab, arena_elems=arena.peak, out_numel=size(final),
-             macs_per_slice=macs, slice_range=(lo, hi), ops=ops)
+             macs_per_slice=macs, slice_range=(lo, hi), ops=ops, storage=storage)
     if projs is None:
         return p
     # the device holds the distinct rows of the final tensor; the result has one per projection, duplicates included
@@ -492,32 +564,38 @@ def _sub_output(ts_inds, leaves, output) -> frozenset:
 
 
 def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=None, device=None,
-             sparse_inds=(), projs=None) -> ContractionResult:
+             sparse_inds=(), projs=None, storage=None, _intermediates=()) -> ContractionResult:
     """Contract `arrays` (numpy, in ts_inds order) along the linear `path` on the GPU; see the module docstring.
     A path that leaves several tensors gives lists in `inds` / `array` (the sliced and the projected form need one
-    tensor)."""
+    tensor).  `_intermediates` (contract_results): positions of arrays that are results of earlier storage-mode calls,
+    not leaves of the user: a value of theirs beyond the storage range becomes inf instead of being refused."""
+    loose = frozenset(_intermediates)
     ts_inds = [tuple(xs) for xs in ts_inds]
     arrays = [np.asarray(a) for a in arrays]
     dims = _dims_of(ts_inds, [a.shape for a in arrays])
     dtype = _compute_dtype(arrays)
+    _check_storage(storage, dtype, projs)
     steps = _check_path(path, len(ts_inds))
     final, out = tnmod.contract(steps, ts_inds, output_inds, dims)
     if len(final) == 1:
         p = plan(steps, ts_inds, [a.shape for a in arrays], out, slices=slices, slice_range=slice_range, dtype=dtype,
-                 sparse_inds=sparse_inds, projs=projs)
-        return _run(p, arrays, device)
+                 sparse_inds=sparse_inds, projs=projs, storage=storage)
+        return _run(p, arrays, device, loose)
     if slices:
         raise NotImplementedError("slices need a path that leaves one tensor.")
     if projs is not None or tuple(sparse_inds):
         raise NotImplementedError("projections need a path that leaves one tensor.")
     parts = []
     for leaves, sub in _split(steps, len(ts_inds)):
-        if not sub:
+        if not sub:  # a tensor the path does not touch: as the single-leaf plan gives it, rounded to storage
             a = arrays[leaves[0]].astype(dtype, copy=True)
+            if storage is not None:
+                a = _from_storage_bits(_storage_bits(a, storage, leaves[0] not in loose), storage, a)
             parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0))
             continue
         parts.append(contract(sub, [ts_inds[t] for t in leaves], [arrays[t].astype(dtype, copy=False) for t in leaves],
-                              _sub_output(ts_inds, leaves, out), device=device))
+                              _sub_output(ts_inds, leaves, out), device=device, storage=storage,
+                              _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
     assert [tuple(r.inds) for r in parts] == [tuple(f) for f in final]
     return ContractionResult([r.inds for r in parts], [r.array for r in parts], sum(r.macs for r in parts), 1,
                              max(r.peak_device_bytes for r in parts), sum(r.launches for r in parts),
@@ -529,11 +607,13 @@ def _add_counts(*counts) -> tuple:
     return tuple(sum(c) for c in zip(*counts))
 
 
-def _run(p: Plan, arrays, device) -> ContractionResult:
+def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
     from . import _lib, parallel
+    leaves = [np.ascontiguousarray(a, dtype=p.dtype) for a in arrays]
+    if p.storage is not None:  # (before the device is touched: a leaf beyond the storage type's range is refused)
+        leaves = [_storage_bits(a, p.storage, t not in loose) for t, a in enumerate(leaves)]
     L = _lib.load()
     device = parallel.local_device() if device is None else int(device)
-    leaves = [np.ascontiguousarray(a, dtype=p.dtype) for a in arrays]
     for t, rows in enumerate(p.leaf_rows):
         if rows is not None:  # [rows][the other axes]: the leaf at the distinct projections of its sparse indices
             axes, values = rows
@@ -544,7 +624,8 @@ def _run(p: Plan, arrays, device) -> ContractionResult:
                 slice_dims=np.array(p.slice_dims, np.int64).reshape(-1),
                 block=np.array([p.slice_inds.index(x) for x in p.block_inds], np.int64).reshape(-1))
     d = _lib.ContractDesc()
-    d.dtype, d.device, d.max_axes = DTYPES[p.dtype], device, MAX_AXES
+    code = DTYPES[p.dtype] if p.storage is None else STORAGES[p.storage] + (p.dtype.kind == "c")
+    d.dtype, d.device, d.max_axes = code, device, MAX_AXES
     d.n_leaves, d.leaf_numel, d.leaf_sl = len(leaves), i64p(keep["leaf_numel"]), i64p(keep["leaf_sl"])
     d.n_perms, d.perms = len(p.perms), i64p(keep["perms"])
     d.n_steps, d.steps = len(p.steps), i64p(keep["steps"])
@@ -592,7 +673,8 @@ def _host_layout(p: Plan, staging) -> np.ndarray:
     return array.take(row_of_proj, axis=0)
 
 
-def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse_inds=None) -> ContractionResult:
+def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse_inds=None,
+                     storage=None) -> ContractionResult:
     """Run a result of `Optimizer.optimize` over the arrays of the network as given.
 
     tn0: the network before pre-fusing (`load_tn(obj, fuse=None)`); arrays: in tn0.tensors order, or {name: array}
@@ -602,7 +684,11 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
 
     A network with sparse indices needs `projs`, [P, number of sparse indices]: the result is then taken at those
     assignments of the sparse indices (axes ("proj",) + the others).  The columns are the sparse indices in
-    `sorted(tn.sparse_inds, key=str)` order, or in the order of `sparse_inds` when that is given."""
+    `sorted(tn.sparse_inds, key=str)` order, or in the order of `sparse_inds` when that is given.
+
+    storage: "float16" / "bfloat16" runs `result.path` in storage mode (module docstring); the fuse stage, unsliced and
+    small, stays in the arrays' own precision."""
+    _check_storage(storage, np.float32, projs)
     if (tn0.sparse_inds or tn.sparse_inds) and projs is None:
         raise NotImplementedError("sparse indices (n_projs) have an array meaning only at given projections: "
                                   "pass projs=, an integer array [P, number of sparse indices].")
@@ -621,6 +707,7 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         except KeyError as e:
             raise ValueError("'ts_inds' is not consistent with 'arrays'.") from e
     arrays = [np.asarray(a) for a in arrays]
+    _check_storage(storage, _compute_dtype(arrays))
     fuse_macs = 0
     if tn.tags.get("fuse_path"):
         fused = contract(tn.tags["fuse_path"], tn0.ts_inds, arrays, tn0.output_inds, device=device)
@@ -633,7 +720,7 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     comp_paths = [list(q) for q in getattr(result, "disconnected_paths", ()) if q]
     if len(comp_paths) <= 1:  # one component to contract: the path with its slices, in one call
         r = contract(result.path, tn.ts_inds, arrays, tn.output_inds, slices=getattr(result, "slices", ()),
-                     device=device, sparse_inds=sparse_inds or (), projs=projs)
+                     device=device, sparse_inds=sparse_inds or (), projs=projs, storage=storage)
         return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
                                  fuse_macs, r.kernel_launches, r.row_kernel_launches)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
@@ -647,7 +734,7 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         n_comp_steps += len(q)
         (leaves, sub), = [(lv, s) for lv, s in _split(_check_path(q, n), n) if s]
         r = contract(sub, [ts[t] for t in leaves], [arrays[t] for t in leaves], _sub_output(ts, leaves, tn.output_inds),
-                     slices=cut, device=device)
+                     slices=cut, device=device, storage=storage)
         done |= set(leaves)
         results.append(r)
         macs, n_slices, launches = macs + r.macs, n_slices + r.n_slices, launches + r.launches
@@ -661,7 +748,8 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     tail = result.path[n_comp_steps:]
     if tail:
         r = contract(tail, state_inds, state_arrays, frozenset(tn.output_inds) & {x for xs in state_inds for x in xs},
-                     device=device)
+                     device=device, storage=storage,
+                     _intermediates=range(len(state_arrays) - len(results), len(state_arrays)))
         macs, launches, peak = macs + r.macs, launches + r.launches, max(peak, r.peak_device_bytes)
         device_s += r.device_s
         by_kernel = _add_counts(by_kernel, r.kernel_launches)

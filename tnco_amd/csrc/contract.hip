@@ -10,6 +10,9 @@
 //                          the same three with a row axis outermost (the distinct projections of the sparse indices a
 //                          tensor holds): Z[r][h] = X[a_map[r]][h] Y[b_map[r]][h], the operand rows taken through int32
 //                          maps (tnco_hip.h, row_steps).  Steps without a row axis do not come here.
+// Storage mode (dtype codes 4..7, contract_half.h): leaves and intermediates in float16 / bfloat16, sums in float32; its
+// tiled class runs on the matrix cores (ct_mfma_tiled_kernel), dot, stream and gather are the bodies below with a
+// widening load.  Steps with a row axis do not come there.
 // No atomics: every sum runs in one fixed order, so a run is bit-reproducible.
 #include "../../include/tnco_hip.h"
 
@@ -20,6 +23,7 @@
 #include <cstring>
 #include <iterator>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace tnco {
@@ -70,6 +74,23 @@ __device__ inline cplx<R> ct_add(cplx<R> a, cplx<R> b) { return cplx<R>{a.re + b
 template <class T>
 __device__ inline T ct_zero() { return ct_zero((T*)nullptr); }
 
+// the type an element is summed in: itself; contract_half.h adds the 16-bit storage types, summed in float32, and their
+// ct_widen
+template <class E>
+struct ct_acc {
+  using type = E;
+};
+template <class E>
+using ct_acc_t = typename ct_acc<E>::type;
+
+#include "contract_half.h"
+
+template <class E>
+__device__ inline ct_acc_t<E> ct_load(const E* p) {
+  if constexpr (std::is_same<ct_acc_t<E>, E>::value) return *p;
+  else return ct_widen(*p);
+}
+
 struct GatherArgs {
   const int64_t* rows;         // the rows of this launch
   const int64_t* leaf_sl;      // [n_leaves][LEAF_SL_W]
@@ -82,12 +103,13 @@ struct GatherArgs {
   int64_t out_off;  // its block of the output
 };
 
-template <class T>
-__global__ __launch_bounds__(256) void ct_gather_kernel(GatherArgs g) {
+// D: the element as it is written, SI: as it is read (another type only where storage is widened into the output)
+template <class D, class SI>
+__device__ inline void ct_gather_body(const GatherArgs& g) {
   const int64_t* row = g.rows + (int64_t)blockIdx.y * PERM_W;
   const int64_t numel = row[5];
   const int nd = (int)row[4];
-  const T* src;
+  const SI* src;
   int64_t base = 0;
   if (row[0] == K_LEAF) {
     const int64_t* ls = g.leaf_sl + row[1] * LEAF_SL_W;
@@ -95,11 +117,11 @@ __global__ __launch_bounds__(256) void ct_gather_kernel(GatherArgs g) {
       const int64_t s = ls[1 + j];
       base += ((g.sid / g.slice_place[s]) % g.slice_dims[s]) * ls[1 + CT_MAX_AXES + j];
     }
-    src = (const T*)g.leaves[row[1]];
+    src = (const SI*)g.leaves[row[1]];
   } else {
-    src = (const T*)g.arena + row[1];
+    src = (const SI*)g.arena + row[1];
   }
-  T* dst = row[2] == K_ARENA ? (T*)g.arena + row[3] : (T*)g.out + g.out_off;
+  D* dst = row[2] == K_ARENA ? (D*)g.arena + row[3] : (D*)g.out + g.out_off;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (int64_t)gridDim.x * blockDim.x) {
     int64_t rem = e, off = base;
     for (int k = nd - 1; k >= 0; --k) {
@@ -107,8 +129,20 @@ __global__ __launch_bounds__(256) void ct_gather_kernel(GatherArgs g) {
       off += (rem - q * d) * row[8 + CT_MAX_AXES + k];
       rem = q;
     }
-    dst[e] = src[off];
+    dst[e] = ct_load(src + off);
   }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void ct_gather_kernel(GatherArgs g) {
+  ct_gather_body<T, T>(g);
+}
+
+// the gathers of storage mode: D = SI = uint16_t / uint32_t moves real elements / (re, im) pairs as they are; the single
+// leaf of a plan without steps is widened into the float32 output (SI the storage element, D float / cplx<float>)
+template <class D, class SI>
+__global__ __launch_bounds__(256) void ct_half_gather_kernel(GatherArgs g) {
+  ct_gather_body<D, SI>(g);
 }
 
 template <class T>
@@ -120,6 +154,11 @@ struct GemmArgs {
   int64_t H, M, N, K;
   int beta;  // 1: C += A B, 0: C = A B
 };
+
+template <class T>
+__device__ inline void ct_store(const GemmArgs<T>& p, int64_t e, T acc) {
+  p.C[e] = p.beta ? ct_add(p.C[e], acc) : acc;
+}
 
 constexpr int TB = 64, TK = 16;
 
@@ -179,39 +218,62 @@ __global__ __launch_bounds__(256) void ct_gemm_tiled_kernel(GemmArgs<T> p) {
   }
 }
 
-template <class T>
-__global__ __launch_bounds__(256) void ct_gemm_stream_kernel(GemmArgs<T> p) {
+// E: the element as the operands hold it, P: GemmArgs<E>, or HalfGemmArgs<E> (sums in float32, contract_half.h)
+template <class E, class P>
+__device__ inline void ct_stream_body(const P& p) {
+  using T = ct_acc_t<E>;
   const int64_t total = p.H * p.M * p.N;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int64_t n = e % p.N, r = e / p.N, m = r % p.M, h = r / p.M;
-    const T* a = p.A + h * p.M * p.K + m * p.a_m;
-    const T* b = p.B + h * p.K * p.N + n * p.b_n;
+    const E* a = p.A + h * p.M * p.K + m * p.a_m;
+    const E* b = p.B + h * p.K * p.N + n * p.b_n;
     T acc = ct_zero<T>();
-    for (int64_t k = 0; k < p.K; ++k) acc = ct_mac(acc, a[k * p.a_k], b[k * p.b_k]);
-    p.C[e] = p.beta ? ct_add(p.C[e], acc) : acc;
+    for (int64_t k = 0; k < p.K; ++k) acc = ct_mac(acc, ct_load(a + k * p.a_k), ct_load(b + k * p.b_k));
+    ct_store(p, e, acc);
   }
 }
 
 template <class T>
-__global__ __launch_bounds__(256) void ct_gemm_dot_kernel(GemmArgs<T> p) {
+__global__ __launch_bounds__(256) void ct_gemm_stream_kernel(GemmArgs<T> p) {
+  ct_stream_body<T>(p);
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void ct_half_stream_kernel(HalfGemmArgs<E> p) {
+  ct_stream_body<E>(p);
+}
+
+template <class E, class P>
+__device__ inline void ct_dot_body(const P& p) {
+  using T = ct_acc_t<E>;
   __shared__ T part[256];
   const int tid = threadIdx.x;
   const int64_t total = p.H * p.M * p.N;
   for (int64_t e = blockIdx.x; e < total; e += gridDim.x) {
     const int64_t n = e % p.N, r = e / p.N, m = r % p.M, h = r / p.M;
-    const T* a = p.A + h * p.M * p.K + m * p.a_m;
-    const T* b = p.B + h * p.K * p.N + n * p.b_n;
+    const E* a = p.A + h * p.M * p.K + m * p.a_m;
+    const E* b = p.B + h * p.K * p.N + n * p.b_n;
     T acc = ct_zero<T>();
-    for (int64_t k = tid; k < p.K; k += 256) acc = ct_mac(acc, a[k * p.a_k], b[k * p.b_k]);
+    for (int64_t k = tid; k < p.K; k += 256) acc = ct_mac(acc, ct_load(a + k * p.a_k), ct_load(b + k * p.b_k));
     part[tid] = acc;
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
       if (tid < w) part[tid] = ct_add(part[tid], part[tid + w]);
       __syncthreads();
     }
-    if (tid == 0) p.C[e] = p.beta ? ct_add(p.C[e], part[0]) : part[0];
+    if (tid == 0) ct_store(p, e, part[0]);
     __syncthreads();
   }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void ct_gemm_dot_kernel(GemmArgs<T> p) {
+  ct_dot_body<T>(p);
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void ct_half_dot_kernel(HalfGemmArgs<E> p) {
+  ct_dot_body<E>(p);
 }
 
 // A step with a row axis: row r of the result reads row a_map[r] of A and row b_map[r] of B.  A null map with a row
@@ -343,7 +405,7 @@ __global__ __launch_bounds__(256) void ct_rows_dot_kernel(RowGemmArgs<T> p) {
 
 struct tnco_hip_contract_s {
   int device = 0, dtype = 0;
-  size_t elem = 4;
+  size_t elem = 4, out_elem = 4;  // bytes of an element of the leaves and the arena / of the output (storage mode: not the same)
   std::vector<int64_t> leaf_numel, leaf_off, leaf_sl, perms, steps, slice_dims, place, block;
   std::vector<int64_t> group_first, group_count, group_max;  // perm rows of group g at index g + 1
   std::vector<int64_t> row_steps;  // [n_steps][ROW_W], empty: no step has a row axis
@@ -383,7 +445,8 @@ int64_t leaf_slice_reach(const tnco_hip_contract_s* c, int64_t leaf) {  // the l
 
 const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
   const int64_t L = d->n_leaves, P = d->n_perms, S = d->n_steps;
-  if (d->dtype < 0 || d->dtype > 3) return "'dtype' is not valid.";
+  if (d->dtype < 0 || d->dtype > 7) return "'dtype' is not valid.";
+  if (d->dtype > 3 && (d->row_steps || d->n_row_maps)) return "row axes are not supported with a storage dtype.";
   if (d->max_axes != CT_MAX_AXES) return "'max_axes' must be 32.";
   if (L < 0 || P < 0 || S < 0 || d->n_slice_dims < 0 || d->n_block < 0 || d->arena_elems < 0 || d->out_numel < 1)
     return "negative sizes.";
@@ -508,7 +571,7 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
   return nullptr;
 }
 
-template <class T>
+template <class D, class SI = D, bool half = false>
 int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t out_off) {
   const int64_t n = c->group_count[group + 1];
   if (!n) return TNCO_HIP_OK;
@@ -521,7 +584,10 @@ int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t o
   g.leaves = (const void* const*)c->d_leaf_ptrs;
   g.arena = c->d_arena, g.out = c->d_out, g.sid = sid, g.out_off = out_off;
   const int64_t blocks = std::min<int64_t>((c->group_max[group + 1] + 255) / 256, 2048);
-  hipLaunchKernelGGL(ct_gather_kernel<T>, dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, c->stream, g);
+  if constexpr (!half)
+    hipLaunchKernelGGL(ct_gather_kernel<D>, dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, c->stream, g);
+  else
+    hipLaunchKernelGGL((ct_half_gather_kernel<D, SI>), dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, c->stream, g);
   CT_TRY(hipGetLastError());
   c->launches += 1;
   c->by_kernel[0] += 1;
@@ -556,6 +622,39 @@ int launch_gemm(tnco_hip_contract_s* c, const GemmArgs<T>& p) {
   return TNCO_HIP_OK;
 }
 
+// launch_gemm in storage mode: the same shape classes and slots, the tiled class on the matrix cores
+template <class S, bool CPLX>
+int launch_half_gemm(tnco_hip_contract_s* c, HalfGemmArgs<typename std::conditional<CPLX, cplx<S>, S>::type> p) {
+  using E = typename std::conditional<CPLX, cplx<S>, S>::type;
+  const bool ak = p.a_k == 1, bn = p.b_n == 1;
+  const int64_t outs = p.H * p.M * p.N;
+  // 16-byte loads of 8 elements along the contiguous axis: the base and every row (column) of it aligned
+  p.a_vec = (uintptr_t)p.A % 16 == 0 && (ak ? p.a_m : p.a_k) % 8 == 0;
+  p.b_vec = (uintptr_t)p.B % 16 == 0 && (bn ? p.b_k : p.b_n) % 8 == 0;
+  int path;
+  if (p.M >= 64 && p.N >= 64 && p.K > 32) {
+    const int64_t tiles = p.H * ((p.M + HB - 1) / HB) * ((p.N + HB - 1) / HB);
+    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20));
+    if (ak && bn) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, true, true>), grid, dim3(256), 0, c->stream, p);
+    else if (ak) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, true, false>), grid, dim3(256), 0, c->stream, p);
+    else if (bn) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, false, true>), grid, dim3(256), 0, c->stream, p);
+    else hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, false, false>), grid, dim3(256), 0, c->stream, p);
+    path = 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0);
+  } else if (p.K >= 512 && outs <= 8192) {
+    hipLaunchKernelGGL(ct_half_dot_kernel<E>, dim3((unsigned)outs), dim3(256), 0, c->stream, p);
+    path = 5;
+  } else {
+    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16));
+    hipLaunchKernelGGL(ct_half_stream_kernel<E>, grid, dim3(256), 0, c->stream, p);
+    path = 6;
+  }
+  CT_TRY(hipGetLastError());
+  c->launches += 1;
+  c->by_kernel[path] += 1;
+  c->macs += outs * p.K;
+  return TNCO_HIP_OK;
+}
+
 // launch_gemm for a step with a row axis: the same shape classes, outputs counted with the rows
 template <class T>
 int launch_rows_gemm(tnco_hip_contract_s* c, const RowGemmArgs<T>& p) {
@@ -585,11 +684,15 @@ int launch_rows_gemm(tnco_hip_contract_s* c, const RowGemmArgs<T>& p) {
   return TNCO_HIP_OK;
 }
 
-template <class T>
+// T: the type of the sums and of the output; E: of the leaves and the arena (storage mode: st_f16 / st_bf16 or a pair)
+template <class T, class E = T>
 int run_impl(tnco_hip_contract_s* c) {
+  constexpr bool half = !std::is_same<T, E>::value;
+  // gathers move elements as they are, by width; only a single leaf gathered into the output is widened
+  using W = typename std::conditional<!half, T, typename std::conditional<sizeof(E) == 2, uint16_t, uint32_t>::type>::type;
   std::vector<char> visited(c->n_blocks, 0);
   const int64_t S = (int64_t)c->steps.size() / STEP_W;
-  T* arena = (T*)c->d_arena;
+  E* arena = (E*)c->d_arena;
   T* out = (T*)c->d_out;
   for (int64_t sid = c->start; sid < c->stop; ++sid) {
     int64_t blk = 0;
@@ -597,17 +700,29 @@ int run_impl(tnco_hip_contract_s* c) {
     const int beta = visited[blk];
     visited[blk] = 1;
     const int64_t out_off = blk * c->block_numel;
-    int rc = launch_gathers<T>(c, -1, sid, out_off);
+    int rc = half && S == 0 ? launch_gathers<T, E, half>(c, -1, sid, out_off) : launch_gathers<W, W, half>(c, -1, sid, out_off);
     if (rc) return rc;
     for (int64_t k = 0; k < S; ++k) {
-      if ((rc = launch_gathers<T>(c, k, sid, out_off))) return rc;
+      if ((rc = launch_gathers<W, W, half>(c, k, sid, out_off))) return rc;
       const int64_t* st = &c->steps[k * STEP_W];
-      const T* opnd[2];
+      const E* opnd[2];
       for (int side = 0; side < 2; ++side) {
         const int64_t kind = st[4 * side], ref = st[4 * side + 1];
-        opnd[side] = kind == K_LEAF ? (const T*)(c->d_leaves + c->leaf_off[ref] * c->elem) + leaf_slice_offset(c, ref, sid)
+        opnd[side] = kind == K_LEAF ? (const E*)(c->d_leaves + c->leaf_off[ref] * c->elem) + leaf_slice_offset(c, ref, sid)
                                     : arena + ref;
       }
+      if constexpr (half) {
+        HalfGemmArgs<E> p;
+        p.A = opnd[0], p.B = opnd[1];
+        p.Cs = st[8] == K_OUT ? nullptr : arena + st[9];
+        p.C = st[8] == K_OUT ? out + out_off : nullptr;
+        p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
+        p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
+        p.beta = st[8] == K_OUT ? beta : 0;
+        p.a_vec = p.b_vec = 0;
+        if ((rc = launch_half_gemm<typename ct_storage_of<E>::type, sizeof(E) == 4>(c, p))) return rc;
+        continue;
+      } else {
       T* dest = st[8] == K_OUT ? out + out_off : arena + st[9];
       const int64_t* rw = c->row_steps.empty() ? nullptr : &c->row_steps[k * ROW_W];
       if (rw && (rw[0] > 1 || rw[2] >= 0 || rw[4] >= 0)) {
@@ -630,6 +745,7 @@ int run_impl(tnco_hip_contract_s* c) {
       p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
       p.beta = st[8] == K_OUT ? beta : 0;
       if ((rc = launch_gemm<T>(c, p))) return rc;
+      }
     }
   }
   return TNCO_HIP_OK;
@@ -647,8 +763,8 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
     delete c;
     return fail(TNCO_HIP_EINVAL, e);
   }
-  static const size_t elem[4] = {4, 8, 8, 16};
-  c->dtype = d->dtype, c->elem = elem[d->dtype], c->device = d->device;
+  static const size_t elem[8] = {4, 8, 8, 16, 2, 4, 2, 4}, out_elem[8] = {4, 8, 8, 16, 4, 8, 4, 8};
+  c->dtype = d->dtype, c->elem = elem[d->dtype], c->out_elem = out_elem[d->dtype], c->device = d->device;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || d->device < 0 || d->device >= ndev) {
     delete c;
@@ -656,7 +772,7 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
   }
   const size_t n_tab = c->perms.size() + c->leaf_sl.size() + c->place.size() + c->slice_dims.size();
   const size_t leaves = (size_t)c->leaf_off.back() * c->elem;
-  const size_t arena = (size_t)std::max<int64_t>(c->arena_elems, 1) * c->elem, outb = (size_t)c->out_numel * c->elem;
+  const size_t arena = (size_t)std::max<int64_t>(c->arena_elems, 1) * c->elem, outb = (size_t)c->out_numel * c->out_elem;
   const size_t ptrs = std::max<size_t>(c->leaf_numel.size(), 1) * sizeof(void*);
   const size_t maps = c->row_maps.size() * sizeof(int32_t);
   c->bytes = (int64_t)(leaves + arena + outb + n_tab * 8 + ptrs + maps);
@@ -703,7 +819,7 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
     CT_TRY(hipMemcpyAsync(c->d_leaves + c->leaf_off[t] * c->elem, leaves[t], (size_t)c->leaf_numel[t] * c->elem,
                           hipMemcpyHostToDevice, c->stream));
   }
-  CT_TRY(hipMemsetAsync(c->d_out, 0, (size_t)c->out_numel * c->elem, c->stream));
+  CT_TRY(hipMemsetAsync(c->d_out, 0, (size_t)c->out_numel * c->out_elem, c->stream));
   c->macs = c->launches = 0;
   std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
   std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
@@ -711,10 +827,14 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
   int rc = c->dtype == 0 ? run_impl<float>(c)
            : c->dtype == 1 ? run_impl<double>(c)
            : c->dtype == 2 ? run_impl<cplx<float>>(c)
-                           : run_impl<cplx<double>>(c);
+           : c->dtype == 3 ? run_impl<cplx<double>>(c)
+           : c->dtype == 4 ? run_impl<float, st_f16>(c)
+           : c->dtype == 5 ? run_impl<cplx<float>, cplx<st_f16>>(c)
+           : c->dtype == 6 ? run_impl<float, st_bf16>(c)
+                           : run_impl<cplx<float>, cplx<st_bf16>>(c);
   if (rc) return rc;
   CT_TRY(hipEventRecord(c->ev[1], c->stream));
-  CT_TRY(hipMemcpyAsync(out, c->d_out, (size_t)c->out_numel * c->elem, hipMemcpyDeviceToHost, c->stream));
+  CT_TRY(hipMemcpyAsync(out, c->d_out, (size_t)c->out_numel * c->out_elem, hipMemcpyDeviceToHost, c->stream));
   CT_TRY(hipStreamSynchronize(c->stream));
   float ms = 0.f;
   CT_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));

@@ -1,0 +1,257 @@
+// contract_half.h -- the half-precision storage mode of the contraction engine (tnco_hip.h, dtype codes 4..7); included
+// by contract.hip inside its anonymous namespace, after cplx / ct_zero / ct_mac / ct_add / ct_acc.
+// Leaves and intermediates are float16 or bfloat16 (a complex element an interleaved (re, im) pair), every sum is
+// float32, a value is rounded once, to nearest even, when it is stored to the arena; the output stays float32.
+//   ct_mfma_tiled_kernel   the tiled shape class on the matrix cores (v_mfma_f32_16x16x32_{f16,bf16});
+//   the dot and stream classes and the gathers are the bodies of contract.hip, instantiated with a widening load and a
+//   store chosen by the destination.
+#pragma once
+
+struct st_f16 {
+  uint16_t v;
+};
+struct st_bf16 {
+  uint16_t v;
+};
+
+// the 16-bit storage types are summed in float32 (ct_acc: contract.hip)
+template <>
+struct ct_acc<st_f16> {
+  using type = float;
+};
+template <>
+struct ct_acc<st_bf16> {
+  using type = float;
+};
+template <>
+struct ct_acc<cplx<st_f16>> {
+  using type = cplx<float>;
+};
+template <>
+struct ct_acc<cplx<st_bf16>> {
+  using type = cplx<float>;
+};
+template <class E>
+struct ct_storage_of {
+  using type = E;
+};
+template <class S>
+struct ct_storage_of<cplx<S>> {
+  using type = S;
+};
+
+__device__ inline float ct_widen(st_f16 s) { return (float)__builtin_bit_cast(_Float16, s.v); }
+__device__ inline float ct_widen(st_bf16 s) { return __uint_as_float((uint32_t)s.v << 16); }
+template <class S>
+__device__ inline cplx<float> ct_widen(cplx<S> s) {
+  return cplx<float>{ct_widen(s.re), ct_widen(s.im)};
+}
+// to nearest, ties to even; beyond the range: inf, as the conversion instruction gives it
+__device__ inline void ct_narrow(float x, st_f16* d) { d->v = __builtin_bit_cast(uint16_t, (_Float16)x); }
+__device__ inline void ct_narrow(float x, st_bf16* d) {  // (the integer form of contraction.py _bf16_bits)
+  const uint32_t u = __float_as_uint(x);
+  d->v = (u & 0x7fffffffu) > 0x7f800000u ? (uint16_t)((u >> 16) | 0x40u) : (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+template <class S>
+__device__ inline void ct_narrow(cplx<float> x, cplx<S>* d) {
+  ct_narrow(x.re, &d->re);
+  ct_narrow(x.im, &d->im);
+}
+
+// GemmArgs of a storage-mode step: operands in storage, the result to the arena in storage (Cs) or to the output in
+// float32 (C, with beta); exactly one of the two is set
+template <class E>
+struct HalfGemmArgs {
+  const E* A;
+  const E* B;
+  E* Cs;
+  ct_acc_t<E>* C;
+  int64_t a_m, a_k, b_k, b_n;
+  int64_t H, M, N, K;
+  int beta;
+  int a_vec, b_vec;  // the operand's runs of 8 elements along its contiguous axis are 16-byte aligned
+};
+
+template <class E>
+__device__ inline void ct_store(const HalfGemmArgs<E>& p, int64_t e, ct_acc_t<E> acc) {
+  if (p.Cs) ct_narrow(acc, p.Cs + e);
+  else p.C[e] = p.beta ? ct_add(p.C[e], acc) : acc;
+}
+
+typedef float ct_f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t ct_u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 ct_f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 ct_bf16x8 __attribute__((ext_vector_type(8)));
+
+// D = A B + C of one 16 x 16 x 32 tile: lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15]
+// in element j of its fragments, and D[row 4 (l >> 4) + r][col l & 15] in register r
+__device__ inline ct_f32x4 ct_mfma(st_f16*, ct_u32x4 a, ct_u32x4 b, ct_f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ct_f16x8, a), __builtin_bit_cast(ct_f16x8, b), c, 0, 0, 0);
+}
+__device__ inline ct_f32x4 ct_mfma(st_bf16*, ct_u32x4 a, ct_u32x4 b, ct_f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(ct_bf16x8, a), __builtin_bit_cast(ct_bf16x8, b), c, 0, 0, 0);
+}
+
+constexpr int HB = 128;  // block tile in m and in n
+constexpr int HK = 32;   // k block: one MFMA deep
+constexpr int HLD = 20;  // 32-bit words between two rows of an LDS image: 16 of data (32 k) + 4, see the kernel comment
+
+// One operand tile, HB rows (m of A, n of B) x HK k, global -> registers: element (r, k) is G[r sr + k sk].  KC: the
+// operand is contiguous along k (sk == 1), else along its rows (sr == 1).  A lane takes two runs of 8 elements along
+// the contiguous axis: KC: rows tid / 4 and tid / 4 + 64, k 8 (tid % 4) ...; else: k 2 (tid % 16) and + 1, rows
+// 8 (tid / 16) ....  w: the runs as they lie in memory (real: 2 x 4 words, complex: 2 x 8), zeros beyond R and K.
+template <class E, bool KC>
+__device__ inline void ct_half_fetch(uint32_t (&w)[4 * sizeof(E)], const E* G, int64_t sr, int64_t sk, int64_t r0, int64_t R,
+                                     int64_t k0, int64_t K, int vec, int tid) {
+  constexpr int NW = 2 * sizeof(E);  // words of a run
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const int64_t r = KC ? r0 + tid / 4 + 64 * g : r0 + 8 * (tid / 16);
+    const int64_t k = KC ? k0 + 8 * (tid % 4) : k0 + 2 * (tid % 16) + g;
+    const int64_t left = KC ? (r < R ? K - k : 0) : (k < K ? R - r : 0);  // elements of the run inside the operand
+    const E* src = G + r * sr + k * sk;
+    if (vec && left >= 8) {
+#pragma unroll
+      for (int q = 0; q < NW / 4; ++q) {
+        const ct_u32x4 v = ((const ct_u32x4*)src)[q];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[g * NW + 4 * q + j] = v[j];
+      }
+    } else {
+      const uint16_t* s16 = (const uint16_t*)src;
+#pragma unroll
+      for (int j = 0; j < NW; ++j) {
+        const bool in = j * 4 < left * (int64_t)sizeof(E);  // word j holds elements 2 j, 2 j + 1 (real) or element j
+        const bool in_hi = sizeof(E) == 4 ? in : 2 * j + 1 < left;
+        const uint32_t lo = in ? s16[2 * j] : 0u, hi = in_hi ? s16[2 * j + 1] : 0u;
+        w[g * NW + j] = lo | (hi << 16);
+      }
+    }
+  }
+}
+
+// ... registers -> the LDS image(s) [row][k], k contiguous: one plane, or the planes of the real and of the imaginary
+// parts.  The runs along rows are transposed here: a word takes the same row at k and k + 1 from the lane's two runs.
+template <class E, bool KC>
+__device__ inline void ct_half_stash(uint32_t (*img)[HB][HLD], const uint32_t (&w)[4 * sizeof(E)], int tid) {
+  constexpr bool CPLX = sizeof(E) == 4;
+  if constexpr (KC) {
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      ct_u32x4 re, im;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if constexpr (CPLX) {
+          const uint32_t e0 = w[8 * g + 2 * j], e1 = w[8 * g + 2 * j + 1];
+          re[j] = (e0 & 0xffffu) | (e1 << 16);
+          im[j] = (e0 >> 16) | (e1 & 0xffff0000u);
+        } else {
+          re[j] = w[4 * g + j];
+        }
+      }
+      *(ct_u32x4*)&img[0][tid / 4 + 64 * g][4 * (tid % 4)] = re;
+      if constexpr (CPLX) *(ct_u32x4*)&img[1][tid / 4 + 64 * g][4 * (tid % 4)] = im;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if constexpr (CPLX) {
+        const uint32_t e0 = w[j], e1 = w[8 + j];
+        img[0][8 * (tid / 16) + j][tid % 16] = (e0 & 0xffffu) | (e1 << 16);
+        img[1][8 * (tid / 16) + j][tid % 16] = (e0 >> 16) | (e1 & 0xffff0000u);
+      } else {
+        const uint32_t e0 = (w[j / 2] >> (16 * (j & 1))) & 0xffffu, e1 = (w[4 + j / 2] >> (16 * (j & 1))) & 0xffffu;
+        img[0][8 * (tid / 16) + j][tid % 16] = e0 | (e1 << 16);
+      }
+    }
+  }
+}
+
+// C[h] = beta C[h] + A[h] B[h] on the matrix cores: the shape class of ct_gemm_tiled_kernel (M, N >= 64, K > 32).
+// S: st_f16 / st_bf16; CPLX: elements are (re, im) pairs; AK, BN: the operand layouts as in ct_gemm_tiled_kernel.
+// A block of 4 wavefronts takes a 128 x 128 tile, a wavefront 64 x 64 of it as 4 x 4 MFMA tiles of 16 x 16, k in blocks
+// of 32 (one v_mfma_f32_16x16x32 per tile and block).  Both operands are staged as [row][k] images with k contiguous,
+// whatever their layout in memory (ct_half_stash transposes the other one), so every fragment is one 16-byte LDS read;
+// K tails and edge rows are zeros in LDS.  The next k block's global loads are issued before the MFMAs of this one.
+// Complex: real and imaginary planes, four real products per k block in the fixed order re += Ar Br, re += (-Ai) Bi,
+// im += Ar Bi, im += Ai Br; -Ai is Ai with the sign bits flipped (exact).  Accumulators are float32; the epilogue rounds
+// once to storage for an arena destination, or writes / adds float32 to the output.  No atomics.
+// LDS: rows of 80 bytes (64 of data): the 16 rows a 16-byte read takes per quarter wavefront start 20 banks apart, which
+// covers the 64 banks once.  The writes of the stage are not free of conflicts: the 16-byte writes of an operand that is
+// contiguous along k are 2-way (4 rows x 4 chunks per quarter wavefront; row 3 wraps onto the banks of row 0), and so are
+// the 32-bit writes of the transposing stage (a wavefront writes 4 rows 8 apart, 160 words: two pairs of rows share banks).
+// One LDS buffer, two barriers per k block; what that costs against the plain tiled kernel is measured, not estimated
+// (profiles/contract_timing.txt, the storage leg).  Real: 2 x 128 x 80 B = 20 KiB a block; complex: 40 KiB.  Registers: 64 accumulators real,
+// 128 complex, 32 / 80 of fragments, 16 / 32 of staging; the compiler gives about 180 real (two blocks a CU) and about
+// 300 complex (one block a CU: a wavefront per SIMD, which 64 MFMAs per k block keep busy), no scratch.
+template <class S, bool CPLX, bool AK, bool BN>
+__global__ __launch_bounds__(256) void ct_mfma_tiled_kernel(HalfGemmArgs<typename std::conditional<CPLX, cplx<S>, S>::type> p) {
+  using E = typename std::conditional<CPLX, cplx<S>, S>::type;
+  constexpr int NP = CPLX ? 2 : 1;
+  __shared__ __attribute__((aligned(16))) uint32_t As[NP][HB][HLD];
+  __shared__ __attribute__((aligned(16))) uint32_t Bs[NP][HB][HLD];
+  const int tid = threadIdx.x, lane = tid % 64, wave = tid / 64;
+  const int lr = lane & 15, lq = lane >> 4, wm = 64 * (wave / 2), wn = 64 * (wave % 2);
+  const int64_t tm = (p.M + HB - 1) / HB, tn = (p.N + HB - 1) / HB;
+  for (int64_t t = blockIdx.x; t < p.H * tm * tn; t += gridDim.x) {
+    const int64_t h = t / (tm * tn), m0 = (t / tn % tm) * HB, n0 = t % tn * HB;
+    const E* A = p.A + h * p.M * p.K;
+    const E* B = p.B + h * p.K * p.N;
+    ct_f32x4 acc[NP][4][4];
+#pragma unroll
+    for (int c = 0; c < NP; ++c)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[c][i][j] = ct_f32x4{0.f, 0.f, 0.f, 0.f};
+    uint32_t wa[4 * sizeof(E)], wb[4 * sizeof(E)];
+    ct_half_fetch<E, AK>(wa, A, p.a_m, p.a_k, m0, p.M, 0, p.K, p.a_vec, tid);
+    ct_half_fetch<E, !BN>(wb, B, p.b_n, p.b_k, n0, p.N, 0, p.K, p.b_vec, tid);
+    for (int64_t k0 = 0; k0 < p.K; k0 += HK) {
+      ct_half_stash<E, AK>(As, wa, tid);
+      ct_half_stash<E, !BN>(Bs, wb, tid);
+      __syncthreads();
+      if (k0 + HK < p.K) {
+        ct_half_fetch<E, AK>(wa, A, p.a_m, p.a_k, m0, p.M, k0 + HK, p.K, p.a_vec, tid);
+        ct_half_fetch<E, !BN>(wb, B, p.b_n, p.b_k, n0, p.N, k0 + HK, p.K, p.b_vec, tid);
+      }
+      ct_u32x4 a[NP][4], b[NP][4];
+#pragma unroll
+      for (int c = 0; c < NP; ++c)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          a[c][i] = *(const ct_u32x4*)&As[c][wm + 16 * i + lr][4 * lq];
+          b[c][i] = *(const ct_u32x4*)&Bs[c][wn + 16 * i + lr][4 * lq];
+        }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        ct_u32x4 a_neg;
+        if constexpr (CPLX) a_neg = a[NP - 1][i] ^ 0x80008000u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          acc[0][i][j] = ct_mfma((S*)nullptr, a[0][i], b[0][j], acc[0][i][j]);
+          if constexpr (CPLX) {
+            acc[0][i][j] = ct_mfma((S*)nullptr, a_neg, b[NP - 1][j], acc[0][i][j]);
+            acc[NP - 1][i][j] = ct_mfma((S*)nullptr, a[0][i], b[NP - 1][j], acc[NP - 1][i][j]);
+            acc[NP - 1][i][j] = ct_mfma((S*)nullptr, a[NP - 1][i], b[0][j], acc[NP - 1][i][j]);
+          }
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t m = m0 + wm + 16 * i + 4 * lq + r, n = n0 + wn + 16 * j + lr;
+          if (m < p.M && n < p.N) {
+            ct_acc_t<E> v;
+            if constexpr (CPLX) v = cplx<float>{acc[0][i][j][r], acc[NP - 1][i][j][r]};
+            else v = acc[0][i][j][r];
+            ct_store(p, (h * p.M + m) * p.N + n, v);
+          }
+        }
+  }
+}

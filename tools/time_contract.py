@@ -8,7 +8,8 @@ GB/s: operands read once + result written once, against the ~6.3 TB/s an MI355X 
 amplitude from the finite-width optimizer (wall time, device time, launches per slice, MACs/s); P output bitstrings
 of that circuit in one projected call (`--projs`: the 53 output indices sparse, an infinite-memory path from
 optimize(n_projs=P)) against a loop of plain contract() calls over leaves indexed at one bitstring each, along the same
-path.  Engine figures are its
+path; the storage mode (`--storage`: the large square step in float32 and complex64 with `storage` unset, float16 and
+bfloat16, and the sliced Sycamore leg once more with storage="bfloat16").  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device).
 """
@@ -135,6 +136,53 @@ def sycamore(lines, depth, max_width, max_slices):
     print("\n".join(lines[-4:]), flush=True)
 
 
+def storage(lines, n, depth, max_width, max_slices):
+    """The storage mode against the plain engine on the same box: the large square step (the MFMA kernel against the
+    tiled LDS kernel), and the sliced Sycamore amplitude with bfloat16 leaves and intermediates."""
+    lines.append("")
+    lines.append(f"## storage mode, large square step M = N = K = {n}: leaves in float16 / bfloat16, float32 sums on the "
+                 "matrix cores (ct_mfma_tiled_kernel) against the tiled LDS kernel (storage unset)")
+    lines.append(f"{'dtype':>10} {'storage':>9} {'engine s':>10} {'TFLOP/s':>9} {'unset / this':>13} {'rel. diff to unset':>19}")
+    rng = np.random.RandomState(4)
+    for dt in (np.float32, np.complex64):
+        x, y = _rand((n, n), dt, rng), _rand((n, n), dt, rng)
+        fl = FLOPS_PER_MAC[dt] * n ** 3
+        base = t_base = None
+        for st in (None, "float16", "bfloat16"):
+            call = lambda st=st: ctr.contract([(0, 1)], [("i", "k"), ("k", "j")], [x, y], storage=st)  # noqa: E731
+            r = call()
+            t = min(r.device_s, _engine_time(call))
+            if st is None:
+                base, t_base = r.array, t
+            diff = float(np.linalg.norm(r.array - base) / np.linalg.norm(base))
+            lines.append(f"{np.dtype(dt).name:>10} {str(st):>9} {t:10.5f} {fl / t / 1e12:9.1f} {t_base / t:13.2f} {diff:19.2e}")
+            del r
+        del base, x, y
+    ts, d, o = syn.sycamore53_tn(depth=depth)
+    tn0 = tnmod.TensorNetwork([tnmod.Tensor(xs, [d] * len(xs)) for xs in ts], output_inds=o)
+    tn, res = Optimizer(method="sa", max_width=max_width, seed=0).optimize(tn0, betas=(0, 50), n_steps=200, n_runs=256)
+    r0 = res[0]
+    rng = np.random.RandomState(2)
+    # unit-modulus entries give an amplitude of about 2^(indices / 2), far beyond float32 here (the sycamore leg above
+    # times such a run; its numbers are not finite): every tensor is scaled so that the amplitude stays near 1
+    n_inds = len({x for xs in ts for x in xs})
+    scale = 2.0 ** (-n_inds / (2 * len(ts)))
+    arrays = [(_rand(tuple(d for _ in xs), np.complex64, rng) * scale).astype(np.complex64) for xs in ts]
+    fused = ctr.contract(tn.tags["fuse_path"], tn0.ts_inds, arrays, tn0.output_inds)
+    leaves = fused.array if isinstance(fused.array, list) else [fused.array]
+    p = ctr.plan(r0.path, tn.ts_inds, [a.shape for a in leaves], tn.output_inds, slices=r0.slices)
+    m = min(p.n_slices, max_slices)
+    runs = {st: ctr.contract(r0.path, tn.ts_inds, leaves, tn.output_inds, slices=r0.slices, slice_range=(0, m), storage=st)
+            for st in (None, "bfloat16")}
+    a, b = runs[None], runs["bfloat16"]
+    err = float(np.linalg.norm(np.ravel(b.array - a.array)) / np.linalg.norm(np.ravel(a.array)))
+    lines.append(f"## storage mode, sliced Sycamore-53 amplitude, depth {depth}, complex64, max_width {max_width}, "
+                 f"assignments [0, {m}): storage unset: device {a.device_s:.3f} s, peak device bytes {a.peak_device_bytes}; "
+                 f"storage=\"bfloat16\": device {b.device_s:.3f} s, peak device bytes {b.peak_device_bytes}, relative "
+                 f"error to the complex64 run {err:.2e}; launches {dict(zip(ctr.KERNEL_PATHS, b.kernel_launches))}")
+    print("\n".join(lines[-9:]), flush=True)
+
+
 def projections(lines, depth, counts, loop_max):
     """P amplitudes per call.  The network: the circuit without its 53 <x| tensors, the open wires its output and
     sparse indices.  The largest depth <= `depth` whose unsliced plan fits the free device memory at every P is used."""
@@ -201,12 +249,18 @@ def main():
     ap.add_argument("--max-width", type=float, default=14)
     ap.add_argument("--max-slices", type=int, default=4096)
     ap.add_argument("--projs", action="store_true", help="only the projections leg, appended to --out")
+    ap.add_argument("--storage", action="store_true", help="only the storage-mode leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
+    if a.projs and a.storage:
+        ap.error("--projs and --storage each append one leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs:  # (the other legs' sections stay as they are)
-        projections(lines, a.depth, a.counts, a.loop_max)
+    if a.projs or a.storage:  # (the other legs' sections stay as they are)
+        if a.storage:
+            storage(lines, a.n, a.depth, a.max_width, a.max_slices)
+        else:
+            projections(lines, a.depth, a.counts, a.loop_max)
         with open(a.out, "a") as f:
             f.write("\n".join(lines[1:]) + "\n")
         return
@@ -214,6 +268,7 @@ def main():
     skinny(lines)
     sycamore(lines, a.depth, a.max_width, a.max_slices)
     projections(lines, a.depth, a.counts, a.loop_max)
+    storage(lines, a.n, a.depth, a.max_width, a.max_slices)
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
