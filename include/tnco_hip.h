@@ -425,8 +425,20 @@ const char* tnco_hip_comm_last_error(void);
  *   4 float16 -> float32;  5 float16 pairs (re, im) -> complex64;  6 bfloat16 -> float32;  7 bfloat16 pairs -> complex64.
  * The leaves passed to tnco_hip_contract_run are in storage layout, `out` is float32 / complex64; arena_elems, leaf_numel
  * and every offset of the tables count storage elements (a pair is one element).  row_steps must be NULL (EINVAL).  No
- * scaling: a sum beyond the storage type's range is stored as inf.  The launch slots keep their meaning (shape class and
- * operand layout of the step); the four tiled slots then count launches of the MFMA kernel.
+ * scaling unless `scaling` is set: a sum beyond the storage type's range is stored as inf.  The launch slots keep their
+ * meaning (shape class and operand layout of the step); the four tiled slots then count launches of the MFMA kernel.
+ *
+ * Per-tensor scaling, scaling = 1 (storage dtypes only, EINVAL otherwise): every stored tensor T, leaf or intermediate, has
+ * one int32 exponent e in a device array of n_leaves + n_steps slots (leaf t: slot t; the result of step j: slot
+ * n_leaves + j); its 16-bit values are round_nearest_even(x 2^-e) and mean stored 2^e.  e = floor(log2 m) - 14 with m the
+ * largest |part| over the finite parts of the whole tensor, from the float32 bit pattern (subnormals included); e = 0 when
+ * m == 0 or no part is finite.  The leaves come scaled from the host with their exponents (tnco_hip_contract_set_exponents).
+ * Columns 14 and 15 of a steps row are the exponent slots of A and of B.  A step for the arena sums its stored operands in
+ * float32 into a staging buffer of the arena (stage_refs[k]: its offset in storage elements, a multiple of 8; it takes
+ * 2 H M N of them), the largest finite |part| is taken with an integer max over the bit patterns, and a narrowing pass
+ * stores round(acc 2^-s) with e_C = e_A + e_B + s, s the rule applied to the sums.  The step for the output adds or places
+ * ldexpf(acc, e_A + e_B); a single leaf gathered into the output is widened and scaled the same way.  Permutes move 16-bit
+ * values as they are.  Exponents are recomputed in every slice assignment; nothing synchronises with the host in a run.
  */
 typedef struct tnco_hip_contract_s* tnco_hip_contract;
 typedef struct tnco_hip_contract_desc {
@@ -451,6 +463,8 @@ typedef struct tnco_hip_contract_desc {
   const int64_t* row_steps;  /* NULL: no row axes */
   int64_t n_row_maps;
   const int32_t* row_maps;
+  int64_t scaling;           /* 0, or 1: per-tensor power-of-two scaling (storage dtypes only) */
+  const int64_t* stage_refs; /* [n_steps] with scaling: arena offset of the step's float32 staging buffer, -1 for the output step */
 } tnco_hip_contract_desc;
 /* validates the plan, allocates leaves + arena + output on the device (ERUNTIME when they exceed its free memory) */
 int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract* out);
@@ -472,6 +486,13 @@ int tnco_hip_contract_kernel_launches(tnco_hip_contract h, int64_t* counts);
  * 2 rows_stream. */
 #define TNCO_HIP_CONTRACT_N_ROW_KERNELS 3
 int tnco_hip_contract_row_launches(tnco_hip_contract h, int64_t* counts);
+/* scaling: the leaves' exponents, n_leaves of them, for the runs that follow (zeros until set) */
+int tnco_hip_contract_set_exponents(tnco_hip_contract h, const int32_t* exps);
+/* scaling: the n_leaves + n_steps exponent slots as the last assignment of the last run left them (the slot of the
+ * step that writes the output is not used and stays 0) */
+int tnco_hip_contract_exponents(tnco_hip_contract h, int32_t* exps);
+/* scaling: the last run's launches of the narrowing pass; they are part of stats[1] and of none of the slots above */
+int tnco_hip_contract_narrow_launches(tnco_hip_contract h, int64_t* count);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

@@ -74,6 +74,8 @@ class ContractDesc(C.Structure):
         ("row_steps", C.c_void_p),
         ("n_row_maps", C.c_int64),
         ("row_maps", C.c_void_p),
+        ("scaling", C.c_int64),
+        ("stage_refs", C.c_void_p),
     ]
 
 
@@ -87,7 +89,8 @@ EXPORTS = [
     "tnco_hip_comm_unique_id", "tnco_hip_comm_init", "tnco_hip_comm_destroy", "tnco_hip_comm_allreduce_min", "tnco_hip_comm_allgather",
     "tnco_hip_comm_barrier", "tnco_hip_comm_last_error",
     "tnco_hip_contract_create", "tnco_hip_contract_run", "tnco_hip_contract_stats", "tnco_hip_contract_kernel_launches",
-    "tnco_hip_contract_row_launches", "tnco_hip_contract_destroy",
+    "tnco_hip_contract_row_launches", "tnco_hip_contract_set_exponents", "tnco_hip_contract_exponents",
+    "tnco_hip_contract_narrow_launches", "tnco_hip_contract_destroy",
     "tnco_hip_device_name", "tnco_hip_device_count", "tnco_hip_last_error", "tnco_hip_version",
 ]
 
@@ -191,6 +194,9 @@ def load() -> C.CDLL:
     L.tnco_hip_contract_stats.argtypes = [vp, vp]
     L.tnco_hip_contract_kernel_launches.argtypes = [vp, vp]
     L.tnco_hip_contract_row_launches.argtypes = [vp, vp]
+    L.tnco_hip_contract_set_exponents.argtypes = [vp, vp]
+    L.tnco_hip_contract_exponents.argtypes = [vp, vp]
+    L.tnco_hip_contract_narrow_launches.argtypes = [vp, vp]
     L.tnco_hip_contract_destroy.argtypes = [vp]
     L.tnco_hip_contract_destroy.restype = None
     L.tnco_hip_device_name.argtypes = [C.c_int, vp, C.c_int]

@@ -24,8 +24,28 @@ give the rows of X and of Y that each row of Z restricts to; the leaves are rest
 Storage mode: with `storage="float16"` or `"bfloat16"` (float32 / complex64 arrays only) the leaves are rounded to that
 type on the host, to nearest even, and every intermediate is rounded once when a step stores it; every step sums in
 float32, the big steps on the matrix cores, and the output, the sum over slice assignments included, stays float32 /
-complex64.  Leaves and intermediates take half the device memory.  There is no scaling: an intermediate beyond the
-storage type's range becomes inf or 0.  Projections are not supported with it.
+complex64.  Leaves and intermediates take half the device memory.  Without `scaling` an intermediate beyond the
+storage type's range becomes inf or 0, and a leaf beyond it is refused.  Projections are not supported with it.
+
+Scaling: with `scaling="tensor"` (it needs `storage`) every stored tensor T, leaf or intermediate, has one int32
+exponent e: the stored 16-bit values are round_nearest_even(x 2^-e) and the tensor means stored 2^e.  The rule, the same
+on host (`scale_exponent`) and device (csrc/contract_half.h ct_scale_exponent):
+    m = the largest |part| over the finite parts of the whole tensor (a complex element contributes its two parts);
+    e = 0 when m == 0 or no part is finite, else e = floor(log2 m) - 14, read from the float32 bit pattern of m
+    (float32 subnormals included).
+The largest stored magnitude then lies in [2^14, 2^15]: finite in float16 even when it rounds up; bfloat16 uses the same
+14.  x 2^-e is taken with ldexp and is exact (a part that falls below float32's normal range on the way is far below
+the storage type's resolution at that scale).  Parts that are not finite do not enter m and are stored as they are; a
+finite leaf is never beyond the range.  A leaf has one exponent for the whole leaf, every slice value included,
+computed on the host (`scale_to_storage`).  A step whose result goes to the arena sums its stored operands in float32,
+acc = sum A_stored B_stored, meaning acc 2^(e_A + e_B); with s the rule applied to the acc of the whole result it stores
+round(acc 2^-s) and e_C = e_A + e_B + s.  The step for the output adds or places ldexp(acc, e_A + e_B) in float32, which
+beyond float32's range is inf or 0 as float32 itself gives it; a single leaf gathered into the output is widened and
+scaled the same way.  Permutes and gathers move the 16-bit values as they are.  The exponents live in a device array
+(leaves first, then one slot per step) and are recomputed in every slice assignment; nothing synchronises with the host
+inside a run, and the maximum is an integer max over sign-cleared bit patterns, so a call stays bit-reproducible.  Under
+scaling a part smaller than 2^-28 of its tensor's largest lands in float16's subnormal range or below: that is below the
+noise of the float32 sums themselves.
 """
 from __future__ import annotations
 
@@ -38,7 +58,7 @@ import numpy as np
 from .app import tn as tnmod
 
 __all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
-           "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage"]
+           "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage", "SCALINGS", "scale_exponent", "scale_to_storage"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -46,6 +66,8 @@ DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex6
 # storage mode: leaves and intermediates in a 16-bit type, sums and the output in float32 / complex64.  The dtype code
 # of include/tnco_hip.h is STORAGES[name] + (1 when complex)
 STORAGES = {"float16": 4, "bfloat16": 6}
+SCALINGS = ("tensor",)  # per-tensor power-of-two scaling of storage mode (module docstring)
+SCALE_BITS = 14  # the largest stored magnitude of a scaled tensor lies in [2^14, 2^15]
 
 # operand / destination kinds and table widths: include/tnco_hip.h (tnco_hip_contract_desc)
 LEAF, ARENA, OUT = 0, 1, 2
@@ -73,7 +95,11 @@ class ContractionResult:
     device_s: float = 0.0  # device time of the kernels (copies in and out excluded)
     fuse_macs: int = 0  # contract_results: multiply-adds of the fuse stage (not part of `macs`)
     kernel_launches: tuple = (0,) * len(KERNEL_PATHS)  # launches per kernel path, in KERNEL_PATHS order
-    row_kernel_launches: tuple = (0, 0, 0)  # ... per row-mapped path, in ROW_KERNEL_PATHS order; `launches` is both
+    row_kernel_launches: tuple = (0, 0, 0)  # ... per row-mapped path, in ROW_KERNEL_PATHS order
+    scaling: str = None  # "tensor": per-tensor scaling of storage mode
+    exponents: tuple = None  # scaling: the exponents after the last slice assignment, leaves first, then one per step
+    #                          (the step that writes the output: 0); None without scaling (a list of them: as `array`)
+    narrow_launches: int = 0  # scaling: launches of the narrowing pass; `launches` is the three counts together
 
 
 @dataclass
@@ -101,6 +127,8 @@ class Plan:
     row_maps: np.ndarray = None  # int32 pool of the maps
     leaf_rows: tuple = ()  # per leaf: None, or (axes of its sparse indices, their values [rows, len(axes)])
     out_rows: tuple = None  # (rows of the final tensor, row of it for each of the P projections)
+    scaling: str = None  # "tensor": steps columns 14, 15 are the exponent slots of A and B (leaf t: t, step j: n_leaves + j)
+    stage_refs: np.ndarray = None  # scaling: [n_steps] arena offset of a stored step's float32 staging buffer, -1 none
 
     @property
     def n_slices(self) -> int:
@@ -116,7 +144,9 @@ class Plan:
         held = item if self.storage is None else _storage_itemsize(self.dtype)  # of leaves and arena
         tables = 8 * (self.leaf_sl.size + self.perms.size + 2 * self.leaf_numel.size)
         maps = 0 if self.row_maps is None else 4 * self.row_maps.size + 8 * self.row_steps.size
-        return held * (int(self.leaf_numel.sum()) + self.arena_elems) + item * self.out_numel + tables + maps
+        # scaling: an int32 exponent per leaf and step, a max word per step
+        scale = 0 if self.scaling is None else 4 * (self.leaf_numel.size + 2 * len(self.steps))
+        return held * (int(self.leaf_numel.sum()) + self.arena_elems) + item * self.out_numel + tables + maps + scale
 
 
 class _Arena:
@@ -199,6 +229,15 @@ def _check_storage(storage, dtype, projs=None) -> None:
         raise NotImplementedError("projections are not supported with 'storage'.")
 
 
+def _check_scaling(scaling, storage) -> None:
+    if scaling is None:
+        return
+    if not isinstance(scaling, str) or scaling not in SCALINGS:
+        raise ValueError("'scaling' must be None or 'tensor'.")
+    if storage is None:
+        raise ValueError("'scaling' needs 'storage'.")
+
+
 def _bf16_bits(x) -> np.ndarray:
     """The bfloat16 nearest to each float32 of x, ties to even, as uint16; NaN stays NaN (quiet), what lies beyond the
     largest bfloat16 becomes inf."""
@@ -232,6 +271,48 @@ def round_to_storage(a, storage) -> np.ndarray:
     a = np.asarray(a)
     _check_storage(storage, a.dtype)
     return _from_storage_bits(_storage_bits(a, storage), storage, a)
+
+
+def _parts(a) -> np.ndarray:
+    """The float32 parts of a float32 / complex64 array (complex: one more axis of 2, re and im), contiguous."""
+    a = np.ascontiguousarray(a)
+    return a.reshape(-1).view(np.float32).reshape(a.shape + (2,)) if a.dtype.kind == "c" else a.astype(np.float32, copy=False)
+
+
+def scale_exponent(a) -> int:
+    """The exponent the scaling rule (module docstring) gives the tensor `a` (float32 / complex64), in integer
+    arithmetic on the float32 bit patterns: csrc/contract_half.h ct_scale_exponent restated."""
+    u = _parts(a).reshape(-1).view(np.uint32) & np.uint32(0x7FFFFFFF)
+    u = u[u < 0x7F800000]
+    m = int(u.max()) if u.size else 0
+    if m == 0:
+        return 0
+    lg = (m >> 23) - 127 if m >> 23 else (m.bit_length() - 1) - 149
+    return lg - SCALE_BITS
+
+
+def _scaled_bits(a, storage):
+    """(_storage_bits of `a` scaled by its exponent, the exponent)."""
+    e = scale_exponent(a)
+    with np.errstate(under="ignore"):
+        scaled = np.ldexp(_parts(a), np.int32(-e)).astype(np.float32, copy=False)
+    return _storage_bits(scaled, storage, check=False), e
+
+
+def scale_to_storage(a, storage):
+    """(values, exponent): `a` (float32 / complex64) as the engine holds it as a leaf under scaling="tensor" -- every
+    part scaled by 2^-exponent, rounded to `storage` and scaled back: same dtype and shape -- and the leaf's exponent,
+    a Python int (module docstring)."""
+    a = np.asarray(a)
+    if storage not in STORAGES:
+        raise ValueError(f"'storage' must be {' or '.join(repr(s) for s in STORAGES)}.")
+    _check_storage(storage, a.dtype)
+    bits, e = _scaled_bits(a, storage)
+    like = np.empty(bits.shape, np.float32)
+    with np.errstate(over="ignore"):
+        parts = np.ldexp(_from_storage_bits(bits, storage, like), np.int32(e)).astype(np.float32, copy=False)
+    values = parts.reshape(-1).view(np.complex64).reshape(a.shape) if a.dtype.kind == "c" else parts.reshape(a.shape)
+    return values, e
 
 
 def _from_storage_bits(bits, storage, like) -> np.ndarray:
@@ -306,10 +387,12 @@ def _unique_rows(table):
 
 
 def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
-         sparse_inds=(), projs=None, storage=None) -> Plan:
+         sparse_inds=(), projs=None, storage=None, scaling=None) -> Plan:
     """The device plan of one contraction along a path that leaves one tensor (no GPU).
-    `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`: see the module docstring."""
+    `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`: see the module
+    docstring."""
     _check_storage(storage, dtype, projs)
+    _check_scaling(scaling, storage)
     ts_inds = [tuple(xs) for xs in ts_inds]
     shapes = [tuple(int(d) for d in s) for s in shapes]
     dims = _dims_of(ts_inds, shapes)
@@ -381,10 +464,11 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         # a leaf is read in place when its kept axes are one contiguous block (sliced axes outermost, or none)
         dense = all(st[x] == size(kept[k + 1:]) for k, x in enumerate(kept))
         live.append(_Live(kept, LEAF if dense else None, t, t))
+        live[-1].slot = t  # (scaling: the exponent slot; a permute keeps it)
 
     # buffers are symbolic (numbers) until the event list is replayed on the arena
     buf_size, front, events = [], [], []
-    perms, rows, ops = [], [], []
+    perms, rows, ops, stage = [], [], [], []
 
     def new_buf(numel, at_start=False):
         buf_size.append(numel)
@@ -448,6 +532,13 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         H, M, N, K = size(h), size(xs), size(ys), size(s_order)
         z = rz + h + xs + ys
         c_kind, c_ref = (OUT, 0) if k == len(steps) - 1 else (ARENA, new_buf(size(z)))
+        if scaling is not None:
+            # a stored result is summed into a float32 staging buffer (2 storage elements per element) and narrowed
+            # from there: live beside the operands and the result for this step alone.  Allocated after everything
+            # else of the step and released at once, it leaves every other offset as the plan without scaling has it.
+            stage.append(new_buf(2 * size(z)) if c_kind == ARENA else -1)
+            if c_kind == ARENA:
+                events.append(("free", stage[-1]))
         op = dict(h=h, x=xs, y=ys, s=s_order, form_a=form_a, form_b=form_b, H=H, M=M, N=N, K=K)
         if projs is not None:
             R = size(rz)
@@ -474,12 +565,14 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
                 row_steps.append([R, size(ra), at[0], size(rb), at[1]])
                 op.update(R=R, folded=False, a_map=maps[0], b_map=maps[1])
         rows.append([A.kind, A.ref, *((K, 1) if form_a == 0 else (1, M)),
-                     B.kind, B.ref, *((N, 1) if form_b == 0 else (1, K)), c_kind, c_ref, H, M, N, K, 0, 0])
+                     B.kind, B.ref, *((N, 1) if form_b == 0 else (1, K)), c_kind, c_ref, H, M, N, K,
+                     *((A.slot, B.slot) if scaling is not None else (0, 0))])
         ops.append(op)
         for T in (A, B):
             if T.kind == ARENA:
                 events.append(("free", T.ref))
         live.append(_Live(z, ARENA, c_ref))
+        live[-1].slot = len(ts_inds) + k
 
     arena, offset = _Arena(), {}
     for what, buf in front + events:
@@ -504,6 +597,9 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
              slice_dims=slice_dims, block_inds=tuple(x for x in slice_inds if x in final), leaf_numel=leaf_numel,
              leaf_sl=leaf_sl, perms=perm_tab, steps=step_tab, arena_elems=arena.peak, out_numel=size(final),
              macs_per_slice=macs, slice_range=(lo, hi), ops=ops, storage=storage)
+    if scaling is not None:
+        p.scaling = scaling
+        p.stage_refs = np.array([offset[b] if b >= 0 else -1 for b in stage], np.int64)
     if projs is None:
         return p
     # the device holds the distinct rows of the final tensor; the result has one per projection, duplicates included
@@ -564,22 +660,24 @@ def _sub_output(ts_inds, leaves, output) -> frozenset:
 
 
 def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=None, device=None,
-             sparse_inds=(), projs=None, storage=None, _intermediates=()) -> ContractionResult:
+             sparse_inds=(), projs=None, storage=None, scaling=None, _intermediates=()) -> ContractionResult:
     """Contract `arrays` (numpy, in ts_inds order) along the linear `path` on the GPU; see the module docstring.
     A path that leaves several tensors gives lists in `inds` / `array` (the sliced and the projected form need one
     tensor).  `_intermediates` (contract_results): positions of arrays that are results of earlier storage-mode calls,
-    not leaves of the user: a value of theirs beyond the storage range becomes inf instead of being refused."""
+    not leaves of the user: a value of theirs beyond the storage range becomes inf instead of being refused (with
+    `scaling` they are scaled as leaves and nothing finite is beyond the range)."""
     loose = frozenset(_intermediates)
     ts_inds = [tuple(xs) for xs in ts_inds]
     arrays = [np.asarray(a) for a in arrays]
     dims = _dims_of(ts_inds, [a.shape for a in arrays])
     dtype = _compute_dtype(arrays)
     _check_storage(storage, dtype, projs)
+    _check_scaling(scaling, storage)
     steps = _check_path(path, len(ts_inds))
     final, out = tnmod.contract(steps, ts_inds, output_inds, dims)
     if len(final) == 1:
         p = plan(steps, ts_inds, [a.shape for a in arrays], out, slices=slices, slice_range=slice_range, dtype=dtype,
-                 sparse_inds=sparse_inds, projs=projs, storage=storage)
+                 sparse_inds=sparse_inds, projs=projs, storage=storage, scaling=scaling)
         return _run(p, arrays, device, loose)
     if slices:
         raise NotImplementedError("slices need a path that leaves one tensor.")
@@ -589,18 +687,24 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     for leaves, sub in _split(steps, len(ts_inds)):
         if not sub:  # a tensor the path does not touch: as the single-leaf plan gives it, rounded to storage
             a = arrays[leaves[0]].astype(dtype, copy=True)
+            if scaling is not None:
+                a, e = scale_to_storage(a, storage)
+                parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, scaling=scaling, exponents=(e,)))
+                continue
             if storage is not None:
                 a = _from_storage_bits(_storage_bits(a, storage, leaves[0] not in loose), storage, a)
             parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0))
             continue
         parts.append(contract(sub, [ts_inds[t] for t in leaves], [arrays[t].astype(dtype, copy=False) for t in leaves],
-                              _sub_output(ts_inds, leaves, out), device=device, storage=storage,
+                              _sub_output(ts_inds, leaves, out), device=device, storage=storage, scaling=scaling,
                               _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
     assert [tuple(r.inds) for r in parts] == [tuple(f) for f in final]
     return ContractionResult([r.inds for r in parts], [r.array for r in parts], sum(r.macs for r in parts), 1,
                              max(r.peak_device_bytes for r in parts), sum(r.launches for r in parts),
                              kernel_launches=_add_counts(*(r.kernel_launches for r in parts)),
-                             row_kernel_launches=_add_counts(*(r.row_kernel_launches for r in parts)))
+                             row_kernel_launches=_add_counts(*(r.row_kernel_launches for r in parts)), scaling=scaling,
+                             exponents=None if scaling is None else [r.exponents for r in parts],
+                             narrow_launches=sum(r.narrow_launches for r in parts))
 
 
 def _add_counts(*counts) -> tuple:
@@ -610,7 +714,11 @@ def _add_counts(*counts) -> tuple:
 def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
     from . import _lib, parallel
     leaves = [np.ascontiguousarray(a, dtype=p.dtype) for a in arrays]
-    if p.storage is not None:  # (before the device is touched: a leaf beyond the storage type's range is refused)
+    leaf_exps = None
+    if p.scaling is not None:  # one exponent per leaf; nothing finite is beyond the range
+        leaves, leaf_exps = (list(q) for q in zip(*(_scaled_bits(a, p.storage) for a in leaves)))
+        leaf_exps = np.array(leaf_exps, np.int32)
+    elif p.storage is not None:  # (before the device is touched: a leaf beyond the storage type's range is refused)
         leaves = [_storage_bits(a, p.storage, t not in loose) for t, a in enumerate(leaves)]
     L = _lib.load()
     device = parallel.local_device() if device is None else int(device)
@@ -636,9 +744,15 @@ def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
     if p.row_steps is not None:
         keep.update(row_steps=np.ascontiguousarray(p.row_steps), row_maps=np.ascontiguousarray(p.row_maps))
         d.row_steps, d.n_row_maps, d.row_maps = i64p(keep["row_steps"]), p.row_maps.size, i64p(keep["row_maps"])
+    if p.scaling is not None:
+        keep.update(stage_refs=np.ascontiguousarray(p.stage_refs, np.int64))
+        d.scaling, d.stage_refs = 1, i64p(keep["stage_refs"])
     h = C.c_void_p()
     _lib.check(L.tnco_hip_contract_create(C.byref(d), C.byref(h)))
+    exponents, narrow = None, 0
     try:
+        if p.scaling is not None:
+            _lib.check(L.tnco_hip_contract_set_exponents(h, leaf_exps.ctypes.data_as(C.c_void_p)))
         staging = np.empty(p.out_numel, p.dtype)
         ptrs = (C.c_void_p * max(1, len(leaves)))(*[a.ctypes.data for a in leaves])
         _lib.check(L.tnco_hip_contract_run(h, ptrs, staging.ctypes.data_as(C.c_void_p)))
@@ -648,12 +762,19 @@ def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
         _lib.check(L.tnco_hip_contract_kernel_launches(h, by_kernel.ctypes.data_as(C.c_void_p)))
         by_row_kernel = np.zeros(len(ROW_KERNEL_PATHS), np.int64)
         _lib.check(L.tnco_hip_contract_row_launches(h, by_row_kernel.ctypes.data_as(C.c_void_p)))
+        if p.scaling is not None:
+            slots = np.zeros(len(leaves) + len(p.steps), np.int32)
+            _lib.check(L.tnco_hip_contract_exponents(h, slots.ctypes.data_as(C.c_void_p)))
+            count = C.c_int64()
+            _lib.check(L.tnco_hip_contract_narrow_launches(h, C.byref(count)))
+            exponents, narrow = tuple(int(v) for v in slots), int(count.value)
     finally:
         L.tnco_hip_contract_destroy(h)
     array = _host_layout(p, staging)
     return ContractionResult(p.inds, array, int(stats[0]), p.slice_range[1] - p.slice_range[0], int(stats[2]),
                              int(stats[1]), float(stats[3]) * 1e-9, kernel_launches=tuple(int(v) for v in by_kernel),
-                             row_kernel_launches=tuple(int(v) for v in by_row_kernel))
+                             row_kernel_launches=tuple(int(v) for v in by_row_kernel), scaling=p.scaling,
+                             exponents=exponents, narrow_launches=narrow)
 
 
 def _host_layout(p: Plan, staging) -> np.ndarray:
@@ -674,7 +795,7 @@ def _host_layout(p: Plan, staging) -> np.ndarray:
 
 
 def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse_inds=None,
-                     storage=None) -> ContractionResult:
+                     storage=None, scaling=None) -> ContractionResult:
     """Run a result of `Optimizer.optimize` over the arrays of the network as given.
 
     tn0: the network before pre-fusing (`load_tn(obj, fuse=None)`); arrays: in tn0.tensors order, or {name: array}
@@ -687,8 +808,11 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     `sorted(tn.sparse_inds, key=str)` order, or in the order of `sparse_inds` when that is given.
 
     storage: "float16" / "bfloat16" runs `result.path` in storage mode (module docstring); the fuse stage, unsliced and
-    small, stays in the arrays' own precision."""
+    small, stays in the arrays' own precision.  scaling: "tensor" adds per-tensor scaling to it; the results of the fuse
+    stage, and the components' results that enter a later call, are then scaled as leaves (`exponents`: those of the
+    last call made)."""
     _check_storage(storage, np.float32, projs)
+    _check_scaling(scaling, storage)
     if (tn0.sparse_inds or tn.sparse_inds) and projs is None:
         raise NotImplementedError("sparse indices (n_projs) have an array meaning only at given projections: "
                                   "pass projs=, an integer array [P, number of sparse indices].")
@@ -720,13 +844,15 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     comp_paths = [list(q) for q in getattr(result, "disconnected_paths", ()) if q]
     if len(comp_paths) <= 1:  # one component to contract: the path with its slices, in one call
         r = contract(result.path, tn.ts_inds, arrays, tn.output_inds, slices=getattr(result, "slices", ()),
-                     device=device, sparse_inds=sparse_inds or (), projs=projs, storage=storage)
+                     device=device, sparse_inds=sparse_inds or (), projs=projs, storage=storage, scaling=scaling)
         return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
-                                 fuse_macs, r.kernel_launches, r.row_kernel_launches)
+                                 fuse_macs, r.kernel_launches, r.row_kernel_launches, r.scaling, r.exponents,
+                                 r.narrow_launches)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
     ts, n = [tuple(x) for x in tn.ts_inds], len(tn.ts_inds)
     done, results, macs, n_slices, peak, launches, device_s = set(), [], 0, 0, 0, 0, 0.0
     by_kernel = (0,) * len(KERNEL_PATHS)
+    exponents, narrow = None, 0
     n_comp_steps = 0
     for q, cut in zip(result.disconnected_paths, result.disconnected_slices):
         if not q:
@@ -734,7 +860,8 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         n_comp_steps += len(q)
         (leaves, sub), = [(lv, s) for lv, s in _split(_check_path(q, n), n) if s]
         r = contract(sub, [ts[t] for t in leaves], [arrays[t] for t in leaves], _sub_output(ts, leaves, tn.output_inds),
-                     slices=cut, device=device, storage=storage)
+                     slices=cut, device=device, storage=storage, scaling=scaling)
+        exponents, narrow = r.exponents, narrow + r.narrow_launches
         done |= set(leaves)
         results.append(r)
         macs, n_slices, launches = macs + r.macs, n_slices + r.n_slices, launches + r.launches
@@ -748,12 +875,14 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     tail = result.path[n_comp_steps:]
     if tail:
         r = contract(tail, state_inds, state_arrays, frozenset(tn.output_inds) & {x for xs in state_inds for x in xs},
-                     device=device, storage=storage,
+                     device=device, storage=storage, scaling=scaling,
                      _intermediates=range(len(state_arrays) - len(results), len(state_arrays)))
+        exponents, narrow = r.exponents, narrow + r.narrow_launches
         macs, launches, peak = macs + r.macs, launches + r.launches, max(peak, r.peak_device_bytes)
         device_s += r.device_s
         by_kernel = _add_counts(by_kernel, r.kernel_launches)
         inds, array = r.inds, r.array
     else:
         inds, array = (state_inds[0], state_arrays[0]) if len(state_inds) == 1 else (state_inds, state_arrays)
-    return ContractionResult(inds, array, macs, n_slices, peak, launches, device_s, fuse_macs, by_kernel)
+    return ContractionResult(inds, array, macs, n_slices, peak, launches, device_s, fuse_macs, by_kernel,
+                             scaling=scaling, exponents=exponents, narrow_launches=narrow)

@@ -12,8 +12,10 @@
 //                          maps (tnco_hip.h, row_steps).  Steps without a row axis do not come here.
 // Storage mode (dtype codes 4..7, contract_half.h): leaves and intermediates in float16 / bfloat16, sums in float32; its
 // tiled class runs on the matrix cores (ct_mfma_tiled_kernel), dot, stream and gather are the bodies below with a
-// widening load.  Steps with a row axis do not come there.
-// No atomics: every sum runs in one fixed order, so a run is bit-reproducible.
+// widening load.  Steps with a row axis do not come there.  With per-tensor scaling (contract_half.h) a stored result
+// passes through a float32 staging buffer of the arena and ct_scale_narrow_kernel.
+// No atomics in any sum: every sum runs in one fixed order, so a run is bit-reproducible (the one atomic, the integer max
+// behind a scaled tensor's exponent, does not depend on order).
 #include "../../include/tnco_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -104,8 +106,9 @@ struct GatherArgs {
 };
 
 // D: the element as it is written, SI: as it is read (another type only where storage is widened into the output)
-template <class D, class SI>
-__device__ inline void ct_gather_body(const GatherArgs& g) {
+// SC: the source is widened and scaled by its exponent, exps[leaf] (a scaled plan without steps: its single leaf)
+template <class D, class SI, bool SC = false>
+__device__ inline void ct_gather_body(const GatherArgs& g, const int32_t* exps = nullptr) {
   const int64_t* row = g.rows + (int64_t)blockIdx.y * PERM_W;
   const int64_t numel = row[5];
   const int nd = (int)row[4];
@@ -122,6 +125,8 @@ __device__ inline void ct_gather_body(const GatherArgs& g) {
     src = (const SI*)g.arena + row[1];
   }
   D* dst = row[2] == K_ARENA ? (D*)g.arena + row[3] : (D*)g.out + g.out_off;
+  [[maybe_unused]] int sh = 0;
+  if constexpr (SC) sh = row[0] == K_LEAF ? exps[row[1]] : 0;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (int64_t)gridDim.x * blockDim.x) {
     int64_t rem = e, off = base;
     for (int k = nd - 1; k >= 0; --k) {
@@ -129,7 +134,8 @@ __device__ inline void ct_gather_body(const GatherArgs& g) {
       off += (rem - q * d) * row[8 + CT_MAX_AXES + k];
       rem = q;
     }
-    dst[e] = ct_load(src + off);
+    if constexpr (SC) dst[e] = ct_ldexp(ct_load(src + off), sh);
+    else dst[e] = ct_load(src + off);
   }
 }
 
@@ -143,6 +149,10 @@ __global__ __launch_bounds__(256) void ct_gather_kernel(GatherArgs g) {
 template <class D, class SI>
 __global__ __launch_bounds__(256) void ct_half_gather_kernel(GatherArgs g) {
   ct_gather_body<D, SI>(g);
+}
+template <class D, class SI>
+__global__ __launch_bounds__(256) void ct_half_gather_scaled_kernel(GatherArgs g, const int32_t* exps) {
+  ct_gather_body<D, SI, true>(g, exps);
 }
 
 template <class T>
@@ -219,18 +229,24 @@ __global__ __launch_bounds__(256) void ct_gemm_tiled_kernel(GemmArgs<T> p) {
 }
 
 // E: the element as the operands hold it, P: GemmArgs<E>, or HalfGemmArgs<E> (sums in float32, contract_half.h)
-template <class E, class P>
+// SC: per-tensor scaling of a storage-mode step (contract_half.h: ct_store_scaled, ct_amax_finish)
+template <class E, class P, bool SC = false>
 __device__ inline void ct_stream_body(const P& p) {
   using T = ct_acc_t<E>;
   const int64_t total = p.H * p.M * p.N;
+  [[maybe_unused]] uint32_t mx = 0;
+  [[maybe_unused]] int sh = 0;
+  if constexpr (SC) sh = ct_scale_shift(p);
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int64_t n = e % p.N, r = e / p.N, m = r % p.M, h = r / p.M;
     const E* a = p.A + h * p.M * p.K + m * p.a_m;
     const E* b = p.B + h * p.K * p.N + n * p.b_n;
     T acc = ct_zero<T>();
     for (int64_t k = 0; k < p.K; ++k) acc = ct_mac(acc, ct_load(a + k * p.a_k), ct_load(b + k * p.b_k));
-    ct_store(p, e, acc);
+    if constexpr (SC) ct_store_scaled(p, e, acc, sh, mx);
+    else ct_store(p, e, acc);
   }
+  if constexpr (SC) ct_amax_finish(p.amax, mx);
 }
 
 template <class T>
@@ -238,17 +254,20 @@ __global__ __launch_bounds__(256) void ct_gemm_stream_kernel(GemmArgs<T> p) {
   ct_stream_body<T>(p);
 }
 
-template <class E>
+template <class E, bool SC>
 __global__ __launch_bounds__(256) void ct_half_stream_kernel(HalfGemmArgs<E> p) {
-  ct_stream_body<E>(p);
+  ct_stream_body<E, HalfGemmArgs<E>, SC>(p);
 }
 
-template <class E, class P>
+template <class E, class P, bool SC = false>
 __device__ inline void ct_dot_body(const P& p) {
   using T = ct_acc_t<E>;
   __shared__ T part[256];
   const int tid = threadIdx.x;
   const int64_t total = p.H * p.M * p.N;
+  [[maybe_unused]] uint32_t mx = 0;  // (of thread 0, which stores)
+  [[maybe_unused]] int sh = 0;
+  if constexpr (SC) sh = ct_scale_shift(p);
   for (int64_t e = blockIdx.x; e < total; e += gridDim.x) {
     const int64_t n = e % p.N, r = e / p.N, m = r % p.M, h = r / p.M;
     const E* a = p.A + h * p.M * p.K + m * p.a_m;
@@ -261,9 +280,14 @@ __device__ inline void ct_dot_body(const P& p) {
       if (tid < w) part[tid] = ct_add(part[tid], part[tid + w]);
       __syncthreads();
     }
-    if (tid == 0) ct_store(p, e, part[0]);
+    if constexpr (SC) {
+      if (tid == 0) ct_store_scaled(p, e, part[0], sh, mx);
+    } else {
+      if (tid == 0) ct_store(p, e, part[0]);
+    }
     __syncthreads();
   }
+  if constexpr (SC) ct_amax_finish(p.amax, mx);
 }
 
 template <class T>
@@ -271,9 +295,9 @@ __global__ __launch_bounds__(256) void ct_gemm_dot_kernel(GemmArgs<T> p) {
   ct_dot_body<T>(p);
 }
 
-template <class E>
+template <class E, bool SC>
 __global__ __launch_bounds__(256) void ct_half_dot_kernel(HalfGemmArgs<E> p) {
-  ct_dot_body<E>(p);
+  ct_dot_body<E, HalfGemmArgs<E>, SC>(p);
 }
 
 // A step with a row axis: row r of the result reads row a_map[r] of A and row b_map[r] of B.  A null map with a row
@@ -410,6 +434,12 @@ struct tnco_hip_contract_s {
   std::vector<int64_t> group_first, group_count, group_max;  // perm rows of group g at index g + 1
   std::vector<int64_t> row_steps;  // [n_steps][ROW_W], empty: no step has a row axis
   std::vector<int32_t> row_maps;
+  int scaling = 0;                 // per-tensor scaling of a storage dtype (tnco_hip.h)
+  std::vector<int64_t> stage_refs;  // [n_steps]: arena offset of a stored step's float32 staging buffer, -1: none
+  std::vector<int32_t> leaf_exps;  // the leaves' exponents (tnco_hip_contract_set_exponents)
+  int32_t* d_exps = nullptr;       // [n_leaves + n_steps] exponent slots
+  uint32_t* d_amax = nullptr;      // [n_steps] max words
+  int64_t narrow_launches = 0;     // launches of ct_scale_narrow_kernel in the last run
   int64_t arena_elems = 0, out_numel = 0, block_numel = 1, n_blocks = 1, start = 0, stop = 1;
   char* d_leaves = nullptr;  // every leaf, back to back
   void* d_arena = nullptr;
@@ -447,6 +477,9 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
   const int64_t L = d->n_leaves, P = d->n_perms, S = d->n_steps;
   if (d->dtype < 0 || d->dtype > 7) return "'dtype' is not valid.";
   if (d->dtype > 3 && (d->row_steps || d->n_row_maps)) return "row axes are not supported with a storage dtype.";
+  if (d->scaling != 0 && d->scaling != 1) return "'scaling' is not valid.";
+  if (d->scaling && d->dtype < 4) return "scaling needs a storage dtype.";
+  if (d->scaling && S > 0 && !d->stage_refs) return "null table.";
   if (d->max_axes != CT_MAX_AXES) return "'max_axes' must be 32.";
   if (L < 0 || P < 0 || S < 0 || d->n_slice_dims < 0 || d->n_block < 0 || d->arena_elems < 0 || d->out_numel < 1)
     return "negative sizes.";
@@ -460,6 +493,8 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
   c->leaf_sl.assign(d->leaf_sl, d->leaf_sl + L * LEAF_SL_W);
   c->perms.assign(d->perms, d->perms + P * PERM_W);
   c->steps.assign(d->steps, d->steps + S * STEP_W);
+  c->scaling = d->scaling;
+  if (d->scaling) c->stage_refs.assign(d->stage_refs, d->stage_refs + S);
   c->slice_dims.assign(d->slice_dims, d->slice_dims + d->n_slice_dims);
   c->block.assign(d->block_slices, d->block_slices + d->n_block);
   const int64_t NS = d->n_slice_dims;
@@ -557,6 +592,13 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
         return "step operand kind is not valid.";
       }
     }
+    if (c->scaling) {  // the operands' exponent slots: a leaf's own, or that of an earlier step's result
+      for (int side = 0; side < 2; ++side) {
+        const int64_t slot = st[14 + side];
+        // (an operand in the arena: an earlier step's result, or a leaf that a gather moved there)
+        if (st[4 * side] == K_LEAF ? slot != st[4 * side + 1] : (slot < 0 || slot >= L + k)) return "step exponent slot is not valid.";
+      }
+    }
     const int64_t nc = R * H * M * N;
     if (st[8] == K_OUT) {
       if (k != S - 1 || nc != c->block_numel) return "only the last step writes the output, one block.";
@@ -564,6 +606,13 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
       if (st[9] < 0 || st[9] + nc > c->arena_elems) return "step result out of range.";
       for (int side = 0; side < 2; ++side)
         if (lo[side] >= 0 && st[9] < hi[side] && lo[side] < st[9] + nc) return "step result overlaps an operand.";
+      if (c->scaling) {  // the float32 staging buffer: 2 nc storage elements, apart from the operands and the result
+        const int64_t sg = c->stage_refs[k];
+        if (sg < 0 || sg % 8 || st[9] % 8 || sg + 2 * nc > c->arena_elems) return "step staging out of range.";
+        if (sg < st[9] + nc && st[9] < sg + 2 * nc) return "step staging overlaps the result.";
+        for (int side = 0; side < 2; ++side)
+          if (lo[side] >= 0 && sg < hi[side] && lo[side] < sg + 2 * nc) return "step staging overlaps an operand.";
+      }
     } else {
       return "the last step must write the output.";
     }
@@ -571,7 +620,7 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
   return nullptr;
 }
 
-template <class D, class SI = D, bool half = false>
+template <class D, class SI = D, bool half = false, bool scaled = false>
 int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t out_off) {
   const int64_t n = c->group_count[group + 1];
   if (!n) return TNCO_HIP_OK;
@@ -586,6 +635,9 @@ int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t o
   const int64_t blocks = std::min<int64_t>((c->group_max[group + 1] + 255) / 256, 2048);
   if constexpr (!half)
     hipLaunchKernelGGL(ct_gather_kernel<D>, dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, c->stream, g);
+  else if constexpr (scaled)
+    hipLaunchKernelGGL((ct_half_gather_scaled_kernel<D, SI>), dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, c->stream, g,
+                       (const int32_t*)c->d_exps);
   else
     hipLaunchKernelGGL((ct_half_gather_kernel<D, SI>), dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, c->stream, g);
   CT_TRY(hipGetLastError());
@@ -623,7 +675,7 @@ int launch_gemm(tnco_hip_contract_s* c, const GemmArgs<T>& p) {
 }
 
 // launch_gemm in storage mode: the same shape classes and slots, the tiled class on the matrix cores
-template <class S, bool CPLX>
+template <class S, bool CPLX, bool SC>
 int launch_half_gemm(tnco_hip_contract_s* c, HalfGemmArgs<typename std::conditional<CPLX, cplx<S>, S>::type> p) {
   using E = typename std::conditional<CPLX, cplx<S>, S>::type;
   const bool ak = p.a_k == 1, bn = p.b_n == 1;
@@ -635,17 +687,17 @@ int launch_half_gemm(tnco_hip_contract_s* c, HalfGemmArgs<typename std::conditio
   if (p.M >= 64 && p.N >= 64 && p.K > 32) {
     const int64_t tiles = p.H * ((p.M + HB - 1) / HB) * ((p.N + HB - 1) / HB);
     const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20));
-    if (ak && bn) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, true, true>), grid, dim3(256), 0, c->stream, p);
-    else if (ak) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, true, false>), grid, dim3(256), 0, c->stream, p);
-    else if (bn) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, false, true>), grid, dim3(256), 0, c->stream, p);
-    else hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, false, false>), grid, dim3(256), 0, c->stream, p);
+    if (ak && bn) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, true, true, SC>), grid, dim3(256), 0, c->stream, p);
+    else if (ak) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, true, false, SC>), grid, dim3(256), 0, c->stream, p);
+    else if (bn) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, false, true, SC>), grid, dim3(256), 0, c->stream, p);
+    else hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, false, false, SC>), grid, dim3(256), 0, c->stream, p);
     path = 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0);
   } else if (p.K >= 512 && outs <= 8192) {
-    hipLaunchKernelGGL(ct_half_dot_kernel<E>, dim3((unsigned)outs), dim3(256), 0, c->stream, p);
+    hipLaunchKernelGGL((ct_half_dot_kernel<E, SC>), dim3((unsigned)outs), dim3(256), 0, c->stream, p);
     path = 5;
   } else {
     const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16));
-    hipLaunchKernelGGL(ct_half_stream_kernel<E>, grid, dim3(256), 0, c->stream, p);
+    hipLaunchKernelGGL((ct_half_stream_kernel<E, SC>), grid, dim3(256), 0, c->stream, p);
     path = 6;
   }
   CT_TRY(hipGetLastError());
@@ -700,7 +752,11 @@ int run_impl(tnco_hip_contract_s* c) {
     const int beta = visited[blk];
     visited[blk] = 1;
     const int64_t out_off = blk * c->block_numel;
-    int rc = half && S == 0 ? launch_gathers<T, E, half>(c, -1, sid, out_off) : launch_gathers<W, W, half>(c, -1, sid, out_off);
+    // scaling: the max words of every step are cleared at the start of an assignment, in stream order after the narrowing
+    // passes of the one before
+    if (half && c->scaling && S) CT_TRY(hipMemsetAsync(c->d_amax, 0, (size_t)S * sizeof(uint32_t), c->stream));
+    int rc = half && S == 0 ? (c->scaling ? launch_gathers<T, E, half, half>(c, -1, sid, out_off) : launch_gathers<T, E, half>(c, -1, sid, out_off))
+                            : launch_gathers<W, W, half>(c, -1, sid, out_off);
     if (rc) return rc;
     for (int64_t k = 0; k < S; ++k) {
       if ((rc = launch_gathers<W, W, half>(c, k, sid, out_off))) return rc;
@@ -720,7 +776,27 @@ int run_impl(tnco_hip_contract_s* c) {
         p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
         p.beta = st[8] == K_OUT ? beta : 0;
         p.a_vec = p.b_vec = 0;
-        if ((rc = launch_half_gemm<typename ct_storage_of<E>::type, sizeof(E) == 4>(c, p))) return rc;
+        p.exps = nullptr, p.sa = p.sb = 0, p.amax = nullptr;
+        using St = typename ct_storage_of<E>::type;
+        if (!c->scaling) {
+          if ((rc = launch_half_gemm<St, sizeof(E) == 4, false>(c, p))) return rc;
+          continue;
+        }
+        const int64_t L = (int64_t)c->leaf_numel.size();
+        p.exps = c->d_exps, p.sa = (int)st[14], p.sb = (int)st[15];
+        if (st[8] != K_OUT) {  // unrounded to the staging buffer, then narrowed at the exponent of the whole result
+          p.Cs = nullptr, p.C = (T*)(arena + c->stage_refs[k]), p.amax = c->d_amax + k;
+        }
+        if ((rc = launch_half_gemm<St, sizeof(E) == 4, true>(c, p))) return rc;
+        if (st[8] != K_OUT) {
+          const int64_t nc = p.H * p.M * p.N, quads = nc * (sizeof(E) == 4 ? 2 : 1) / 4;
+          const dim3 grid((unsigned)std::min<int64_t>(std::max<int64_t>((quads + 255) / 256, 1), 2048));
+          hipLaunchKernelGGL((ct_scale_narrow_kernel<St, sizeof(E) == 4>), grid, dim3(256), 0, c->stream, (const float*)p.C,
+                             (St*)(arena + st[9]), nc, (const uint32_t*)p.amax, c->d_exps, p.sa, p.sb, (int)(L + k));
+          CT_TRY(hipGetLastError());
+          c->launches += 1;
+          c->narrow_launches += 1;
+        }
         continue;
       } else {
       T* dest = st[8] == K_OUT ? out + out_off : arena + st[9];
@@ -775,7 +851,9 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
   const size_t arena = (size_t)std::max<int64_t>(c->arena_elems, 1) * c->elem, outb = (size_t)c->out_numel * c->out_elem;
   const size_t ptrs = std::max<size_t>(c->leaf_numel.size(), 1) * sizeof(void*);
   const size_t maps = c->row_maps.size() * sizeof(int32_t);
-  c->bytes = (int64_t)(leaves + arena + outb + n_tab * 8 + ptrs + maps);
+  const size_t n_slots = c->leaf_numel.size() + c->steps.size() / STEP_W, n_words = c->steps.size() / STEP_W;
+  const size_t scale_b = c->scaling ? 4 * (n_slots + n_words) : 0;  // exponent slots, then the steps' max words
+  c->bytes = (int64_t)(leaves + arena + outb + n_tab * 8 + ptrs + maps + scale_b);
   auto bail = [&](int code, const std::string& msg) {
     tnco_hip_contract_destroy(c);
     return fail(code, msg);
@@ -792,8 +870,15 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
       hipMalloc(&c->d_arena, arena) != hipSuccess || hipMalloc(&c->d_out, outb) != hipSuccess ||
       hipMalloc((void**)&c->d_tables, std::max<size_t>(n_tab, 1) * 8) != hipSuccess ||
       hipMalloc((void**)&c->d_leaf_ptrs, ptrs) != hipSuccess ||
-      (maps && hipMalloc((void**)&c->d_row_maps, maps) != hipSuccess))
+      (maps && hipMalloc((void**)&c->d_row_maps, maps) != hipSuccess) ||
+      (c->scaling && hipMalloc((void**)&c->d_exps, std::max<size_t>(scale_b, 4)) != hipSuccess))
     return bail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+  if (c->scaling) {
+    c->d_amax = (uint32_t*)(c->d_exps + n_slots);
+    c->leaf_exps.assign(c->leaf_numel.size(), 0);
+    if (hipMemsetAsync(c->d_exps, 0, std::max<size_t>(scale_b, 4), c->stream) != hipSuccess)
+      return bail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+  }
   std::vector<int64_t> tab;
   tab.reserve(n_tab);
   for (auto* v : {&c->perms, &c->leaf_sl, &c->place, &c->slice_dims}) tab.insert(tab.end(), v->begin(), v->end());
@@ -820,7 +905,9 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
                           hipMemcpyHostToDevice, c->stream));
   }
   CT_TRY(hipMemsetAsync(c->d_out, 0, (size_t)c->out_numel * c->out_elem, c->stream));
-  c->macs = c->launches = 0;
+  if (c->scaling && !c->leaf_exps.empty())
+    CT_TRY(hipMemcpyAsync(c->d_exps, c->leaf_exps.data(), c->leaf_exps.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  c->macs = c->launches = c->narrow_launches = 0;
   std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
   std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
   CT_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -860,10 +947,34 @@ int tnco_hip_contract_row_launches(tnco_hip_contract c, int64_t* counts) {
   return TNCO_HIP_OK;
 }
 
+int tnco_hip_contract_set_exponents(tnco_hip_contract c, const int32_t* exps) {
+  if (!c || (!exps && !c->leaf_numel.empty())) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (!c->scaling) return fail(TNCO_HIP_EINVAL, "the plan has no scaling.");
+  c->leaf_exps.assign(exps, exps + c->leaf_numel.size());
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_exponents(tnco_hip_contract c, int32_t* exps) {
+  if (!c || !exps) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (!c->scaling) return fail(TNCO_HIP_EINVAL, "the plan has no scaling.");
+  CT_TRY(hipSetDevice(c->device));
+  const size_t n = c->leaf_numel.size() + c->steps.size() / STEP_W;
+  if (n) CT_TRY(hipMemcpyAsync(exps, c->d_exps, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  CT_TRY(hipStreamSynchronize(c->stream));
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_narrow_launches(tnco_hip_contract c, int64_t* count) {
+  if (!c || !count) return fail(TNCO_HIP_EINVAL, "null argument.");
+  *count = c->narrow_launches;
+  return TNCO_HIP_OK;
+}
+
 void tnco_hip_contract_destroy(tnco_hip_contract c) {
   if (!c) return;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (void* p : {(void*)c->d_leaves, c->d_arena, c->d_out, (void*)c->d_tables, (void*)c->d_leaf_ptrs, (void*)c->d_row_maps})
+  for (void* p : {(void*)c->d_leaves, c->d_arena, c->d_out, (void*)c->d_tables, (void*)c->d_leaf_ptrs, (void*)c->d_row_maps,
+                  (void*)c->d_exps})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);

@@ -5,6 +5,12 @@
 //   ct_mfma_tiled_kernel   the tiled shape class on the matrix cores (v_mfma_f32_16x16x32_{f16,bf16});
 //   the dot and stream classes and the gathers are the bodies of contract.hip, instantiated with a widening load and a
 //   store chosen by the destination.
+// Per-tensor scaling (tnco_hip_contract_desc.scaling): every stored tensor has one int32 exponent e in a device array,
+// stored = round(x 2^-e), e = floor(log2 m) - 14 with m the largest finite |part| of the tensor (ct_scale_exponent).  The
+// SC instantiations of the three GEMM kernels write an arena-destined result unrounded to a float32 staging buffer and
+// keep the largest sign-cleared bit pattern of its finite parts (one atomicMax per wavefront into the step's max word);
+//   ct_scale_narrow_kernel derives the exponent from that word, rounds the staged values to storage and records it.
+// A result for the output is scaled back with ldexpf by the operands' exponents.
 #pragma once
 
 struct st_f16 {
@@ -58,8 +64,27 @@ __device__ inline void ct_narrow(cplx<float> x, cplx<S>* d) {
   ct_narrow(x.im, &d->im);
 }
 
+// the exponent of a tensor whose largest finite |part| has the float32 bit pattern m (sign cleared, m < 0x7f800000):
+// floor(log2 m) - 14, float32 subnormals included; 0 for m == 0 (a zero tensor, or none of its parts finite).  The one
+// statement of the rule on the device; contraction.py scale_exponent is the same integer arithmetic on the host.
+__host__ __device__ inline int32_t ct_scale_exponent(uint32_t m) {
+  if (m == 0) return 0;
+  const int32_t lg = (m >> 23) ? (int32_t)(m >> 23) - 127 : (31 - __builtin_clz(m)) - 149;
+  return lg - 14;
+}
+__device__ inline float ct_ldexp(float x, int e) { return ldexpf(x, e); }
+__device__ inline cplx<float> ct_ldexp(cplx<float> x, int e) { return cplx<float>{ldexpf(x.re, e), ldexpf(x.im, e)}; }
+// the sign-cleared pattern of a finite part, 0 for inf and NaN; of a pair: the larger
+__device__ inline uint32_t ct_finite_bits(float x) {
+  const uint32_t u = __float_as_uint(x) & 0x7fffffffu;
+  return u < 0x7f800000u ? u : 0u;
+}
+__device__ inline uint32_t ct_finite_bits(cplx<float> x) { return max(ct_finite_bits(x.re), ct_finite_bits(x.im)); }
+
 // GemmArgs of a storage-mode step: operands in storage, the result to the arena in storage (Cs) or to the output in
-// float32 (C, with beta); exactly one of the two is set
+// float32 (C, with beta); exactly one of the two is set.  Scaling (the SC instantiations; the others read none of it):
+// exps, the exponent slots of the handle, sa and sb the operands' slots; a result for the output is C with exps set, a
+// result for the arena is C = the float32 staging buffer with beta 0 and amax = the step's max word
 template <class E>
 struct HalfGemmArgs {
   const E* A;
@@ -70,6 +95,9 @@ struct HalfGemmArgs {
   int64_t H, M, N, K;
   int beta;
   int a_vec, b_vec;  // the operand's runs of 8 elements along its contiguous axis are 16-byte aligned
+  const int32_t* exps;
+  int sa, sb;
+  uint32_t* amax;
 };
 
 template <class E>
@@ -78,8 +106,33 @@ __device__ inline void ct_store(const HalfGemmArgs<E>& p, int64_t e, ct_acc_t<E>
   else p.C[e] = p.beta ? ct_add(p.C[e], acc) : acc;
 }
 
+// ... of an SC instantiation.  sh: exps[sa] + exps[sb], read once per lane (ct_scale_shift); mx: the lane's running max
+template <class E>
+__device__ inline int ct_scale_shift(const HalfGemmArgs<E>& p) {
+  return p.amax ? 0 : p.exps[p.sa] + p.exps[p.sb];
+}
+template <class E>
+__device__ inline void ct_store_scaled(const HalfGemmArgs<E>& p, int64_t e, ct_acc_t<E> acc, int sh, uint32_t& mx) {
+  if (p.amax) {
+    p.C[e] = acc;
+    mx = max(mx, ct_finite_bits(acc));
+  } else {
+    acc = ct_ldexp(acc, sh);
+    p.C[e] = p.beta ? ct_add(p.C[e], acc) : acc;
+  }
+}
+// the lane maxima of a wavefront reduced across its lanes, one atomicMax per wavefront (an integer max: the word does
+// not depend on the order the wavefronts arrive in).  Every lane of the wavefront comes here.
+__device__ inline void ct_amax_finish(uint32_t* amax, uint32_t mx) {
+  if (!amax) return;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, 64));
+  if ((threadIdx.x & 63) == 0 && mx) atomicMax(amax, mx);
+}
+
 typedef float ct_f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t ct_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t ct_u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 ct_f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 ct_bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -184,7 +237,8 @@ __device__ inline void ct_half_stash(uint32_t (*img)[HB][HLD], const uint32_t (&
 // (profiles/contract_timing.txt, the storage leg).  Real: 2 x 128 x 80 B = 20 KiB a block; complex: 40 KiB.  Registers: 64 accumulators real,
 // 128 complex, 32 / 80 of fragments, 16 / 32 of staging; the compiler gives about 180 real (two blocks a CU) and about
 // 300 complex (one block a CU: a wavefront per SIMD, which 64 MFMAs per k block keep busy), no scratch.
-template <class S, bool CPLX, bool AK, bool BN>
+// SC: per-tensor scaling (ct_store_scaled, and the reduction of the lane maxima after the last tile).
+template <class S, bool CPLX, bool AK, bool BN, bool SC>
 __global__ __launch_bounds__(256) void ct_mfma_tiled_kernel(HalfGemmArgs<typename std::conditional<CPLX, cplx<S>, S>::type> p) {
   using E = typename std::conditional<CPLX, cplx<S>, S>::type;
   constexpr int NP = CPLX ? 2 : 1;
@@ -193,6 +247,9 @@ __global__ __launch_bounds__(256) void ct_mfma_tiled_kernel(HalfGemmArgs<typenam
   const int tid = threadIdx.x, lane = tid % 64, wave = tid / 64;
   const int lr = lane & 15, lq = lane >> 4, wm = 64 * (wave / 2), wn = 64 * (wave % 2);
   const int64_t tm = (p.M + HB - 1) / HB, tn = (p.N + HB - 1) / HB;
+  [[maybe_unused]] uint32_t mx = 0;
+  [[maybe_unused]] int sh = 0;
+  if constexpr (SC) sh = ct_scale_shift(p);
   for (int64_t t = blockIdx.x; t < p.H * tm * tn; t += gridDim.x) {
     const int64_t h = t / (tm * tn), m0 = (t / tn % tm) * HB, n0 = t % tn * HB;
     const E* A = p.A + h * p.M * p.K;
@@ -250,8 +307,36 @@ __global__ __launch_bounds__(256) void ct_mfma_tiled_kernel(HalfGemmArgs<typenam
             ct_acc_t<E> v;
             if constexpr (CPLX) v = cplx<float>{acc[0][i][j][r], acc[NP - 1][i][j][r]};
             else v = acc[0][i][j][r];
-            ct_store(p, (h * p.M + m) * p.N + n, v);
+            if constexpr (SC) ct_store_scaled(p, (h * p.M + m) * p.N + n, v, sh, mx);
+            else ct_store(p, (h * p.M + m) * p.N + n, v);
           }
         }
   }
+  if constexpr (SC) ct_amax_finish(p.amax, mx);
+}
+
+// The narrowing pass of a scaled step whose result goes to the arena: n float32 parts of the staging buffer (a complex
+// element is two of them, interleaved there as in storage) -> 16-bit parts at dst, each round(ldexpf(x, -s)) with s the
+// rule applied to the step's max word; inf and NaN pass as they are.  Four parts per lane and trip: one 16-byte load,
+// one 8-byte store (both buffers start at multiples of 64 elements of the arena); the last n % 4 parts one lane each.
+// Thread 0 of block 0 records the result's exponent exps[sc] = exps[sa] + exps[sb] + s; the operands' slots were
+// written by earlier kernels of the stream or by the host, nobody else writes sc during this kernel.
+template <class S, bool CPLX>
+__global__ __launch_bounds__(256) void ct_scale_narrow_kernel(const float* stage, S* dst, int64_t numel, const uint32_t* amax,
+                                                              int32_t* exps, int sa, int sb, int sc) {
+  const int64_t n = numel * (CPLX ? 2 : 1);
+  const int s = ct_scale_exponent(*amax);
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  if (first == 0) exps[sc] = exps[sa] + exps[sb] + s;
+  for (int64_t q = first; q < n / 4; q += stride) {
+    const ct_f32x4 v = ((const ct_f32x4*)stage)[q];
+    S r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ct_narrow(ldexpf(v[j], -s), &r[j]);
+    ct_u32x2 w;
+    w[0] = (uint32_t)r[0].v | ((uint32_t)r[1].v << 16);
+    w[1] = (uint32_t)r[2].v | ((uint32_t)r[3].v << 16);
+    ((ct_u32x2*)dst)[q] = w;
+  }
+  for (int64_t e = n / 4 * 4 + first; e < n; e += stride) ct_narrow(ldexpf(stage[e], -s), dst + e);
 }

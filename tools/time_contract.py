@@ -183,6 +183,56 @@ def storage(lines, n, depth, max_width, max_slices):
     print("\n".join(lines[-9:]), flush=True)
 
 
+def scaling(lines, n, depth, max_width, max_slices):
+    """What per-tensor scaling costs in time, storage mode with and without it on the same box in the same run: a large
+    step whose result is stored (staging + narrowing pass) followed by a product with a few vectors, and the sliced
+    Sycamore amplitude of the storage leg."""
+    lines.append("")
+    lines.append(f"## scaling=\"tensor\" against storage mode alone, A ({n}, {n}) B ({n}, {n}) -> Z stored, Z w ({n}, 8): "
+                 "the MFMA step writes float32 staging, ct_scale_narrow_kernel rounds it to storage")
+    lines.append(f"{'dtype':>10} {'storage':>9} {'scaling':>8} {'engine s':>10} {'scaled / unscaled':>18} {'launches':>9} {'narrow':>7}")
+    rng = np.random.RandomState(5)
+    ts = [("i", "k"), ("k", "j"), ("j", "l")]
+    for dt in (np.float32, np.complex64):
+        arrays = [(_rand(shape, dt, rng) * np.float32(n ** -0.5)).astype(dt) for shape in ((n, n), (n, n), (n, 8))]
+        for st in ("float16", "bfloat16"):
+            t_plain = None
+            for sc in (None, "tensor"):
+                call = lambda st=st, sc=sc: ctr.contract([(0, 1), (0, 1)], ts, arrays, storage=st, scaling=sc)  # noqa: E731
+                r = call()
+                t = min(r.device_s, _engine_time(call))
+                t_plain = t if sc is None else t_plain
+                lines.append(f"{np.dtype(dt).name:>10} {st:>9} {str(sc):>8} {t:10.5f} {t / t_plain:18.3f} {r.launches:9d} "
+                             f"{r.narrow_launches:7d}")
+                del r
+        del arrays
+    ts, d, o = syn.sycamore53_tn(depth=depth)
+    tn0 = tnmod.TensorNetwork([tnmod.Tensor(xs, [d] * len(xs)) for xs in ts], output_inds=o)
+    tn, res = Optimizer(method="sa", max_width=max_width, seed=0).optimize(tn0, betas=(0, 50), n_steps=200, n_runs=256)
+    r0 = res[0]
+    rng = np.random.RandomState(2)
+    n_inds = len({x for xs in ts for x in xs})
+    scale = 2.0 ** (-n_inds / (2 * len(ts)))  # (as in the storage leg: the amplitude stays near 1)
+    arrays = [(_rand(tuple(d for _ in xs), np.complex64, rng) * scale).astype(np.complex64) for xs in ts]
+    fused = ctr.contract(tn.tags["fuse_path"], tn0.ts_inds, arrays, tn0.output_inds)
+    leaves = fused.array if isinstance(fused.array, list) else [fused.array]
+    p = ctr.plan(r0.path, tn.ts_inds, [a.shape for a in leaves], tn.output_inds, slices=r0.slices)
+    m = min(p.n_slices, max_slices)
+    run = lambda st, sc: ctr.contract(r0.path, tn.ts_inds, leaves, tn.output_inds, slices=r0.slices,  # noqa: E731
+                                      slice_range=(0, m), storage=st, scaling=sc)
+    base = run(None, None)
+    lines.append(f"## scaling, sliced Sycamore-53 amplitude, depth {depth}, complex64, max_width {max_width}, assignments "
+                 f"[0, {m}); storage unset: device {base.device_s:.3f} s, {base.launches} launches")
+    for st in ("float16", "bfloat16"):
+        for sc in (None, "tensor"):
+            r = run(st, sc)
+            err = float(np.linalg.norm(np.ravel(r.array - base.array)) / np.linalg.norm(np.ravel(base.array)))
+            lines.append(f"  storage={st} scaling={sc}: device {r.device_s:.3f} s, {r.launches} launches of which "
+                         f"{r.narrow_launches} narrowing passes, peak device bytes {r.peak_device_bytes}, relative error to "
+                         f"the complex64 run {err:.2e}")
+    print("\n".join(lines[-16:]), flush=True)
+
+
 def projections(lines, depth, counts, loop_max):
     """P amplitudes per call.  The network: the circuit without its 53 <x| tensors, the open wires its output and
     sparse indices.  The largest depth <= `depth` whose unsliced plan fits the free device memory at every P is used."""
@@ -250,14 +300,17 @@ def main():
     ap.add_argument("--max-slices", type=int, default=4096)
     ap.add_argument("--projs", action="store_true", help="only the projections leg, appended to --out")
     ap.add_argument("--storage", action="store_true", help="only the storage-mode leg, appended to --out")
+    ap.add_argument("--scaling", action="store_true", help="only the scaling leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs and a.storage:
-        ap.error("--projs and --storage each append one leg: run them one after the other")
+    if a.projs + a.storage + a.scaling > 1:
+        ap.error("--projs, --storage and --scaling each append one leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage:  # (the other legs' sections stay as they are)
-        if a.storage:
+    if a.projs or a.storage or a.scaling:  # (the other legs' sections stay as they are)
+        if a.scaling:
+            scaling(lines, a.n, a.depth, a.max_width, a.max_slices)
+        elif a.storage:
             storage(lines, a.n, a.depth, a.max_width, a.max_slices)
         else:
             projections(lines, a.depth, a.counts, a.loop_max)
@@ -269,6 +322,7 @@ def main():
     sycamore(lines, a.depth, a.max_width, a.max_slices)
     projections(lines, a.depth, a.counts, a.loop_max)
     storage(lines, a.n, a.depth, a.max_width, a.max_slices)
+    scaling(lines, a.n, a.depth, a.max_width, a.max_slices)
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
