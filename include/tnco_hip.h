@@ -439,6 +439,16 @@ const char* tnco_hip_comm_last_error(void);
  * stores round(acc 2^-s) with e_C = e_A + e_B + s, s the rule applied to the sums.  The step for the output adds or places
  * ldexpf(acc, e_A + e_B); a single leaf gathered into the output is widened and scaled the same way.  Permutes move 16-bit
  * values as they are.  Exponents are recomputed in every slice assignment; nothing synchronises with the host in a run.
+ *
+ * Slice batches (tnco_hip_contract_set_slice_batch): with a batch of B the run takes the assignments in groups of up to
+ * B consecutive numbers, the first group starting at slice_start, the last one possibly partial, and every step of the
+ * path is one launch per group: member b of a group (assignment first + b) is one plane of the grid and works in its own
+ * copy of the arena, at arena + b arena_elems, and with scaling in its own copy of the exponent slots and max words (the
+ * leaves' exponents the same in every copy).  The tables are those of the unbatched plan.  The last step writes the
+ * members' blocks, unrounded and with beta 0, to a staging buffer [B][block] of the output's type, and one more kernel per
+ * group adds or places them in the output, one lane per element, the members in assignment order: the sum over the
+ * assignments keeps its order, and the result is bit for bit that of the unbatched run.  Steps with row axes are not
+ * supported.  A plan without steps takes the call and runs as it does without it.
  */
 typedef struct tnco_hip_contract_s* tnco_hip_contract;
 typedef struct tnco_hip_contract_desc {
@@ -493,6 +503,15 @@ int tnco_hip_contract_set_exponents(tnco_hip_contract h, const int32_t* exps);
 int tnco_hip_contract_exponents(tnco_hip_contract h, int32_t* exps);
 /* scaling: the last run's launches of the narrowing pass; they are part of stats[1] and of none of the slots above */
 int tnco_hip_contract_narrow_launches(tnco_hip_contract h, int64_t* count);
+/* after create, before run: the runs that follow take `batch` assignments per launch (above).  EINVAL for a batch
+ * outside [1, 64] and on a handle with row axes.  Reserves `batch` arenas, the batch staging buffer of the output, and with
+ * scaling `batch` copies of the exponent slots and max words (ERUNTIME when they exceed the device's free memory; the
+ * handle then stays as it was); stats[2] counts them.  A handle on which this was never called runs unbatched.
+ * tnco_hip_contract_exponents then gives the slots of the last member of the last group */
+int tnco_hip_contract_set_slice_batch(tnco_hip_contract h, int64_t batch);
+/* the last run's launches of the kernel that folds a group's blocks into the output (one per group; 0 unbatched); they
+ * are part of stats[1] and of none of the slots above */
+int tnco_hip_contract_batch_launches(tnco_hip_contract h, int64_t* count);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

@@ -46,6 +46,16 @@ scaled the same way.  Permutes and gathers move the 16-bit values as they are.  
 inside a run, and the maximum is an integer max over sign-cleared bit patterns, so a call stays bit-reproducible.  Under
 scaling a part smaller than 2^-28 of its tensor's largest lands in float16's subnormal range or below: that is below the
 noise of the float32 sums themselves.
+
+Slice batches: with `slice_batch=B` (1 to 64) the run takes the assignments of `slice_range` in groups of up to B
+consecutive numbers, the first group starting at slice_range[0], the last one possibly partial, and every step of the
+path is one launch per group instead of one per assignment: a sliced run of small steps is bound by its launches, and
+this trades device memory for fewer and fuller ones.  Each member of a group works in its own copy of the arena (with
+scaling: of the exponent slots and max words too), mapped to lanes, tiles and k order exactly as alone; the last step
+leaves the members' blocks in a staging buffer and one more kernel per group adds or places them in the output in
+assignment order.  The result is bit for bit that of `slice_batch=None`; device memory grows by B - 1 arenas and B blocks
+of the output (`Plan.peak_device_bytes`).  The plan's tables do not change.  Projections are not supported with it; a
+plan without steps takes the keyword and runs as without it.
 """
 from __future__ import annotations
 
@@ -58,7 +68,8 @@ import numpy as np
 from .app import tn as tnmod
 
 __all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
-           "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage", "SCALINGS", "scale_exponent", "scale_to_storage"]
+           "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage", "SCALINGS", "scale_exponent", "scale_to_storage",
+           "MAX_SLICE_BATCH"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -68,6 +79,7 @@ DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex6
 STORAGES = {"float16": 4, "bfloat16": 6}
 SCALINGS = ("tensor",)  # per-tensor power-of-two scaling of storage mode (module docstring)
 SCALE_BITS = 14  # the largest stored magnitude of a scaled tensor lies in [2^14, 2^15]
+MAX_SLICE_BATCH = 64  # slice assignments per launch at most (csrc/contract.hip MAX_SLICE_BATCH)
 
 # operand / destination kinds and table widths: include/tnco_hip.h (tnco_hip_contract_desc)
 LEAF, ARENA, OUT = 0, 1, 2
@@ -99,7 +111,11 @@ class ContractionResult:
     scaling: str = None  # "tensor": per-tensor scaling of storage mode
     exponents: tuple = None  # scaling: the exponents after the last slice assignment, leaves first, then one per step
     #                          (the step that writes the output: 0); None without scaling (a list of them: as `array`)
-    narrow_launches: int = 0  # scaling: launches of the narrowing pass; `launches` is the three counts together
+    narrow_launches: int = 0  # scaling: launches of the narrowing pass
+    slice_batch: int = None  # slice assignments per launch, the effective value (`Plan.slice_batch`; of several calls
+    #                          the largest, of an unsliced call 1); None: unbatched
+    batch_launches: int = 0  # slice_batch: launches of the kernel that folds a group's blocks into the output;
+    #                          `launches` is the four counts together
 
 
 @dataclass
@@ -129,6 +145,7 @@ class Plan:
     out_rows: tuple = None  # (rows of the final tensor, row of it for each of the P projections)
     scaling: str = None  # "tensor": steps columns 14, 15 are the exponent slots of A and B (leaf t: t, step j: n_leaves + j)
     stage_refs: np.ndarray = None  # scaling: [n_steps] arena offset of a stored step's float32 staging buffer, -1 none
+    slice_batch: int = None  # assignments per launch: min(what was asked for, assignments of slice_range); 1 without steps
 
     @property
     def n_slices(self) -> int:
@@ -146,7 +163,13 @@ class Plan:
         maps = 0 if self.row_maps is None else 4 * self.row_maps.size + 8 * self.row_steps.size
         # scaling: an int32 exponent per leaf and step, a max word per step
         scale = 0 if self.scaling is None else 4 * (self.leaf_numel.size + 2 * len(self.steps))
-        return held * (int(self.leaf_numel.sum()) + self.arena_elems) + item * self.out_numel + tables + maps + scale
+        # a slice batch: an arena and the scale words per member, and a block of the output per member as staging
+        batch, stage = 1, 0
+        if self.slice_batch is not None and len(self.steps):
+            batch = self.slice_batch
+            stage = item * batch * self.out_numel // math.prod(self.shape[self.inds.index(x)] for x in self.block_inds)
+        return held * (int(self.leaf_numel.sum()) + self.arena_elems * batch) + item * self.out_numel + tables + maps + \
+            scale * batch + stage
 
 
 class _Arena:
@@ -236,6 +259,15 @@ def _check_scaling(scaling, storage) -> None:
         raise ValueError("'scaling' must be None or 'tensor'.")
     if storage is None:
         raise ValueError("'scaling' needs 'storage'.")
+
+
+def _check_slice_batch(slice_batch, projs=None) -> None:
+    if slice_batch is None:
+        return
+    if isinstance(slice_batch, bool) or not isinstance(slice_batch, int) or not 1 <= slice_batch <= MAX_SLICE_BATCH:
+        raise ValueError(f"'slice_batch' must be None or an integer from 1 to {MAX_SLICE_BATCH}.")
+    if projs is not None:
+        raise NotImplementedError("projections are not supported with 'slice_batch'.")
 
 
 def _bf16_bits(x) -> np.ndarray:
@@ -387,12 +419,13 @@ def _unique_rows(table):
 
 
 def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
-         sparse_inds=(), projs=None, storage=None, scaling=None) -> Plan:
+         sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None) -> Plan:
     """The device plan of one contraction along a path that leaves one tensor (no GPU).
-    `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`: see the module
-    docstring."""
+    `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`, `slice_batch`: see
+    the module docstring."""
     _check_storage(storage, dtype, projs)
     _check_scaling(scaling, storage)
+    _check_slice_batch(slice_batch, projs)
     ts_inds = [tuple(xs) for xs in ts_inds]
     shapes = [tuple(int(d) for d in s) for s in shapes]
     dims = _dims_of(ts_inds, shapes)
@@ -600,6 +633,8 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     if scaling is not None:
         p.scaling = scaling
         p.stage_refs = np.array([offset[b] if b >= 0 else -1 for b in stage], np.int64)
+    if slice_batch is not None:  # (the tables are those of the unbatched plan)
+        p.slice_batch = min(int(slice_batch), hi - lo) if steps else 1
     if projs is None:
         return p
     # the device holds the distinct rows of the final tensor; the result has one per projection, duplicates included
@@ -660,7 +695,8 @@ def _sub_output(ts_inds, leaves, output) -> frozenset:
 
 
 def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=None, device=None,
-             sparse_inds=(), projs=None, storage=None, scaling=None, _intermediates=()) -> ContractionResult:
+             sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None,
+             _intermediates=()) -> ContractionResult:
     """Contract `arrays` (numpy, in ts_inds order) along the linear `path` on the GPU; see the module docstring.
     A path that leaves several tensors gives lists in `inds` / `array` (the sliced and the projected form need one
     tensor).  `_intermediates` (contract_results): positions of arrays that are results of earlier storage-mode calls,
@@ -673,38 +709,42 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     dtype = _compute_dtype(arrays)
     _check_storage(storage, dtype, projs)
     _check_scaling(scaling, storage)
+    _check_slice_batch(slice_batch, projs)
     steps = _check_path(path, len(ts_inds))
     final, out = tnmod.contract(steps, ts_inds, output_inds, dims)
     if len(final) == 1:
         p = plan(steps, ts_inds, [a.shape for a in arrays], out, slices=slices, slice_range=slice_range, dtype=dtype,
-                 sparse_inds=sparse_inds, projs=projs, storage=storage, scaling=scaling)
+                 sparse_inds=sparse_inds, projs=projs, storage=storage, scaling=scaling, slice_batch=slice_batch)
         return _run(p, arrays, device, loose)
     if slices:
         raise NotImplementedError("slices need a path that leaves one tensor.")
     if projs is not None or tuple(sparse_inds):
         raise NotImplementedError("projections need a path that leaves one tensor.")
     parts = []
+    effective = None if slice_batch is None else 1  # (every part is unsliced: one assignment)
     for leaves, sub in _split(steps, len(ts_inds)):
         if not sub:  # a tensor the path does not touch: as the single-leaf plan gives it, rounded to storage
             a = arrays[leaves[0]].astype(dtype, copy=True)
             if scaling is not None:
                 a, e = scale_to_storage(a, storage)
-                parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, scaling=scaling, exponents=(e,)))
+                parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, scaling=scaling, exponents=(e,),
+                                               slice_batch=effective))
                 continue
             if storage is not None:
                 a = _from_storage_bits(_storage_bits(a, storage, leaves[0] not in loose), storage, a)
-            parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0))
+            parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, slice_batch=effective))
             continue
         parts.append(contract(sub, [ts_inds[t] for t in leaves], [arrays[t].astype(dtype, copy=False) for t in leaves],
                               _sub_output(ts_inds, leaves, out), device=device, storage=storage, scaling=scaling,
-                              _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
+                              slice_batch=slice_batch, _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
     assert [tuple(r.inds) for r in parts] == [tuple(f) for f in final]
     return ContractionResult([r.inds for r in parts], [r.array for r in parts], sum(r.macs for r in parts), 1,
                              max(r.peak_device_bytes for r in parts), sum(r.launches for r in parts),
                              kernel_launches=_add_counts(*(r.kernel_launches for r in parts)),
                              row_kernel_launches=_add_counts(*(r.row_kernel_launches for r in parts)), scaling=scaling,
                              exponents=None if scaling is None else [r.exponents for r in parts],
-                             narrow_launches=sum(r.narrow_launches for r in parts))
+                             narrow_launches=sum(r.narrow_launches for r in parts), slice_batch=effective,
+                             batch_launches=sum(r.batch_launches for r in parts))
 
 
 def _add_counts(*counts) -> tuple:
@@ -726,6 +766,16 @@ def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
         if rows is not None:  # [rows][the other axes]: the leaf at the distinct projections of its sparse indices
             axes, values = rows
             leaves[t] = np.ascontiguousarray(np.moveaxis(leaves[t], axes, range(len(axes)))[tuple(values.T)])
+    d, keep = _describe(p, device)
+    h = C.c_void_p()
+    _lib.check(L.tnco_hip_contract_create(C.byref(d), C.byref(h)))
+    del keep  # (the tables are copied by create)
+    return _run_handle(L, h, p, leaves, leaf_exps)
+
+
+def _describe(p: Plan, device: int):
+    """(the tnco_hip_contract_desc of the plan, the arrays its pointers refer to: to be kept until create returns)."""
+    from . import _lib
     i64p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     keep = dict(leaf_numel=np.ascontiguousarray(p.leaf_numel), leaf_sl=np.ascontiguousarray(p.leaf_sl),
                 perms=np.ascontiguousarray(p.perms), steps=np.ascontiguousarray(p.steps),
@@ -734,7 +784,7 @@ def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
     d = _lib.ContractDesc()
     code = DTYPES[p.dtype] if p.storage is None else STORAGES[p.storage] + (p.dtype.kind == "c")
     d.dtype, d.device, d.max_axes = code, device, MAX_AXES
-    d.n_leaves, d.leaf_numel, d.leaf_sl = len(leaves), i64p(keep["leaf_numel"]), i64p(keep["leaf_sl"])
+    d.n_leaves, d.leaf_numel, d.leaf_sl = len(p.leaf_numel), i64p(keep["leaf_numel"]), i64p(keep["leaf_sl"])
     d.n_perms, d.perms = len(p.perms), i64p(keep["perms"])
     d.n_steps, d.steps = len(p.steps), i64p(keep["steps"])
     d.arena_elems, d.out_numel = p.arena_elems, p.out_numel
@@ -747,10 +797,15 @@ def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
     if p.scaling is not None:
         keep.update(stage_refs=np.ascontiguousarray(p.stage_refs, np.int64))
         d.scaling, d.stage_refs = 1, i64p(keep["stage_refs"])
-    h = C.c_void_p()
-    _lib.check(L.tnco_hip_contract_create(C.byref(d), C.byref(h)))
-    exponents, narrow = None, 0
+    return d, keep
+
+
+def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
+    from . import _lib
+    exponents, narrow, folds = None, 0, 0
     try:
+        if p.slice_batch is not None:
+            _lib.check(L.tnco_hip_contract_set_slice_batch(h, p.slice_batch))
         if p.scaling is not None:
             _lib.check(L.tnco_hip_contract_set_exponents(h, leaf_exps.ctypes.data_as(C.c_void_p)))
         staging = np.empty(p.out_numel, p.dtype)
@@ -768,13 +823,17 @@ def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
             count = C.c_int64()
             _lib.check(L.tnco_hip_contract_narrow_launches(h, C.byref(count)))
             exponents, narrow = tuple(int(v) for v in slots), int(count.value)
+        if p.slice_batch is not None:
+            count = C.c_int64()
+            _lib.check(L.tnco_hip_contract_batch_launches(h, C.byref(count)))
+            folds = int(count.value)
     finally:
         L.tnco_hip_contract_destroy(h)
     array = _host_layout(p, staging)
     return ContractionResult(p.inds, array, int(stats[0]), p.slice_range[1] - p.slice_range[0], int(stats[2]),
                              int(stats[1]), float(stats[3]) * 1e-9, kernel_launches=tuple(int(v) for v in by_kernel),
                              row_kernel_launches=tuple(int(v) for v in by_row_kernel), scaling=p.scaling,
-                             exponents=exponents, narrow_launches=narrow)
+                             exponents=exponents, narrow_launches=narrow, slice_batch=p.slice_batch, batch_launches=folds)
 
 
 def _host_layout(p: Plan, staging) -> np.ndarray:
@@ -795,7 +854,7 @@ def _host_layout(p: Plan, staging) -> np.ndarray:
 
 
 def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse_inds=None,
-                     storage=None, scaling=None) -> ContractionResult:
+                     storage=None, scaling=None, slice_batch=None) -> ContractionResult:
     """Run a result of `Optimizer.optimize` over the arrays of the network as given.
 
     tn0: the network before pre-fusing (`load_tn(obj, fuse=None)`); arrays: in tn0.tensors order, or {name: array}
@@ -810,9 +869,11 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     storage: "float16" / "bfloat16" runs `result.path` in storage mode (module docstring); the fuse stage, unsliced and
     small, stays in the arrays' own precision.  scaling: "tensor" adds per-tensor scaling to it; the results of the fuse
     stage, and the components' results that enter a later call, are then scaled as leaves (`exponents`: those of the
-    last call made)."""
+    last call made).  slice_batch: that many slice assignments per launch in every sliced call (module docstring);
+    `batch_launches` is the sum over the calls, `slice_batch` of the result the largest effective value of a component."""
     _check_storage(storage, np.float32, projs)
     _check_scaling(scaling, storage)
+    _check_slice_batch(slice_batch, projs)
     if (tn0.sparse_inds or tn.sparse_inds) and projs is None:
         raise NotImplementedError("sparse indices (n_projs) have an array meaning only at given projections: "
                                   "pass projs=, an integer array [P, number of sparse indices].")
@@ -844,15 +905,16 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     comp_paths = [list(q) for q in getattr(result, "disconnected_paths", ()) if q]
     if len(comp_paths) <= 1:  # one component to contract: the path with its slices, in one call
         r = contract(result.path, tn.ts_inds, arrays, tn.output_inds, slices=getattr(result, "slices", ()),
-                     device=device, sparse_inds=sparse_inds or (), projs=projs, storage=storage, scaling=scaling)
+                     device=device, sparse_inds=sparse_inds or (), projs=projs, storage=storage, scaling=scaling,
+                     slice_batch=slice_batch)
         return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
                                  fuse_macs, r.kernel_launches, r.row_kernel_launches, r.scaling, r.exponents,
-                                 r.narrow_launches)
+                                 r.narrow_launches, r.slice_batch, r.batch_launches)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
     ts, n = [tuple(x) for x in tn.ts_inds], len(tn.ts_inds)
     done, results, macs, n_slices, peak, launches, device_s = set(), [], 0, 0, 0, 0, 0.0
     by_kernel = (0,) * len(KERNEL_PATHS)
-    exponents, narrow = None, 0
+    exponents, narrow, folds, effective = None, 0, 0, None
     n_comp_steps = 0
     for q, cut in zip(result.disconnected_paths, result.disconnected_slices):
         if not q:
@@ -860,8 +922,10 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         n_comp_steps += len(q)
         (leaves, sub), = [(lv, s) for lv, s in _split(_check_path(q, n), n) if s]
         r = contract(sub, [ts[t] for t in leaves], [arrays[t] for t in leaves], _sub_output(ts, leaves, tn.output_inds),
-                     slices=cut, device=device, storage=storage, scaling=scaling)
-        exponents, narrow = r.exponents, narrow + r.narrow_launches
+                     slices=cut, device=device, storage=storage, scaling=scaling, slice_batch=slice_batch)
+        exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
+        if slice_batch is not None:
+            effective = max(effective or 1, r.slice_batch)
         done |= set(leaves)
         results.append(r)
         macs, n_slices, launches = macs + r.macs, n_slices + r.n_slices, launches + r.launches
@@ -875,9 +939,9 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     tail = result.path[n_comp_steps:]
     if tail:
         r = contract(tail, state_inds, state_arrays, frozenset(tn.output_inds) & {x for xs in state_inds for x in xs},
-                     device=device, storage=storage, scaling=scaling,
+                     device=device, storage=storage, scaling=scaling, slice_batch=slice_batch,
                      _intermediates=range(len(state_arrays) - len(results), len(state_arrays)))
-        exponents, narrow = r.exponents, narrow + r.narrow_launches
+        exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
         macs, launches, peak = macs + r.macs, launches + r.launches, max(peak, r.peak_device_bytes)
         device_s += r.device_s
         by_kernel = _add_counts(by_kernel, r.kernel_launches)
@@ -885,4 +949,5 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     else:
         inds, array = (state_inds[0], state_arrays[0]) if len(state_inds) == 1 else (state_inds, state_arrays)
     return ContractionResult(inds, array, macs, n_slices, peak, launches, device_s, fuse_macs, by_kernel,
-                             scaling=scaling, exponents=exponents, narrow_launches=narrow)
+                             scaling=scaling, exponents=exponents, narrow_launches=narrow, slice_batch=effective,
+                             batch_launches=folds)

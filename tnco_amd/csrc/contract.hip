@@ -14,6 +14,14 @@
 // tiled class runs on the matrix cores (ct_mfma_tiled_kernel), dot, stream and gather are the bodies below with a
 // widening load.  Steps with a row axis do not come there.  With per-tensor scaling (contract_half.h) a stored result
 // passes through a float32 staging buffer of the arena and ct_scale_narrow_kernel.
+// Slice batches (tnco_hip_contract_set_slice_batch): B consecutive assignments per launch.  Every kernel of the slice
+// loop has a member axis, blockIdx.z = b for assignment sid0 + b (MemberArgs): member b works in its own copy of the arena
+// (and of the exponent slots and max words), reads a leaf in place at the slice offset of its own assignment, computed on
+// the device from the tables, and is mapped to lanes, tiles and k order as an unbatched launch is.  The last step writes
+// the members' blocks to a staging buffer [B][block] and
+//   ct_batch_reduce_kernel folds them into the output, one lane per element, the members in assignment order,
+// so the sum over assignments keeps its order and a batched run is bit-equal to the unbatched one.  An unbatched launch
+// is the same kernel with one member and every member stride 0.
 // No atomics in any sum: every sum runs in one fixed order, so a run is bit-reproducible (the one atomic, the integer max
 // behind a scaled tensor's exponent, does not depend on order).
 #include "../../include/tnco_hip.h"
@@ -85,6 +93,35 @@ struct ct_acc {
 template <class E>
 using ct_acc_t = typename ct_acc<E>::type;
 
+// the offset that assignment sid gives a leaf through its sliced axes (ls: the leaf's row of leaf_sl)
+__host__ __device__ inline int64_t ct_slice_offset(const int64_t* ls, const int64_t* place, const int64_t* dims, int64_t sid) {
+  int64_t off = 0;
+  for (int j = 0; j < (int)ls[0]; ++j) {
+    const int64_t s = ls[1 + j];
+    off += ((sid / place[s]) % dims[s]) * ls[1 + CT_MAX_AXES + j];
+  }
+  return off;
+}
+
+// The member axis of a GEMM launch: block z is member b = blockIdx.z, assignment sid0 + b.  Steps are in bytes between
+// two members' A, B, C (a copy of the arena, a block of the batch staging, 0 for a leaf); a leaf read in place comes
+// without a slice offset and with its row of leaf_sl, and the member adds the offset of its assignment.  All zero: an
+// unbatched launch, the operands as the host resolved them.
+struct MemberArgs {
+  const int64_t* a_ls;
+  const int64_t* b_ls;
+  const int64_t* slice_place;
+  const int64_t* slice_dims;
+  int64_t sid0;
+  int64_t a_step, b_step, c_step;
+  int exp_step, amax_step;  // exponent slots / max words between two members (scaling)
+};
+
+template <class X>
+__device__ inline X* ct_shift(X* p, int64_t bytes) {
+  return (X*)((const char*)p + bytes);
+}
+
 #include "contract_half.h"
 
 template <class E>
@@ -101,8 +138,9 @@ struct GatherArgs {
   const void* const* leaves;
   void* arena;
   void* out;
-  int64_t sid;      // the assignment
+  int64_t sid;      // the assignment (of member 0)
   int64_t out_off;  // its block of the output
+  int64_t arena_step;  // elements between two members' arenas (member b = blockIdx.z: assignment sid + b), 0 unbatched
 };
 
 // D: the element as it is written, SI: as it is read (another type only where storage is widened into the output)
@@ -114,17 +152,14 @@ __device__ inline void ct_gather_body(const GatherArgs& g, const int32_t* exps =
   const int nd = (int)row[4];
   const SI* src;
   int64_t base = 0;
+  const int64_t member = (int64_t)blockIdx.z * g.arena_step;
   if (row[0] == K_LEAF) {
-    const int64_t* ls = g.leaf_sl + row[1] * LEAF_SL_W;
-    for (int j = 0; j < (int)ls[0]; ++j) {
-      const int64_t s = ls[1 + j];
-      base += ((g.sid / g.slice_place[s]) % g.slice_dims[s]) * ls[1 + CT_MAX_AXES + j];
-    }
+    base = ct_slice_offset(g.leaf_sl + row[1] * LEAF_SL_W, g.slice_place, g.slice_dims, g.sid + blockIdx.z);
     src = (const SI*)g.leaves[row[1]];
   } else {
-    src = (const SI*)g.arena + row[1];
+    src = (const SI*)g.arena + member + row[1];
   }
-  D* dst = row[2] == K_ARENA ? (D*)g.arena + row[3] : (D*)g.out + g.out_off;
+  D* dst = row[2] == K_ARENA ? (D*)g.arena + member + row[3] : (D*)g.out + g.out_off;
   [[maybe_unused]] int sh = 0;
   if constexpr (SC) sh = row[0] == K_LEAF ? exps[row[1]] : 0;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (int64_t)gridDim.x * blockDim.x) {
@@ -163,7 +198,18 @@ struct GemmArgs {
   int64_t a_m, a_k, b_k, b_n;  // strides inside a batch; batches are dense: M K, K N, M N
   int64_t H, M, N, K;
   int beta;  // 1: C += A B, 0: C = A B
+  MemberArgs mb;
 };
+
+// the operands and the result of this block's member
+template <class T>
+__device__ inline void ct_member(GemmArgs<T>& p) {
+  const MemberArgs& mb = p.mb;
+  const int64_t b = blockIdx.z;
+  p.A = ct_shift(p.A, b * mb.a_step) + (mb.a_ls ? ct_slice_offset(mb.a_ls, mb.slice_place, mb.slice_dims, mb.sid0 + b) : 0);
+  p.B = ct_shift(p.B, b * mb.b_step) + (mb.b_ls ? ct_slice_offset(mb.b_ls, mb.slice_place, mb.slice_dims, mb.sid0 + b) : 0);
+  p.C = ct_shift(p.C, b * mb.c_step);
+}
 
 template <class T>
 __device__ inline void ct_store(const GemmArgs<T>& p, int64_t e, T acc) {
@@ -175,6 +221,7 @@ constexpr int TB = 64, TK = 16;
 // AK: A contiguous along k (A[h][m][k]), else along m; BN: B contiguous along n (B[h][k][n]), else along k
 template <class T, bool AK, bool BN>
 __global__ __launch_bounds__(256) void ct_gemm_tiled_kernel(GemmArgs<T> p) {
+  ct_member(p);
   __shared__ T As[TK][TB + 1];
   __shared__ T Bs[TK][TB + 1];
   const int tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
@@ -251,11 +298,13 @@ __device__ inline void ct_stream_body(const P& p) {
 
 template <class T>
 __global__ __launch_bounds__(256) void ct_gemm_stream_kernel(GemmArgs<T> p) {
+  ct_member(p);
   ct_stream_body<T>(p);
 }
 
 template <class E, bool SC>
 __global__ __launch_bounds__(256) void ct_half_stream_kernel(HalfGemmArgs<E> p) {
+  ct_member(p);
   ct_stream_body<E, HalfGemmArgs<E>, SC>(p);
 }
 
@@ -292,12 +341,35 @@ __device__ inline void ct_dot_body(const P& p) {
 
 template <class T>
 __global__ __launch_bounds__(256) void ct_gemm_dot_kernel(GemmArgs<T> p) {
+  ct_member(p);
   ct_dot_body<T>(p);
 }
 
 template <class E, bool SC>
 __global__ __launch_bounds__(256) void ct_half_dot_kernel(HalfGemmArgs<E> p) {
+  ct_member(p);
   ct_dot_body<E, HalfGemmArgs<E>, SC>(p);
+}
+
+// Where the members of a batch go in the output: member b adds its block of the staging buffer to the output at element
+// off[b] when bit b of beta is set, and places it there otherwise (the host's `visited` bookkeeping, by value).
+constexpr int MAX_SLICE_BATCH = 64;
+struct BatchPlace {
+  int64_t off[MAX_SLICE_BATCH];
+  uint64_t beta;
+};
+
+// stage [n][numel], as the last step of every member left it (unrounded, beta 0) -> out: one lane per element of a
+// block, the members one after the other in assignment order, each exactly the store of an unbatched last step
+// (ct_store).  Members of one batch may share a block: the lane then adds to what it wrote itself.  No atomics.
+template <class T>
+__global__ __launch_bounds__(256) void ct_batch_reduce_kernel(T* out, const T* stage, int64_t numel, int n, BatchPlace pl) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (int64_t)gridDim.x * blockDim.x)
+    for (int b = 0; b < n; ++b) {
+      T* o = out + pl.off[b] + e;
+      const T v = stage[b * numel + e];
+      *o = (pl.beta >> b) & 1 ? ct_add(*o, v) : v;
+    }
 }
 
 // A step with a row axis: row r of the result reads row a_map[r] of A and row b_map[r] of B.  A null map with a row
@@ -440,6 +512,12 @@ struct tnco_hip_contract_s {
   int32_t* d_exps = nullptr;       // [n_leaves + n_steps] exponent slots
   uint32_t* d_amax = nullptr;      // [n_steps] max words
   int64_t narrow_launches = 0;     // launches of ct_scale_narrow_kernel in the last run
+  int64_t batch = 0;               // tnco_hip_contract_set_slice_batch: assignments per launch, 0: never set
+  void* d_batch_out = nullptr;     // [batch][block_numel] of the output's type: the members' last steps
+  int64_t batch_launches = 0;      // launches of ct_batch_reduce_kernel in the last run
+  int64_t last_member = 0;         // the member that ran the last assignment of the last run (its exponent slots)
+  int64_t base_bytes = 0;          // `bytes` as create reserved them
+  std::vector<int32_t> exps_image;  // the leaves' exponents, once per member
   int64_t arena_elems = 0, out_numel = 0, block_numel = 1, n_blocks = 1, start = 0, stop = 1;
   char* d_leaves = nullptr;  // every leaf, back to back
   void* d_arena = nullptr;
@@ -457,13 +535,7 @@ struct tnco_hip_contract_s {
 namespace {
 
 int64_t leaf_slice_offset(const tnco_hip_contract_s* c, int64_t leaf, int64_t sid) {
-  const int64_t* ls = &c->leaf_sl[leaf * LEAF_SL_W];
-  int64_t off = 0;
-  for (int j = 0; j < (int)ls[0]; ++j) {
-    const int64_t s = ls[1 + j];
-    off += (sid / c->place[s]) % c->slice_dims[s] * ls[1 + CT_MAX_AXES + j];
-  }
-  return off;
+  return ct_slice_offset(&c->leaf_sl[leaf * LEAF_SL_W], c->place.data(), c->slice_dims.data(), sid);
 }
 
 int64_t leaf_slice_reach(const tnco_hip_contract_s* c, int64_t leaf) {  // the largest offset an assignment gives
@@ -621,7 +693,7 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
 }
 
 template <class D, class SI = D, bool half = false, bool scaled = false>
-int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t out_off) {
+int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t out_off, int64_t members = 0) {
   const int64_t n = c->group_count[group + 1];
   if (!n) return TNCO_HIP_OK;
   const int64_t P = (int64_t)c->perms.size() / PERM_W;
@@ -632,14 +704,15 @@ int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t o
   g.slice_dims = g.slice_place + c->place.size();
   g.leaves = (const void* const*)c->d_leaf_ptrs;
   g.arena = c->d_arena, g.out = c->d_out, g.sid = sid, g.out_off = out_off;
+  g.arena_step = members ? c->arena_elems : 0;  // (members: of a batch, 0: an unbatched launch)
   const int64_t blocks = std::min<int64_t>((c->group_max[group + 1] + 255) / 256, 2048);
+  const dim3 grid((unsigned)blocks, (unsigned)n, (unsigned)std::max<int64_t>(members, 1));
   if constexpr (!half)
-    hipLaunchKernelGGL(ct_gather_kernel<D>, dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, c->stream, g);
+    hipLaunchKernelGGL(ct_gather_kernel<D>, grid, dim3(256), 0, c->stream, g);
   else if constexpr (scaled)
-    hipLaunchKernelGGL((ct_half_gather_scaled_kernel<D, SI>), dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, c->stream, g,
-                       (const int32_t*)c->d_exps);
+    hipLaunchKernelGGL((ct_half_gather_scaled_kernel<D, SI>), grid, dim3(256), 0, c->stream, g, (const int32_t*)c->d_exps);
   else
-    hipLaunchKernelGGL((ct_half_gather_kernel<D, SI>), dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, c->stream, g);
+    hipLaunchKernelGGL((ct_half_gather_kernel<D, SI>), grid, dim3(256), 0, c->stream, g);
   CT_TRY(hipGetLastError());
   c->launches += 1;
   c->by_kernel[0] += 1;
@@ -647,63 +720,64 @@ int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t o
 }
 
 template <class T>
-int launch_gemm(tnco_hip_contract_s* c, const GemmArgs<T>& p) {
+int launch_gemm(tnco_hip_contract_s* c, const GemmArgs<T>& p, unsigned members = 1) {
   const bool ak = p.a_k == 1, bn = p.b_n == 1;
   const int64_t outs = p.H * p.M * p.N;
-  int path;  // slot of tnco_hip_contract_kernel_launches
+  int path;  // slot of tnco_hip_contract_kernel_launches; the members of a batch (grid z) do not enter the choice
   if (p.M >= 64 && p.N >= 64 && p.K > 32) {  // tiled: every operand element reused 64 times from LDS
     const int64_t tiles = p.H * ((p.M + TB - 1) / TB) * ((p.N + TB - 1) / TB);
-    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20));
+    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20), 1, members);
     if (ak && bn) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, true, true>), grid, dim3(256), 0, c->stream, p);
     else if (ak) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, true, false>), grid, dim3(256), 0, c->stream, p);
     else if (bn) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, false, true>), grid, dim3(256), 0, c->stream, p);
     else hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, false, false>), grid, dim3(256), 0, c->stream, p);
     path = 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0);
   } else if (p.K >= 512 && outs <= 8192) {  // few outputs, long sums: K split over a block
-    hipLaunchKernelGGL(ct_gemm_dot_kernel<T>, dim3((unsigned)outs), dim3(256), 0, c->stream, p);
+    hipLaunchKernelGGL(ct_gemm_dot_kernel<T>, dim3((unsigned)outs, 1, members), dim3(256), 0, c->stream, p);
     path = 5;
   } else {
-    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16));
+    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16), 1, members);
     hipLaunchKernelGGL(ct_gemm_stream_kernel<T>, grid, dim3(256), 0, c->stream, p);
     path = 6;
   }
   CT_TRY(hipGetLastError());
   c->launches += 1;
   c->by_kernel[path] += 1;
-  c->macs += p.H * p.M * p.N * p.K;
+  c->macs += p.H * p.M * p.N * p.K * members;
   return TNCO_HIP_OK;
 }
 
 // launch_gemm in storage mode: the same shape classes and slots, the tiled class on the matrix cores
 template <class S, bool CPLX, bool SC>
-int launch_half_gemm(tnco_hip_contract_s* c, HalfGemmArgs<typename std::conditional<CPLX, cplx<S>, S>::type> p) {
+int launch_half_gemm(tnco_hip_contract_s* c, HalfGemmArgs<typename std::conditional<CPLX, cplx<S>, S>::type> p, unsigned members = 1) {
   using E = typename std::conditional<CPLX, cplx<S>, S>::type;
   const bool ak = p.a_k == 1, bn = p.b_n == 1;
   const int64_t outs = p.H * p.M * p.N;
-  // 16-byte loads of 8 elements along the contiguous axis: the base and every row (column) of it aligned
+  // 16-byte loads of 8 elements along the contiguous axis: the base and every row (column) of it aligned (the base of a
+  // member of a batch: ct_member)
   p.a_vec = (uintptr_t)p.A % 16 == 0 && (ak ? p.a_m : p.a_k) % 8 == 0;
   p.b_vec = (uintptr_t)p.B % 16 == 0 && (bn ? p.b_k : p.b_n) % 8 == 0;
   int path;
   if (p.M >= 64 && p.N >= 64 && p.K > 32) {
     const int64_t tiles = p.H * ((p.M + HB - 1) / HB) * ((p.N + HB - 1) / HB);
-    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20));
+    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20), 1, members);
     if (ak && bn) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, true, true, SC>), grid, dim3(256), 0, c->stream, p);
     else if (ak) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, true, false, SC>), grid, dim3(256), 0, c->stream, p);
     else if (bn) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, false, true, SC>), grid, dim3(256), 0, c->stream, p);
     else hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, false, false, SC>), grid, dim3(256), 0, c->stream, p);
     path = 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0);
   } else if (p.K >= 512 && outs <= 8192) {
-    hipLaunchKernelGGL((ct_half_dot_kernel<E, SC>), dim3((unsigned)outs), dim3(256), 0, c->stream, p);
+    hipLaunchKernelGGL((ct_half_dot_kernel<E, SC>), dim3((unsigned)outs, 1, members), dim3(256), 0, c->stream, p);
     path = 5;
   } else {
-    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16));
+    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16), 1, members);
     hipLaunchKernelGGL((ct_half_stream_kernel<E, SC>), grid, dim3(256), 0, c->stream, p);
     path = 6;
   }
   CT_TRY(hipGetLastError());
   c->launches += 1;
   c->by_kernel[path] += 1;
-  c->macs += outs * p.K;
+  c->macs += outs * p.K * members;
   return TNCO_HIP_OK;
 }
 
@@ -743,63 +817,95 @@ int run_impl(tnco_hip_contract_s* c) {
   // gathers move elements as they are, by width; only a single leaf gathered into the output is widened
   using W = typename std::conditional<!half, T, typename std::conditional<sizeof(E) == 2, uint16_t, uint32_t>::type>::type;
   std::vector<char> visited(c->n_blocks, 0);
-  const int64_t S = (int64_t)c->steps.size() / STEP_W;
+  const int64_t S = (int64_t)c->steps.size() / STEP_W, L = (int64_t)c->leaf_numel.size();
+  // a batch: up to c->batch assignments per launch, each in its own arena; a plan without steps runs as it does unbatched
+  const bool batched = c->batch > 0 && S > 0;
+  const int64_t per = batched ? c->batch : 1;
   E* arena = (E*)c->d_arena;
   T* out = (T*)c->d_out;
-  for (int64_t sid = c->start; sid < c->stop; ++sid) {
-    int64_t blk = 0;
-    for (int64_t b : c->block) blk = blk * c->slice_dims[b] + (sid / c->place[b]) % c->slice_dims[b];
-    const int beta = visited[blk];
-    visited[blk] = 1;
-    const int64_t out_off = blk * c->block_numel;
-    // scaling: the max words of every step are cleared at the start of an assignment, in stream order after the narrowing
-    // passes of the one before
-    if (half && c->scaling && S) CT_TRY(hipMemsetAsync(c->d_amax, 0, (size_t)S * sizeof(uint32_t), c->stream));
+  const int64_t* d_leaf_sl = c->d_tables + c->perms.size();
+  MemberArgs mb0{};
+  if (batched) {
+    mb0.slice_place = d_leaf_sl + c->leaf_sl.size(), mb0.slice_dims = mb0.slice_place + c->place.size();
+    mb0.exp_step = (int)(L + S), mb0.amax_step = (int)S;
+  }
+  const int64_t arena_bytes = batched ? c->arena_elems * (int64_t)sizeof(E) : 0;
+  for (int64_t sid = c->start; sid < c->stop; sid += per) {
+    const int64_t n = std::min(per, c->stop - sid);  // members of this launch
+    const unsigned members = (unsigned)n;
+    BatchPlace pl{};
+    for (int64_t m = 0; m < n; ++m) {
+      int64_t blk = 0;
+      for (int64_t b : c->block) blk = blk * c->slice_dims[b] + ((sid + m) / c->place[b]) % c->slice_dims[b];
+      pl.off[m] = blk * c->block_numel;
+      pl.beta |= (uint64_t)visited[blk] << m;  // (visited by an earlier batch, or by an earlier member of this one)
+      visited[blk] = 1;
+    }
+    const int beta = (int)(pl.beta & 1);
+    const int64_t out_off = pl.off[0];
+    c->last_member = n - 1;
+    mb0.sid0 = sid;
+    // scaling: the max words of every step are cleared at the start of an assignment (of a batch: of all its members),
+    // in stream order after the narrowing passes of the one before
+    if (half && c->scaling && S) CT_TRY(hipMemsetAsync(c->d_amax, 0, (size_t)(S * per) * sizeof(uint32_t), c->stream));
     int rc = half && S == 0 ? (c->scaling ? launch_gathers<T, E, half, half>(c, -1, sid, out_off) : launch_gathers<T, E, half>(c, -1, sid, out_off))
-                            : launch_gathers<W, W, half>(c, -1, sid, out_off);
+                            : launch_gathers<W, W, half>(c, -1, sid, out_off, batched ? n : 0);
     if (rc) return rc;
     for (int64_t k = 0; k < S; ++k) {
-      if ((rc = launch_gathers<W, W, half>(c, k, sid, out_off))) return rc;
+      if ((rc = launch_gathers<W, W, half>(c, k, sid, out_off, batched ? n : 0))) return rc;
       const int64_t* st = &c->steps[k * STEP_W];
       const E* opnd[2];
+      MemberArgs mb = mb0;
       for (int side = 0; side < 2; ++side) {
         const int64_t kind = st[4 * side], ref = st[4 * side + 1];
-        opnd[side] = kind == K_LEAF ? (const E*)(c->d_leaves + c->leaf_off[ref] * c->elem) + leaf_slice_offset(c, ref, sid)
-                                    : arena + ref;
+        if (kind != K_LEAF) {  // (of a batch: each member's own arena)
+          opnd[side] = arena + ref;
+          (side ? mb.b_step : mb.a_step) = arena_bytes;
+          continue;
+        }
+        // a leaf read in place: at the slice offset of the assignment, which a member of a batch adds for its own
+        opnd[side] = (const E*)(c->d_leaves + c->leaf_off[ref] * c->elem) + (batched ? 0 : leaf_slice_offset(c, ref, sid));
+        if (batched) (side ? mb.b_ls : mb.a_ls) = d_leaf_sl + ref * LEAF_SL_W;
       }
+      // batched: the last step writes every member's block, with beta 0, to the batch staging buffer
+      const bool last = st[8] == K_OUT;
+      T* out_dest = batched ? (T*)c->d_batch_out : out + out_off;
+      const int out_beta = batched ? 0 : beta;
+      if (batched) mb.c_step = last ? c->block_numel * (int64_t)sizeof(T) : arena_bytes;
       if constexpr (half) {
         HalfGemmArgs<E> p;
         p.A = opnd[0], p.B = opnd[1];
-        p.Cs = st[8] == K_OUT ? nullptr : arena + st[9];
-        p.C = st[8] == K_OUT ? out + out_off : nullptr;
+        p.Cs = last ? nullptr : arena + st[9];
+        p.C = last ? out_dest : nullptr;
         p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
         p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
-        p.beta = st[8] == K_OUT ? beta : 0;
+        p.beta = last ? out_beta : 0;
         p.a_vec = p.b_vec = 0;
         p.exps = nullptr, p.sa = p.sb = 0, p.amax = nullptr;
+        p.mb = mb;
         using St = typename ct_storage_of<E>::type;
         if (!c->scaling) {
-          if ((rc = launch_half_gemm<St, sizeof(E) == 4, false>(c, p))) return rc;
+          if ((rc = launch_half_gemm<St, sizeof(E) == 4, false>(c, p, members))) return rc;
           continue;
         }
-        const int64_t L = (int64_t)c->leaf_numel.size();
         p.exps = c->d_exps, p.sa = (int)st[14], p.sb = (int)st[15];
         if (st[8] != K_OUT) {  // unrounded to the staging buffer, then narrowed at the exponent of the whole result
           p.Cs = nullptr, p.C = (T*)(arena + c->stage_refs[k]), p.amax = c->d_amax + k;
         }
-        if ((rc = launch_half_gemm<St, sizeof(E) == 4, true>(c, p))) return rc;
+        if ((rc = launch_half_gemm<St, sizeof(E) == 4, true>(c, p, members))) return rc;
         if (st[8] != K_OUT) {
           const int64_t nc = p.H * p.M * p.N, quads = nc * (sizeof(E) == 4 ? 2 : 1) / 4;
-          const dim3 grid((unsigned)std::min<int64_t>(std::max<int64_t>((quads + 255) / 256, 1), 2048));
+          const dim3 grid((unsigned)std::min<int64_t>(std::max<int64_t>((quads + 255) / 256, 1), 2048), 1, members);
           hipLaunchKernelGGL((ct_scale_narrow_kernel<St, sizeof(E) == 4>), grid, dim3(256), 0, c->stream, (const float*)p.C,
-                             (St*)(arena + st[9]), nc, (const uint32_t*)p.amax, c->d_exps, p.sa, p.sb, (int)(L + k));
+                             (St*)(arena + st[9]), nc, (const uint32_t*)p.amax, c->d_exps, p.sa, p.sb, (int)(L + k),
+                             arena_bytes, mb.exp_step, mb.amax_step);
           CT_TRY(hipGetLastError());
           c->launches += 1;
           c->narrow_launches += 1;
         }
         continue;
       } else {
-      T* dest = st[8] == K_OUT ? out + out_off : arena + st[9];
+      T* dest = last ? out_dest : arena + st[9];
       const int64_t* rw = c->row_steps.empty() ? nullptr : &c->row_steps[k * ROW_W];
       if (rw && (rw[0] > 1 || rw[2] >= 0 || rw[4] >= 0)) {
         RowGemmArgs<T> p;
@@ -819,9 +925,18 @@ int run_impl(tnco_hip_contract_s* c) {
       p.C = dest;
       p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
       p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
-      p.beta = st[8] == K_OUT ? beta : 0;
-      if ((rc = launch_gemm<T>(c, p))) return rc;
+      p.beta = last ? out_beta : 0;
+      p.mb = mb;
+      if ((rc = launch_gemm<T>(c, p, members))) return rc;
       }
+    }
+    if (batched) {  // the members' blocks into the output, in assignment order
+      const dim3 grid((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048));
+      hipLaunchKernelGGL(ct_batch_reduce_kernel<T>, grid, dim3(256), 0, c->stream, out, (const T*)c->d_batch_out, c->block_numel,
+                         (int)n, pl);
+      CT_TRY(hipGetLastError());
+      c->launches += 1;
+      c->batch_launches += 1;
     }
   }
   return TNCO_HIP_OK;
@@ -853,7 +968,7 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
   const size_t maps = c->row_maps.size() * sizeof(int32_t);
   const size_t n_slots = c->leaf_numel.size() + c->steps.size() / STEP_W, n_words = c->steps.size() / STEP_W;
   const size_t scale_b = c->scaling ? 4 * (n_slots + n_words) : 0;  // exponent slots, then the steps' max words
-  c->bytes = (int64_t)(leaves + arena + outb + n_tab * 8 + ptrs + maps + scale_b);
+  c->bytes = c->base_bytes = (int64_t)(leaves + arena + outb + n_tab * 8 + ptrs + maps + scale_b);
   auto bail = [&](int code, const std::string& msg) {
     tnco_hip_contract_destroy(c);
     return fail(code, msg);
@@ -905,9 +1020,18 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
                           hipMemcpyHostToDevice, c->stream));
   }
   CT_TRY(hipMemsetAsync(c->d_out, 0, (size_t)c->out_numel * c->out_elem, c->stream));
-  if (c->scaling && !c->leaf_exps.empty())
-    CT_TRY(hipMemcpyAsync(c->d_exps, c->leaf_exps.data(), c->leaf_exps.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  c->macs = c->launches = c->narrow_launches = 0;
+  const size_t n_steps = c->steps.size() / STEP_W;
+  if (c->scaling && !c->leaf_exps.empty()) {
+    if (c->batch && n_steps) {  // every member's copy of the slots starts with the same leaf exponents
+      const size_t n_slots = c->leaf_exps.size() + n_steps;
+      c->exps_image.assign((size_t)c->batch * n_slots, 0);
+      for (int64_t b = 0; b < c->batch; ++b) std::copy(c->leaf_exps.begin(), c->leaf_exps.end(), c->exps_image.begin() + b * n_slots);
+      CT_TRY(hipMemcpyAsync(c->d_exps, c->exps_image.data(), c->exps_image.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    } else {
+      CT_TRY(hipMemcpyAsync(c->d_exps, c->leaf_exps.data(), c->leaf_exps.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+  }
+  c->macs = c->launches = c->narrow_launches = c->batch_launches = c->last_member = 0;
   std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
   std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
   CT_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -959,7 +1083,7 @@ int tnco_hip_contract_exponents(tnco_hip_contract c, int32_t* exps) {
   if (!c->scaling) return fail(TNCO_HIP_EINVAL, "the plan has no scaling.");
   CT_TRY(hipSetDevice(c->device));
   const size_t n = c->leaf_numel.size() + c->steps.size() / STEP_W;
-  if (n) CT_TRY(hipMemcpyAsync(exps, c->d_exps, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (n) CT_TRY(hipMemcpyAsync(exps, c->d_exps + c->last_member * (int64_t)n, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   CT_TRY(hipStreamSynchronize(c->stream));
   return TNCO_HIP_OK;
 }
@@ -970,11 +1094,61 @@ int tnco_hip_contract_narrow_launches(tnco_hip_contract c, int64_t* count) {
   return TNCO_HIP_OK;
 }
 
+int tnco_hip_contract_set_slice_batch(tnco_hip_contract c, int64_t batch) {
+  if (!c) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (batch < 1 || batch > MAX_SLICE_BATCH) return fail(TNCO_HIP_EINVAL, "'batch' must be from 1 to 64.");
+  if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with a slice batch.");
+  const size_t n_steps = c->steps.size() / STEP_W, n_slots = c->leaf_numel.size() + n_steps;
+  if (!n_steps) {  // a single leaf gathered into the output: runs as it does without a batch, nothing to reserve
+    c->batch = batch;
+    return TNCO_HIP_OK;
+  }
+  CT_TRY(hipSetDevice(c->device));
+  CT_TRY(hipStreamSynchronize(c->stream));
+  // B arenas, B blocks of the output's type, and with scaling the B-fold exponent slots and max words
+  // (`bytes` counts arena_elems per member, as Plan.peak_device_bytes does; a plan whose steps need no arena keeps the
+  // one element create allocated for it)
+  const size_t arena = (size_t)c->arena_elems * c->elem, B = (size_t)batch;
+  const size_t stage = B * (size_t)c->block_numel * c->out_elem;
+  const size_t scale_b = c->scaling ? 4 * (n_slots + n_steps) : 0;
+  const int64_t bytes = c->base_bytes + (int64_t)((B - 1) * (arena + scale_b) + stage);
+  size_t free_b = 0, total_b = 0;
+  CT_TRY(hipMemGetInfo(&free_b, &total_b));
+  // what the batch adds to `bytes` must be free.  (The new buffers are allocated before the old ones are released, so
+  // that a failure leaves the handle as it was: a device with the growth free but not the new buffers fails below.)
+  const size_t need = (size_t)(bytes - c->bytes);
+  if (bytes > c->bytes && need > free_b)
+    return fail(TNCO_HIP_ERUNTIME, "the slice batch needs " + std::to_string(need) + " bytes of device memory, " +
+                                       std::to_string(free_b) + " are free.");
+  // the new buffers first: a handle that this call fails on stays as it was
+  void *d_arena = nullptr, *d_stage = nullptr, *d_exps = nullptr;
+  if (hipMalloc(&d_arena, std::max<size_t>(B * arena, c->elem)) != hipSuccess || hipMalloc(&d_stage, std::max<size_t>(stage, 4)) != hipSuccess ||
+      (c->scaling && (hipMalloc(&d_exps, B * scale_b) != hipSuccess ||
+                      hipMemsetAsync(d_exps, 0, B * scale_b, c->stream) != hipSuccess ||
+                      hipStreamSynchronize(c->stream) != hipSuccess))) {
+    for (void* p : {d_arena, d_stage, d_exps})
+      if (p) (void)hipFree(p);
+    return fail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+  }
+  for (void* p : {c->d_arena, c->d_batch_out, c->scaling ? (void*)c->d_exps : nullptr})
+    if (p) (void)hipFree(p);
+  c->d_arena = d_arena, c->d_batch_out = d_stage;
+  if (c->scaling) c->d_exps = (int32_t*)d_exps, c->d_amax = (uint32_t*)(c->d_exps + B * n_slots);
+  c->batch = batch, c->bytes = bytes;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_batch_launches(tnco_hip_contract c, int64_t* count) {
+  if (!c || !count) return fail(TNCO_HIP_EINVAL, "null argument.");
+  *count = c->batch_launches;
+  return TNCO_HIP_OK;
+}
+
 void tnco_hip_contract_destroy(tnco_hip_contract c) {
   if (!c) return;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_leaves, c->d_arena, c->d_out, (void*)c->d_tables, (void*)c->d_leaf_ptrs, (void*)c->d_row_maps,
-                  (void*)c->d_exps})
+                  (void*)c->d_exps, c->d_batch_out})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);

@@ -1,5 +1,5 @@
 // contract_half.h -- the half-precision storage mode of the contraction engine (tnco_hip.h, dtype codes 4..7); included
-// by contract.hip inside its anonymous namespace, after cplx / ct_zero / ct_mac / ct_add / ct_acc.
+// by contract.hip inside its anonymous namespace, after cplx / ct_zero / ct_mac / ct_add / ct_acc / MemberArgs.
 // Leaves and intermediates are float16 or bfloat16 (a complex element an interleaved (re, im) pair), every sum is
 // float32, a value is rounded once, to nearest even, when it is stored to the arena; the output stays float32.
 //   ct_mfma_tiled_kernel   the tiled shape class on the matrix cores (v_mfma_f32_16x16x32_{f16,bf16});
@@ -98,7 +98,26 @@ struct HalfGemmArgs {
   const int32_t* exps;
   int sa, sb;
   uint32_t* amax;
+  MemberArgs mb;
 };
+
+// the operands, the result, the exponent slots and the max word of this block's member (contract.hip, MemberArgs).
+// a_vec / b_vec are checked again at the member's own base: a precaution only, since with the row stride a multiple of 8
+// elements every slice offset is one too, and the arenas are a multiple of 64 elements apart, so a member's alignment
+// is that of the base the host looked at (no test reaches a member where they differ)
+template <class E>
+__device__ inline void ct_member(HalfGemmArgs<E>& p) {
+  const MemberArgs& mb = p.mb;
+  const int64_t b = blockIdx.z;
+  p.A = ct_shift(p.A, b * mb.a_step) + (mb.a_ls ? ct_slice_offset(mb.a_ls, mb.slice_place, mb.slice_dims, mb.sid0 + b) : 0);
+  p.B = ct_shift(p.B, b * mb.b_step) + (mb.b_ls ? ct_slice_offset(mb.b_ls, mb.slice_place, mb.slice_dims, mb.sid0 + b) : 0);
+  p.a_vec = p.a_vec && (uintptr_t)p.A % 16 == 0;
+  p.b_vec = p.b_vec && (uintptr_t)p.B % 16 == 0;
+  if (p.Cs) p.Cs = ct_shift(p.Cs, b * mb.c_step);
+  if (p.C) p.C = ct_shift(p.C, b * mb.c_step);
+  if (p.exps) p.exps += b * mb.exp_step;
+  if (p.amax) p.amax += b * mb.amax_step;
+}
 
 template <class E>
 __device__ inline void ct_store(const HalfGemmArgs<E>& p, int64_t e, ct_acc_t<E> acc) {
@@ -242,6 +261,7 @@ template <class S, bool CPLX, bool AK, bool BN, bool SC>
 __global__ __launch_bounds__(256) void ct_mfma_tiled_kernel(HalfGemmArgs<typename std::conditional<CPLX, cplx<S>, S>::type> p) {
   using E = typename std::conditional<CPLX, cplx<S>, S>::type;
   constexpr int NP = CPLX ? 2 : 1;
+  ct_member(p);
   __shared__ __attribute__((aligned(16))) uint32_t As[NP][HB][HLD];
   __shared__ __attribute__((aligned(16))) uint32_t Bs[NP][HB][HLD];
   const int tid = threadIdx.x, lane = tid % 64, wave = tid / 64;
@@ -321,9 +341,14 @@ __global__ __launch_bounds__(256) void ct_mfma_tiled_kernel(HalfGemmArgs<typenam
 // one 8-byte store (both buffers start at multiples of 64 elements of the arena); the last n % 4 parts one lane each.
 // Thread 0 of block 0 records the result's exponent exps[sc] = exps[sa] + exps[sb] + s; the operands' slots were
 // written by earlier kernels of the stream or by the host, nobody else writes sc during this kernel.
+// Member b = blockIdx.z of a batched launch (contract.hip, MemberArgs) has stage and dst arena_step bytes, its slots
+// exp_step and its max word amax_step entries further on; all three 0 when unbatched.
 template <class S, bool CPLX>
 __global__ __launch_bounds__(256) void ct_scale_narrow_kernel(const float* stage, S* dst, int64_t numel, const uint32_t* amax,
-                                                              int32_t* exps, int sa, int sb, int sc) {
+                                                              int32_t* exps, int sa, int sb, int sc, int64_t arena_step,
+                                                              int exp_step, int amax_step) {
+  stage = ct_shift(stage, blockIdx.z * arena_step), dst = ct_shift(dst, blockIdx.z * arena_step);
+  exps += blockIdx.z * exp_step, amax += blockIdx.z * amax_step;
   const int64_t n = numel * (CPLX ? 2 : 1);
   const int s = ct_scale_exponent(*amax);
   const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;

@@ -9,7 +9,8 @@ amplitude from the finite-width optimizer (wall time, device time, launches per 
 of that circuit in one projected call (`--projs`: the 53 output indices sparse, an infinite-memory path from
 optimize(n_projs=P)) against a loop of plain contract() calls over leaves indexed at one bitstring each, along the same
 path; the storage mode (`--storage`: the large square step in float32 and complex64 with `storage` unset, float16 and
-bfloat16, and the sliced Sycamore leg once more with storage="bfloat16").  Engine figures are its
+bfloat16, and the sliced Sycamore leg once more with storage="bfloat16"); slice batches (`--slice-batch`: the sliced
+Sycamore leg with slice_batch None, 1, 8 and 64, plain, in storage mode and with scaling).  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device).
 """
@@ -233,6 +234,46 @@ def scaling(lines, n, depth, max_width, max_slices):
     print("\n".join(lines[-16:]), flush=True)
 
 
+def slice_batch(lines, depth, max_width, max_slices, batches=(None, 1, 8, 64)):
+    """Slice assignments per launch on the sliced Sycamore amplitude of the storage leg: device time (the minimum and
+    the spread of three runs after a warm-up, all in this process), launches, memory and rate per batch size, plain, in
+    storage mode and with scaling; every batched result is compared bit for bit with the unbatched one of its mode."""
+    lines.append("")
+    ts, d, o = syn.sycamore53_tn(depth=depth)
+    tn0 = tnmod.TensorNetwork([tnmod.Tensor(xs, [d] * len(xs)) for xs in ts], output_inds=o)
+    tn, res = Optimizer(method="sa", max_width=max_width, seed=0).optimize(tn0, betas=(0, 50), n_steps=200, n_runs=256)
+    r0 = res[0]
+    rng = np.random.RandomState(2)
+    n_inds = len({x for xs in ts for x in xs})
+    scale = 2.0 ** (-n_inds / (2 * len(ts)))  # (as in the storage leg: the amplitude stays near 1)
+    arrays = [(_rand(tuple(d for _ in xs), np.complex64, rng) * scale).astype(np.complex64) for xs in ts]
+    fused = ctr.contract(tn.tags["fuse_path"], tn0.ts_inds, arrays, tn0.output_inds)
+    leaves = fused.array if isinstance(fused.array, list) else [fused.array]
+    p = ctr.plan(r0.path, tn.ts_inds, [a.shape for a in leaves], tn.output_inds, slices=r0.slices)
+    m = min(p.n_slices, max_slices)
+    lines.append(f"## slice_batch, sliced Sycamore-53 amplitude, depth {depth}, complex64, max_width {max_width}, cost "
+                 f"{r0.cost}, {len(r0.path)} steps, assignments [0, {m}) of {p.n_slices}: device seconds are the minimum "
+                 "of three runs after a warm-up, spread = (max - min) / min of the three; all runs in one process")
+    lines.append(f"{'storage':>9} {'scaling':>8} {'slice_batch':>11} {'device s':>9} {'spread':>7} {'None / this':>11} "
+                 f"{'launches':>9} {'reduce':>7} {'peak bytes':>11} {'GMAC/s':>8} {'bits equal None':>15}")
+    for st, sc in ((None, None), ("bfloat16", None), ("float16", "tensor")):
+        base = t_base = None
+        for B in batches:
+            call = lambda B=B: ctr.contract(r0.path, tn.ts_inds, leaves, tn.output_inds, slices=r0.slices,  # noqa: E731
+                                            slice_range=(0, m), storage=st, scaling=sc, slice_batch=B)
+            r = call()
+            times = [call().device_s for _ in range(3)]
+            t = min(times)
+            if B is None:
+                base, t_base = r.array, t
+            same = np.array_equal(np.ravel(r.array).view(np.uint32), np.ravel(base).view(np.uint32))
+            lines.append(f"{str(st):>9} {str(sc):>8} {str(B):>11} {t:9.4f} {(max(times) - t) / t:7.3f} {t_base / t:11.2f} "
+                         f"{r.launches:9d} {r.batch_launches:7d} {r.peak_device_bytes:11d} {r.macs / t / 1e9:8.2f} "
+                         f"{str(bool(same)):>15}")
+            print(lines[-1], flush=True)
+            del r
+
+
 def projections(lines, depth, counts, loop_max):
     """P amplitudes per call.  The network: the circuit without its 53 <x| tensors, the open wires its output and
     sparse indices.  The largest depth <= `depth` whose unsliced plan fits the free device memory at every P is used."""
@@ -301,14 +342,17 @@ def main():
     ap.add_argument("--projs", action="store_true", help="only the projections leg, appended to --out")
     ap.add_argument("--storage", action="store_true", help="only the storage-mode leg, appended to --out")
     ap.add_argument("--scaling", action="store_true", help="only the scaling leg, appended to --out")
+    ap.add_argument("--slice-batch", action="store_true", help="only the slice-batch leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling > 1:
-        ap.error("--projs, --storage and --scaling each append one leg: run them one after the other")
+    if a.projs + a.storage + a.scaling + a.slice_batch > 1:
+        ap.error("--projs, --storage, --scaling and --slice-batch each append one leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling:  # (the other legs' sections stay as they are)
-        if a.scaling:
+    if a.projs or a.storage or a.scaling or a.slice_batch:  # (the other legs' sections stay as they are)
+        if a.slice_batch:
+            slice_batch(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+        elif a.scaling:
             scaling(lines, a.n, a.depth, a.max_width, a.max_slices)
         elif a.storage:
             storage(lines, a.n, a.depth, a.max_width, a.max_slices)
@@ -323,6 +367,7 @@ def main():
     projections(lines, a.depth, a.counts, a.loop_max)
     storage(lines, a.n, a.depth, a.max_width, a.max_slices)
     scaling(lines, a.n, a.depth, a.max_width, a.max_slices)
+    slice_batch(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
