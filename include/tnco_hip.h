@@ -449,6 +449,15 @@ const char* tnco_hip_comm_last_error(void);
  * group adds or places them in the output, one lane per element, the members in assignment order: the sum over the
  * assignments keeps its order, and the result is bit for bit that of the unbatched run.  Steps with row axes are not
  * supported.  A plan without steps takes the call and runs as it does without it.
+ *
+ * Compute mode bf16x3 (tnco_hip_contract_set_compute, mode 1; dtype codes 0 and 2 only): nothing changes in what is
+ * stored, the tables or the memory; a step of the tiled shape class (M, N >= 64, K > 32) runs on the matrix cores with
+ * every float32 part x of its operands split, as it is staged, into hi = bf16(x) (to nearest even) and lo = bf16(x - hi)
+ * (exact subtraction; lo = 0 where hi is not finite), and every product summed in float32 as a_lo b_hi + a_hi b_lo +
+ * a_hi b_hi, in that order, a_lo b_lo dropped (v_mfma_f32_16x16x32_bf16; a complex product: re += Ar Br, re += (-Ai) Bi,
+ * im += Ar Bi, im += Ai Br, each as those three).  The result is stored unrounded as float32; no atomics, a run stays
+ * bit-reproducible.  Every other kernel is that of mode 0.  A finite part with |x| >= 2^128 - 2^119 has an infinite hi:
+ * the elements it feeds become non-finite (the host refuses such leaves).  Works with slice batches.
  */
 typedef struct tnco_hip_contract_s* tnco_hip_contract;
 typedef struct tnco_hip_contract_desc {
@@ -512,6 +521,12 @@ int tnco_hip_contract_set_slice_batch(tnco_hip_contract h, int64_t batch);
 /* the last run's launches of the kernel that folds a group's blocks into the output (one per group; 0 unbatched); they
  * are part of stats[1] and of none of the slots above */
 int tnco_hip_contract_batch_launches(tnco_hip_contract h, int64_t* count);
+/* after create: the runs that follow use compute mode `mode`, 0 plain (as a handle on which this was never called) or
+ * 1 bf16x3 (above).  EINVAL for other values, for dtype codes other than 0 and 2, and on a handle with row axes */
+int tnco_hip_contract_set_compute(tnco_hip_contract h, int32_t mode);
+/* the last run's launches of the split kernel of mode 1; they are also counted in their tiled slot of
+ * tnco_hip_contract_kernel_launches (by operand layout), so the slots still sum to stats[1] as before */
+int tnco_hip_contract_split_launches(tnco_hip_contract h, int64_t* count);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

@@ -56,6 +56,21 @@ leaves the members' blocks in a staging buffer and one more kernel per group add
 assignment order.  The result is bit for bit that of `slice_batch=None`; device memory grows by B - 1 arenas and B blocks
 of the output (`Plan.peak_device_bytes`).  The plan's tables do not change.  Projections are not supported with it; a
 plan without steps takes the keyword and runs as without it.
+
+Compute mode: with `compute="bf16x3"` (float32 / complex64 arrays only; exclusive with `storage`) nothing changes in
+what is stored -- arrays, leaves, arena, intermediates and output stay float32 / complex64, and the plan's tables and
+`peak_device_bytes` are those of `compute=None` -- but the steps of the tiled shape class (M, N >= 64 and K > 32) run on
+the matrix cores: every float32 part x of an operand is split into hi = bf16(x), rounded to nearest even, and
+lo = bf16(x - hi) (the subtraction is exact; lo = 0 where hi is not finite), and a product a b is summed in float32 as
+a_lo b_hi + a_hi b_lo + a_hi b_hi, in that order; a_lo b_lo is dropped.  A complex product is its four real products,
+each of them those three.  An element of such a step is within [2^-14 + (2 c 3 kt + 2) 2^-24] (|A| @ |B|) of the exact
+one (c = 1 real, 2 complex, kt products per element).  The dot and stream classes, the gathers and the batch reduce are
+the float32 kernels, so a network without a tiled-class step returns the bytes of `compute=None`.  An inf or NaN part
+makes the elements it feeds non-finite and leaves the others alone.  A finite part with |x| >= 2^128 - 2^119 (about
+3.396e38) has a hi that rounds to infinity and is out of range: in a leaf it is refused (ValueError), in an
+intermediate the elements it feeds become non-finite.  Projections are not supported with it; `slice_batch` is, and
+stays bit-equal to the unbatched run; `split_launches` of the result counts the launches of the split kernel (they
+are also counted in their tiled slot of `kernel_launches`).
 """
 from __future__ import annotations
 
@@ -69,7 +84,7 @@ from .app import tn as tnmod
 
 __all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
            "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage", "SCALINGS", "scale_exponent", "scale_to_storage",
-           "MAX_SLICE_BATCH"]
+           "MAX_SLICE_BATCH", "COMPUTES", "split_bf16"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -79,6 +94,7 @@ DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex6
 STORAGES = {"float16": 4, "bfloat16": 6}
 SCALINGS = ("tensor",)  # per-tensor power-of-two scaling of storage mode (module docstring)
 SCALE_BITS = 14  # the largest stored magnitude of a scaled tensor lies in [2^14, 2^15]
+COMPUTES = {"bf16x3": 1}  # compute modes (module docstring) and their codes for tnco_hip_contract_set_compute
 MAX_SLICE_BATCH = 64  # slice assignments per launch at most (csrc/contract.hip MAX_SLICE_BATCH)
 
 # operand / destination kinds and table widths: include/tnco_hip.h (tnco_hip_contract_desc)
@@ -116,6 +132,8 @@ class ContractionResult:
     #                          the largest, of an unsliced call 1); None: unbatched
     batch_launches: int = 0  # slice_batch: launches of the kernel that folds a group's blocks into the output;
     #                          `launches` is the four counts together
+    compute: str = None  # "bf16x3": the tiled-class steps ran as three bfloat16 products on the matrix cores
+    split_launches: int = 0  # compute: launches of the split kernel (they are part of their tiled slot of kernel_launches)
 
 
 @dataclass
@@ -146,6 +164,7 @@ class Plan:
     scaling: str = None  # "tensor": steps columns 14, 15 are the exponent slots of A and B (leaf t: t, step j: n_leaves + j)
     stage_refs: np.ndarray = None  # scaling: [n_steps] arena offset of a stored step's float32 staging buffer, -1 none
     slice_batch: int = None  # assignments per launch: min(what was asked for, assignments of slice_range); 1 without steps
+    compute: str = None  # "bf16x3": the tiled-class steps on the matrix cores; the tables do not depend on it
 
     @property
     def n_slices(self) -> int:
@@ -268,6 +287,42 @@ def _check_slice_batch(slice_batch, projs=None) -> None:
         raise ValueError(f"'slice_batch' must be None or an integer from 1 to {MAX_SLICE_BATCH}.")
     if projs is not None:
         raise NotImplementedError("projections are not supported with 'slice_batch'.")
+
+
+def _check_compute(compute, storage, dtype, projs=None) -> None:
+    if compute is None:
+        return
+    if not isinstance(compute, str) or compute not in COMPUTES:
+        raise ValueError(f"'compute' must be None or {' or '.join(repr(s) for s in COMPUTES)}.")
+    if storage is not None:
+        raise ValueError("'compute' and 'storage' are exclusive.")
+    if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.complex64)):
+        raise TypeError(f"with 'compute' the compute dtype must be float32 or complex64, not {np.dtype(dtype)}.")
+    if projs is not None:
+        raise NotImplementedError("projections are not supported with 'compute'.")
+
+
+def split_bf16(a):
+    """(hi, lo) as the split kernel (csrc/contract_split.h) takes a float32 / complex64 array apart, both of its
+    dtype and shape: per float32 part hi = bfloat16(x) to nearest even, lo = bfloat16(x - hi), and lo = 0 where hi is
+    not finite."""
+    a = np.asarray(a)
+    x = _parts(a)
+    like = np.empty(x.shape, np.float32)
+    hi = _from_storage_bits(_bf16_bits(x).reshape(x.shape), "bfloat16", like)
+    with np.errstate(invalid="ignore"):
+        rest = np.where(np.isfinite(hi), x - hi, np.float32(0)).astype(np.float32)
+    lo = _from_storage_bits(_bf16_bits(rest).reshape(x.shape), "bfloat16", like)
+    if a.dtype.kind == "c":
+        return tuple(q.reshape(-1).view(np.complex64).reshape(a.shape) for q in (hi, lo))
+    return hi.reshape(a.shape), lo.reshape(a.shape)
+
+
+def _check_split_range(a) -> None:
+    """ValueError when a finite part of `a` rounds to an infinite bfloat16 (the hi of the split)."""
+    x = _parts(a)
+    if (np.isfinite(x) & ((_bf16_bits(x) & 0x7F80) == 0x7F80).reshape(x.shape)).any():
+        raise ValueError("an array has finite values beyond the range of the bfloat16 split (|x| >= 2^128 - 2^119).")
 
 
 def _bf16_bits(x) -> np.ndarray:
@@ -419,10 +474,11 @@ def _unique_rows(table):
 
 
 def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
-         sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None) -> Plan:
+         sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None) -> Plan:
     """The device plan of one contraction along a path that leaves one tensor (no GPU).
-    `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`, `slice_batch`: see
-    the module docstring."""
+    `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`, `slice_batch`,
+    `compute`: see the module docstring."""
+    _check_compute(compute, storage, dtype, projs)
     _check_storage(storage, dtype, projs)
     _check_scaling(scaling, storage)
     _check_slice_batch(slice_batch, projs)
@@ -629,7 +685,7 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     p = Plan(dtype=np.dtype(dtype), inds=final, shape=tuple(dims[x] for x in final), slice_inds=slice_inds,
              slice_dims=slice_dims, block_inds=tuple(x for x in slice_inds if x in final), leaf_numel=leaf_numel,
              leaf_sl=leaf_sl, perms=perm_tab, steps=step_tab, arena_elems=arena.peak, out_numel=size(final),
-             macs_per_slice=macs, slice_range=(lo, hi), ops=ops, storage=storage)
+             macs_per_slice=macs, slice_range=(lo, hi), ops=ops, storage=storage, compute=compute)
     if scaling is not None:
         p.scaling = scaling
         p.stage_refs = np.array([offset[b] if b >= 0 else -1 for b in stage], np.int64)
@@ -695,7 +751,7 @@ def _sub_output(ts_inds, leaves, output) -> frozenset:
 
 
 def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=None, device=None,
-             sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None,
+             sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None,
              _intermediates=()) -> ContractionResult:
     """Contract `arrays` (numpy, in ts_inds order) along the linear `path` on the GPU; see the module docstring.
     A path that leaves several tensors gives lists in `inds` / `array` (the sliced and the projected form need one
@@ -707,6 +763,7 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     arrays = [np.asarray(a) for a in arrays]
     dims = _dims_of(ts_inds, [a.shape for a in arrays])
     dtype = _compute_dtype(arrays)
+    _check_compute(compute, storage, dtype, projs)
     _check_storage(storage, dtype, projs)
     _check_scaling(scaling, storage)
     _check_slice_batch(slice_batch, projs)
@@ -714,7 +771,8 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     final, out = tnmod.contract(steps, ts_inds, output_inds, dims)
     if len(final) == 1:
         p = plan(steps, ts_inds, [a.shape for a in arrays], out, slices=slices, slice_range=slice_range, dtype=dtype,
-                 sparse_inds=sparse_inds, projs=projs, storage=storage, scaling=scaling, slice_batch=slice_batch)
+                 sparse_inds=sparse_inds, projs=projs, storage=storage, scaling=scaling, slice_batch=slice_batch,
+                 compute=compute)
         return _run(p, arrays, device, loose)
     if slices:
         raise NotImplementedError("slices need a path that leaves one tensor.")
@@ -732,11 +790,14 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
                 continue
             if storage is not None:
                 a = _from_storage_bits(_storage_bits(a, storage, leaves[0] not in loose), storage, a)
-            parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, slice_batch=effective))
+            if compute is not None and leaves[0] not in loose:
+                _check_split_range(a)
+            parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, slice_batch=effective, compute=compute))
             continue
         parts.append(contract(sub, [ts_inds[t] for t in leaves], [arrays[t].astype(dtype, copy=False) for t in leaves],
                               _sub_output(ts_inds, leaves, out), device=device, storage=storage, scaling=scaling,
-                              slice_batch=slice_batch, _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
+                              slice_batch=slice_batch, compute=compute,
+                              _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
     assert [tuple(r.inds) for r in parts] == [tuple(f) for f in final]
     return ContractionResult([r.inds for r in parts], [r.array for r in parts], sum(r.macs for r in parts), 1,
                              max(r.peak_device_bytes for r in parts), sum(r.launches for r in parts),
@@ -744,7 +805,8 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
                              row_kernel_launches=_add_counts(*(r.row_kernel_launches for r in parts)), scaling=scaling,
                              exponents=None if scaling is None else [r.exponents for r in parts],
                              narrow_launches=sum(r.narrow_launches for r in parts), slice_batch=effective,
-                             batch_launches=sum(r.batch_launches for r in parts))
+                             batch_launches=sum(r.batch_launches for r in parts), compute=compute,
+                             split_launches=sum(r.split_launches for r in parts))
 
 
 def _add_counts(*counts) -> tuple:
@@ -760,6 +822,10 @@ def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
         leaf_exps = np.array(leaf_exps, np.int32)
     elif p.storage is not None:  # (before the device is touched: a leaf beyond the storage type's range is refused)
         leaves = [_storage_bits(a, p.storage, t not in loose) for t, a in enumerate(leaves)]
+    elif p.compute is not None:  # (before the device is touched: a leaf beyond the range of the split is refused)
+        for t, a in enumerate(leaves):
+            if t not in loose:
+                _check_split_range(a)
     L = _lib.load()
     device = parallel.local_device() if device is None else int(device)
     for t, rows in enumerate(p.leaf_rows):
@@ -802,8 +868,10 @@ def _describe(p: Plan, device: int):
 
 def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
     from . import _lib
-    exponents, narrow, folds = None, 0, 0
+    exponents, narrow, folds, splits = None, 0, 0, 0
     try:
+        if p.compute is not None:
+            _lib.check(L.tnco_hip_contract_set_compute(h, COMPUTES[p.compute]))
         if p.slice_batch is not None:
             _lib.check(L.tnco_hip_contract_set_slice_batch(h, p.slice_batch))
         if p.scaling is not None:
@@ -827,13 +895,18 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
             count = C.c_int64()
             _lib.check(L.tnco_hip_contract_batch_launches(h, C.byref(count)))
             folds = int(count.value)
+        if p.compute is not None:
+            count = C.c_int64()
+            _lib.check(L.tnco_hip_contract_split_launches(h, C.byref(count)))
+            splits = int(count.value)
     finally:
         L.tnco_hip_contract_destroy(h)
     array = _host_layout(p, staging)
     return ContractionResult(p.inds, array, int(stats[0]), p.slice_range[1] - p.slice_range[0], int(stats[2]),
                              int(stats[1]), float(stats[3]) * 1e-9, kernel_launches=tuple(int(v) for v in by_kernel),
                              row_kernel_launches=tuple(int(v) for v in by_row_kernel), scaling=p.scaling,
-                             exponents=exponents, narrow_launches=narrow, slice_batch=p.slice_batch, batch_launches=folds)
+                             exponents=exponents, narrow_launches=narrow, slice_batch=p.slice_batch, batch_launches=folds,
+                             compute=p.compute, split_launches=splits)
 
 
 def _host_layout(p: Plan, staging) -> np.ndarray:
@@ -854,7 +927,7 @@ def _host_layout(p: Plan, staging) -> np.ndarray:
 
 
 def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse_inds=None,
-                     storage=None, scaling=None, slice_batch=None) -> ContractionResult:
+                     storage=None, scaling=None, slice_batch=None, compute=None) -> ContractionResult:
     """Run a result of `Optimizer.optimize` over the arrays of the network as given.
 
     tn0: the network before pre-fusing (`load_tn(obj, fuse=None)`); arrays: in tn0.tensors order, or {name: array}
@@ -870,7 +943,10 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     small, stays in the arrays' own precision.  scaling: "tensor" adds per-tensor scaling to it; the results of the fuse
     stage, and the components' results that enter a later call, are then scaled as leaves (`exponents`: those of the
     last call made).  slice_batch: that many slice assignments per launch in every sliced call (module docstring);
-    `batch_launches` is the sum over the calls, `slice_batch` of the result the largest effective value of a component."""
+    `batch_launches` is the sum over the calls, `slice_batch` of the result the largest effective value of a component.
+    compute: "bf16x3" runs the tiled-class steps of `result.path` on the matrix cores (module docstring); the fuse stage
+    stays in plain precision; `split_launches` is the sum over the calls."""
+    _check_compute(compute, storage, np.float32, projs)
     _check_storage(storage, np.float32, projs)
     _check_scaling(scaling, storage)
     _check_slice_batch(slice_batch, projs)
@@ -892,6 +968,7 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         except KeyError as e:
             raise ValueError("'ts_inds' is not consistent with 'arrays'.") from e
     arrays = [np.asarray(a) for a in arrays]
+    _check_compute(compute, storage, _compute_dtype(arrays))
     _check_storage(storage, _compute_dtype(arrays))
     fuse_macs = 0
     if tn.tags.get("fuse_path"):
@@ -906,15 +983,15 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     if len(comp_paths) <= 1:  # one component to contract: the path with its slices, in one call
         r = contract(result.path, tn.ts_inds, arrays, tn.output_inds, slices=getattr(result, "slices", ()),
                      device=device, sparse_inds=sparse_inds or (), projs=projs, storage=storage, scaling=scaling,
-                     slice_batch=slice_batch)
+                     slice_batch=slice_batch, compute=compute)
         return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
                                  fuse_macs, r.kernel_launches, r.row_kernel_launches, r.scaling, r.exponents,
-                                 r.narrow_launches, r.slice_batch, r.batch_launches)
+                                 r.narrow_launches, r.slice_batch, r.batch_launches, r.compute, r.split_launches)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
     ts, n = [tuple(x) for x in tn.ts_inds], len(tn.ts_inds)
     done, results, macs, n_slices, peak, launches, device_s = set(), [], 0, 0, 0, 0, 0.0
     by_kernel = (0,) * len(KERNEL_PATHS)
-    exponents, narrow, folds, effective = None, 0, 0, None
+    exponents, narrow, folds, effective, splits = None, 0, 0, None, 0
     n_comp_steps = 0
     for q, cut in zip(result.disconnected_paths, result.disconnected_slices):
         if not q:
@@ -922,8 +999,9 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         n_comp_steps += len(q)
         (leaves, sub), = [(lv, s) for lv, s in _split(_check_path(q, n), n) if s]
         r = contract(sub, [ts[t] for t in leaves], [arrays[t] for t in leaves], _sub_output(ts, leaves, tn.output_inds),
-                     slices=cut, device=device, storage=storage, scaling=scaling, slice_batch=slice_batch)
+                     slices=cut, device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute)
         exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
+        splits += r.split_launches
         if slice_batch is not None:
             effective = max(effective or 1, r.slice_batch)
         done |= set(leaves)
@@ -939,9 +1017,10 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     tail = result.path[n_comp_steps:]
     if tail:
         r = contract(tail, state_inds, state_arrays, frozenset(tn.output_inds) & {x for xs in state_inds for x in xs},
-                     device=device, storage=storage, scaling=scaling, slice_batch=slice_batch,
+                     device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute,
                      _intermediates=range(len(state_arrays) - len(results), len(state_arrays)))
         exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
+        splits += r.split_launches
         macs, launches, peak = macs + r.macs, launches + r.launches, max(peak, r.peak_device_bytes)
         device_s += r.device_s
         by_kernel = _add_counts(by_kernel, r.kernel_launches)
@@ -950,4 +1029,4 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         inds, array = (state_inds[0], state_arrays[0]) if len(state_inds) == 1 else (state_inds, state_arrays)
     return ContractionResult(inds, array, macs, n_slices, peak, launches, device_s, fuse_macs, by_kernel,
                              scaling=scaling, exponents=exponents, narrow_launches=narrow, slice_batch=effective,
-                             batch_launches=folds)
+                             batch_launches=folds, compute=compute, split_launches=splits)

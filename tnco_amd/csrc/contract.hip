@@ -14,6 +14,9 @@
 // tiled class runs on the matrix cores (ct_mfma_tiled_kernel), dot, stream and gather are the bodies below with a
 // widening load.  Steps with a row axis do not come there.  With per-tensor scaling (contract_half.h) a stored result
 // passes through a float32 staging buffer of the arena and ct_scale_narrow_kernel.
+// Compute mode bf16x3 (tnco_hip_contract_set_compute, contract_split.h): float32 / complex64 plans keep their storage and
+// run the tiled class on the matrix cores, every product as three bfloat16 products (ct_split_tiled_kernel); every other
+// kernel is the one of the plain mode.
 // Slice batches (tnco_hip_contract_set_slice_batch): B consecutive assignments per launch.  Every kernel of the slice
 // loop has a member axis, blockIdx.z = b for assignment sid0 + b (MemberArgs): member b works in its own copy of the arena
 // (and of the exponent slots and max words), reads a leaf in place at the slice offset of its own assignment, computed on
@@ -215,6 +218,8 @@ template <class T>
 __device__ inline void ct_store(const GemmArgs<T>& p, int64_t e, T acc) {
   p.C[e] = p.beta ? ct_add(p.C[e], acc) : acc;
 }
+
+#include "contract_split.h"
 
 constexpr int TB = 64, TK = 16;
 
@@ -515,6 +520,8 @@ struct tnco_hip_contract_s {
   int64_t batch = 0;               // tnco_hip_contract_set_slice_batch: assignments per launch, 0: never set
   void* d_batch_out = nullptr;     // [batch][block_numel] of the output's type: the members' last steps
   int64_t batch_launches = 0;      // launches of ct_batch_reduce_kernel in the last run
+  int compute = 0;                 // tnco_hip_contract_set_compute: 0 plain, 1 bf16x3
+  int64_t split_launches = 0;      // launches of ct_split_tiled_kernel in the last run
   int64_t last_member = 0;         // the member that ran the last assignment of the last run (its exponent slots)
   int64_t base_bytes = 0;          // `bytes` as create reserved them
   std::vector<int32_t> exps_image;  // the leaves' exponents, once per member
@@ -724,7 +731,20 @@ int launch_gemm(tnco_hip_contract_s* c, const GemmArgs<T>& p, unsigned members =
   const bool ak = p.a_k == 1, bn = p.b_n == 1;
   const int64_t outs = p.H * p.M * p.N;
   int path;  // slot of tnco_hip_contract_kernel_launches; the members of a batch (grid z) do not enter the choice
-  if (p.M >= 64 && p.N >= 64 && p.K > 32) {  // tiled: every operand element reused 64 times from LDS
+  constexpr bool single = std::is_same<T, float>::value || std::is_same<T, cplx<float>>::value;
+  if (p.M >= 64 && p.N >= 64 && p.K > 32 && single && c->compute == 1) {  // tiled, on the matrix cores (contract_split.h)
+    if constexpr (single) {
+      constexpr bool CP = std::is_same<T, cplx<float>>::value;
+      const int64_t tiles = p.H * ((p.M + HB - 1) / HB) * ((p.N + HB - 1) / HB);
+      const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20), 1, members);
+      if (ak && bn) hipLaunchKernelGGL((ct_split_tiled_kernel<CP, true, true>), grid, dim3(256), 0, c->stream, p);
+      else if (ak) hipLaunchKernelGGL((ct_split_tiled_kernel<CP, true, false>), grid, dim3(256), 0, c->stream, p);
+      else if (bn) hipLaunchKernelGGL((ct_split_tiled_kernel<CP, false, true>), grid, dim3(256), 0, c->stream, p);
+      else hipLaunchKernelGGL((ct_split_tiled_kernel<CP, false, false>), grid, dim3(256), 0, c->stream, p);
+    }
+    path = 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0);
+    c->split_launches += 1;
+  } else if (p.M >= 64 && p.N >= 64 && p.K > 32) {  // tiled: every operand element reused 64 times from LDS
     const int64_t tiles = p.H * ((p.M + TB - 1) / TB) * ((p.N + TB - 1) / TB);
     const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20), 1, members);
     if (ak && bn) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, true, true>), grid, dim3(256), 0, c->stream, p);
@@ -1031,7 +1051,7 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
       CT_TRY(hipMemcpyAsync(c->d_exps, c->leaf_exps.data(), c->leaf_exps.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
   }
-  c->macs = c->launches = c->narrow_launches = c->batch_launches = c->last_member = 0;
+  c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->last_member = 0;
   std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
   std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
   CT_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -1135,6 +1155,21 @@ int tnco_hip_contract_set_slice_batch(tnco_hip_contract c, int64_t batch) {
   c->d_arena = d_arena, c->d_batch_out = d_stage;
   if (c->scaling) c->d_exps = (int32_t*)d_exps, c->d_amax = (uint32_t*)(c->d_exps + B * n_slots);
   c->batch = batch, c->bytes = bytes;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_set_compute(tnco_hip_contract c, int32_t mode) {
+  if (!c) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (mode != 0 && mode != 1) return fail(TNCO_HIP_EINVAL, "'mode' must be 0 (plain) or 1 (bf16x3).");
+  if (c->dtype != 0 && c->dtype != 2) return fail(TNCO_HIP_EINVAL, "a compute mode needs a float32 or complex64 plan.");
+  if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with a compute mode.");
+  c->compute = mode;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_split_launches(tnco_hip_contract c, int64_t* count) {
+  if (!c || !count) return fail(TNCO_HIP_EINVAL, "null argument.");
+  *count = c->split_launches;
   return TNCO_HIP_OK;
 }
 

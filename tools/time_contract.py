@@ -10,7 +10,9 @@ of that circuit in one projected call (`--projs`: the 53 output indices sparse, 
 optimize(n_projs=P)) against a loop of plain contract() calls over leaves indexed at one bitstring each, along the same
 path; the storage mode (`--storage`: the large square step in float32 and complex64 with `storage` unset, float16 and
 bfloat16, and the sliced Sycamore leg once more with storage="bfloat16"); slice batches (`--slice-batch`: the sliced
-Sycamore leg with slice_batch None, 1, 8 and 64, plain, in storage mode and with scaling).  Engine figures are its
+Sycamore leg with slice_batch None, 1, 8 and 64, plain, in storage mode and with scaling); the compute mode
+(`--compute`: the large square step in float32 and complex64 with compute=None, compute="bf16x3" and
+storage="bfloat16" in one process, and the sliced Sycamore leg with compute=None and "bf16x3").  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device).
 """
@@ -274,6 +276,58 @@ def slice_batch(lines, depth, max_width, max_slices, batches=(None, 1, 8, 64)):
             del r
 
 
+def compute(lines, n, depth, max_width, max_slices):
+    """The compute mode against the plain engine in the same process: the large square step with compute=None (the tiled
+    LDS kernel, the yardstick), compute="bf16x3" (ct_split_tiled_kernel) and storage="bfloat16" (ct_mfma_tiled_kernel), and
+    the sliced Sycamore amplitude of the storage leg with compute=None and "bf16x3"."""
+    lines.append("")
+    lines.append(f"## compute mode, large square step M = N = K = {n}: float32 / complex64 storage, every product as three "
+                 "bfloat16 products on the matrix cores (ct_split_tiled_kernel), against compute=None (the tiled LDS kernel) "
+                 "and storage=\"bfloat16\" (ct_mfma_tiled_kernel) in one process; seconds: the minimum of four runs")
+    lines.append(f"{'dtype':>10} {'mode':>20} {'engine s':>10} {'TFLOP/s':>9} {'None / this':>12} {'rel. error to float64':>22}")
+    rng = np.random.RandomState(6)
+    for dt in (np.float32, np.complex64):
+        x, y = _rand((n, n), dt, rng), _rand((n, n), dt, rng)
+        fl = FLOPS_PER_MAC[dt] * n ** 3
+        ref = x.astype(np.complex128 if np.dtype(dt).kind == "c" else np.float64) @ y
+        t_base = None
+        for name, kw in (("compute=None", dict()), ("compute=bf16x3", dict(compute="bf16x3")),
+                         ("storage=bfloat16", dict(storage="bfloat16"))):
+            call = lambda kw=kw: ctr.contract([(0, 1)], [("i", "k"), ("k", "j")], [x, y], **kw)  # noqa: E731
+            r = call()
+            t = min(r.device_s, _engine_time(call))
+            t_base = t if t_base is None else t_base
+            err = float(np.linalg.norm(r.array - ref) / np.linalg.norm(ref))
+            lines.append(f"{np.dtype(dt).name:>10} {name:>20} {t:10.5f} {fl / t / 1e12:9.1f} {t_base / t:12.2f} {err:22.2e}")
+            print(lines[-1], flush=True)
+            del r
+        del ref, x, y
+    ts, d, o = syn.sycamore53_tn(depth=depth)
+    tn0 = tnmod.TensorNetwork([tnmod.Tensor(xs, [d] * len(xs)) for xs in ts], output_inds=o)
+    tn, res = Optimizer(method="sa", max_width=max_width, seed=0).optimize(tn0, betas=(0, 50), n_steps=200, n_runs=256)
+    r0 = res[0]
+    rng = np.random.RandomState(2)
+    n_inds = len({x for xs in ts for x in xs})
+    scale = 2.0 ** (-n_inds / (2 * len(ts)))  # (as in the storage leg: the amplitude stays near 1)
+    arrays = [(_rand(tuple(d for _ in xs), np.complex64, rng) * scale).astype(np.complex64) for xs in ts]
+    fused = ctr.contract(tn.tags["fuse_path"], tn0.ts_inds, arrays, tn0.output_inds)
+    leaves = fused.array if isinstance(fused.array, list) else [fused.array]
+    p = ctr.plan(r0.path, tn.ts_inds, [a.shape for a in leaves], tn.output_inds, slices=r0.slices)
+    m = min(p.n_slices, max_slices)
+    run = lambda c: ctr.contract(r0.path, tn.ts_inds, leaves, tn.output_inds, slices=r0.slices, slice_range=(0, m),  # noqa: E731
+                                 compute=c)
+    run(None)
+    a, b = run(None), run("bf16x3")
+    err = float(np.linalg.norm(np.ravel(b.array - a.array)) / np.linalg.norm(np.ravel(a.array)))
+    tiled = sum(1 for op in p.ops if op["M"] >= 64 and op["N"] >= 64 and op["K"] > 32)
+    lines.append(f"## compute mode, sliced Sycamore-53 amplitude, depth {depth}, complex64, max_width {max_width}, "
+                 f"assignments [0, {m}), {tiled} of {len(p.ops)} steps of the tiled class: compute=None: device "
+                 f"{a.device_s:.3f} s; compute=\"bf16x3\": device {b.device_s:.3f} s, {b.split_launches} launches of the "
+                 f"split kernel of {b.launches}, None / this {a.device_s / b.device_s:.2f}, relative difference to the "
+                 f"compute=None run {err:.2e}, peak device bytes {b.peak_device_bytes} (None: {a.peak_device_bytes})")
+    print(lines[-1], flush=True)
+
+
 def projections(lines, depth, counts, loop_max):
     """P amplitudes per call.  The network: the circuit without its 53 <x| tensors, the open wires its output and
     sparse indices.  The largest depth <= `depth` whose unsliced plan fits the free device memory at every P is used."""
@@ -343,14 +397,18 @@ def main():
     ap.add_argument("--storage", action="store_true", help="only the storage-mode leg, appended to --out")
     ap.add_argument("--scaling", action="store_true", help="only the scaling leg, appended to --out")
     ap.add_argument("--slice-batch", action="store_true", help="only the slice-batch leg, appended to --out")
+    ap.add_argument("--compute", action="store_true", help="only the compute-mode leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling + a.slice_batch > 1:
-        ap.error("--projs, --storage, --scaling and --slice-batch each append one leg: run them one after the other")
+    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute > 1:
+        ap.error("--projs, --storage, --scaling, --slice-batch and --compute each append one leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling or a.slice_batch:  # (the other legs' sections stay as they are)
-        if a.slice_batch:
+    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute:  # (the other legs' sections stay as they are)
+        if a.compute:
+            lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
+            compute(lines, a.n, a.depth, a.max_width, a.max_slices)
+        elif a.slice_batch:
             slice_batch(lines, a.depth, a.max_width, min(a.max_slices, 2048))
         elif a.scaling:
             scaling(lines, a.n, a.depth, a.max_width, a.max_slices)
@@ -368,6 +426,7 @@ def main():
     storage(lines, a.n, a.depth, a.max_width, a.max_slices)
     scaling(lines, a.n, a.depth, a.max_width, a.max_slices)
     slice_batch(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+    compute(lines, a.n, a.depth, a.max_width, a.max_slices)
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
