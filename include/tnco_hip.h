@@ -458,6 +458,21 @@ const char* tnco_hip_comm_last_error(void);
  * im += Ar Bi, im += Ai Br, each as those three).  The result is stored unrounded as float32; no atomics, a run stays
  * bit-reproducible.  Every other kernel is that of mode 0.  A finite part with |x| >= 2^128 - 2^119 has an infinite hi:
  * the elements it feeds become non-finite (the host refuses such leaves).  Works with slice batches.
+ *
+ * Path kernel (tnco_hip_contract_set_path_kernel; dtype codes 0..3 only): with a group of G the run takes the assignments
+ * in groups of up to G consecutive numbers, the first group starting at slice_start, the last one possibly partial, and a
+ * group is two launches.  In the first, one workgroup per member (block b: assignment first + b) interprets the whole
+ * path in its own copy of the arena, at arena + b arena_elems: permute group -1, then for each step its permute group
+ * and the step, a workgroup barrier between consecutive operations; leaves are read in place at the slice offset of the
+ * member's assignment.  A step sums in the order of the kernel the unfused loop launches for its shape (tiled and stream
+ * class: k ascending per element; dot class: 256 partials per element and their tree).  The last step writes the
+ * member's block, unrounded and with beta 0, to a staging buffer [G][block] of the output's type; the second launch adds
+ * or places the blocks in the output, one lane per element, the members in assignment order, from a device table of
+ * block offsets and beta bits that is filled for the whole run beforehand.  The result is bit for bit that of the unfused
+ * run.  The tables are those of the plan; steps, the permute groups and the placement table are copied to the device in
+ * addition.  A step may have 2^24 multiply-adds (H M N K) at most: one workgroup runs it.  Steps with row axes, storage
+ * dtypes, slice batches and compute modes are not supported.  A plan without steps takes the call and runs as it does
+ * without it.
  */
 typedef struct tnco_hip_contract_s* tnco_hip_contract;
 typedef struct tnco_hip_contract_desc {
@@ -527,6 +542,18 @@ int tnco_hip_contract_set_compute(tnco_hip_contract h, int32_t mode);
 /* the last run's launches of the split kernel of mode 1; they are also counted in their tiled slot of
  * tnco_hip_contract_kernel_launches (by operand layout), so the slots still sum to stats[1] as before */
 int tnco_hip_contract_split_launches(tnco_hip_contract h, int64_t* count);
+/* after create, before run, once per handle: the runs that follow take `group` assignments per launch of the path
+ * kernel (above).  EINVAL for a group outside [1, 1024], on a handle with row axes, a storage dtype, a slice batch or a
+ * compute mode, and when a step has more than 2^24 multiply-adds (the message names the step); a handle that took this
+ * call refuses a slice batch and a compute mode in turn.  Reserves `group` arenas and the staging buffer of the output,
+ * and uploads the steps, the permute groups and the placement of every assignment of [slice_start, slice_stop) (ERUNTIME
+ * when they exceed the device's free memory; the handle then stays as it was); stats[2] counts them.  A handle on which
+ * this was never called runs the unfused loop */
+int tnco_hip_contract_set_path_kernel(tnco_hip_contract h, int64_t group);
+/* counts[2]: the last run's launches of the path kernel and of the kernel that folds a group's blocks into the output
+ * (one each per group; 0, 0 without a path kernel and for a plan without steps).  stats[1] is their sum, and every slot
+ * of tnco_hip_contract_kernel_launches and tnco_hip_contract_row_launches is 0 on such a run */
+int tnco_hip_contract_path_launches(tnco_hip_contract h, int64_t* counts);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

@@ -71,6 +71,20 @@ makes the elements it feeds non-finite and leaves the others alone.  A finite pa
 intermediate the elements it feeds become non-finite.  Projections are not supported with it; `slice_batch` is, and
 stays bit-equal to the unbatched run; `split_launches` of the result counts the launches of the split kernel (they
 are also counted in their tiled slot of `kernel_launches`).
+
+Path kernel: with `path_kernel=G` (1 to 1024; exclusive with `slice_batch`; the four plain dtypes, no `storage`, `compute`
+or `projs`) the run takes the assignments of `slice_range` in groups of up to G consecutive numbers, the first group
+starting at slice_range[0], the last one possibly partial, and a group is two launches whatever the length of the path.
+In the first, one workgroup per assignment interprets the whole path -- the gathers, the permutes and the steps, a
+workgroup barrier between them -- in its own copy of the arena (csrc/contract_path.h); every step sums in the order of
+the kernel the unfused run launches for its shape.  The last step leaves the members' blocks in a staging buffer and the
+second launch adds or places them in the output in assignment order, from a device table of block offsets that is filled
+for the whole run beforehand.  The result is bit for bit that of `path_kernel=None`.  One workgroup runs each step, so a
+step may have 2^24 multiply-adds (H M N K) at most (MAX_PATH_STEP_MACS; ValueError beyond): the keyword is for width-bounded
+slices, whose steps are small and whose runs are bound by their launches.  Device memory grows by G - 1 arenas, G blocks
+of the output and the tables that are new on the device (`Plan.peak_device_bytes`).  The plan's tables do not change; a
+plan without steps takes the keyword and runs as without it.  `path_launches` of the result counts the two kernels;
+`kernel_launches`, `row_kernel_launches` and `batch_launches` are zeros on such a run.
 """
 from __future__ import annotations
 
@@ -84,7 +98,7 @@ from .app import tn as tnmod
 
 __all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
            "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage", "SCALINGS", "scale_exponent", "scale_to_storage",
-           "MAX_SLICE_BATCH", "COMPUTES", "split_bf16"]
+           "MAX_SLICE_BATCH", "COMPUTES", "split_bf16", "MAX_PATH_KERNEL", "MAX_PATH_STEP_MACS"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -96,6 +110,10 @@ SCALINGS = ("tensor",)  # per-tensor power-of-two scaling of storage mode (modul
 SCALE_BITS = 14  # the largest stored magnitude of a scaled tensor lies in [2^14, 2^15]
 COMPUTES = {"bf16x3": 1}  # compute modes (module docstring) and their codes for tnco_hip_contract_set_compute
 MAX_SLICE_BATCH = 64  # slice assignments per launch at most (csrc/contract.hip MAX_SLICE_BATCH)
+MAX_PATH_KERNEL = 1024  # path kernel: assignments per launch at most (csrc/contract_path.h MAX_PATH_GROUP)
+# path kernel: multiply-adds (H M N K) of one step at most -- one workgroup runs it.  A guard against a step that would
+# hold one compute unit of a shared card for long, not a tuned threshold (csrc/contract_path.h MAX_PATH_STEP_MACS)
+MAX_PATH_STEP_MACS = 1 << 24
 
 # operand / destination kinds and table widths: include/tnco_hip.h (tnco_hip_contract_desc)
 LEAF, ARENA, OUT = 0, 1, 2
@@ -134,6 +152,10 @@ class ContractionResult:
     #                          `launches` is the four counts together
     compute: str = None  # "bf16x3": the tiled-class steps ran as three bfloat16 products on the matrix cores
     split_launches: int = 0  # compute: launches of the split kernel (they are part of their tiled slot of kernel_launches)
+    path_kernel: int = None  # assignments per launch of the path kernel, the effective value (`Plan.path_kernel`; of several
+    #                          calls the largest, of an unsliced call 1); None: the unfused run
+    path_launches: tuple = (0, 0)  # path_kernel: launches of the path kernel and of the kernel that folds a group's blocks
+    #                                into the output; `launches` is their sum and the other launch counts are zeros
 
 
 @dataclass
@@ -165,6 +187,8 @@ class Plan:
     stage_refs: np.ndarray = None  # scaling: [n_steps] arena offset of a stored step's float32 staging buffer, -1 none
     slice_batch: int = None  # assignments per launch: min(what was asked for, assignments of slice_range); 1 without steps
     compute: str = None  # "bf16x3": the tiled-class steps on the matrix cores; the tables do not depend on it
+    path_kernel: int = None  # assignments per launch of the path kernel: min(what was asked for, assignments of slice_range);
+    #                          1 without steps
 
     @property
     def n_slices(self) -> int:
@@ -187,6 +211,12 @@ class Plan:
         if self.slice_batch is not None and len(self.steps):
             batch = self.slice_batch
             stage = item * batch * self.out_numel // math.prod(self.shape[self.inds.index(x)] for x in self.block_inds)
+        # a path kernel: an arena and a block of the output as staging per member, and the tables that are new on the
+        # device: the steps, the first row and the count of every permute group, the placement of every assignment
+        if self.path_kernel is not None and len(self.steps):
+            batch = self.path_kernel
+            stage = item * batch * self.out_numel // math.prod(self.shape[self.inds.index(x)] for x in self.block_inds)
+            tables += 8 * (self.steps.size + 2 * (len(self.steps) + 1) + self.slice_range[1] - self.slice_range[0])
         return held * (int(self.leaf_numel.sum()) + self.arena_elems * batch) + item * self.out_numel + tables + maps + \
             scale * batch + stage
 
@@ -300,6 +330,29 @@ def _check_compute(compute, storage, dtype, projs=None) -> None:
         raise TypeError(f"with 'compute' the compute dtype must be float32 or complex64, not {np.dtype(dtype)}.")
     if projs is not None:
         raise NotImplementedError("projections are not supported with 'compute'.")
+
+
+def _check_path_kernel(path_kernel, slice_batch=None, storage=None, compute=None, projs=None) -> None:
+    if path_kernel is None:
+        return
+    if isinstance(path_kernel, bool) or not isinstance(path_kernel, int) or not 1 <= path_kernel <= MAX_PATH_KERNEL:
+        raise ValueError(f"'path_kernel' must be None or an integer from 1 to {MAX_PATH_KERNEL}.")
+    if slice_batch is not None:
+        raise ValueError("'path_kernel' and 'slice_batch' are exclusive.")
+    for name, value in (("storage", storage), ("compute", compute)):
+        if value is not None:
+            raise NotImplementedError(f"'{name}' is not supported with 'path_kernel'.")
+    if projs is not None:
+        raise NotImplementedError("projections are not supported with 'path_kernel'.")
+
+
+def _check_path_steps(p) -> None:
+    """ValueError when a step of the plan is beyond what one workgroup of the path kernel is given."""
+    for k, row in enumerate(p.steps):
+        H, M, N, K = (int(v) for v in row[10:14])
+        if H * M * N * K > MAX_PATH_STEP_MACS:
+            raise ValueError(f"step {k} (H M N K = {H} x {M} x {N} x {K}) has more than 2^24 multiply-adds: too large for "
+                             "'path_kernel', which runs a step in one workgroup.")
 
 
 def split_bf16(a):
@@ -474,14 +527,15 @@ def _unique_rows(table):
 
 
 def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
-         sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None) -> Plan:
+         sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None) -> Plan:
     """The device plan of one contraction along a path that leaves one tensor (no GPU).
     `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`, `slice_batch`,
-    `compute`: see the module docstring."""
+    `compute`, `path_kernel`: see the module docstring."""
     _check_compute(compute, storage, dtype, projs)
     _check_storage(storage, dtype, projs)
     _check_scaling(scaling, storage)
     _check_slice_batch(slice_batch, projs)
+    _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
     ts_inds = [tuple(xs) for xs in ts_inds]
     shapes = [tuple(int(d) for d in s) for s in shapes]
     dims = _dims_of(ts_inds, shapes)
@@ -691,6 +745,9 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         p.stage_refs = np.array([offset[b] if b >= 0 else -1 for b in stage], np.int64)
     if slice_batch is not None:  # (the tables are those of the unbatched plan)
         p.slice_batch = min(int(slice_batch), hi - lo) if steps else 1
+    if path_kernel is not None:  # (the tables are those of the unfused plan; projections were refused above)
+        _check_path_steps(p)
+        p.path_kernel = min(int(path_kernel), hi - lo) if steps else 1
     if projs is None:
         return p
     # the device holds the distinct rows of the final tensor; the result has one per projection, duplicates included
@@ -751,7 +808,7 @@ def _sub_output(ts_inds, leaves, output) -> frozenset:
 
 
 def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=None, device=None,
-             sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None,
+             sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
              _intermediates=()) -> ContractionResult:
     """Contract `arrays` (numpy, in ts_inds order) along the linear `path` on the GPU; see the module docstring.
     A path that leaves several tensors gives lists in `inds` / `array` (the sliced and the projected form need one
@@ -767,12 +824,13 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     _check_storage(storage, dtype, projs)
     _check_scaling(scaling, storage)
     _check_slice_batch(slice_batch, projs)
+    _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
     steps = _check_path(path, len(ts_inds))
     final, out = tnmod.contract(steps, ts_inds, output_inds, dims)
     if len(final) == 1:
         p = plan(steps, ts_inds, [a.shape for a in arrays], out, slices=slices, slice_range=slice_range, dtype=dtype,
                  sparse_inds=sparse_inds, projs=projs, storage=storage, scaling=scaling, slice_batch=slice_batch,
-                 compute=compute)
+                 compute=compute, path_kernel=path_kernel)
         return _run(p, arrays, device, loose)
     if slices:
         raise NotImplementedError("slices need a path that leaves one tensor.")
@@ -780,23 +838,25 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
         raise NotImplementedError("projections need a path that leaves one tensor.")
     parts = []
     effective = None if slice_batch is None else 1  # (every part is unsliced: one assignment)
+    fused = None if path_kernel is None else 1
     for leaves, sub in _split(steps, len(ts_inds)):
         if not sub:  # a tensor the path does not touch: as the single-leaf plan gives it, rounded to storage
             a = arrays[leaves[0]].astype(dtype, copy=True)
             if scaling is not None:
                 a, e = scale_to_storage(a, storage)
                 parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, scaling=scaling, exponents=(e,),
-                                               slice_batch=effective))
+                                               slice_batch=effective, path_kernel=fused))
                 continue
             if storage is not None:
                 a = _from_storage_bits(_storage_bits(a, storage, leaves[0] not in loose), storage, a)
             if compute is not None and leaves[0] not in loose:
                 _check_split_range(a)
-            parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, slice_batch=effective, compute=compute))
+            parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, slice_batch=effective, compute=compute,
+                                           path_kernel=fused))
             continue
         parts.append(contract(sub, [ts_inds[t] for t in leaves], [arrays[t].astype(dtype, copy=False) for t in leaves],
                               _sub_output(ts_inds, leaves, out), device=device, storage=storage, scaling=scaling,
-                              slice_batch=slice_batch, compute=compute,
+                              slice_batch=slice_batch, compute=compute, path_kernel=path_kernel,
                               _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
     assert [tuple(r.inds) for r in parts] == [tuple(f) for f in final]
     return ContractionResult([r.inds for r in parts], [r.array for r in parts], sum(r.macs for r in parts), 1,
@@ -806,7 +866,8 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
                              exponents=None if scaling is None else [r.exponents for r in parts],
                              narrow_launches=sum(r.narrow_launches for r in parts), slice_batch=effective,
                              batch_launches=sum(r.batch_launches for r in parts), compute=compute,
-                             split_launches=sum(r.split_launches for r in parts))
+                             split_launches=sum(r.split_launches for r in parts), path_kernel=fused,
+                             path_launches=_add_counts(*(r.path_launches for r in parts)))
 
 
 def _add_counts(*counts) -> tuple:
@@ -868,12 +929,14 @@ def _describe(p: Plan, device: int):
 
 def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
     from . import _lib
-    exponents, narrow, folds, splits = None, 0, 0, 0
+    exponents, narrow, folds, splits, fused = None, 0, 0, 0, (0, 0)
     try:
         if p.compute is not None:
             _lib.check(L.tnco_hip_contract_set_compute(h, COMPUTES[p.compute]))
         if p.slice_batch is not None:
             _lib.check(L.tnco_hip_contract_set_slice_batch(h, p.slice_batch))
+        if p.path_kernel is not None:
+            _lib.check(L.tnco_hip_contract_set_path_kernel(h, p.path_kernel))
         if p.scaling is not None:
             _lib.check(L.tnco_hip_contract_set_exponents(h, leaf_exps.ctypes.data_as(C.c_void_p)))
         staging = np.empty(p.out_numel, p.dtype)
@@ -899,6 +962,10 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
             count = C.c_int64()
             _lib.check(L.tnco_hip_contract_split_launches(h, C.byref(count)))
             splits = int(count.value)
+        if p.path_kernel is not None:
+            counts = np.zeros(2, np.int64)
+            _lib.check(L.tnco_hip_contract_path_launches(h, counts.ctypes.data_as(C.c_void_p)))
+            fused = tuple(int(v) for v in counts)
     finally:
         L.tnco_hip_contract_destroy(h)
     array = _host_layout(p, staging)
@@ -906,7 +973,7 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
                              int(stats[1]), float(stats[3]) * 1e-9, kernel_launches=tuple(int(v) for v in by_kernel),
                              row_kernel_launches=tuple(int(v) for v in by_row_kernel), scaling=p.scaling,
                              exponents=exponents, narrow_launches=narrow, slice_batch=p.slice_batch, batch_launches=folds,
-                             compute=p.compute, split_launches=splits)
+                             compute=p.compute, split_launches=splits, path_kernel=p.path_kernel, path_launches=fused)
 
 
 def _host_layout(p: Plan, staging) -> np.ndarray:
@@ -927,7 +994,7 @@ def _host_layout(p: Plan, staging) -> np.ndarray:
 
 
 def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse_inds=None,
-                     storage=None, scaling=None, slice_batch=None, compute=None) -> ContractionResult:
+                     storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None) -> ContractionResult:
     """Run a result of `Optimizer.optimize` over the arrays of the network as given.
 
     tn0: the network before pre-fusing (`load_tn(obj, fuse=None)`); arrays: in tn0.tensors order, or {name: array}
@@ -945,11 +1012,14 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     last call made).  slice_batch: that many slice assignments per launch in every sliced call (module docstring);
     `batch_launches` is the sum over the calls, `slice_batch` of the result the largest effective value of a component.
     compute: "bf16x3" runs the tiled-class steps of `result.path` on the matrix cores (module docstring); the fuse stage
-    stays in plain precision; `split_launches` is the sum over the calls."""
+    stays in plain precision; `split_launches` is the sum over the calls.  path_kernel: that many slice assignments per
+    launch of the path kernel in every call over `result.path` (module docstring); the fuse stage stays as it is;
+    `path_launches` is the sum over the calls, `path_kernel` of the result the largest effective value of a component."""
     _check_compute(compute, storage, np.float32, projs)
     _check_storage(storage, np.float32, projs)
     _check_scaling(scaling, storage)
     _check_slice_batch(slice_batch, projs)
+    _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
     if (tn0.sparse_inds or tn.sparse_inds) and projs is None:
         raise NotImplementedError("sparse indices (n_projs) have an array meaning only at given projections: "
                                   "pass projs=, an integer array [P, number of sparse indices].")
@@ -983,15 +1053,17 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     if len(comp_paths) <= 1:  # one component to contract: the path with its slices, in one call
         r = contract(result.path, tn.ts_inds, arrays, tn.output_inds, slices=getattr(result, "slices", ()),
                      device=device, sparse_inds=sparse_inds or (), projs=projs, storage=storage, scaling=scaling,
-                     slice_batch=slice_batch, compute=compute)
+                     slice_batch=slice_batch, compute=compute, path_kernel=path_kernel)
         return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
                                  fuse_macs, r.kernel_launches, r.row_kernel_launches, r.scaling, r.exponents,
-                                 r.narrow_launches, r.slice_batch, r.batch_launches, r.compute, r.split_launches)
+                                 r.narrow_launches, r.slice_batch, r.batch_launches, r.compute, r.split_launches,
+                                 r.path_kernel, r.path_launches)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
     ts, n = [tuple(x) for x in tn.ts_inds], len(tn.ts_inds)
     done, results, macs, n_slices, peak, launches, device_s = set(), [], 0, 0, 0, 0, 0.0
     by_kernel = (0,) * len(KERNEL_PATHS)
     exponents, narrow, folds, effective, splits = None, 0, 0, None, 0
+    fused, fused_launches = None, (0, 0)
     n_comp_steps = 0
     for q, cut in zip(result.disconnected_paths, result.disconnected_slices):
         if not q:
@@ -999,11 +1071,14 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         n_comp_steps += len(q)
         (leaves, sub), = [(lv, s) for lv, s in _split(_check_path(q, n), n) if s]
         r = contract(sub, [ts[t] for t in leaves], [arrays[t] for t in leaves], _sub_output(ts, leaves, tn.output_inds),
-                     slices=cut, device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute)
+                     slices=cut, device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute,
+                     path_kernel=path_kernel)
         exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
         splits += r.split_launches
         if slice_batch is not None:
             effective = max(effective or 1, r.slice_batch)
+        if path_kernel is not None:
+            fused, fused_launches = max(fused or 1, r.path_kernel), _add_counts(fused_launches, r.path_launches)
         done |= set(leaves)
         results.append(r)
         macs, n_slices, launches = macs + r.macs, n_slices + r.n_slices, launches + r.launches
@@ -1018,7 +1093,8 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     if tail:
         r = contract(tail, state_inds, state_arrays, frozenset(tn.output_inds) & {x for xs in state_inds for x in xs},
                      device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute,
-                     _intermediates=range(len(state_arrays) - len(results), len(state_arrays)))
+                     path_kernel=path_kernel, _intermediates=range(len(state_arrays) - len(results), len(state_arrays)))
+        fused_launches = _add_counts(fused_launches, r.path_launches)
         exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
         splits += r.split_launches
         macs, launches, peak = macs + r.macs, launches + r.launches, max(peak, r.peak_device_bytes)
@@ -1029,4 +1105,5 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         inds, array = (state_inds[0], state_arrays[0]) if len(state_inds) == 1 else (state_inds, state_arrays)
     return ContractionResult(inds, array, macs, n_slices, peak, launches, device_s, fuse_macs, by_kernel,
                              scaling=scaling, exponents=exponents, narrow_launches=narrow, slice_batch=effective,
-                             batch_launches=folds, compute=compute, split_launches=splits)
+                             batch_launches=folds, compute=compute, split_launches=splits, path_kernel=fused,
+                             path_launches=fused_launches)

@@ -25,6 +25,10 @@
 //   ct_batch_reduce_kernel folds them into the output, one lane per element, the members in assignment order,
 // so the sum over assignments keeps its order and a batched run is bit-equal to the unbatched one.  An unbatched launch
 // is the same kernel with one member and every member stride 0.
+// Path kernel (tnco_hip_contract_set_path_kernel, contract_path.h): a group of up to 1024 assignments per launch, one
+// workgroup per assignment interpreting the whole path in its own copy of the arena (ct_path_kernel), and
+//   ct_path_reduce_kernel  folds the group's blocks into the output as ct_batch_reduce_kernel does;
+// two launches per group, the sums in the order of the unfused kernels: bit-equal to the loop above.
 // No atomics in any sum: every sum runs in one fixed order, so a run is bit-reproducible (the one atomic, the integer max
 // behind a scaled tensor's exponent, does not depend on order).
 #include "../../include/tnco_hip.h"
@@ -377,6 +381,8 @@ __global__ __launch_bounds__(256) void ct_batch_reduce_kernel(T* out, const T* s
     }
 }
 
+#include "contract_path.h"
+
 // A step with a row axis: row r of the result reads row a_map[r] of A and row b_map[r] of B.  A null map with a row
 // stride: row r itself; a row stride of 0: the operand has one row, read for every r.
 template <class T>
@@ -522,6 +528,11 @@ struct tnco_hip_contract_s {
   int64_t batch_launches = 0;      // launches of ct_batch_reduce_kernel in the last run
   int compute = 0;                 // tnco_hip_contract_set_compute: 0 plain, 1 bf16x3
   int64_t split_launches = 0;      // launches of ct_split_tiled_kernel in the last run
+  int64_t path_group = 0;          // tnco_hip_contract_set_path_kernel: assignments per launch of ct_path_kernel, 0: never set
+  void* d_path_stage = nullptr;    // [path_group][block_numel] of the output's type: the members' last steps
+  int64_t* d_path_tables = nullptr;  // steps | first row and count of every permute group | placement of every assignment
+  std::vector<int64_t> path_image;   // the host copy of d_path_tables
+  int64_t path_launches[2] = {0, 0};  // launches of ct_path_kernel and of ct_path_reduce_kernel in the last run
   int64_t last_member = 0;         // the member that ran the last assignment of the last run (its exponent slots)
   int64_t base_bytes = 0;          // `bytes` as create reserved them
   std::vector<int32_t> exps_image;  // the leaves' exponents, once per member
@@ -962,6 +973,44 @@ int run_impl(tnco_hip_contract_s* c) {
   return TNCO_HIP_OK;
 }
 
+// The fused loop of a handle with a path kernel: per group of up to c->path_group assignments one ct_path_kernel and
+// one ct_path_reduce_kernel.
+template <class T>
+int run_path(tnco_hip_contract_s* c) {
+  const int64_t S = (int64_t)c->steps.size() / STEP_W, P = (int64_t)c->perms.size() / PERM_W;
+  PathArgs a;
+  a.perms = c->d_tables;
+  a.leaf_sl = c->d_tables + P * PERM_W;
+  a.slice_place = a.leaf_sl + c->leaf_sl.size();
+  a.slice_dims = a.slice_place + c->place.size();
+  a.steps = c->d_path_tables;
+  a.groups = a.steps + S * STEP_W;
+  a.leaves = (const void* const*)c->d_leaf_ptrs;
+  a.arena = c->d_arena, a.stage = c->d_path_stage;
+  a.arena_elems = c->arena_elems, a.block_numel = c->block_numel;
+  a.n_steps = (int)S;
+  const int64_t* d_place = a.groups + 2 * (S + 1);
+  int64_t per_slice = 0;
+  for (int64_t k = 0; k < S; ++k) {
+    const int64_t* st = &c->steps[k * STEP_W];
+    per_slice += st[10] * st[11] * st[12] * st[13];
+  }
+  for (int64_t sid = c->start; sid < c->stop; sid += c->path_group) {
+    const int64_t n = std::min(c->path_group, c->stop - sid);
+    a.sid0 = sid;
+    hipLaunchKernelGGL(ct_path_kernel<T>, dim3((unsigned)n), dim3(PATH_LANES), 0, c->stream, a);
+    CT_TRY(hipGetLastError());
+    const dim3 grid((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048));
+    hipLaunchKernelGGL(ct_path_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (T*)c->d_out, (const T*)c->d_path_stage,
+                       c->block_numel, (int)n, d_place + (sid - c->start));
+    CT_TRY(hipGetLastError());
+    c->launches += 2;
+    c->path_launches[0] += 1, c->path_launches[1] += 1;
+    c->macs += per_slice * n;
+  }
+  return TNCO_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1052,10 +1101,16 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
     }
   }
   c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->last_member = 0;
+  c->path_launches[0] = c->path_launches[1] = 0;
   std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
   std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
   CT_TRY(hipEventRecord(c->ev[0], c->stream));
-  int rc = c->dtype == 0 ? run_impl<float>(c)
+  const bool fused = c->path_group > 0 && n_steps > 0;  // (a plan without steps runs as it does without the call)
+  int rc = fused ? (c->dtype == 0 ? run_path<float>(c)
+                    : c->dtype == 1 ? run_path<double>(c)
+                    : c->dtype == 2 ? run_path<cplx<float>>(c)
+                                    : run_path<cplx<double>>(c))
+           : c->dtype == 0 ? run_impl<float>(c)
            : c->dtype == 1 ? run_impl<double>(c)
            : c->dtype == 2 ? run_impl<cplx<float>>(c)
            : c->dtype == 3 ? run_impl<cplx<double>>(c)
@@ -1118,6 +1173,7 @@ int tnco_hip_contract_set_slice_batch(tnco_hip_contract c, int64_t batch) {
   if (!c) return fail(TNCO_HIP_EINVAL, "null argument.");
   if (batch < 1 || batch > MAX_SLICE_BATCH) return fail(TNCO_HIP_EINVAL, "'batch' must be from 1 to 64.");
   if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with a slice batch.");
+  if (c->path_group) return fail(TNCO_HIP_EINVAL, "a slice batch and a path kernel are exclusive.");
   const size_t n_steps = c->steps.size() / STEP_W, n_slots = c->leaf_numel.size() + n_steps;
   if (!n_steps) {  // a single leaf gathered into the output: runs as it does without a batch, nothing to reserve
     c->batch = batch;
@@ -1163,6 +1219,7 @@ int tnco_hip_contract_set_compute(tnco_hip_contract c, int32_t mode) {
   if (mode != 0 && mode != 1) return fail(TNCO_HIP_EINVAL, "'mode' must be 0 (plain) or 1 (bf16x3).");
   if (c->dtype != 0 && c->dtype != 2) return fail(TNCO_HIP_EINVAL, "a compute mode needs a float32 or complex64 plan.");
   if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with a compute mode.");
+  if (mode && c->path_group) return fail(TNCO_HIP_EINVAL, "a compute mode is not supported with a path kernel.");
   c->compute = mode;
   return TNCO_HIP_OK;
 }
@@ -1170,6 +1227,80 @@ int tnco_hip_contract_set_compute(tnco_hip_contract c, int32_t mode) {
 int tnco_hip_contract_split_launches(tnco_hip_contract c, int64_t* count) {
   if (!c || !count) return fail(TNCO_HIP_EINVAL, "null argument.");
   *count = c->split_launches;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_set_path_kernel(tnco_hip_contract c, int64_t group) {
+  if (!c) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (group < 1 || group > MAX_PATH_GROUP) return fail(TNCO_HIP_EINVAL, "'group' must be from 1 to 1024.");
+  if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with a path kernel.");
+  if (c->dtype > 3) return fail(TNCO_HIP_EINVAL, "a path kernel needs a plain dtype.");
+  if (c->batch) return fail(TNCO_HIP_EINVAL, "a slice batch and a path kernel are exclusive.");
+  if (c->compute) return fail(TNCO_HIP_EINVAL, "a compute mode is not supported with a path kernel.");
+  if (c->path_group) return fail(TNCO_HIP_EINVAL, "the path kernel is already set.");
+  const int64_t S = (int64_t)c->steps.size() / STEP_W;
+  for (int64_t k = 0; k < S; ++k) {
+    const int64_t* st = &c->steps[k * STEP_W];
+    int64_t macs = 1;  // H M N K, every factor checked before it enters the product
+    bool over = false;
+    for (int q = 10; q <= 13 && !over; ++q) {
+      over = st[q] > MAX_PATH_STEP_MACS / macs;
+      macs *= over ? 1 : st[q];
+    }
+    if (over)
+      return fail(TNCO_HIP_EINVAL, "step " + std::to_string(k) + " has more than 2^24 multiply-adds: too large for a path kernel.");
+  }
+  if (!S) {  // a single leaf gathered into the output: runs as it does without the call, nothing to reserve
+    c->path_group = group;
+    return TNCO_HIP_OK;
+  }
+  CT_TRY(hipSetDevice(c->device));
+  CT_TRY(hipStreamSynchronize(c->stream));
+  // the tables that are new on the device: the steps, the permute groups, and where every assignment of the run goes in
+  // the output (the `visited` bookkeeping of the unfused loop, which does not depend on the data)
+  std::vector<int64_t>& tab = c->path_image;
+  tab.assign(c->steps.begin(), c->steps.end());
+  for (int64_t g = 0; g <= S; ++g) tab.push_back(c->group_first[g]), tab.push_back(c->group_count[g]);
+  std::vector<char> visited(c->n_blocks, 0);
+  for (int64_t sid = c->start; sid < c->stop; ++sid) {
+    int64_t blk = 0;
+    for (int64_t b : c->block) blk = blk * c->slice_dims[b] + (sid / c->place[b]) % c->slice_dims[b];
+    tab.push_back(blk * c->block_numel * 2 + visited[blk]);
+    visited[blk] = 1;
+  }
+  // G arenas, G blocks of the output's type and the tables (`bytes` counts arena_elems per member, as
+  // Plan.peak_device_bytes does)
+  const size_t arena = (size_t)c->arena_elems * c->elem, G = (size_t)group;
+  const size_t stage = G * (size_t)c->block_numel * c->out_elem, tables = tab.size() * sizeof(int64_t);
+  const int64_t bytes = c->base_bytes + (int64_t)((G - 1) * arena + stage + tables);
+  size_t free_b = 0, total_b = 0;
+  CT_TRY(hipMemGetInfo(&free_b, &total_b));
+  const size_t need = (size_t)(bytes - c->bytes);
+  if (need > free_b) {
+    tab.clear();
+    return fail(TNCO_HIP_ERUNTIME, "the path kernel needs " + std::to_string(need) + " bytes of device memory, " +
+                                       std::to_string(free_b) + " are free.");
+  }
+  // the new buffers first: a handle that this call fails on stays as it was
+  void *d_arena = nullptr, *d_stage = nullptr, *d_tab = nullptr;
+  if (hipMalloc(&d_arena, std::max<size_t>(G * arena, c->elem)) != hipSuccess || hipMalloc(&d_stage, std::max<size_t>(stage, 4)) != hipSuccess ||
+      hipMalloc(&d_tab, tables) != hipSuccess ||
+      hipMemcpyAsync(d_tab, tab.data(), tables, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) {
+    for (void* p : {d_arena, d_stage, d_tab})
+      if (p) (void)hipFree(p);
+    tab.clear();
+    return fail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+  }
+  if (c->d_arena) (void)hipFree(c->d_arena);
+  c->d_arena = d_arena, c->d_path_stage = d_stage, c->d_path_tables = (int64_t*)d_tab;
+  c->path_group = group, c->bytes = bytes;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_path_launches(tnco_hip_contract c, int64_t* counts) {
+  if (!c || !counts) return fail(TNCO_HIP_EINVAL, "null argument.");
+  counts[0] = c->path_launches[0], counts[1] = c->path_launches[1];
   return TNCO_HIP_OK;
 }
 
@@ -1183,7 +1314,7 @@ void tnco_hip_contract_destroy(tnco_hip_contract c) {
   if (!c) return;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_leaves, c->d_arena, c->d_out, (void*)c->d_tables, (void*)c->d_leaf_ptrs, (void*)c->d_row_maps,
-                  (void*)c->d_exps, c->d_batch_out})
+                  (void*)c->d_exps, c->d_batch_out, c->d_path_stage, (void*)c->d_path_tables})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);

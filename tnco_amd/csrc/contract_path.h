@@ -1,0 +1,157 @@
+// contract_path.h -- a whole slice assignment in one kernel (tnco_hip_contract_set_path_kernel); included by contract.hip
+// inside its anonymous namespace, after ct_slice_offset, ct_zero / ct_mac / ct_add and the table widths.
+// The sliced runs are bound by launches: a width-bounded assignment is a few hundred small gathers and steps.  Here one
+// workgroup interprets the whole path for one assignment, so a group of up to MAX_PATH_GROUP assignments is one launch,
+// and a second launch folds the group's blocks into the output:
+//   ct_path_kernel         block b = assignment first + b, in its own copy of the arena: permute group -1, then for each
+//                          step its permute group and the step, a workgroup barrier between consecutive operations; the
+//                          last step leaves the member's block, unrounded and with beta 0, in stage[b];
+//   ct_path_reduce_kernel  stage [n][block] -> the output, one lane per element, the members in assignment order, block
+//                          offsets and beta bits from a device table filled before the first launch.
+// The four plain dtypes only.  Every sum keeps the order of the kernel launch_gemm would have chosen for the step, so a
+// run is bit for bit that of the unfused loop (see ct_path_step).  The tables are read through uniform addresses only,
+// and every loop bound and branch around a barrier is a table value: all lanes of a block pass the same barriers.
+#pragma once
+
+constexpr int MAX_PATH_GROUP = 1024;  // assignments per launch at most (tnco_amd/contraction.py MAX_PATH_KERNEL)
+// One workgroup runs each step: a step beyond this many multiply-adds (H M N K) would hold one compute unit of a shared
+// card for long, so a plan that has one is refused.  A guard, not a tuned threshold.  It also bounds every operand, every
+// result and every permuted intermediate of a step by 2^24 elements: the element arithmetic below is 32-bit.
+constexpr int64_t MAX_PATH_STEP_MACS = (int64_t)1 << 24;
+constexpr int PATH_LANES = 1024;  // lanes of a block: four 256-lane quarters, each ct_dot_body's block for one output
+
+struct PathArgs {
+  const int64_t* perms;        // [n_perms][PERM_W], sorted by group
+  const int64_t* leaf_sl;      // [n_leaves][LEAF_SL_W]
+  const int64_t* slice_place;  // place value of every slice position
+  const int64_t* slice_dims;
+  const int64_t* steps;        // [n_steps][STEP_W]
+  const int64_t* groups;       // [n_steps + 1][2]: first row and number of rows of permute group g at g + 1
+  const void* const* leaves;
+  void* arena;                 // a copy of arena_elems elements per member
+  void* stage;                 // [members][block_numel]
+  int64_t arena_elems, block_numel;
+  int64_t sid0;                // the assignment of block 0
+  int n_steps;
+};
+
+// the rows of one permute group, one after the other (they are independent of each other: one launch in the unfused
+// loop): ct_gather_body's element loop, strided over the block.  A permute feeds a step, so numel < 2^24.
+template <class T>
+__device__ inline void ct_path_permutes(const PathArgs& p, int64_t group, T* arena, int64_t sid) {
+  const int64_t first = p.groups[2 * (group + 1)], count = p.groups[2 * (group + 1) + 1];
+  for (int64_t r = first; r < first + count; ++r) {
+    const int64_t* row = p.perms + r * PERM_W;
+    const uint32_t numel = (uint32_t)row[5];
+    const int nd = (int)row[4];
+    const T* src;
+    if (row[0] == K_LEAF)
+      src = (const T*)p.leaves[row[1]] + ct_slice_offset(p.leaf_sl + row[1] * LEAF_SL_W, p.slice_place, p.slice_dims, sid);
+    else
+      src = arena + row[1];
+    T* dst = arena + row[3];
+    for (uint32_t e = threadIdx.x; e < numel; e += PATH_LANES) {
+      uint32_t rem = e;
+      int64_t off = 0;  // (a stride of a leaf's axis may be beyond 32 bits: the sliced axes lie between the kept ones)
+      for (int k = nd - 1; k >= 0; --k) {
+        const uint32_t d = (uint32_t)row[8 + k], q = rem / d;
+        off += (int64_t)(rem - q * d) * row[8 + CT_MAX_AXES + k];
+        rem = q;
+      }
+      dst[e] = src[off];
+    }
+  }
+}
+
+// One step, C = A B with beta 0, in the summation order of the kernel launch_gemm picks for its shape:
+//   tiled and stream class: one lane per output element, k ascending from ct_zero with ct_mac -- ct_stream_body's order,
+//     and ct_gemm_tiled_kernel's too (its zero fill at a k tail adds fma(0, 0, acc) = acc);
+//   dot class (K >= 512, at most 8192 outputs, not tiled): an output per 256-lane quarter of the block, lane t of the
+//     quarter k = t, t + 256, ..., then ct_dot_body's tree over the quarter's 256 partials; four outputs per trip.
+// The trip count of the dot loop is the same for every lane: a quarter without an output (1 or 5 outputs) sums nothing,
+// stores nothing and passes the barriers.  H M N K <= 2^24: every offset inside an operand fits 32 bits.
+template <class T>
+__device__ inline void ct_path_step(const int64_t* st, const T* A, const T* B, T* C, T* part) {
+  const uint32_t a_m = (uint32_t)st[2], a_k = (uint32_t)st[3], b_k = (uint32_t)st[6], b_n = (uint32_t)st[7];
+  const uint32_t H = (uint32_t)st[10], M = (uint32_t)st[11], N = (uint32_t)st[12], K = (uint32_t)st[13];
+  const uint32_t total = H * M * N;
+  const bool tiled = M >= 64 && N >= 64 && K > 32;
+  if (!tiled && K >= 512 && total <= 8192) {
+    const uint32_t quarter = threadIdx.x / 256, t = threadIdx.x % 256;
+    T* mine = part + 256 * quarter;
+    const uint32_t trips = (total + 3) / 4;
+    for (uint32_t trip = 0; trip < trips; ++trip) {
+      const uint32_t e = 4 * trip + quarter;
+      const bool active = e < total;
+      T acc = ct_zero<T>();
+      if (active) {
+        const uint32_t n = e % N, r = e / N, m = r % M, h = r / M;
+        const T* a = A + (h * M * K + m * a_m);
+        const T* b = B + (h * K * N + n * b_n);
+        for (uint32_t k = t; k < K; k += 256) acc = ct_mac(acc, a[k * a_k], b[k * b_k]);
+      }
+      mine[t] = acc;
+      __syncthreads();
+      for (uint32_t w = 128; w > 0; w >>= 1) {
+        if (t < w) mine[t] = ct_add(mine[t], mine[t + w]);
+        __syncthreads();
+      }
+      if (active && t == 0) C[e] = mine[0];
+      __syncthreads();
+    }
+    return;
+  }
+  for (uint32_t e = threadIdx.x; e < total; e += PATH_LANES) {
+    const uint32_t n = e % N, r = e / N, m = r % M, h = r / M;
+    const T* a = A + (h * M * K + m * a_m);
+    const T* b = B + (h * K * N + n * b_n);
+    T acc = ct_zero<T>();
+    for (uint32_t k = 0; k < K; ++k) acc = ct_mac(acc, a[k * a_k], b[k * b_k]);
+    C[e] = acc;
+  }
+}
+
+// One block per member of the group, PATH_LANES lanes (the four quarters of the dot class; 16 wavefronts leave a lane
+// 128 registers).  Registers (gfx950, ROCm 7.0 hipcc): 34 VGPRs for float, 38 for double, 38 for cplx<float>, 44 for
+// cplx<double>; no scratch; LDS: the 1024 partials of the dot class, 4 to 16 KiB.  __syncthreads() orders the block's
+// global writes for the block, and an arena copy and a block of the staging belong to one block only.
+template <class T>
+__global__ __launch_bounds__(PATH_LANES) void ct_path_kernel(PathArgs p) {
+  __shared__ T part[PATH_LANES];
+  const int64_t b = blockIdx.x, sid = p.sid0 + b;
+  T* arena = (T*)p.arena + b * p.arena_elems;
+  ct_path_permutes<T>(p, -1, arena, sid);
+  __syncthreads();
+  for (int k = 0; k < p.n_steps; ++k) {
+    ct_path_permutes<T>(p, k, arena, sid);
+    __syncthreads();
+    const int64_t* st = p.steps + (int64_t)k * STEP_W;
+    const T* opnd[2];
+    for (int side = 0; side < 2; ++side) {
+      const int64_t kind = st[4 * side], ref = st[4 * side + 1];
+      // a leaf read in place: at the slice offset of this member's assignment, as ct_member has it
+      opnd[side] = kind == K_LEAF
+                       ? (const T*)p.leaves[ref] + ct_slice_offset(p.leaf_sl + ref * LEAF_SL_W, p.slice_place, p.slice_dims, sid)
+                       : arena + ref;
+    }
+    T* C = st[8] == K_OUT ? (T*)p.stage + b * p.block_numel : arena + st[9];
+    ct_path_step<T>(st, opnd[0], opnd[1], C, part);
+    __syncthreads();
+  }
+}
+
+// What ct_batch_reduce_kernel does, for up to MAX_PATH_GROUP members: place[b] = (element offset of member b's block of
+// the output) * 2 + beta, beta 1 when an earlier assignment of the run wrote that block (the host's `visited`
+// bookkeeping, which does not depend on the data: the table of the whole run is on the device before the first launch).
+// One lane per element of a block, the members one after the other in assignment order, each exactly the store of an
+// unfused last step (ct_store).  No atomics.
+template <class T>
+__global__ __launch_bounds__(256) void ct_path_reduce_kernel(T* out, const T* stage, int64_t numel, int n, const int64_t* place) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (int64_t)gridDim.x * blockDim.x)
+    for (int b = 0; b < n; ++b) {
+      const int64_t pl = place[b];
+      T* o = out + (pl >> 1) + e;
+      const T v = stage[b * numel + e];
+      *o = pl & 1 ? ct_add(*o, v) : v;
+    }
+}

@@ -12,7 +12,9 @@ path; the storage mode (`--storage`: the large square step in float32 and comple
 bfloat16, and the sliced Sycamore leg once more with storage="bfloat16"); slice batches (`--slice-batch`: the sliced
 Sycamore leg with slice_batch None, 1, 8 and 64, plain, in storage mode and with scaling); the compute mode
 (`--compute`: the large square step in float32 and complex64 with compute=None, compute="bf16x3" and
-storage="bfloat16" in one process, and the sliced Sycamore leg with compute=None and "bf16x3").  Engine figures are its
+storage="bfloat16" in one process, and the sliced Sycamore leg with compute=None and "bf16x3"); the path kernel
+(`--path-kernel`: the sliced Sycamore leg with path_kernel=None, slice_batch=64 and path_kernel 64, 256 and 1024 in one
+process).  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device).
 """
@@ -276,6 +278,56 @@ def slice_batch(lines, depth, max_width, max_slices, batches=(None, 1, 8, 64)):
             del r
 
 
+def path_kernel(lines, depth, max_width, max_slices):
+    """A whole assignment per workgroup on the sliced Sycamore amplitude of the storage leg, complex64: the unfused run,
+    slice_batch=64 and path_kernel 64, 256 and 1024, all in this process: device time (the minimum and the spread of three
+    runs after a warm-up), launches, memory and rate per setting, and the largest relative difference of an element to
+    the unfused run, which must be 0."""
+    lines.append("")
+    ts, d, o = syn.sycamore53_tn(depth=depth)
+    tn0 = tnmod.TensorNetwork([tnmod.Tensor(xs, [d] * len(xs)) for xs in ts], output_inds=o)
+    tn, res = Optimizer(method="sa", max_width=max_width, seed=0).optimize(tn0, betas=(0, 50), n_steps=200, n_runs=256)
+    r0 = res[0]
+    rng = np.random.RandomState(2)
+    n_inds = len({x for xs in ts for x in xs})
+    scale = 2.0 ** (-n_inds / (2 * len(ts)))  # (as in the storage leg: the amplitude stays near 1)
+    arrays = [(_rand(tuple(d for _ in xs), np.complex64, rng) * scale).astype(np.complex64) for xs in ts]
+    fused = ctr.contract(tn.tags["fuse_path"], tn0.ts_inds, arrays, tn0.output_inds)
+    leaves = fused.array if isinstance(fused.array, list) else [fused.array]
+    p = ctr.plan(r0.path, tn.ts_inds, [a.shape for a in leaves], tn.output_inds, slices=r0.slices)
+    m = min(p.n_slices, max_slices)
+    big = max(op["H"] * op["M"] * op["N"] * op["K"] for op in p.ops)
+    lines.append(f"## path_kernel, sliced Sycamore-53 amplitude, depth {depth}, complex64, max_width {max_width}, cost "
+                 f"{r0.cost}, {len(r0.path)} steps, largest step {big} MACs, arena {p.arena_elems} elements, assignments "
+                 f"[0, {m}) of {p.n_slices}: device seconds are the minimum of three runs after a warm-up, spread = "
+                 "(max - min) / min of the three; all runs in one process")
+    lines.append(f"{'setting':>18} {'device s':>9} {'spread':>7} {'None / this':>11} {'us / slice':>10} {'launches':>9} "
+                 f"{'path, reduce':>14} {'peak bytes':>11} {'GMAC/s':>8} {'max rel. diff to None':>21}")
+    base = t_base = None
+    times_of = {}
+    for name, kw in (("None", dict()), ("slice_batch=64", dict(slice_batch=64)), ("path_kernel=64", dict(path_kernel=64)),
+                     ("path_kernel=256", dict(path_kernel=256)), ("path_kernel=1024", dict(path_kernel=1024))):
+        call = lambda kw=kw: ctr.contract(r0.path, tn.ts_inds, leaves, tn.output_inds, slices=r0.slices,  # noqa: E731
+                                          slice_range=(0, m), **kw)
+        r = call()
+        times = [call().device_s for _ in range(3)]
+        t = times_of[name] = min(times)
+        if base is None:
+            base, t_base = r.array, t
+        with np.errstate(divide="ignore", invalid="ignore"):
+            diff = float(np.nanmax(np.where(r.array == base, 0.0, np.abs(r.array - base) / np.abs(base))))
+        same = np.array_equal(np.ravel(r.array).view(np.uint32), np.ravel(base).view(np.uint32))
+        lines.append(f"{name:>18} {t:9.4f} {(max(times) - t) / t:7.3f} {t_base / t:11.2f} {t / m * 1e6:10.2f} {r.launches:9d} "
+                     f"{str(r.path_launches):>14} {r.peak_device_bytes:11d} {r.macs / t / 1e9:8.2f} "
+                     f"{diff:21.2e}{'' if same else '  (bits differ)'}")
+        print(lines[-1], flush=True)
+        del r
+    a, b = times_of["slice_batch=64"], times_of["path_kernel=1024"]
+    lines.append(f"  path_kernel=1024 against slice_batch=64: {a:.4f} s / {b:.4f} s = {a / b:.2f}"
+                 f"{'' if b < a else ' -- NOT faster than slice_batch=64 on this leg'}")
+    print(lines[-1], flush=True)
+
+
 def compute(lines, n, depth, max_width, max_slices):
     """The compute mode against the plain engine in the same process: the large square step with compute=None (the tiled
     LDS kernel, the yardstick), compute="bf16x3" (ct_split_tiled_kernel) and storage="bfloat16" (ct_mfma_tiled_kernel), and
@@ -398,14 +450,19 @@ def main():
     ap.add_argument("--scaling", action="store_true", help="only the scaling leg, appended to --out")
     ap.add_argument("--slice-batch", action="store_true", help="only the slice-batch leg, appended to --out")
     ap.add_argument("--compute", action="store_true", help="only the compute-mode leg, appended to --out")
+    ap.add_argument("--path-kernel", action="store_true", help="only the path-kernel leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute > 1:
-        ap.error("--projs, --storage, --scaling, --slice-batch and --compute each append one leg: run them one after the other")
+    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel > 1:
+        ap.error("--projs, --storage, --scaling, --slice-batch, --compute and --path-kernel each append one leg: run them one "
+                 "after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute:  # (the other legs' sections stay as they are)
-        if a.compute:
+    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel:  # (the other legs' sections stay as they are)
+        if a.path_kernel:
+            lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
+            path_kernel(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+        elif a.compute:
             lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
             compute(lines, a.n, a.depth, a.max_width, a.max_slices)
         elif a.slice_batch:
@@ -427,6 +484,7 @@ def main():
     scaling(lines, a.n, a.depth, a.max_width, a.max_slices)
     slice_batch(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     compute(lines, a.n, a.depth, a.max_width, a.max_slices)
+    path_kernel(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
