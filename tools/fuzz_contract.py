@@ -1,0 +1,61 @@
+#!/usr/bin/env python3
+"""Every way of running a plan of the contraction engine, on random networks beyond the table of the tests.
+
+    python tools/fuzz_contract.py --seeds 3000:3400
+
+For every seed of the range the generator of tests/mode_cases.py gives a network (or none, when the seed's network is
+beyond the caps of a case); it is replayed by the numpy interpreter in its own dtype against the plain bound and then run
+on the device in every mode with the checks of tests/test_gpu_contract_modes.py (`check_case`).  One process.  The run
+stops at the first mismatch or exception and prints the case as a line that can be pasted into `mode_cases`; at the end
+it prints the largest error / bound per mode.  Not part of the suite.
+"""
+import argparse
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--seeds", default="3000:3100", help="A:B, the seeds A .. B - 1")
+    ap.add_argument("--cpu-only", action="store_true", help="the replay of the tables alone, no device")
+    args = ap.parse_args()
+    lo, hi = (int(v) for v in args.seeds.split(":"))
+    from tests import mode_cases as mc
+    from tests.test_contraction_plan import _interpret
+    ctr = check_case = None
+    if not args.cpu_only:
+        from tests.test_gpu_contract_modes import check_case
+        from tnco_amd import contraction as ctr
+    worst, ran = {}, 0
+    for seed in range(lo, hi):
+        case = mc.generate(seed)
+        if case is None:
+            continue
+        ran += 1
+        try:
+            p, arrays = case.plan(), mc.fill(case)
+            ref, mag = mc.reference(case, p, arrays)
+            err = np.abs(_interpret(p, arrays).astype(ref.dtype) - ref)
+            bound = mc.plain_bound(case, p, mag)
+            assert (err <= bound).all(), "the replay of the tables leaves the plain bound"
+            ratios = {"replay": float(np.divide(err, bound, out=np.zeros_like(err), where=bound > 0).max())}
+            if check_case is not None:
+                ratios.update(check_case(ctr, case, out=lambda line: None))
+        except Exception as e:  # noqa: BLE001 -- whatever it is, the case is what is wanted
+            print(f"seed {seed}: {type(e).__name__}: {e}\n{case.paste()}")
+            return 1
+        for mode, ratio in ratios.items():
+            if ratio > worst.get(mode, (0.0, None))[0] or mode not in worst:
+                worst[mode] = (ratio, seed)
+    print(f"{ran} networks of seeds {lo}:{hi}, every check passed")
+    for mode, (ratio, seed) in worst.items():
+        print(f"  {mode:18s} largest error / bound {ratio:.4f} (seed {seed})")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
