@@ -473,6 +473,17 @@ const char* tnco_hip_comm_last_error(void);
  * addition.  A step may have 2^24 multiply-adds (H M N K) at most: one workgroup runs it.  Steps with row axes, storage
  * dtypes, slice batches and compute modes are not supported.  A plan without steps takes the call and runs as it does
  * without it.
+ *
+ * Hoisting (tnco_hip_contract_set_hoist): a step or a permute whose operands do not depend on the assignment -- no leaf
+ * below them holds a sliced axis -- is flagged by the plan and runs once per run, before the first assignment, instead of
+ * once per assignment: first the flagged rows of permute group -1, then for each step k the flagged rows of its permute
+ * group and the step itself when it is flagged, as one-member launches of the kernels the loop would launch.  The loop
+ * over the assignments skips what is flagged.  A flagged item reads leaves without sliced axes and arena tensors that
+ * flagged items wrote, and writes the arena; what an unflagged step reads of it (a kept tensor) stays where it is for the
+ * whole run, and the plan places nothing an assignment writes over it.  With a slice batch the flagged items work in arena
+ * copy 0 and every member reads a kept tensor there; with scaling the exponent slots of copy 0 are copied to every member's
+ * slots after the flagged items, in stream order.  Every step runs the kernel it runs unhoisted on the same operands, so
+ * the result is bit for bit that of a handle without the call; stats[0] and the launch counts are of what ran.
  */
 typedef struct tnco_hip_contract_s* tnco_hip_contract;
 typedef struct tnco_hip_contract_desc {
@@ -554,6 +565,15 @@ int tnco_hip_contract_set_path_kernel(tnco_hip_contract h, int64_t group);
  * (one each per group; 0, 0 without a path kernel and for a plan without steps).  stats[1] is their sum, and every slot
  * of tnco_hip_contract_kernel_launches and tnco_hip_contract_row_launches is 0 on such a run */
 int tnco_hip_contract_path_launches(tnco_hip_contract h, int64_t* counts);
+/* after create, before run: step_flags[n_steps] and perm_flags[n_perms] (in the rows' order), 1 for what the runs that
+ * follow do once per run instead of once per assignment (above), 0 for the rest.  EINVAL for a value other than 0 and 1,
+ * on a handle with row axes or a path kernel (which refuses this handle in turn), for a flagged step that writes the
+ * output or has an operand with a sliced axis or an arena operand that an unflagged item wrote, for a flagged permute
+ * that writes the output or whose source has a sliced axis or was written by an unflagged item, for an unflagged permute
+ * whose source a flagged item wrote, for a permute group whose flagged rows do not come first, and when an unflagged item
+ * writes over a kept tensor.  Reserves nothing.  A handle on which this was never called, or with no flag set, runs
+ * everything per assignment */
+int tnco_hip_contract_set_hoist(tnco_hip_contract h, const int64_t* step_flags, const int64_t* perm_flags);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

@@ -92,7 +92,7 @@ EXPORTS = [
     "tnco_hip_contract_row_launches", "tnco_hip_contract_set_exponents", "tnco_hip_contract_exponents",
     "tnco_hip_contract_narrow_launches", "tnco_hip_contract_set_slice_batch", "tnco_hip_contract_batch_launches",
     "tnco_hip_contract_set_compute", "tnco_hip_contract_split_launches", "tnco_hip_contract_set_path_kernel",
-    "tnco_hip_contract_path_launches", "tnco_hip_contract_destroy",
+    "tnco_hip_contract_path_launches", "tnco_hip_contract_set_hoist", "tnco_hip_contract_destroy",
     "tnco_hip_device_name", "tnco_hip_device_count", "tnco_hip_last_error", "tnco_hip_version",
 ]
 
@@ -205,6 +205,7 @@ def load() -> C.CDLL:
     L.tnco_hip_contract_split_launches.argtypes = [vp, vp]
     L.tnco_hip_contract_set_path_kernel.argtypes = [vp, i64]
     L.tnco_hip_contract_path_launches.argtypes = [vp, vp]
+    L.tnco_hip_contract_set_hoist.argtypes = [vp, vp, vp]
     L.tnco_hip_contract_destroy.argtypes = [vp]
     L.tnco_hip_contract_destroy.restype = None
     L.tnco_hip_device_name.argtypes = [C.c_int, vp, C.c_int]

@@ -85,6 +85,20 @@ slices, whose steps are small and whose runs are bound by their launches.  Devic
 of the output and the tables that are new on the device (`Plan.peak_device_bytes`).  The plan's tables do not change; a
 plan without steps takes the keyword and runs as without it.  `path_launches` of the result counts the two kernels;
 `kernel_launches`, `row_kernel_launches` and `batch_launches` are zeros on such a run.
+
+Hoisting: with `hoist=True` (not with `path_kernel` or `projs`) what does not depend on the assignment runs once per call.
+A tensor is slice-free when no leaf below it holds an index of `slices`; a step is hoisted when both its operands are
+slice-free, a permute when its source is (the layout permute of a slice-free leaf, the arena-to-arena permute of a
+slice-free intermediate, a permute that feeds a step which is not hoisted).  The hoisted work runs before the first
+assignment of `slice_range`, in path order; everything else runs per assignment as without the keyword.  A slice-free
+tensor that a step of the assignments reads is kept: its buffer is never released, and the arena is planned in two
+phases on one allocator, the hoisted events first (their temporaries released, the kept buffers not), the events of an
+assignment on top of what that left; `arena_elems` and `peak_device_bytes` are the peak over both.  Every step runs the
+kernel it runs unhoisted on the same shapes and strides, so the result is bit for bit that of `hoist=None`, with
+`storage`, `scaling`, `compute` and `slice_batch` too (a batch: the hoisted phase works in arena copy 0, every member
+reads a kept tensor there).  `macs` is the sum of the hoisted steps plus assignments x the sum of the others; the launch
+counts are of what ran; `hoisted` of the plan and of the result is (steps hoisted, permutes hoisted).  Without a sliced
+index, or when nothing is slice-free, the plan and the run are those of `hoist=None`.
 """
 from __future__ import annotations
 
@@ -156,6 +170,8 @@ class ContractionResult:
     #                          calls the largest, of an unsliced call 1); None: the unfused run
     path_launches: tuple = (0, 0)  # path_kernel: launches of the path kernel and of the kernel that folds a group's blocks
     #                                into the output; `launches` is their sum and the other launch counts are zeros
+    hoisted: tuple = None  # hoist=True: (steps, permutes) that ran once per call instead of once per assignment
+    #                        (`Plan.hoisted`; of several calls the sums); None without the keyword
 
 
 @dataclass
@@ -189,6 +205,11 @@ class Plan:
     compute: str = None  # "bf16x3": the tiled-class steps on the matrix cores; the tables do not depend on it
     path_kernel: int = None  # assignments per launch of the path kernel: min(what was asked for, assignments of slice_range);
     #                          1 without steps
+    hoisted: tuple = None  # hoist=True: (steps hoisted, permutes hoisted); None without the keyword
+    step_hoist: np.ndarray = None  # hoist=True: [n_steps] 1 where the step runs once per call, before the first assignment
+    perm_hoist: np.ndarray = None  # hoist=True: [n_perms] the same per row of `perms` (within a group the hoisted rows first)
+    kept: tuple = ()  # hoist=True: (arena offset, elements) of every slice-free tensor that a step of the assignments reads
+    hoisted_macs: int = 0  # multiply-adds of the hoisted steps (they are part of macs_per_slice)
 
     @property
     def n_slices(self) -> int:
@@ -196,7 +217,7 @@ class Plan:
 
     @property
     def macs(self) -> int:
-        return self.macs_per_slice * (self.slice_range[1] - self.slice_range[0])
+        return self.hoisted_macs + (self.macs_per_slice - self.hoisted_macs) * (self.slice_range[1] - self.slice_range[0])
 
     @property
     def peak_device_bytes(self) -> int:
@@ -344,6 +365,17 @@ def _check_path_kernel(path_kernel, slice_batch=None, storage=None, compute=None
             raise NotImplementedError(f"'{name}' is not supported with 'path_kernel'.")
     if projs is not None:
         raise NotImplementedError("projections are not supported with 'path_kernel'.")
+
+
+def _check_hoist(hoist, path_kernel=None, projs=None) -> None:
+    if hoist is None:
+        return
+    if hoist is not True:
+        raise ValueError("'hoist' must be None or True.")
+    if path_kernel is not None:
+        raise NotImplementedError("'hoist' is not supported with 'path_kernel'.")
+    if projs is not None:
+        raise NotImplementedError("projections are not supported with 'hoist'.")
 
 
 def _check_path_steps(p) -> None:
@@ -527,15 +559,17 @@ def _unique_rows(table):
 
 
 def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
-         sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None) -> Plan:
+         sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
+         hoist=None) -> Plan:
     """The device plan of one contraction along a path that leaves one tensor (no GPU).
     `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`, `slice_batch`,
-    `compute`, `path_kernel`: see the module docstring."""
+    `compute`, `path_kernel`, `hoist`: see the module docstring."""
     _check_compute(compute, storage, dtype, projs)
     _check_storage(storage, dtype, projs)
     _check_scaling(scaling, storage)
     _check_slice_batch(slice_batch, projs)
     _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
+    _check_hoist(hoist, path_kernel, projs)
     ts_inds = [tuple(xs) for xs in ts_inds]
     shapes = [tuple(int(d) for d in s) for s in shapes]
     dims = _dims_of(ts_inds, shapes)
@@ -608,14 +642,17 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         dense = all(st[x] == size(kept[k + 1:]) for k, x in enumerate(kept))
         live.append(_Live(kept, LEAF if dense else None, t, t))
         live[-1].slot = t  # (scaling: the exponent slot; a permute keeps it)
+        live[-1].free = hoist is True and bool(sl) and not cut  # hoist: slice-free, no leaf below it holds a sliced index
 
-    # buffers are symbolic (numbers) until the event list is replayed on the arena
-    buf_size, front, events = [], [], []
+    # buffers are symbolic (numbers) until the event list is replayed on the arena.  Two phases, [1] the hoisted work
+    # of a call, [0] the work of an assignment: without `hoist` everything is in [0]
+    buf_size, front, events = [], ([], []), ([], [])
     perms, rows, ops, stage = [], [], [], []
+    perm_h, step_h, kept_bufs = [], [], []
 
-    def new_buf(numel, at_start=False):
+    def new_buf(numel, at_start=False, h=False):
         buf_size.append(numel)
-        (front if at_start else events).append(("alloc", len(buf_size) - 1))
+        (front if at_start else events)[h].append(("alloc", len(buf_size) - 1))
         return len(buf_size) - 1
 
     def permute(src, layout, group, dst_kind=ARENA):
@@ -625,7 +662,9 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         else:
             skind, sref = ARENA, src.ref
             st = {x: size(src.inds[k + 1:]) for k, x in enumerate(src.inds)}
-        dst = new_buf(numel, at_start=group < 0) if dst_kind == ARENA else 0
+        h = src.free and dst_kind == ARENA  # (hoisted: the source is slice-free)
+        perm_h.append(int(h))
+        dst = new_buf(numel, at_start=group < 0, h=h) if dst_kind == ARENA else 0
         row = [skind, sref, dst_kind, dst, len(layout), numel, group, 0] + [0] * (2 * MAX_AXES)
         row[8:8 + len(layout)] = [dims[x] for x in layout]
         row[8 + MAX_AXES:8 + MAX_AXES + len(layout)] = [st[x] for x in layout]
@@ -662,26 +701,30 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
             if best is None or moved < best[0]:
                 best = (moved, s_order, fa[0] if fa else None, fb[0] if fb else None)
         _, s_order, form_a, form_b = best
+        hst = A.free and B.free  # the step is hoisted: both operands are slice-free
+        step_h.append(int(hst))
         moved_from = []  # (the permutes of one step run in one launch: their sources are released after both)
         for T, form, target in ((A, form_a, ra + h + xs + s_order), (B, form_b, rb + h + s_order + ys)):
             if form is None:
                 ref = permute(T, target, -1 if T.leaf is not None else k)
                 if T.kind == ARENA:
-                    moved_from.append(T.ref)
+                    moved_from.append((T.ref, T.free))
                 T.inds, T.kind, T.ref, T.leaf = target, ARENA, ref, None
-        events.extend(("free", q) for q in moved_from)
+        for q, free in moved_from:  # (a hoisted permute releases its source in the hoisted phase)
+            events[free].append(("free", q))
         form_a = 0 if form_a is None else form_a
         form_b = 0 if form_b is None else form_b
         H, M, N, K = size(h), size(xs), size(ys), size(s_order)
         z = rz + h + xs + ys
-        c_kind, c_ref = (OUT, 0) if k == len(steps) - 1 else (ARENA, new_buf(size(z)))
+        assert not (hst and k == len(steps) - 1)  # (some leaf holds a sliced index, and the last step is above it)
+        c_kind, c_ref = (OUT, 0) if k == len(steps) - 1 else (ARENA, new_buf(size(z), h=hst))
         if scaling is not None:
             # a stored result is summed into a float32 staging buffer (2 storage elements per element) and narrowed
             # from there: live beside the operands and the result for this step alone.  Allocated after everything
             # else of the step and released at once, it leaves every other offset as the plan without scaling has it.
-            stage.append(new_buf(2 * size(z)) if c_kind == ARENA else -1)
+            stage.append(new_buf(2 * size(z), h=hst) if c_kind == ARENA else -1)
             if c_kind == ARENA:
-                events.append(("free", stage[-1]))
+                events[hst].append(("free", stage[-1]))
         op = dict(h=h, x=xs, y=ys, s=s_order, form_a=form_a, form_b=form_b, H=H, M=M, N=N, K=K)
         if projs is not None:
             R = size(rz)
@@ -712,13 +755,17 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
                      *((A.slot, B.slot) if scaling is not None else (0, 0))])
         ops.append(op)
         for T in (A, B):
-            if T.kind == ARENA:
-                events.append(("free", T.ref))
+            if T.kind == ARENA and T.free and not hst:  # kept: written once, read by every assignment, never released
+                kept_bufs.append(T.ref)
+            elif T.kind == ARENA:
+                events[hst].append(("free", T.ref))
         live.append(_Live(z, ARENA, c_ref))
         live[-1].slot = len(ts_inds) + k
+        live[-1].free = hst
 
+    # the hoisted phase first; the assignments then run on top of what it left, the kept buffers
     arena, offset = _Arena(), {}
-    for what, buf in front + events:
+    for what, buf in front[1] + events[1] + front[0] + events[0]:
         if what == "alloc":
             offset[buf] = arena.alloc(buf_size[buf])
         else:
@@ -733,7 +780,10 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
             if row[at] == ARENA:
                 row[at + 1] = offset[row[at + 1]]
     perm_tab = np.array(perms, np.int64).reshape(-1, PERM_W)
-    perm_tab = perm_tab[np.argsort(perm_tab[:, 6], kind="stable")]  # slice-start gathers (group -1) first
+    perm_h = np.array(perm_h, np.int64)
+    # slice-start gathers (group -1) first; within a group the hoisted rows first
+    order = np.argsort(2 * perm_tab[:, 6] - perm_h, kind="stable")
+    perm_tab, perm_h = perm_tab[order], perm_h[order]
     step_tab = np.array(rows, np.int64).reshape(-1, STEP_W)
     macs = int(sum(int(r[10]) * int(r[11]) * int(r[12]) * int(r[13]) for r in rows))
     p = Plan(dtype=np.dtype(dtype), inds=final, shape=tuple(dims[x] for x in final), slice_inds=slice_inds,
@@ -748,6 +798,11 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     if path_kernel is not None:  # (the tables are those of the unfused plan; projections were refused above)
         _check_path_steps(p)
         p.path_kernel = min(int(path_kernel), hi - lo) if steps else 1
+    if hoist is not None:  # (without a hoisted step or permute the tables are those of the plan without the keyword)
+        p.step_hoist, p.perm_hoist = np.array(step_h, np.int64), perm_h
+        p.hoisted = (int(p.step_hoist.sum()), int(perm_h.sum()))
+        p.kept = tuple((offset[b], buf_size[b]) for b in kept_bufs)
+        p.hoisted_macs = int(sum(int(r[10]) * int(r[11]) * int(r[12]) * int(r[13]) for r, h in zip(rows, step_h) if h))
     if projs is None:
         return p
     # the device holds the distinct rows of the final tensor; the result has one per projection, duplicates included
@@ -809,7 +864,7 @@ def _sub_output(ts_inds, leaves, output) -> frozenset:
 
 def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=None, device=None,
              sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
-             _intermediates=()) -> ContractionResult:
+             hoist=None, _intermediates=()) -> ContractionResult:
     """Contract `arrays` (numpy, in ts_inds order) along the linear `path` on the GPU; see the module docstring.
     A path that leaves several tensors gives lists in `inds` / `array` (the sliced and the projected form need one
     tensor).  `_intermediates` (contract_results): positions of arrays that are results of earlier storage-mode calls,
@@ -825,12 +880,13 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     _check_scaling(scaling, storage)
     _check_slice_batch(slice_batch, projs)
     _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
+    _check_hoist(hoist, path_kernel, projs)
     steps = _check_path(path, len(ts_inds))
     final, out = tnmod.contract(steps, ts_inds, output_inds, dims)
     if len(final) == 1:
         p = plan(steps, ts_inds, [a.shape for a in arrays], out, slices=slices, slice_range=slice_range, dtype=dtype,
                  sparse_inds=sparse_inds, projs=projs, storage=storage, scaling=scaling, slice_batch=slice_batch,
-                 compute=compute, path_kernel=path_kernel)
+                 compute=compute, path_kernel=path_kernel, hoist=hoist)
         return _run(p, arrays, device, loose)
     if slices:
         raise NotImplementedError("slices need a path that leaves one tensor.")
@@ -839,24 +895,25 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     parts = []
     effective = None if slice_batch is None else 1  # (every part is unsliced: one assignment)
     fused = None if path_kernel is None else 1
+    none_hoisted = None if hoist is None else (0, 0)  # (every part is unsliced: nothing to hoist)
     for leaves, sub in _split(steps, len(ts_inds)):
         if not sub:  # a tensor the path does not touch: as the single-leaf plan gives it, rounded to storage
             a = arrays[leaves[0]].astype(dtype, copy=True)
             if scaling is not None:
                 a, e = scale_to_storage(a, storage)
                 parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, scaling=scaling, exponents=(e,),
-                                               slice_batch=effective, path_kernel=fused))
+                                               slice_batch=effective, path_kernel=fused, hoisted=none_hoisted))
                 continue
             if storage is not None:
                 a = _from_storage_bits(_storage_bits(a, storage, leaves[0] not in loose), storage, a)
             if compute is not None and leaves[0] not in loose:
                 _check_split_range(a)
             parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, slice_batch=effective, compute=compute,
-                                           path_kernel=fused))
+                                           path_kernel=fused, hoisted=none_hoisted))
             continue
         parts.append(contract(sub, [ts_inds[t] for t in leaves], [arrays[t].astype(dtype, copy=False) for t in leaves],
                               _sub_output(ts_inds, leaves, out), device=device, storage=storage, scaling=scaling,
-                              slice_batch=slice_batch, compute=compute, path_kernel=path_kernel,
+                              slice_batch=slice_batch, compute=compute, path_kernel=path_kernel, hoist=hoist,
                               _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
     assert [tuple(r.inds) for r in parts] == [tuple(f) for f in final]
     return ContractionResult([r.inds for r in parts], [r.array for r in parts], sum(r.macs for r in parts), 1,
@@ -867,7 +924,7 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
                              narrow_launches=sum(r.narrow_launches for r in parts), slice_batch=effective,
                              batch_launches=sum(r.batch_launches for r in parts), compute=compute,
                              split_launches=sum(r.split_launches for r in parts), path_kernel=fused,
-                             path_launches=_add_counts(*(r.path_launches for r in parts)))
+                             path_launches=_add_counts(*(r.path_launches for r in parts)), hoisted=none_hoisted)
 
 
 def _add_counts(*counts) -> tuple:
@@ -939,6 +996,9 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
             _lib.check(L.tnco_hip_contract_set_path_kernel(h, p.path_kernel))
         if p.scaling is not None:
             _lib.check(L.tnco_hip_contract_set_exponents(h, leaf_exps.ctypes.data_as(C.c_void_p)))
+        if p.hoisted is not None and any(p.hoisted):  # (nothing hoisted: the run of the plan without the keyword)
+            flags = [np.ascontiguousarray(q, np.int64) for q in (p.step_hoist, p.perm_hoist)]
+            _lib.check(L.tnco_hip_contract_set_hoist(h, *(q.ctypes.data_as(C.c_void_p) for q in flags)))
         staging = np.empty(p.out_numel, p.dtype)
         ptrs = (C.c_void_p * max(1, len(leaves)))(*[a.ctypes.data for a in leaves])
         _lib.check(L.tnco_hip_contract_run(h, ptrs, staging.ctypes.data_as(C.c_void_p)))
@@ -973,7 +1033,8 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
                              int(stats[1]), float(stats[3]) * 1e-9, kernel_launches=tuple(int(v) for v in by_kernel),
                              row_kernel_launches=tuple(int(v) for v in by_row_kernel), scaling=p.scaling,
                              exponents=exponents, narrow_launches=narrow, slice_batch=p.slice_batch, batch_launches=folds,
-                             compute=p.compute, split_launches=splits, path_kernel=p.path_kernel, path_launches=fused)
+                             compute=p.compute, split_launches=splits, path_kernel=p.path_kernel, path_launches=fused,
+                             hoisted=p.hoisted)
 
 
 def _host_layout(p: Plan, staging) -> np.ndarray:
@@ -994,7 +1055,8 @@ def _host_layout(p: Plan, staging) -> np.ndarray:
 
 
 def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse_inds=None,
-                     storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None) -> ContractionResult:
+                     storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
+                     hoist=None) -> ContractionResult:
     """Run a result of `Optimizer.optimize` over the arrays of the network as given.
 
     tn0: the network before pre-fusing (`load_tn(obj, fuse=None)`); arrays: in tn0.tensors order, or {name: array}
@@ -1014,12 +1076,15 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     compute: "bf16x3" runs the tiled-class steps of `result.path` on the matrix cores (module docstring); the fuse stage
     stays in plain precision; `split_launches` is the sum over the calls.  path_kernel: that many slice assignments per
     launch of the path kernel in every call over `result.path` (module docstring); the fuse stage stays as it is;
-    `path_launches` is the sum over the calls, `path_kernel` of the result the largest effective value of a component."""
+    `path_launches` is the sum over the calls, `path_kernel` of the result the largest effective value of a component.
+    hoist: True runs the slice-independent steps and permutes of every call over `result.path` once per call (module
+    docstring); the fuse stage, unsliced, stays as it is; `hoisted` is the sum over the calls."""
     _check_compute(compute, storage, np.float32, projs)
     _check_storage(storage, np.float32, projs)
     _check_scaling(scaling, storage)
     _check_slice_batch(slice_batch, projs)
     _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
+    _check_hoist(hoist, path_kernel, projs)
     if (tn0.sparse_inds or tn.sparse_inds) and projs is None:
         raise NotImplementedError("sparse indices (n_projs) have an array meaning only at given projections: "
                                   "pass projs=, an integer array [P, number of sparse indices].")
@@ -1053,17 +1118,18 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     if len(comp_paths) <= 1:  # one component to contract: the path with its slices, in one call
         r = contract(result.path, tn.ts_inds, arrays, tn.output_inds, slices=getattr(result, "slices", ()),
                      device=device, sparse_inds=sparse_inds or (), projs=projs, storage=storage, scaling=scaling,
-                     slice_batch=slice_batch, compute=compute, path_kernel=path_kernel)
+                     slice_batch=slice_batch, compute=compute, path_kernel=path_kernel, hoist=hoist)
         return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
                                  fuse_macs, r.kernel_launches, r.row_kernel_launches, r.scaling, r.exponents,
                                  r.narrow_launches, r.slice_batch, r.batch_launches, r.compute, r.split_launches,
-                                 r.path_kernel, r.path_launches)
+                                 r.path_kernel, r.path_launches, r.hoisted)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
     ts, n = [tuple(x) for x in tn.ts_inds], len(tn.ts_inds)
     done, results, macs, n_slices, peak, launches, device_s = set(), [], 0, 0, 0, 0, 0.0
     by_kernel = (0,) * len(KERNEL_PATHS)
     exponents, narrow, folds, effective, splits = None, 0, 0, None, 0
     fused, fused_launches = None, (0, 0)
+    hoisted = None if hoist is None else (0, 0)
     n_comp_steps = 0
     for q, cut in zip(result.disconnected_paths, result.disconnected_slices):
         if not q:
@@ -1072,7 +1138,9 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         (leaves, sub), = [(lv, s) for lv, s in _split(_check_path(q, n), n) if s]
         r = contract(sub, [ts[t] for t in leaves], [arrays[t] for t in leaves], _sub_output(ts, leaves, tn.output_inds),
                      slices=cut, device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute,
-                     path_kernel=path_kernel)
+                     path_kernel=path_kernel, hoist=hoist)
+        if hoist is not None:
+            hoisted = _add_counts(hoisted, r.hoisted)
         exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
         splits += r.split_launches
         if slice_batch is not None:
@@ -1093,7 +1161,10 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     if tail:
         r = contract(tail, state_inds, state_arrays, frozenset(tn.output_inds) & {x for xs in state_inds for x in xs},
                      device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute,
-                     path_kernel=path_kernel, _intermediates=range(len(state_arrays) - len(results), len(state_arrays)))
+                     path_kernel=path_kernel, hoist=hoist,
+                     _intermediates=range(len(state_arrays) - len(results), len(state_arrays)))
+        if hoist is not None:
+            hoisted = _add_counts(hoisted, r.hoisted)
         fused_launches = _add_counts(fused_launches, r.path_launches)
         exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
         splits += r.split_launches
@@ -1106,4 +1177,4 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     return ContractionResult(inds, array, macs, n_slices, peak, launches, device_s, fuse_macs, by_kernel,
                              scaling=scaling, exponents=exponents, narrow_launches=narrow, slice_batch=effective,
                              batch_launches=folds, compute=compute, split_launches=splits, path_kernel=fused,
-                             path_launches=fused_launches)
+                             path_launches=fused_launches, hoisted=hoisted)

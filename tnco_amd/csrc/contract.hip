@@ -29,6 +29,9 @@
 // workgroup per assignment interpreting the whole path in its own copy of the arena (ct_path_kernel), and
 //   ct_path_reduce_kernel  folds the group's blocks into the output as ct_batch_reduce_kernel does;
 // two launches per group, the sums in the order of the unfused kernels: bit-equal to the loop above.
+// Hoisting (tnco_hip_contract_set_hoist): the steps and permutes the plan flags -- their operands hold no sliced axis
+// anywhere below them -- run once per run, before the slice loop, as one-member launches of the same kernels; the loop
+// skips them, and a step of the loop reads what they left (a kept tensor) in arena copy 0.  No kernel knows of it.
 // No atomics in any sum: every sum runs in one fixed order, so a run is bit-reproducible (the one atomic, the integer max
 // behind a scaled tensor's exponent, does not depend on order).
 #include "../../include/tnco_hip.h"
@@ -533,6 +536,10 @@ struct tnco_hip_contract_s {
   int64_t* d_path_tables = nullptr;  // steps | first row and count of every permute group | placement of every assignment
   std::vector<int64_t> path_image;   // the host copy of d_path_tables
   int64_t path_launches[2] = {0, 0};  // launches of ct_path_kernel and of ct_path_reduce_kernel in the last run
+  std::vector<char> hoist_step, hoist_perm;  // tnco_hip_contract_set_hoist: the flags; empty: never set, or no flag set
+  std::vector<char> kept_opnd;     // [n_steps][2]: the operand is a kept tensor, read in arena copy 0 by every member
+  std::vector<int64_t> hoist_count, hoist_max, rest_max;  // per permute group, at index g + 1: the flagged rows (they come
+                                   // first), the largest numel among them and among the others
   int64_t last_member = 0;         // the member that ran the last assignment of the last run (its exponent slots)
   int64_t base_bytes = 0;          // `bytes` as create reserved them
   std::vector<int32_t> exps_image;  // the leaves' exponents, once per member
@@ -711,19 +718,23 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
 }
 
 template <class D, class SI = D, bool half = false, bool scaled = false>
-int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t out_off, int64_t members = 0) {
-  const int64_t n = c->group_count[group + 1];
+int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t out_off, int64_t members = 0, bool hoisted = false) {
+  // a handle with hoisting: the flagged rows of the group (hoisted) or the others; without: every row
+  const bool split = !c->hoist_count.empty();
+  const int64_t nh = split ? c->hoist_count[group + 1] : 0;
+  const int64_t n = hoisted ? nh : c->group_count[group + 1] - nh;
   if (!n) return TNCO_HIP_OK;
+  const int64_t largest = !split ? c->group_max[group + 1] : hoisted ? c->hoist_max[group + 1] : c->rest_max[group + 1];
   const int64_t P = (int64_t)c->perms.size() / PERM_W;
   GatherArgs g;
-  g.rows = c->d_tables + c->group_first[group + 1] * PERM_W;
+  g.rows = c->d_tables + (c->group_first[group + 1] + (hoisted ? 0 : nh)) * PERM_W;
   g.leaf_sl = c->d_tables + P * PERM_W;
   g.slice_place = g.leaf_sl + c->leaf_sl.size();
   g.slice_dims = g.slice_place + c->place.size();
   g.leaves = (const void* const*)c->d_leaf_ptrs;
   g.arena = c->d_arena, g.out = c->d_out, g.sid = sid, g.out_off = out_off;
   g.arena_step = members ? c->arena_elems : 0;  // (members: of a batch, 0: an unbatched launch)
-  const int64_t blocks = std::min<int64_t>((c->group_max[group + 1] + 255) / 256, 2048);
+  const int64_t blocks = std::min<int64_t>((largest + 255) / 256, 2048);
   const dim3 grid((unsigned)blocks, (unsigned)n, (unsigned)std::max<int64_t>(members, 1));
   if constexpr (!half)
     hipLaunchKernelGGL(ct_gather_kernel<D>, grid, dim3(256), 0, c->stream, g);
@@ -861,6 +872,101 @@ int run_impl(tnco_hip_contract_s* c) {
     mb0.exp_step = (int)(L + S), mb0.amax_step = (int)S;
   }
   const int64_t arena_bytes = batched ? c->arena_elems * (int64_t)sizeof(E) : 0;
+  const bool hoisting = !c->hoist_step.empty() && S > 0;
+  // Step k of the path.  bat: as members launches of a batch starting at assignment sid (the last step to the batch
+  // staging buffer), else one unbatched launch: an assignment's, or a hoisted step's (which reads no sliced leaf and
+  // works in arena copy 0)
+  auto run_step = [&](int64_t k, int64_t sid, bool bat, unsigned members, int beta, int64_t out_off) -> int {
+    int rc;
+    const int64_t* st = &c->steps[k * STEP_W];
+    const int64_t member_bytes = bat ? arena_bytes : 0;
+    const E* opnd[2];
+    MemberArgs mb = bat ? mb0 : MemberArgs{};
+    mb.sid0 = sid;
+    for (int side = 0; side < 2; ++side) {
+      const int64_t kind = st[4 * side], ref = st[4 * side + 1];
+      if (kind != K_LEAF) {  // (of a batch: each member's own arena; a kept tensor: copy 0 for every member)
+        opnd[side] = arena + ref;
+        (side ? mb.b_step : mb.a_step) = hoisting && c->kept_opnd[2 * k + side] ? 0 : member_bytes;
+        continue;
+      }
+      // a leaf read in place: at the slice offset of the assignment, which a member of a batch adds for its own
+      opnd[side] = (const E*)(c->d_leaves + c->leaf_off[ref] * c->elem) + (bat ? 0 : leaf_slice_offset(c, ref, sid));
+      if (bat) (side ? mb.b_ls : mb.a_ls) = d_leaf_sl + ref * LEAF_SL_W;
+    }
+    // batched: the last step writes every member's block, with beta 0, to the batch staging buffer
+    const bool last = st[8] == K_OUT;
+    T* out_dest = bat ? (T*)c->d_batch_out : out + out_off;
+    const int out_beta = bat ? 0 : beta;
+    if (bat) mb.c_step = last ? c->block_numel * (int64_t)sizeof(T) : arena_bytes;
+    if constexpr (half) {
+      HalfGemmArgs<E> p;
+      p.A = opnd[0], p.B = opnd[1];
+      p.Cs = last ? nullptr : arena + st[9];
+      p.C = last ? out_dest : nullptr;
+      p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
+      p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
+      p.beta = last ? out_beta : 0;
+      p.a_vec = p.b_vec = 0;
+      p.exps = nullptr, p.sa = p.sb = 0, p.amax = nullptr;
+      p.mb = mb;
+      using St = typename ct_storage_of<E>::type;
+      if (!c->scaling) return launch_half_gemm<St, sizeof(E) == 4, false>(c, p, members);
+      p.exps = c->d_exps, p.sa = (int)st[14], p.sb = (int)st[15];
+      if (st[8] != K_OUT) {  // unrounded to the staging buffer, then narrowed at the exponent of the whole result
+        p.Cs = nullptr, p.C = (T*)(arena + c->stage_refs[k]), p.amax = c->d_amax + k;
+      }
+      if ((rc = launch_half_gemm<St, sizeof(E) == 4, true>(c, p, members))) return rc;
+      if (st[8] != K_OUT) {
+        const int64_t nc = p.H * p.M * p.N, quads = nc * (sizeof(E) == 4 ? 2 : 1) / 4;
+        const dim3 grid((unsigned)std::min<int64_t>(std::max<int64_t>((quads + 255) / 256, 1), 2048), 1, members);
+        hipLaunchKernelGGL((ct_scale_narrow_kernel<St, sizeof(E) == 4>), grid, dim3(256), 0, c->stream, (const float*)p.C,
+                           (St*)(arena + st[9]), nc, (const uint32_t*)p.amax, c->d_exps, p.sa, p.sb, (int)(L + k),
+                           member_bytes, mb.exp_step, mb.amax_step);
+        CT_TRY(hipGetLastError());
+        c->launches += 1;
+        c->narrow_launches += 1;
+      }
+      return TNCO_HIP_OK;
+    } else {
+      T* dest = last ? out_dest : arena + st[9];
+      const int64_t* rw = c->row_steps.empty() ? nullptr : &c->row_steps[k * ROW_W];
+      if (rw && (rw[0] > 1 || rw[2] >= 0 || rw[4] >= 0)) {
+        RowGemmArgs<T> p;
+        p.A = opnd[0], p.B = opnd[1], p.C = dest;
+        p.a_map = rw[2] >= 0 ? c->d_row_maps + rw[2] : nullptr;
+        p.b_map = rw[4] >= 0 ? c->d_row_maps + rw[4] : nullptr;
+        p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
+        p.R = rw[0], p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
+        p.a_row = rw[2] < 0 && rw[1] == 1 ? 0 : p.H * p.M * p.K;
+        p.b_row = rw[4] < 0 && rw[3] == 1 ? 0 : p.H * p.K * p.N;
+        p.beta = st[8] == K_OUT ? beta : 0;
+        return launch_rows_gemm<T>(c, p);
+      }
+      GemmArgs<T> p;
+      p.A = opnd[0], p.B = opnd[1];
+      p.C = dest;
+      p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
+      p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
+      p.beta = last ? out_beta : 0;
+      p.mb = mb;
+      return launch_gemm<T>(c, p, members);
+    }
+  };
+  if (hoisting) {  // what does not depend on the assignment: once, in path order, in arena copy 0
+    int rc;
+    if (half && c->scaling) CT_TRY(hipMemsetAsync(c->d_amax, 0, (size_t)S * sizeof(uint32_t), c->stream));
+    if ((rc = launch_gathers<W, W, half>(c, -1, c->start, 0, 0, true))) return rc;
+    for (int64_t k = 0; k < S; ++k) {
+      if ((rc = launch_gathers<W, W, half>(c, k, c->start, 0, 0, true))) return rc;
+      if (c->hoist_step[k] && (rc = run_step(k, c->start, false, 1, 0, 0))) return rc;
+    }
+    // scaling in a batch: every member reads the exponents of the kept tensors in its own copy of the slots (the
+    // assignments clear the max words only, d_amax, never a slot)
+    if (half && c->scaling && batched)
+      for (int64_t b = 1; b < c->batch; ++b)
+        CT_TRY(hipMemcpyAsync(c->d_exps + b * (L + S), c->d_exps, (size_t)(L + S) * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+  }
   for (int64_t sid = c->start; sid < c->stop; sid += per) {
     const int64_t n = std::min(per, c->stop - sid);  // members of this launch
     const unsigned members = (unsigned)n;
@@ -875,7 +981,6 @@ int run_impl(tnco_hip_contract_s* c) {
     const int beta = (int)(pl.beta & 1);
     const int64_t out_off = pl.off[0];
     c->last_member = n - 1;
-    mb0.sid0 = sid;
     // scaling: the max words of every step are cleared at the start of an assignment (of a batch: of all its members),
     // in stream order after the narrowing passes of the one before
     if (half && c->scaling && S) CT_TRY(hipMemsetAsync(c->d_amax, 0, (size_t)(S * per) * sizeof(uint32_t), c->stream));
@@ -884,82 +989,8 @@ int run_impl(tnco_hip_contract_s* c) {
     if (rc) return rc;
     for (int64_t k = 0; k < S; ++k) {
       if ((rc = launch_gathers<W, W, half>(c, k, sid, out_off, batched ? n : 0))) return rc;
-      const int64_t* st = &c->steps[k * STEP_W];
-      const E* opnd[2];
-      MemberArgs mb = mb0;
-      for (int side = 0; side < 2; ++side) {
-        const int64_t kind = st[4 * side], ref = st[4 * side + 1];
-        if (kind != K_LEAF) {  // (of a batch: each member's own arena)
-          opnd[side] = arena + ref;
-          (side ? mb.b_step : mb.a_step) = arena_bytes;
-          continue;
-        }
-        // a leaf read in place: at the slice offset of the assignment, which a member of a batch adds for its own
-        opnd[side] = (const E*)(c->d_leaves + c->leaf_off[ref] * c->elem) + (batched ? 0 : leaf_slice_offset(c, ref, sid));
-        if (batched) (side ? mb.b_ls : mb.a_ls) = d_leaf_sl + ref * LEAF_SL_W;
-      }
-      // batched: the last step writes every member's block, with beta 0, to the batch staging buffer
-      const bool last = st[8] == K_OUT;
-      T* out_dest = batched ? (T*)c->d_batch_out : out + out_off;
-      const int out_beta = batched ? 0 : beta;
-      if (batched) mb.c_step = last ? c->block_numel * (int64_t)sizeof(T) : arena_bytes;
-      if constexpr (half) {
-        HalfGemmArgs<E> p;
-        p.A = opnd[0], p.B = opnd[1];
-        p.Cs = last ? nullptr : arena + st[9];
-        p.C = last ? out_dest : nullptr;
-        p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
-        p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
-        p.beta = last ? out_beta : 0;
-        p.a_vec = p.b_vec = 0;
-        p.exps = nullptr, p.sa = p.sb = 0, p.amax = nullptr;
-        p.mb = mb;
-        using St = typename ct_storage_of<E>::type;
-        if (!c->scaling) {
-          if ((rc = launch_half_gemm<St, sizeof(E) == 4, false>(c, p, members))) return rc;
-          continue;
-        }
-        p.exps = c->d_exps, p.sa = (int)st[14], p.sb = (int)st[15];
-        if (st[8] != K_OUT) {  // unrounded to the staging buffer, then narrowed at the exponent of the whole result
-          p.Cs = nullptr, p.C = (T*)(arena + c->stage_refs[k]), p.amax = c->d_amax + k;
-        }
-        if ((rc = launch_half_gemm<St, sizeof(E) == 4, true>(c, p, members))) return rc;
-        if (st[8] != K_OUT) {
-          const int64_t nc = p.H * p.M * p.N, quads = nc * (sizeof(E) == 4 ? 2 : 1) / 4;
-          const dim3 grid((unsigned)std::min<int64_t>(std::max<int64_t>((quads + 255) / 256, 1), 2048), 1, members);
-          hipLaunchKernelGGL((ct_scale_narrow_kernel<St, sizeof(E) == 4>), grid, dim3(256), 0, c->stream, (const float*)p.C,
-                             (St*)(arena + st[9]), nc, (const uint32_t*)p.amax, c->d_exps, p.sa, p.sb, (int)(L + k),
-                             arena_bytes, mb.exp_step, mb.amax_step);
-          CT_TRY(hipGetLastError());
-          c->launches += 1;
-          c->narrow_launches += 1;
-        }
-        continue;
-      } else {
-      T* dest = last ? out_dest : arena + st[9];
-      const int64_t* rw = c->row_steps.empty() ? nullptr : &c->row_steps[k * ROW_W];
-      if (rw && (rw[0] > 1 || rw[2] >= 0 || rw[4] >= 0)) {
-        RowGemmArgs<T> p;
-        p.A = opnd[0], p.B = opnd[1], p.C = dest;
-        p.a_map = rw[2] >= 0 ? c->d_row_maps + rw[2] : nullptr;
-        p.b_map = rw[4] >= 0 ? c->d_row_maps + rw[4] : nullptr;
-        p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
-        p.R = rw[0], p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
-        p.a_row = rw[2] < 0 && rw[1] == 1 ? 0 : p.H * p.M * p.K;
-        p.b_row = rw[4] < 0 && rw[3] == 1 ? 0 : p.H * p.K * p.N;
-        p.beta = st[8] == K_OUT ? beta : 0;
-        if ((rc = launch_rows_gemm<T>(c, p))) return rc;
-        continue;
-      }
-      GemmArgs<T> p;
-      p.A = opnd[0], p.B = opnd[1];
-      p.C = dest;
-      p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
-      p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
-      p.beta = last ? out_beta : 0;
-      p.mb = mb;
-      if ((rc = launch_gemm<T>(c, p, members))) return rc;
-      }
+      if (hoisting && c->hoist_step[k]) continue;
+      if ((rc = run_step(k, sid, batched, members, beta, out_off))) return rc;
     }
     if (batched) {  // the members' blocks into the output, in assignment order
       const dim3 grid((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048));
@@ -1238,6 +1269,7 @@ int tnco_hip_contract_set_path_kernel(tnco_hip_contract c, int64_t group) {
   if (c->batch) return fail(TNCO_HIP_EINVAL, "a slice batch and a path kernel are exclusive.");
   if (c->compute) return fail(TNCO_HIP_EINVAL, "a compute mode is not supported with a path kernel.");
   if (c->path_group) return fail(TNCO_HIP_EINVAL, "the path kernel is already set.");
+  if (!c->hoist_step.empty()) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with a path kernel.");
   const int64_t S = (int64_t)c->steps.size() / STEP_W;
   for (int64_t k = 0; k < S; ++k) {
     const int64_t* st = &c->steps[k * STEP_W];
@@ -1301,6 +1333,109 @@ int tnco_hip_contract_set_path_kernel(tnco_hip_contract c, int64_t group) {
 int tnco_hip_contract_path_launches(tnco_hip_contract c, int64_t* counts) {
   if (!c || !counts) return fail(TNCO_HIP_EINVAL, "null argument.");
   counts[0] = c->path_launches[0], counts[1] = c->path_launches[1];
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_set_hoist(tnco_hip_contract c, const int64_t* step_flags, const int64_t* perm_flags) {
+  if (!c) return fail(TNCO_HIP_EINVAL, "null argument.");
+  const int64_t S = (int64_t)c->steps.size() / STEP_W, P = (int64_t)c->perms.size() / PERM_W;
+  if ((S && !step_flags) || (P && !perm_flags)) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with hoisting.");
+  if (c->path_group) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with a path kernel.");
+  bool any = false;
+  for (int64_t k = 0; k < S; ++k) {
+    if (step_flags[k] != 0 && step_flags[k] != 1) return fail(TNCO_HIP_EINVAL, "a hoist flag must be 0 or 1.");
+    any |= step_flags[k] == 1;
+  }
+  for (int64_t r = 0; r < P; ++r) {
+    if (perm_flags[r] != 0 && perm_flags[r] != 1) return fail(TNCO_HIP_EINVAL, "a hoist flag must be 0 or 1.");
+    any |= perm_flags[r] == 1;
+  }
+  if (!any) {  // nothing to hoist: the handle runs as one on which this was never called
+    c->hoist_step.clear(), c->hoist_perm.clear(), c->kept_opnd.clear();
+    c->hoist_count.clear(), c->hoist_max.clear(), c->rest_max.clear();
+    return TNCO_HIP_OK;
+  }
+  // Replay the path: who wrote what an item reads.  A write: [lo, hi) of the arena and the flag of its item, in path
+  // order; read: an item has consumed it (every tensor has one reader) or nothing reads it (a staging buffer)
+  struct Write {
+    int64_t lo, hi;
+    char flag, read;
+  };
+  struct Kept {
+    int64_t lo, hi;
+    size_t writer;
+  };
+  std::vector<Write> writes;
+  std::vector<Kept> kept;
+  std::vector<char> kept_opnd(2 * S, 0);
+  std::vector<int64_t> count(S + 1, 0), max_h(S + 1, 0), max_rest(S + 1, 0);
+  // The write an item reads at ref, -1: none.  The hoisted items run before every other one, so a hoisted item sees
+  // the latest hoisted write there; another item the latest write of its own kind, or else what a hoisted one left
+  auto writer_of = [&](int64_t ref, char flag) -> int64_t {
+    for (char want : {flag, (char)1})
+      for (int64_t w = (int64_t)writes.size() - 1; w >= 0; --w)
+        if (writes[w].lo == ref && writes[w].flag == want && !writes[w].read) {
+          writes[w].read = 1;
+          return w;
+        }
+    return -1;
+  };
+  auto free_leaf = [&](int64_t leaf) { return c->leaf_sl[leaf * LEAF_SL_W] == 0; };
+  auto perm_rows = [&](int64_t g) -> const char* {  // the rows of permute group g
+    for (int64_t r = c->group_first[g + 1], n = 0; n < c->group_count[g + 1]; ++r, ++n) {
+      const int64_t* row = &c->perms[r * PERM_W];
+      const char f = (char)perm_flags[r];
+      if (f && n && !perm_flags[r - 1]) return "the hoisted rows of a permute group must come first.";
+      if (row[0] == K_LEAF) {
+        if (f && !free_leaf(row[1])) return "a hoisted permute reads a leaf with a sliced axis.";
+      } else {
+        const int64_t w = writer_of(row[1], f);
+        if ((w >= 0 && writes[w].flag) != (bool)f) return "a permute and the item that writes its source must both be hoisted or both not.";
+      }
+      if (f && row[2] != K_ARENA) return "a hoisted permute must write the arena.";
+      if (row[2] == K_ARENA) writes.push_back(Write{row[3], row[3] + row[5], f, 0});
+      count[g + 1] += f;
+      int64_t& largest = (f ? max_h : max_rest)[g + 1];
+      largest = std::max(largest, row[5]);
+    }
+    return nullptr;
+  };
+  const char* e = perm_rows(-1);
+  for (int64_t k = 0; k < S && !e; ++k) {
+    if ((e = perm_rows(k))) break;
+    const int64_t* st = &c->steps[k * STEP_W];
+    const char f = (char)step_flags[k];
+    const int64_t H = st[10], M = st[11], N = st[12], K = st[13], nc = H * M * N;
+    for (int side = 0; side < 2 && !e; ++side) {
+      const int64_t kind = st[4 * side], ref = st[4 * side + 1];
+      if (kind == K_LEAF) {
+        if (f && !free_leaf(ref)) e = "a hoisted step reads a leaf with a sliced axis.";
+        continue;
+      }
+      const int64_t w = writer_of(ref, f);
+      const bool from_hoisted = w >= 0 && writes[w].flag;
+      if (f && !from_hoisted) e = "a hoisted step reads an arena tensor that no hoisted item wrote.";
+      if (!f && from_hoisted) {
+        kept_opnd[2 * k + side] = 1;
+        kept.push_back(Kept{ref, ref + H * K * (side ? N : M), (size_t)w});
+      }
+    }
+    if (e) break;
+    if (f && st[8] != K_ARENA) e = "a hoisted step must write the arena.";
+    if (st[8] == K_ARENA) {
+      writes.push_back(Write{st[9], st[9] + nc, f, 0});
+      if (c->scaling) writes.push_back(Write{c->stage_refs[k], c->stage_refs[k] + 2 * nc, f, 1});
+    }
+  }
+  // a kept tensor stays for the whole run: no assignment writes into it, and no hoisted item after the one that wrote it
+  for (size_t q = 0; q < kept.size() && !e; ++q)
+    for (size_t w = 0; w < writes.size() && !e; ++w)
+      if (w != kept[q].writer && (!writes[w].flag || w > kept[q].writer) && writes[w].lo < kept[q].hi && kept[q].lo < writes[w].hi)
+        e = "a kept tensor is written over.";
+  if (e) return fail(TNCO_HIP_EINVAL, e);
+  c->hoist_step.assign(step_flags, step_flags + S), c->hoist_perm.assign(perm_flags, perm_flags + P);
+  c->kept_opnd = kept_opnd, c->hoist_count = count, c->hoist_max = max_h, c->rest_max = max_rest;
   return TNCO_HIP_OK;
 }
 

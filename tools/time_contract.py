@@ -14,7 +14,8 @@ Sycamore leg with slice_batch None, 1, 8 and 64, plain, in storage mode and with
 (`--compute`: the large square step in float32 and complex64 with compute=None, compute="bf16x3" and
 storage="bfloat16" in one process, and the sliced Sycamore leg with compute=None and "bf16x3"); the path kernel
 (`--path-kernel`: the sliced Sycamore leg with path_kernel=None, slice_batch=64 and path_kernel 64, 256 and 1024 in one
-process).  Engine figures are its
+process); hoisting (`--hoist`: the sliced Sycamore leg with hoist=None and hoist=True, unbatched and with
+slice_batch=64, in one process).  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device).
 """
@@ -328,6 +329,48 @@ def path_kernel(lines, depth, max_width, max_slices):
     print(lines[-1], flush=True)
 
 
+def hoist(lines, depth, max_width, max_slices):
+    """Slice-independent steps once per call on the sliced Sycamore amplitude of the storage leg, complex64: hoist=None
+    against hoist=True, unbatched and with slice_batch=64, all in this process: device time (the minimum and the spread
+    of three runs after a warm-up), launches and multiply-adds per setting; every hoisted result is compared bit for
+    bit with the run without the keyword."""
+    lines.append("")
+    ts, d, o = syn.sycamore53_tn(depth=depth)
+    tn0 = tnmod.TensorNetwork([tnmod.Tensor(xs, [d] * len(xs)) for xs in ts], output_inds=o)
+    tn, res = Optimizer(method="sa", max_width=max_width, seed=0).optimize(tn0, betas=(0, 50), n_steps=200, n_runs=256)
+    r0 = res[0]
+    rng = np.random.RandomState(2)
+    n_inds = len({x for xs in ts for x in xs})
+    scale = 2.0 ** (-n_inds / (2 * len(ts)))  # (as in the storage leg: the amplitude stays near 1)
+    arrays = [(_rand(tuple(d for _ in xs), np.complex64, rng) * scale).astype(np.complex64) for xs in ts]
+    fused = ctr.contract(tn.tags["fuse_path"], tn0.ts_inds, arrays, tn0.output_inds)
+    leaves = fused.array if isinstance(fused.array, list) else [fused.array]
+    p = ctr.plan(r0.path, tn.ts_inds, [a.shape for a in leaves], tn.output_inds, slices=r0.slices, hoist=True)
+    m = min(p.n_slices, max_slices)
+    lines.append(f"## hoist, sliced Sycamore-53 amplitude, depth {depth}, complex64, max_width {max_width}, cost {r0.cost}, "
+                 f"{len(r0.path)} steps and {len(p.perms)} permutes of which {p.hoisted[0]} steps and {p.hoisted[1]} permutes are "
+                 f"hoisted ({p.hoisted_macs} of {p.macs_per_slice} MACs per assignment), {len(p.kept)} kept tensors, arena "
+                 f"{p.arena_elems} elements, assignments [0, {m}) of {p.n_slices}: device seconds are the minimum of three runs "
+                 "after a warm-up, spread = (max - min) / min of the three; all runs in one process")
+    lines.append(f"{'setting':>28} {'device s':>9} {'spread':>7} {'None / this':>11} {'us / slice':>10} {'launches':>9} "
+                 f"{'MACs':>14} {'peak bytes':>11} {'bits equal None':>15}")
+    for B in (None, 64):
+        base = t_base = None
+        for h in (None, True):
+            call = lambda B=B, h=h: ctr.contract(r0.path, tn.ts_inds, leaves, tn.output_inds, slices=r0.slices,  # noqa: E731
+                                                 slice_range=(0, m), slice_batch=B, hoist=h)
+            r = call()
+            times = [call().device_s for _ in range(3)]
+            t = min(times)
+            if h is None:
+                base, t_base = r.array, t
+            same = np.array_equal(np.ravel(r.array).view(np.uint32), np.ravel(base).view(np.uint32))
+            lines.append(f"{f'slice_batch={B} hoist={h}':>28} {t:9.4f} {(max(times) - t) / t:7.3f} {t_base / t:11.2f} "
+                         f"{t / m * 1e6:10.2f} {r.launches:9d} {r.macs:14d} {r.peak_device_bytes:11d} {str(bool(same)):>15}")
+            print(lines[-1], flush=True)
+            del r
+
+
 def compute(lines, n, depth, max_width, max_slices):
     """The compute mode against the plain engine in the same process: the large square step with compute=None (the tiled
     LDS kernel, the yardstick), compute="bf16x3" (ct_split_tiled_kernel) and storage="bfloat16" (ct_mfma_tiled_kernel), and
@@ -451,15 +494,19 @@ def main():
     ap.add_argument("--slice-batch", action="store_true", help="only the slice-batch leg, appended to --out")
     ap.add_argument("--compute", action="store_true", help="only the compute-mode leg, appended to --out")
     ap.add_argument("--path-kernel", action="store_true", help="only the path-kernel leg, appended to --out")
+    ap.add_argument("--hoist", action="store_true", help="only the hoisting leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel > 1:
-        ap.error("--projs, --storage, --scaling, --slice-batch, --compute and --path-kernel each append one leg: run them one "
-                 "after the other")
+    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist > 1:
+        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel and --hoist each append one leg: run "
+                 "them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel:  # (the other legs' sections stay as they are)
-        if a.path_kernel:
+    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist:  # (the other legs' sections stay as they are)
+        if a.hoist:
+            lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
+            hoist(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+        elif a.path_kernel:
             lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
             path_kernel(lines, a.depth, a.max_width, min(a.max_slices, 2048))
         elif a.compute:
@@ -485,6 +532,7 @@ def main():
     slice_batch(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     compute(lines, a.n, a.depth, a.max_width, a.max_slices)
     path_kernel(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+    hoist(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
