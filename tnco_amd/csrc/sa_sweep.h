@@ -31,6 +31,13 @@
 // and waits -- right after the load: leaf / internal-node legs select the address, not the value.
 // The mt19937 stream is produced the same way: a 16-word block (4 words per lane) is requested
 // with the other loads and twisted + tempered into an LDS ring at the top of a later iteration.
+// The child-partial instantiations refill in ROUNDS: a replica alone would want a block every ~7.5
+// iterations, sixteen independent replicas make the wavefront run the request and the twist code
+// in nine iterations out of ten for one to three active lane groups.  There, a group whose ring
+// runs low (MT_ROUND_LOW) opens a round -- a ballot, hence a scalar branch -- and every group with
+// room for a block joins it: the same code about once in 7-8 iterations with all groups active
+// (ring of MT_ROUND_RING words; the stream a replica consumes does not depend on when its blocks
+// are produced).
 //
 // FW = true: the same state machine runs the moves of the memory-constrained optimizer
 // (finite_width/greedy/optimizer.hpp:117-331 without the max_number_new_slices branch, which keeps
@@ -71,6 +78,20 @@ __device__ __forceinline__ uint32_t mt_temper(uint32_t z) {
 // words are kept in a shadow so that the exported state is exactly libstdc++'s at `cons`.
 // ---------------------------------------------------------------------------
 constexpr int MT_SHADOW = 64;  // words of P.mtshadow per replica: the largest ring any kernel uses
+
+// Refill rounds (the child-partial instantiations of sa_run_body).  Once per iteration, behind BEGIN's draw and
+// ahead of MOVE's, a group with fewer than MT_ROUND_LOW words left and no block in flight opens a round for
+// the whole wavefront; every group whose ring has room for a block then requests one.
+//   MT_ROUND_RING: the largest ring the shadow words allow, so that a group joins at avail() <= 64 - 16 = 48 -- in
+//   practice every round -- and the groups stay in step.
+//   MT_ROUND_LOW: a replica-iteration draws at most 1 word ahead of the decision (END -> BEGIN: the leaf) and at most
+//   3 behind it (MOVE: one pick, two for the uniform).  A group that decides NOT to ask in iteration t (avail >= LOW)
+//   draws up to 3 words behind that decision and 1 ahead of the next; asking in t + 1, it draws up to 3 more in
+//   t + 1 before its block is in the ring, at the top of t + 2: 3 + 1 + 3 = 7 words between the last "enough" and
+//   the refill, so LOW >= 7.  8: one word of slack (tests/test_rng_rounds_model.py runs this rule on these numbers).
+constexpr int MT_ROUND_RING = 64;
+constexpr int MT_ROUND_LOW = 8;
+static_assert(MT_ROUND_RING <= MT_SHADOW && MT_ROUND_LOW >= 7, "refill rounds");
 
 template <int LOG2L, int RINGX = 0>
 struct Rng {
@@ -154,6 +175,7 @@ struct Rng {
   }
   __device__ __forceinline__ bool room() const { return !pend && (prod - cons) + SB <= (uint32_t)RING; }
 
+  template <int FILL = 0>
   __device__ __forceinline__ void init(const Params& P, int64_t r, lds_vu32* ring_, int mti, int mtw,
                                        int lig_) {
     mt_base = P.mt; sh_base = P.mtshadow; r32 = (uint32_t)r; ring = ring_; lig = lig_;
@@ -164,7 +186,9 @@ struct Rng {
     for (int j = 0; j < 4; ++j) pc[j] = 0;
     if (mti >= 624) { cons = 624; tw = 624; } else { cons = (uint32_t)mti; tw = (uint32_t)mtw; }
     prod = cons & ~(uint32_t)(SB - 1);
-    while (room()) {  // synchronous prologue fill
+    // synchronous prologue fill, FILL blocks at the most (0: until the ring is full): each block is a dependent round
+    // trip at the start of every launch
+    for (int b = 0; (FILL == 0 || b < FILL) && room(); ++b) {
       request();
       produce();
     }
@@ -373,7 +397,11 @@ __device__ __forceinline__ void sa_run_body(
   constexpr int L = 1 << LOG2L;
   constexpr int GPB = SWT >> LOG2L;  // groups (replicas) per block
   using M = Mask<K>;
-  using R = Rng<LOG2L>;
+  // (the child-partial instantiations -- CP below -- refill their mt19937 rings in wave-synchronous rounds: MT_ROUND_RING)
+  constexpr bool ROUNDS = !HYPER && !GENERIC && !FW;
+  using R = Rng<LOG2L, ROUNDS ? MT_ROUND_RING : 0>;
+  // (a launch enters the loop with two blocks less the up to SB - 1 words consumed of the first)
+  static_assert(!ROUNDS || R::SB + 1 >= MT_ROUND_LOW, "refill rounds: the prologue");
   __shared__ uint32_t rngbuf[GPB * R::RING];
   __shared__ ColdState coldbuf[GPB];
   __shared__ int32_t jbuf[GPB * 16];
@@ -438,7 +466,8 @@ __device__ __forceinline__ void sa_run_body(
   R rng;
   {
     const ReplicaState* rs = P.rs + r;
-    rng.init(P, r, (lds_vu32*)rngbuf + gib * R::RING, rs->mti, rs->mtw, master ? lig : 64);  // (64: no loads, no stores)
+    // (64: no loads, no stores; rounds: two blocks in the prologue, as the default ring takes, the rest in the loop)
+    rng.template init<ROUNDS ? 2 : 0>(P, r, (lds_vu32*)rngbuf + gib * R::RING, rs->mti, rs->mtw, master ? lig : 64);
     if (lane0) {
       cold.min_cost = rs->min_cost;
       cold.jmin = rs->jmin;
@@ -683,7 +712,16 @@ __device__ __forceinline__ void sa_run_body(
     if constexpr (HYPER) {  // own legs of node yN
       if (yN >= 0) v.mask_stage_into(gH, yN);
     }
-    if (rng.room()) rng.request();
+    if constexpr (ROUNDS) {
+      // a refill round (MT_ROUND_LOW): one group running low makes every group with room ask for its next block now, so
+      // that request() here and produce() at the top run for the whole wavefront at once, about every eighth iteration
+      // (no block is in flight at this point: what was requested in the last iteration was produced at the top)
+      const bool need = !rng.pend && rng.avail() < (uint32_t)MT_ROUND_LOW;
+      const bool round = __ballot(need) != 0;  // (wave-uniform: a scalar branch)
+      if (round && rng.room()) rng.request();
+    } else {
+      if (rng.room()) rng.request();
+    }
     TNCO_PROF_F(3);
 
     if (state == S_MOVE) {
