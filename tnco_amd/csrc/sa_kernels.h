@@ -168,10 +168,26 @@ __device__ __forceinline__ Mask<K> msel(bool c, const Mask<K>& a, const Mask<K>&
 
 // Per-replica view of the node blocks.  UNI: layouts whose legs are WS == BS bytes apart only (the infinite-memory sweep
 // kernel: one multiply per node, as before the split layout existed); else whatever Params says.
-template <int LOG2L, int K, bool HYPER, bool UNI = false>
+//
+// PAIRS (the child-partial instantiations of the sweep kernel): the same bytes in HBM, another lane for each word.  Lane j
+// holds the words 2j, 2j + 1 of every PAIR ROW of 2L words -- one 16-byte access, 16-byte aligned -- and, when K is odd,
+// word 2L * (K / 2) + j of a last single row: K = 3 is two accesses per node instead of three, K = 2 one, K = 4 two.
+// The set operations, popcounts and intersects do not care which lane holds which word, as long as every mask of the
+// kernel follows the same map: everything that names a word goes through widx().
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+// the staging registers of one node's legs in the pair map: each pair one 128-bit register tuple, so that the 16-byte
+// load lands in place
+template <int K>
+struct PairStage {
+  u64x2 p[K / 2 ? K / 2 : 1];
+  uint64_t s;
+};
+template <int LOG2L, int K, bool HYPER, bool UNI = false, bool PAIRS = false>
 struct View {
   static constexpr int L = 1 << LOG2L;
   static constexpr int LK = L * K;
+  static constexpr int KP = K / 2;  // pair rows (PAIRS)
   uint8_t* blk;
   int32_t* lpar;
   const uint64_t* leafmask;
@@ -185,9 +201,17 @@ struct View {
   __device__ __forceinline__ NodeRec* hdr(int p) const {
     return reinterpret_cast<NodeRec*>(blk + (int64_t)(p - n) * BS);
   }
+  // byte offset, from blk, of the 8 bytes of p's header that this lane of a quad reads and writes (the sweep kernel's
+  // child-partial instantiations).  32 bits, lane part included: as base + node + lane the compiler keeps base + lane
+  // in a register pair of its own for every base
+  __device__ __forceinline__ uint32_t hdr_piece_off(int p) const { return (uint32_t)(p - n) * (uint32_t)BS + 8u * (uint32_t)(lig & 3); }
   // word index held in slot k of this lane: k-major, so that the 4/8/16 lanes of a group access
   // L consecutive words (one contiguous 8L-byte piece of the line) per instruction
-  __device__ __forceinline__ int widx(int k) const { return k * L + lig; }
+  // (PAIRS: slots 2j, 2j + 1 are pair row j, slot K - 1 of an odd K the single row)
+  __device__ __forceinline__ int widx(int k) const {
+    if constexpr (PAIRS) return k < 2 * KP ? 2 * L * (k >> 1) + 2 * lig + (k & 1) : 2 * L * KP + lig;
+    return k * L + lig;
+  }
   __device__ __forceinline__ uint64_t* words(int p) const {
     if constexpr (UNI) return reinterpret_cast<uint64_t*>(blk + (int64_t)(p - n) * BS + 32);
     return reinterpret_cast<uint64_t*>(blk + WOFF + (int64_t)(p - n) * WS);
@@ -241,6 +265,44 @@ struct View {
     for (int k = 0; k < K; ++k)
       if (widx(k) < W) s[widx(k)] = v.w[k];
   }
+  // PAIRS: the loads of mask_stage_into, one per pair row and one for the single row.  A pair is loaded when its FIRST
+  // word is below W: an odd W's last word brings the block's padding with it (a block is a multiple of 32 bytes: the
+  // word is inside it), which pair_landed() replaces by zero.  A pair that is not loaded keeps its zeros as above.
+  __device__ __forceinline__ void pair_stage_into(PairStage<K>& g, int x) const {
+    const bool leaf = x < n;
+    const uint64_t* s = leaf ? leafmask + (int64_t)x * LK : words(x);
+#pragma unroll
+    for (int j = 0; j < KP; ++j)
+      if (leaf || widx(2 * j) < W) g.p[j] = *reinterpret_cast<const u64x2*>(s + widx(2 * j));
+    if constexpr (K & 1)
+      if (leaf || widx(K - 1) < W) g.s = s[widx(K - 1)];
+  }
+  // what landed, as a mask (behind the landing fence): words at or beyond W are zero
+  __device__ __forceinline__ Mask<K> pair_landed(PairStage<K>& g) const {
+    Mask<K> r;
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+      if (widx(2 * j + 1) >= W) g.p[j].y = 0ull;  // (in place: the registers have landed)
+      r.w[2 * j] = g.p[j].x;
+      r.w[2 * j + 1] = g.p[j].y;
+    }
+    if constexpr (K & 1) r.w[K - 1] = g.s;
+    return r;
+  }
+  // PAIRS: set_mask, 16 bytes per pair row (the second word of an odd W's last pair is the zero the registers hold, written
+  // to the block's padding)
+  __device__ __forceinline__ void set_mask_pairs(int p, const Mask<K>& v) const {
+    uint64_t* s = words(p);
+#pragma unroll
+    for (int j = 0; j < KP; ++j)
+      if (widx(2 * j) < W) {
+        u64x2 t;
+        t.x = v.w[2 * j]; t.y = v.w[2 * j + 1];
+        *reinterpret_cast<u64x2*>(s + widx(2 * j)) = t;
+      }
+    if constexpr (K & 1)
+      if (widx(K - 1) < W) s[widx(K - 1)] = v.w[K - 1];
+  }
   // words 0..L-1 only (slot 0 of every lane): with the 32-byte header, the first 64 bytes of a block
   __device__ __forceinline__ void set_mask_first(int p, const Mask<K>& v) const {
     if (widx(0) < W) words(p)[widx(0)] = v.w[0];
@@ -290,6 +352,11 @@ struct View {
       hdr(x)->parent = p;
     }
   }
+  // the same as ONE store of lane 0 (packed leaf parents): the address is selected, as parent() selects it, not the store
+  __device__ __forceinline__ void set_parent_lane0(int x, int p) const {
+    int32_t* a = x < n ? lpar + (int64_t)x * LPS : &hdr(x)->parent;
+    if (lig == 0) *a = p;
+  }
   __device__ __forceinline__ int left(int x) const { return x < n ? -1 : hdr(x)->left; }
   __device__ __forceinline__ int right(int x) const { return x < n ? -1 : hdr(x)->right; }
 };
@@ -324,6 +391,12 @@ __device__ inline double cpl_partial(const Params& P, const uint8_t* blk, int64_
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+
+// Lane J of every quad to the four lanes of the quad (quad_perm [J,J,J,J]).
+template <int J>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
+  return dpp<J * 0x55>(v);
 }
 
 // Sum of v over the 2^LOG2L lanes of the group, result in every lane.

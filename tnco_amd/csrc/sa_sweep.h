@@ -51,9 +51,21 @@
 #include "sa_kernels.h"
 #include "fw_params.h"
 
+#include <type_traits>
+
 namespace tnco {
 
 #define TNCO_LANDED(x) __asm__ volatile("" : "+v"(x) : : "memory")
+
+// How the child-partial instantiations read and write a node (profiles/r09_node_access.md), cumulative:
+//   1  the header as one 8-byte piece per lane of a quad, broadcast behind the landing fence; B's record stored the same way
+//   2  the legs in pairs of words per lane (sa_kernels.h, View<..., PAIRS>)
+//   3  one store per parent word of an accepted move
+//   4  a refill round's four words mt[k + 397 ...] as one 16-byte load (Rng::request)
+//   0  the parent's form: the whole header in every lane, one word per lane and row
+#ifndef TNCO_NODE_ACCESS
+#define TNCO_NODE_ACCESS 4
+#endif
 
 // LDS pointers must keep their address space: a generic (flat) pointer to LDS makes every access a
 // flat_load / flat_store, which counts in vmcnt and drags an `s_waitcnt vmcnt(0)` behind it.
@@ -93,8 +105,12 @@ constexpr int MT_ROUND_RING = 64;
 constexpr int MT_ROUND_LOW = 8;
 static_assert(MT_ROUND_RING <= MT_SHADOW && MT_ROUND_LOW >= 7, "refill rounds");
 
-template <int LOG2L, int RINGX = 0>
-struct Rng {
+// (PCV, TNCO_NODE_ACCESS >= 4: the four words mt[k + 397 ...] of a block's inputs as one register tuple, for one 16-byte load)
+typedef uint32_t rng_u32x4 __attribute__((ext_vector_type(4)));
+struct RngPcv { rng_u32x4 pcv; };
+struct RngNoPcv {};
+template <int LOG2L, int RINGX = 0, bool PCV = false>
+struct Rng : std::conditional_t<PCV, RngPcv, RngNoPcv> {
   static constexpr int L = 1 << LOG2L;
   static constexpr int NL = L < 4 ? L : 4;         // lanes of the group that work on a block
   static constexpr int SB = 4 * NL;                // words per block: 4 per lane (one dwordx4); 624 % 16 == 0
@@ -114,9 +130,10 @@ struct Rng {
   bool pend, ptw;          // a block's inputs are in flight (for virtual position prod); it needs a twist
   // this lane's inputs: mt[k..k+3], mt[k+4], mt[k+397..k+400] (indices mod 624); written ONLY by
   // the loads of request(), so that the loads land directly in these registers
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  typedef rng_u32x4 u32x4;
   u32x4 pa;                // one 128-bit register tuple: the dwordx4 load lands in place
   uint32_t pb, pc[4];
+  typedef u32x4 u32x4w __attribute__((aligned(4)));  // (PCV: 4 words at any word address)
 
   __device__ __forceinline__ uint32_t gen_of_cons() const { return cons == 0 ? 0u : (cons - 1u) / 624u; }
 
@@ -133,12 +150,17 @@ struct Rng {
       if (ptw) {
         pb = s[(k + 4 == 624) ? 0 : k + 4];
         if (k == 224) {  // 224 + 397 = 621: the only group of 4 that straddles the wrap
-          pc[0] = s[621]; pc[1] = s[622]; pc[2] = s[623]; pc[3] = s[0];
+          if constexpr (PCV) { this->pcv.x = s[621]; this->pcv.y = s[622]; this->pcv.z = s[623]; this->pcv.w = s[0]; }
+          else { pc[0] = s[621]; pc[1] = s[622]; pc[2] = s[623]; pc[3] = s[0]; }
         } else {
           int km = k + 397;
           if (km >= 624) km -= 624;
-          const U4 c = *reinterpret_cast<const U4*>(s + km);
-          pc[0] = c.x[0]; pc[1] = c.x[1]; pc[2] = c.x[2]; pc[3] = c.x[3];
+          if constexpr (PCV) {
+            this->pcv = *reinterpret_cast<const u32x4w*>(s + km);
+          } else {
+            const U4 c = *reinterpret_cast<const U4*>(s + km);
+            pc[0] = c.x[0]; pc[1] = c.x[1]; pc[2] = c.x[2]; pc[3] = c.x[3];
+          }
         }
       }
     }
@@ -156,7 +178,9 @@ struct Rng {
         v[j] = pa[j];
         if (ptw) {
           const uint32_t y = (pa[j] & 0x80000000u) | (nx[j] & 0x7fffffffu);
-          v[j] = pc[j] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+          uint32_t c;
+          if constexpr (PCV) c = this->pcv[j]; else c = pc[j];
+          v[j] = c ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
         }
         ring[(prod + (uint32_t)(4 * lig + j)) & (RING - 1)] = mt_temper(v[j]);
       }
@@ -184,6 +208,7 @@ struct Rng {
     pa = (u32x4)(0u);
 #pragma unroll
     for (int j = 0; j < 4; ++j) pc[j] = 0;
+    if constexpr (PCV) this->pcv = (u32x4)(0u);
     if (mti >= 624) { cons = 624; tw = 624; } else { cons = (uint32_t)mti; tw = (uint32_t)mtw; }
     prod = cons & ~(uint32_t)(SB - 1);
     // synchronous prologue fill, FILL blocks at the most (0: until the ring is full): each block is a dependent round
@@ -399,7 +424,8 @@ __device__ __forceinline__ void sa_run_body(
   using M = Mask<K>;
   // (the child-partial instantiations -- CP below -- refill their mt19937 rings in wave-synchronous rounds: MT_ROUND_RING)
   constexpr bool ROUNDS = !HYPER && !GENERIC && !FW;
-  using R = Rng<LOG2L, ROUNDS ? MT_ROUND_RING : 0>;
+  constexpr bool RPCV = ROUNDS && TNCO_NODE_ACCESS >= 4;
+  using R = Rng<LOG2L, ROUNDS ? MT_ROUND_RING : 0, RPCV>;
   // (a launch enters the loop with two blocks less the up to SB - 1 words consumed of the first)
   static_assert(!ROUNDS || R::SB + 1 >= MT_ROUND_LOW, "refill rounds: the prologue");
   __shared__ uint32_t rngbuf[GPB * R::RING];
@@ -446,7 +472,6 @@ __device__ __forceinline__ void sa_run_body(
   const int slig = master ? lig : (1 << 20);  // (the lane index of loops that store)
 
   const int n = P.n, N = P.N;
-  View<LOG2L, K, HYPER, !FW> v;  // (finite width: the split layout)
   // Hyper-indices.  The reference keeps hyper[p] = legs(p) & legs(c0) & legs(c1) per node (infinite_memory/utils.hpp:82-91)
   // and updates it with that very formula (optimizer.hpp:171-172), so it never has to be STORED: the own legs of B and A
   // sit in the line their headers come from, the children's legs are carried anyway.
@@ -459,6 +484,9 @@ __device__ __forceinline__ void sa_run_body(
   // of the next C) and its legs (legs(C) = legs(parent(A)) ^ legs(A)); the contraction cost of A is derived from the legs.
   // The root's partial cost is ReplicaState::total, carried in S.total from one sweep to the next.
   constexpr bool CP = !HYPER && !GENERIC && !FW;
+  // (how they read and write a node: TNCO_NODE_ACCESS above)
+  constexpr bool QHDR = CP && TNCO_NODE_ACCESS >= 1, PAIRS = CP && TNCO_NODE_ACCESS >= 2, PSEL = CP && TNCO_NODE_ACCESS >= 3 && LPS == 1;
+  View<LOG2L, K, HYPER, !FW, PAIRS> v;  // (finite width: the split layout)
   v.init(P, P.blocks + r * P.RB, nullptr, lig);
   auto lpar = [&]() -> int32_t* { return P.lpar + r * (int64_t)n * LPS; };
   lds_cold& cold = *((lds_cold*)coldbuf + gib);
@@ -566,7 +594,17 @@ __device__ __forceinline__ void sa_run_body(
   //  their own each made the compiler copy them out of the load's destination, a wait right behind the load)
   typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
   [[maybe_unused]] i32x4 gLRP = (i32x4)(-1);
+  // (QHDR: this lane's 8 bytes of the header -- {left, right}, {parent, pad}, partial(left), partial(right) in lanes 0..3 of
+  //  a quad -- as one register tuple, written by the load alone: rule (2))
+  [[maybe_unused]] u32x2 gHq = (u32x2)(0u);
   M gM = mzero<K>(), gH = mzero<K>();
+  // (PAIRS: the legs' staging registers, pair by pair; gM is then what they hold behind the fence)
+  [[maybe_unused]] PairStage<K> gMq;
+  if constexpr (PAIRS) {
+#pragma unroll
+    for (int j = 0; j < (K / 2 ? K / 2 : 1); ++j) gMq.p[j] = (u64x2)(0ull);
+    gMq.s = 0ull;
+  }
   uint32_t gXlo = 0, gXhi = 0;
 
   TNCO_PROF_DECL;
@@ -691,17 +729,31 @@ __device__ __forceinline__ void sa_run_body(
     TNCO_PROF_F(2);
     // ======================= requests (staging registers) ====================
     // Nothing below reads these registers before the landing fence.
+    // (QHDR: the lane index the addresses are made of is re-read here and ahead of the stores, opaquely, as jlog() does
+    //  it: with two lane offsets -- 8 and 16 bytes per lane -- the compiler otherwise keeps base + lane offset in a
+    //  register pair of its own for every base, loop invariants that cost more registers than the staging tuples gave
+    //  back: 8 VGPRs spilled and a reload inside the loop)
+    if constexpr (QHDR) {
+      int lq = lig;
+      __asm__ volatile("" : "+v"(lq));
+      v.lig = lq;
+    }
     if (hN >= 0) {
       const NodeRec* q = v.hdr(hN);
-      if constexpr (CP) gLRP = *reinterpret_cast<const i32x4*>(q);
-      else { gL = q->left; gR = q->right; gP = q->parent; }
-      gC = q->ccost;
-      if constexpr (FW) gW = q->pad;
-      if constexpr (CP) gQ1 = q->pright;
+      if constexpr (QHDR) {
+        gHq = *reinterpret_cast<const u32x2*>(v.blk + v.hdr_piece_off(hN));
+      } else {
+        if constexpr (CP) gLRP = *reinterpret_cast<const i32x4*>(q);
+        else { gL = q->left; gR = q->right; gP = q->parent; }
+        gC = q->ccost;
+        if constexpr (FW) gW = q->pad;
+        if constexpr (CP) gQ1 = q->pright;
+      }
     }
     double gMp = 0;
     if (x1 >= 0) {
-      v.mask_stage_into(gM, x1);
+      if constexpr (PAIRS) v.pair_stage_into(gMq, x1);
+      else v.mask_stage_into(gM, x1);
       if constexpr (!CP)
         if (x1 >= n) gMp = v.hdr(x1)->partial;
     }
@@ -869,22 +921,38 @@ __device__ __forceinline__ void sa_run_body(
     // ======================= landing fence ===================================
     // Everything requested above is needed before the first store below: vmcnt is in order, so
     // waiting for these loads later would also wait for the stores.
-    TNCO_LANDED(gL); TNCO_LANDED(gR); TNCO_LANDED(gP); TNCO_LANDED(gC);
-    if constexpr (CP) { TNCO_LANDED(gQ1); TNCO_LANDED(gLRP); }
+    if constexpr (QHDR) {  // (gL ... gQ1 are what the broadcast makes of it behind the store phase)
+      TNCO_LANDED(gHq);
+    } else {
+      TNCO_LANDED(gL); TNCO_LANDED(gR); TNCO_LANDED(gP); TNCO_LANDED(gC);
+      if constexpr (CP) { TNCO_LANDED(gQ1); TNCO_LANDED(gLRP); }
+    }
     if constexpr (FW) TNCO_LANDED(gW);
     TNCO_LANDED(gMp); TNCO_LANDED(gXlo); TNCO_LANDED(gXhi);
+    if constexpr (PAIRS) {
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      TNCO_LANDED(gM.w[k]);
-      if constexpr (HYPER) { TNCO_LANDED(gH.w[k]); }
+      for (int j = 0; j < K / 2; ++j) TNCO_LANDED(gMq.p[j]);
+      if constexpr (K & 1) TNCO_LANDED(gMq.s);
+    } else {
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        TNCO_LANDED(gM.w[k]);
+        if constexpr (HYPER) { TNCO_LANDED(gH.w[k]); }
+      }
     }
     TNCO_LANDED(rng.pb);
     TNCO_LANDED(rng.pa);
 #pragma unroll
     for (int j = 0; j < 4; ++j) TNCO_LANDED(rng.pc[j]);
+    if constexpr (RPCV) TNCO_LANDED(rng.pcv);
 
     TNCO_PROF_T(3);
     // ======================= store phase =====================================
+    if constexpr (QHDR) {
+      int lq = lig;
+      __asm__ volatile("" : "+v"(lq));
+      v.lig = lq;
+    }
     if (did_move && acc) {
       if (!jinvalid) {
         if (jtail == jcap) {
@@ -901,13 +969,30 @@ __device__ __forceinline__ void sa_run_body(
       }
       v.lpar = lpar();
       if (master) {
-        v.set_parent_group(stC, B);
-        v.set_parent_group(stE, A);
-        v.set_mask(B, mP);  // :170 (accepted: B's legs are the new legs -- B is the path child of the next level)
+        if constexpr (PSEL) {
+          v.set_parent_lane0(stC, B);
+          v.set_parent_lane0(stE, A);
+        } else {
+          v.set_parent_group(stC, B);
+          v.set_parent_group(stE, A);
+        }
+        // :170 (accepted: B's legs are the new legs -- B is the path child of the next level)
+        if constexpr (PAIRS) v.set_mask_pairs(B, mP);
+        else v.set_mask(B, mP);
       }
     }
     if (did_move || did_end) {
-      if (lane0) {
+      if constexpr (QHDR) {
+        // B's record, 8 bytes per lane of the first quad: one instruction, one 32-byte sector, as lane 0's 32 bytes were
+        if (master && v.lig < 4) {
+          const uint64_t q0 = __double_as_longlong(stQ0), q1 = __double_as_longlong(stQ1);
+          u32x2 o;
+          const int lq = v.lig;
+          o.x = lq == 0 ? (uint32_t)bl : (lq == 1 ? (uint32_t)A : (uint32_t)(lq == 2 ? q0 : q1));  // (END: A == -1)
+          o.y = lq == 0 ? (uint32_t)br : (lq == 1 ? 0u : (uint32_t)((lq == 2 ? q0 : q1) >> 32));
+          *reinterpret_cast<u32x2*>(v.blk + v.hdr_piece_off(B)) = o;
+        }
+      } else if (lane0) {
         NodeRec o;
         o.left = bl; o.right = br; o.parent = A; o.pad = FW ? wB : 0;  // (END: A == -1)
         if constexpr (CP) { o.pleft = stQ0; o.pright = stQ1; } else { o.ccost = ccB; o.partial = partB; }
@@ -933,7 +1018,12 @@ __device__ __forceinline__ void sa_run_body(
     // ======================= what landed goes where ==========================
     // (child-partial layout: A's line landed -- its links, the partial cost of its child that is not B, its legs; with
     //  the legs of B = mP ^ mO: legs(C) and the contraction cost of A, popc(legs(B) | legs(C)) = popc(legs(B) | legs(A)))
-    if constexpr (CP) { gL = gLRP.x; gR = gLRP.y; gP = gLRP.z; }
+    if constexpr (QHDR) {
+      gL = (int)quad_bcast<0>(gHq.x); gR = (int)quad_bcast<0>(gHq.y); gP = (int)quad_bcast<1>(gHq.x);
+      gC = __hiloint2double((int)quad_bcast<2>(gHq.y), (int)quad_bcast<2>(gHq.x));
+      gQ1 = __hiloint2double((int)quad_bcast<3>(gHq.y), (int)quad_bcast<3>(gHq.x));
+    } else if constexpr (CP) { gL = gLRP.x; gR = gLRP.y; gP = gLRP.z; }
+    if constexpr (PAIRS) gM = v.pair_landed(gMq);
     auto land_A = [&]() {
       S.raL = gL; S.raR = gR; S.raP = gP;
       const M mB = mxor<K>(mP, mO);
