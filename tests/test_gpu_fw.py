@@ -613,3 +613,27 @@ def test_fw_full_wavefronts_of_the_staged_moves(core, oracle_lib, n, deg, frac, 
             assert all(np.array_equal(a, b) for a, b in zip(gpu.slices(r), o.slices()))
             assert tot[r] == o.total_cost and mn[r] == o.min_total_cost
         assert gpu.validate() == (0, -1)
+
+
+def test_fw_initial_slices_in_rows_with_a_stride_beyond_their_length(core, oracle_lib):
+    """`slices_stride` > W (filler behind every replica's initial slices, tests/helpers.py): every replica starts from
+    its own row, as the oracle given that row does."""
+    prob = H.regular_problem(16, graph_seed=5)
+    seeds = H.replica_seeds(8, S=5)
+    links = prob.links(seeds)
+    max_width = max(3, _initial_max_width(prob, prob.tree(seeds[0])) // 2)
+    init = ct.pack_masks([[(i + 2 * r) % prob.n_inds for i in (1, 2, 4, 5, 7, 8, 10, 11)] for r in range(len(seeds))], prob.n_inds)
+    betas = H.linear_betas(0, 50, 20)
+    with H.padded_rows(core, slices=2):
+        gpu = core.BatchedOptimizer(prob.leaf_masks, links, seeds, n_inds=prob.n_inds, dims=prob.dims, max_width=max_width, slices=init)
+    with gpu:
+        gpu.run(betas, "mh", update_slices_every=10)
+        tot, mn = gpu.costs()
+        for r in range(len(seeds)):
+            o = H.make_oracle(oracle_lib, prob, links[r], seeds[r], max_width=max_width, slices=init[r])
+            o.run(oracle_lib.PROB_MH, betas, update_slices_every=10)
+            assert o.is_valid() == 0
+            H.assert_replica_equal(gpu, r, o)
+            assert all(np.array_equal(x, y) for x, y in zip(gpu.slices(r), o.slices()))
+            assert tot[r] == o.total_cost and mn[r] == o.min_total_cost
+        assert gpu.validate() == (0, -1)

@@ -573,3 +573,16 @@ def test_general_cost_model_on_22_mask_words(core, oracle_lib):
             H.assert_replica_equal(gpu, r, o)
             assert tot[r] == o.total_cost and mn[r] == o.min_total_cost
         assert gpu.validate() == (0, -1)
+
+
+@pytest.mark.parametrize("rows,pad", [("links", 5), ("node_masks", 0), ("node_masks", 3)])
+def test_rows_with_a_stride_beyond_their_length(core, oracle_lib, rows, pad):
+    """`links_stride` > 3 N and `node_masks_stride` > N W (filler behind every replica's row, tests/helpers.py): the
+    handle is the one the back-to-back rows give, which is the oracle's.  Explicit `node_masks` reach no other test, so
+    their back-to-back rows (pad 0) are a case too; they put the handle on the kernels for hyper-indices."""
+    prob = H.regular_problem(16, graph_seed=3)
+    seeds = H.replica_seeds(8)
+    links = prob.links(seeds)
+    kw = dict(node_masks=np.stack([prob.node_masks(l, r) for l, r, _p in links])) if rows == "node_masks" else {}
+    with H.padded_rows(core, **{rows: pad}):
+        _run_both(core, oracle_lib, prob, seeds, H.linear_betas(0, 50, 20), links=links, **kw)

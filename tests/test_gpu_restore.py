@@ -121,6 +121,37 @@ def test_finite_width_batch_survives_destroy_and_restore(core, oracle_lib):
                 assert all(np.array_equal(x, y) for x, y in zip(b.slices(r), oo.slices()))
 
 
+def test_best_trees_in_rows_with_a_stride_beyond_their_length(core, oracle_lib):
+    """`min_links_stride` > 3 N (filler behind every replica's best tree, tests/helpers.py): the restored batch is the
+    one the back-to-back rows restore -- the uninterrupted run's, and the oracle's."""
+    orc = oracle_lib
+    prob = H.regular_problem(16, graph_seed=2)
+    seeds = H.replica_seeds(8, S=5)
+    links = prob.links(seeds)
+    betas = H.linear_betas(0, 60, 20)
+    kw = dict(n_inds=prob.n_inds, dims=2)
+    with core.BatchedOptimizer(prob.leaf_masks, links, seeds, **kw) as full:
+        full.run(betas)
+        want = _state(full)
+    with core.BatchedOptimizer(prob.leaf_masks, links, seeds, **kw) as a:
+        a.run(betas[:9])
+        snap = a.snapshot()
+        mid = _state(a)
+    with H.padded_rows(core, min_links=7):
+        b = core.BatchedOptimizer.restore(snap, prob.leaf_masks, **kw)
+    with b:
+        _assert_same(mid, _state(b))
+        assert b.validate() == (0, -1)
+        b.run(betas[9:])
+        _assert_same(want, _state(b))
+        assert b.validate() == (0, -1)
+        for r in range(len(seeds)):
+            o = H.make_oracle(orc, prob, links[r], seeds[r])
+            o.run(orc.PROB_MH, betas)
+            H.assert_replica_equal(b, r, o)
+            assert o.min_total_cost == want["mn"][r] and o.total_cost == want["tot"][r]
+
+
 def test_restore_arguments_are_checked(core):
     prob = H.regular_problem(16, graph_seed=1)
     seeds = H.replica_seeds(4)

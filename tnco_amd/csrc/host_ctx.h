@@ -20,7 +20,17 @@ struct EventPair {
 enum : int { TNCO_KIND_SWEEP = 0, TNCO_KIND_FW_MOVE = 1, TNCO_KIND_FW_RESLICE = 2, TNCO_KIND_FW_WALK = 3, TNCO_KINDS = 4 };
 
 
-struct tnco_hip_ctx {
+// which sweep kernel a handle runs and in which form: decided at create (tnco_hip.hip, choose_launch), read by launch_impl.h
+struct LaunchForm {
+  bool small_tree = false;  // small trees: LDS-resident sweeps (sa_small.h, sa_small_kernel)
+  int small_seats = 16;     // ... replicas per wavefront (a batch smaller than the chip's wavefront slots is spread)
+  int run_seats = 0;        // > 0: the HBM sweep kernel's SPREAD form, that many replicas per wavefront (a batch smaller than the wavefront slots)
+  bool lds_tree = false;    // any tree whose replicas fit the CUs' LDS in two rounds: sa_lds_kernel with the plan below
+  tnco::LdsPlan lds_plan{};
+  int run_slots = 0;  // resident blocks of the sweep kernel on this device
+};
+
+struct tnco_hip_ctx : LaunchForm {
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
@@ -49,11 +59,6 @@ struct tnco_hip_ctx {
   int64_t fw_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool fw_probed = false;  // the first re-slice interval of the handle has run on its own (tnco_hip_run_fw)
   unsigned long long fw_slow_pending = 0, fw_slow_wide_pending = 0;  // fall-backs collected since tnco_hip_run_fw last chose a form
-  bool small_tree = false;  // small trees: LDS-resident sweeps (sa_small.h, sa_small_kernel)
-  int small_seats = 16;     // ... replicas per wavefront (a batch smaller than the chip's wavefront slots is spread)
-  int run_seats = 0;        // > 0: the HBM sweep kernel's SPREAD form, that many replicas per wavefront (a batch smaller than the wavefront slots)
-  bool lds_tree = false;    // any tree whose replicas fit the CUs' LDS in two rounds: sa_lds_kernel with the plan below
-  tnco::LdsPlan lds_plan{};
   uint64_t* leaf_idx = nullptr;  // [n][lds_plan.leaf_stride] the leaves' index positions (16 bits each), device
   tnco::FwParams F{};
   std::vector<void*> allocs;
@@ -75,7 +80,6 @@ struct tnco_hip_ctx {
   // (event), every other entry point joins them back first (join_groups).
   static constexpr int MAX_GROUPS = 4;
   int n_groups = 1;
-  int run_slots = 0;  // resident blocks of the sweep kernel on this device
   hipStream_t gstream[MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t gfork = nullptr, gjoin[MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
   bool groups_dirty = false;
@@ -118,6 +122,15 @@ struct tnco_hip_ctx {
       bytes += nb;
       *p = (T*)q;
     }
+    return e;
+  }
+  // host data -> a device buffer the handle owns
+  template <typename T, typename Q>
+  hipError_t upload(const std::vector<T>& src, Q** dst) {
+    T* p = nullptr;
+    hipError_t e = alloc(&p, (int64_t)src.size());
+    if (e == hipSuccess) e = hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) *dst = p;
     return e;
   }
   // HIP events on the handle's stream around one kernel launch

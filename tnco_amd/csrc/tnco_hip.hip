@@ -11,7 +11,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <numeric>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -461,6 +463,733 @@ int fetch_rs(tnco_hip_handle h, std::vector<ReplicaState>& rs) {
   return TNCO_HIP_OK;
 }
 
+// ---- tnco_hip_create: the bodies its phases share, the launch-configuration rule, the phases -------------------------
+
+// `rows` rows of `row` elements, `src_stride` apart at the source (0 or `row`: back to back), to rows `dst_stride` apart
+template <typename T>
+hipError_t copy_rows(T* dst, int64_t dst_stride, const T* src, int64_t src_stride, int64_t row, int64_t rows, hipMemcpyKind kind) {
+  if (dst_stride == row && (src_stride == 0 || src_stride == row)) return hipMemcpy(dst, src, (size_t)rows * row * sizeof(T), kind);
+  return hipMemcpy2D(dst, (size_t)dst_stride * sizeof(T), src, (size_t)src_stride * sizeof(T), (size_t)row * sizeof(T), (size_t)rows, kind);
+}
+
+// host-side structural validation of `ntrees` trees, `stride` int32 apart: the message of a failing one, or nullptr
+const char* check_trees_host(int32_t N, const int32_t* links, int64_t stride, int64_t ntrees) {
+  const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ntrees / 64 + 1, 16), std::thread::hardware_concurrency()));
+  std::vector<const char*> errs((size_t)nth, nullptr);
+  std::vector<std::thread> th;
+  for (int t = 0; t < nth; ++t)
+    th.emplace_back([&, t]() {
+      std::vector<int32_t> cp((size_t)N), cc((size_t)N);
+      for (int64_t r = t; r < ntrees && !errs[t]; r += nth) {
+        const int32_t* lk = links + r * stride;
+        errs[t] = tree_check(N, lk, lk + N, lk + 2 * (int64_t)N, cp, cc);
+      }
+    });
+  for (auto& x : th) x.join();
+  for (auto e : errs)
+    if (e) return e;
+  return nullptr;
+}
+
+// the leaves that hold each index, in leaf order: cnt[i] of them, the first `cap` in who[i * cap ...]
+void scan_holders(const uint64_t* leaf_masks, int n, int I, int W, int cap, std::vector<int32_t>& cnt, std::vector<int32_t>& who) {
+  cnt.assign((size_t)I, 0);
+  who.assign((size_t)I * cap, -1);
+  for (int t = 0; t < n; ++t)
+    for (int i = 0; i < I; ++i)
+      if ((leaf_masks[(size_t)t * W + (i >> 6)] >> (i & 63)) & 1ull) {
+        if (cnt[i] < cap) who[(size_t)i * cap + cnt[i]] = t;
+        cnt[i] += 1;
+      }
+}
+
+// A batch that leaves wavefront slots of the HBM kernel empty is spread (sa_sweep.h, SPREAD): fewer replicas per
+// wavefront, the other lane groups shadowing them.  Per-replica move-evals/s at 512 leaves, 16 (full) / 1 / 2 / 4 / 8
+// replicas per wavefront: 1024 replicas 3.2 / 5.3 / 4.4 / 3.8 / 3.5e5; 4096: 3.2 / - / 3.7 / 3.8 / 3.5; 8192: 3.2 / - /
+// 2.1 / 3.2 / 3.5; 16384: 3.2 / - / - / 1.8 / 2.9 -- one replica per wavefront while that takes at most two thirds of
+// the slots, else as few as leave ONE wavefront per SIMD (two half-filled ones lose to a full one).
+// Replicas per wavefront of the spread form, 0: full wavefronts.  `wslots`: the wavefronts of that form the device holds.
+int spread_seats(int64_t R, int64_t wslots, int full, int cus) {
+  int seats = 1;
+  if (3 * R > 2 * wslots)
+    while (seats < full && (R + seats - 1) / seats > 4 * (int64_t)cus) seats *= 2;
+  int run_seats = (wslots > 0 && seats < full) ? seats : 0;
+#ifdef TNCO_NO_SMALL_TREE  // (the A/B library: the batch as it was, 64 / L replicas per wavefront)
+  run_seats = 0;
+#endif
+  return run_seats;
+}
+
+// Which sweep kernel a handle runs, in which form, on how many streams: plain arithmetic on what create knows by then.
+struct LaunchIn {
+  int n, I, W, K, log2l, log2d;  // the shape (log2l, K: the lane layout; log2d: Params::log2d)
+  int64_t R;
+  bool fw, hyper, generic, min_links;  // finite width / hyper-indices / the general cost path / a best tree was restored
+  int64_t fw_max_new_slices;
+  int deg;                   // index positions per leaf at most
+  int cus, lds_bytes;        // the device: CUs, LDS a workgroup may use
+  int bpc_spread, bpc_full;  // blocks per CU of the sweep kernel (finite width: of the staged moves), spread / full form
+  bool lds_refused;          // the runtime would not give sa_lds_kernel its dynamic LDS (lds_kernel_prepare)
+  int groups_env;            // TNCO_HIP_GROUPS, 0: not set
+};
+struct LaunchCfg : LaunchForm { int G = 1; };  // (LaunchForm, host_ctx.h: the fields of the handle that launch_impl.h reads)
+LaunchCfg choose_launch(const LaunchIn& in) {
+  LaunchCfg c;
+  const int n = in.n, N = 2 * n - 1, I = in.I, W = in.W, L = 1 << in.log2l;
+  const int64_t R = in.R;
+  // Infinite memory: more blocks than resident ones (65536 replicas at 512 leaves: 1024 blocks, 768 resident)?  Then
+  // every step is split over two streams (host_ctx.h, tnco_hip_run), unless the last round is nearly full anyway.
+  // TNCO_HIP_GROUPS=1..4 overrides.
+  const int64_t nblocks = (R + (SWT / L) - 1) / (SWT / L);
+  if (!in.fw) {
+    // Few small trees: every replica's whole tree in LDS during a launch (sa_small.h) -- if all the replicas are resident
+    // at once.  (Not after a restored best tree: the LDS-resident kernel assumes the log starts at the checkpoint.)
+    c.small_tree = !in.hyper && !in.generic && W <= 2 && n >= 2 && n - 1 <= SMALL_MAX_INTERNAL && LPS == 1 && !in.min_links;
+#ifdef TNCO_NO_SMALL_TREE  // (the A/B library of tools/small_tree_ab.py: `make nosmall`)
+    c.small_tree = false;
+#endif
+    // The LDS-resident kernel is bound by the instruction stream of one wavefront per SIMD (16 replicas; 1.35 us per
+    // move whatever the load), the HBM kernel by memory latency per replica (3.7 us) until ~50 000 replicas saturate it
+    // at 8-9e9 move-evals/s.  Up to 64 leaves a CU holds 64 LDS-resident replicas and the LDS kernel wins at every
+    // replica count (1.07e10 from 16 384 replicas on); beyond, a CU holds 32 and it wins (x2.3 ... x1.15) while two
+    // rounds of its blocks hold the replicas (profiles/r05_small_tree_ab.txt).
+#ifndef TNCO_SMALL_TREE_ALWAYS  // (the other A/B library of tools/small_tree_ab.py: `make allsmall`)
+    if (c.small_tree && n - 1 > 63 && R > 2 * (int64_t)small_replicas_per_cu(n - 1) * in.cus) c.small_tree = false;
+#endif
+    if (c.small_tree) {
+      // A batch that leaves wavefront slots empty gets fewer replicas per wavefront (the spare lane groups shadow them,
+      // sa_small.h): an iteration then runs only the sections its few replicas are in -- 8.5-8.8e5 move-evals/s per
+      // replica at one per wavefront (up to 1024 replicas of <= 64 leaves), 7.5e5 at four, 6.7e5 at sixteen.
+      const int64_t slots = (int64_t)small_replicas_per_cu(n - 1) / (SMALL_TPB / 4) * in.cus;
+      while (c.small_seats > 1 && (R + c.small_seats / 2 - 1) / (c.small_seats / 2) <= slots) c.small_seats /= 2;
+    }
+    // Any other tree of the fast cost path whose replicas fit the CUs' LDS at once (the latency regime of the larger
+    // networks: 512 leaves of 12 words are 58 KiB, two per CU, up to 512 replicas): sa_lds_kernel.
+    if (!c.small_tree && !in.lds_refused && !in.generic && LPS == 1 && !in.min_links && n >= 2 && in.log2l == 2 && I <= 65535 &&
+        N <= 65534 && (int64_t)in.log2d * 64 * W <= 65535) {
+      const bool table = (int64_t)n * 32 * in.K <= 16384;  // the leaf legs themselves, [n][4 K] words
+      if (table || in.deg <= 32) {
+        const int K = in.K, ni = n - 1;
+        LdsPlan pl{};
+        pl.leaf_stride = table ? 0 : std::max(1, (in.deg + 3) / 4);
+        pl.leaf_words = table ? n * 4 * K : n * pl.leaf_stride;
+        pl.seat0 = (pl.leaf_words * 8 + 15) / 16 * 16;
+        pl.o_part = 8 * ni;
+        pl.o_legs = 16 * ni;
+        pl.o_lpar = pl.o_legs + 32 * K * ni;
+        pl.o_ring = pl.o_lpar + (2 * n + 7) / 8 * 8;
+        pl.o_jb = pl.o_ring + 64 * 4;
+        pl.seat_stride = (pl.o_jb + 16 * 4 + 15) / 16 * 16;
+        // Four blocks (wavefronts of up to 16 replicas) per CU -- one per SIMD -- if they hold the batch, else two, else
+        // one, and as few replicas per wavefront as spread the batch over all of them, the other lane groups shadowing
+        // (sa_small.h): per-replica move-evals/s at 128 leaves, four blocks / one block per CU: 1024 replicas 7.8 / 7.1e5,
+        // 2048: 7.4 / 6.6e5; 256 leaves, 1024: 7.6 / 7.0e5.  (Before the shadows it was the other way round: few active
+        // lanes per CU.)  x1.6 ... x2.8 the HBM kernel per replica, so a second round of blocks would lose.
+        int best = 0;
+        for (int b = 4; b >= 1 && best == 0; b >>= 1) {
+          const int seats = std::min(SMALL_TPB / 4, (in.lds_bytes / b - pl.seat0) / pl.seat_stride);
+          if (seats > 0 && (R <= (int64_t)b * seats * in.cus || b == 1)) { best = b * seats; pl.seats = seats; pl.blocks_per_cu = b; }
+        }
+#ifdef TNCO_NO_SMALL_TREE
+        best = 0;
+#endif
+#ifdef TNCO_SMALL_TREE_ALWAYS
+        const bool fits = best > 0;
+#else
+        const bool fits = best > 0 && R <= (int64_t)best * in.cus;
+#endif
+        if (fits) {
+          const int64_t waves = (int64_t)pl.blocks_per_cu * in.cus;
+          pl.seats = (int)std::max<int64_t>(1, std::min<int64_t>(pl.seats, (R + waves - 1) / waves));
+          pl.total = pl.seat0 + pl.seats * pl.seat_stride;
+          c.lds_plan = pl;
+          c.lds_tree = true;  // (if the runtime gives the kernel that much dynamic LDS; else: the HBM kernel below)
+        }
+      }
+    }
+    if (!c.small_tree && !c.lds_tree) c.run_seats = spread_seats(R, (int64_t)in.bpc_spread * in.cus * (SWT / 64), 64 / L, in.cus);
+    c.run_slots = (c.run_seats > 0 ? in.bpc_spread : in.bpc_full) * in.cus;
+    if (c.run_slots > 0 && nblocks > c.run_slots) {
+      const double rounds = (double)nblocks / (double)c.run_slots, part = rounds - std::floor(rounds);
+      // (also with whole rounds: the blocks of a round do not end together -- the general cost path at two
+      //  wavefronts per SIMD, 1024 blocks on 512 slots: +2 ... +8 % on two streams, profiles/r03_other_configs.md)
+      if (part < 0.85) c.G = 2;
+    }
+  } else if (in.fw_max_new_slices == 0) {
+    // finite width, a batch that leaves wavefront slots of the staged moves empty: their SPREAD form, by the rule of the
+    // infinite-memory kernel above -- the moves are 90 % of such a step (full wavefronts: 5.2 microseconds per move and
+    // replica); otherwise two halves on two streams whatever the rounds -- what overlaps then are KERNELS of different
+    // bounds (the moves wait on memory requests, get_slices and the tree kernel on LDS / instruction latency)
+    c.run_seats = spread_seats(R, (int64_t)in.bpc_spread * in.cus * (SWT / 64), 64 / L, in.cus);
+    if (c.run_seats == 0 && nblocks >= 64) c.G = 2;
+  }
+  if (in.groups_env) c.G = in.groups_env;
+  if (c.small_tree || c.lds_tree || c.run_seats > 0 || nblocks < 2 * c.G) c.G = 1;
+  return c;
+}
+
+// One call of tnco_hip_create: what its phases share, and the phases in the order they run.
+struct Create {
+  const tnco_hip_desc* d;
+  // derived from the descriptor (check_input)
+  int n = 0, N = 0, I = 0, W = 0;
+  int64_t R = 0;
+  bool uniform = true, pow2u = false, f32 = false, fw = false;
+  uint64_t dim_u = 0;
+  bool links_on_device = false;
+  int L = 0;  // padded words per mask row in the shared tables (lanes per replica x words per lane)
+  std::unique_ptr<tnco_hip_ctx> owner;  // the handle, until the call has succeeded
+  tnco_hip_ctx* h = nullptr;
+  // scratch of the whole call: ONE set (giving a set back waits for the device), released before a failed handle is
+  std::optional<TempBufs> tmp;
+  // what a build / init launch leaves per replica: on the device (scratch, R of each), and read back by read_costs
+  double *dtotal = nullptr, *dsum = nullptr;
+  int32_t* dstatus = nullptr;
+  std::vector<double> total, sum;
+  std::vector<int32_t> status;
+  // TNCO_HIP_DEBUG: wall time of the steps of this call on stderr (the device drained at every mark)
+  bool cdbg = false;
+  std::chrono::steady_clock::time_point c_t0;
+
+  void cmark(const char* what) {
+    if (!cdbg) return;
+    (void)hipDeviceSynchronize();
+    const auto t = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "create: %-28s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(t - c_t0).count());
+    c_t0 = t;
+  }
+  double round_cost(double x) const { return f32 ? (double)(float)x : x; }
+  int fw_lanes_per_mask() const { return L <= 16 ? 16 : (L <= 32 ? 32 : 64); }  // (L = FwParams::I64 / 64)
+  int read_costs(const int32_t* dst, int64_t cnt) {  // (the verdicts differ from launch to launch: at the call sites)
+    total.resize((size_t)cnt); sum.resize((size_t)cnt); status.resize((size_t)cnt);
+    HIP_TRY(hipMemcpy(total.data(), dtotal, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sum.data(), dsum, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(status.data(), dst, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    return TNCO_HIP_OK;
+  }
+  // rows of W mask words, `stride` apart, as rows of the shared tables: L words, zero-padded
+  std::vector<uint64_t> padded(const uint64_t* src, int64_t rows, int64_t stride) const {
+    std::vector<uint64_t> m((size_t)rows * L, 0);
+    for (int64_t r = 0; r < rows; ++r)
+      for (int w = 0; w < W; ++w) m[(size_t)r * L + w] = src[r * stride + w];
+    return m;
+  }
+
+  // 1. the descriptor: everything that needs no device
+  int check_input() {
+    if (d->n_leaves < 2) return fail(TNCO_HIP_EINVAL, "Precision is too low.");  // total cost 0 -> log2 = -inf (optimizer.hpp:77-80)
+    if (d->n_inds < 0 || d->n_replicas <= 0) return fail(TNCO_HIP_EINVAL, "'n_inds' / 'n_replicas' are not valid.");
+    if (!d->leaf_masks || !d->links || (!d->seeds && !d->prng_states)) return fail(TNCO_HIP_EINVAL, "null input array.");
+    if (d->prng_states)
+      for (int64_t r = 0; r < d->n_replicas; ++r)
+        if (d->prng_states[r * 625 + 624] > 624) return fail(TNCO_HIP_EINVAL, "prng position out of range.");
+    if (d->cost_dtype != TNCO_HIP_F64 && d->cost_dtype != TNCO_HIP_F32)
+      return fail(TNCO_HIP_ENOTIMPL, "cost_type must be float64 or float32.");
+    n = d->n_leaves; N = 2 * n - 1; I = d->n_inds;
+    W = std::max(1, (I + 63) / 64);
+    if (W > 64) return fail(TNCO_HIP_ENOTIMPL, "more than 4096 indices are not supported yet.");
+    if (d->sparse_mask && d->n_projs == 0) return fail(TNCO_HIP_ERUNTIME, "'n_projs' must be a positive number.");
+    R = d->n_replicas;
+
+    // dims (include/tnco/ctree.hpp:79-89, 121-135)
+    dim_u = d->dim_uniform;
+    if (d->dims) {
+      for (int i = 0; i < I; ++i)
+        if (d->dims[i] == 0) return fail(TNCO_HIP_EINVAL, "Dimensions must be positive numbers");
+      for (int i = 1; i < I; ++i) uniform &= d->dims[i] == d->dims[0];
+      if (I > 0 && uniform) dim_u = d->dims[0];
+      if (I == 0) uniform = false;
+    }
+    if (uniform && dim_u == 0) return fail(TNCO_HIP_EINVAL, "Dimensions must be positive numbers");
+    f32 = d->cost_dtype == TNCO_HIP_F32;
+    pow2u = uniform && (dim_u & (dim_u - 1)) == 0;
+
+    // finite width?  (tnco/app/app.py:866-870: finite max_width selects the finite_width optimizer)
+    fw = std::isfinite(d->max_width);
+    if (fw) {
+      // (the greedy re-slice packs a too-wide count and a shuffled rank into 16 bits each, fw_kernels.h)
+      if (N > 65535) return fail(TNCO_HIP_ENOTIMPL, "finite width: more than 32768 tensors are not supported.");
+      if (d->max_width < 0) return fail(TNCO_HIP_ERUNTIME, "'max_width' must be a non-negative number.");
+      if (d->width_dtype != TNCO_HIP_F32 && d->width_dtype != TNCO_HIP_F64)
+        return fail(TNCO_HIP_ENOTIMPL, "finite width: width_type must be float32 or float64.");
+    }
+
+    // 2. where `links` live; trees in host memory are checked here
+    // links already in device memory (tnco_hip_greedy_trees_device): validated there, never copied
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, d->links) == hipSuccess) {
+      if (at.type == hipMemoryTypeDevice) {
+        if (at.device != d->device) return fail(TNCO_HIP_EINVAL, "'links' are in the memory of another device.");
+        links_on_device = true;
+      }
+    } else {
+      (void)hipGetLastError();  // (plain host memory: not an error)
+    }
+    if (!links_on_device)
+      if (const char* e = check_trees_host(N, d->links, d->links_stride, d->links_stride == 0 ? 1 : R)) return fail(TNCO_HIP_EINVAL, e);
+    return TNCO_HIP_OK;
+  }
+
+  // 3. the device, the handle and its stream; lane layout, hyper-indices, cost path, the layout fields of Params; 4., 5. below
+  int open_handle() {
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (d->device < 0 || d->device >= ndev) return fail(TNCO_HIP_EINVAL, "'device' is not valid.");
+    HIP_TRY(hipSetDevice(d->device));
+
+    cdbg = std::getenv("TNCO_HIP_DEBUG") != nullptr;
+    c_t0 = std::chrono::steady_clock::now();
+    owner.reset(new tnco_hip_ctx());
+    h = owner.get();
+    tmp.emplace();
+    h->device = d->device;
+    HIP_TRY(tnco::StreamCache::get().take(&h->own_stream, d->device));
+    h->stream = h->own_stream;
+
+    choose_lanes(W, &h->log2l, &h->K);
+    h->L = 1 << h->log2l;
+    L = h->L * h->K;
+
+    // hyper legs present?  (an index held by more than two of {leaves, output})
+    h->leafmask_w.assign(d->leaf_masks, d->leaf_masks + (size_t)n * W);
+    h->outmask_w.assign((size_t)W, 0);
+    if (d->output_mask) h->outmask_w.assign(d->output_mask, d->output_mask + W);
+    std::vector<int32_t> cnt, who;
+    scan_holders(d->leaf_masks, n, W * 64, W, 0, cnt, who);
+    h->hyper = d->node_masks != nullptr;
+    for (int p = 0; p < W * 64; ++p) {
+      const int c = cnt[p] + (int)((h->outmask_w[p >> 6] >> (p & 63)) & 1);
+      if (c > 2) h->hyper = true;
+      if (p >= I && cnt[p]) return fail(TNCO_HIP_EINVAL, "index position out of range in 'leaf_masks'.");
+    }
+    h->generic = !(pow2u && !d->sparse_mask && !f32);
+    Params& P = h->P;
+    P.n = n; P.N = N; P.I = I; P.W = W; P.R = R;
+    P.BS = (32 + 8 * W + 31) / 32 * 32;
+    // (Networks with hyper-indices, round 5: hyper[p] = legs(p) & legs(c0) & legs(c1) is derived by the kernels from legs
+    //  they hold anyway, so no layout stores hyper legs: the blocks are those of a network without hyper-indices.)
+    // Blocks longer than a line are PACKED (a 224-byte block at 24 mask words straddles two or three 128-byte lines
+    // depending on where it starts): padding them to whole lines costs as many lines as it saves (round 3), and splitting
+    // them into headers + [partial copy | legs] records loses 5-30 % to the second dirty line per move (round 5).
+    P.WS = P.BS; P.WOFF = 32; P.RB = (int64_t)(n - 1) * P.BS;
+    if (fw) {  // split layout (sa_kernels.h, Params)
+      P.BS = 32;
+      P.WS = (8 * W + 63) / 64 * 64;
+      P.WOFF = ((n - 1) * 32 + 127) / 128 * 128;
+      P.RB = ((int64_t)P.WOFF + (int64_t)(n - 1) * P.WS + 127) / 128 * 128;
+    }
+    P.cpl = !fw && !h->hyper && !h->generic;  // (child-partial layout: sa_kernels.h)
+    P.f32 = f32; P.disable_shared = d->disable_shared_inds ? 1 : 0;
+    P.cost_mode = uniform ? (pow2u ? 0 : 1) : 2;
+    if (!uniform) {  // per-index dims, all powers of two: exponent classes only, no leg loop
+      bool allp2 = true;
+      for (int i = 0; i < I && allp2; ++i) {
+        const uint64_t x = d->dims[i];
+        allp2 = (x & (x - 1)) == 0;
+      }
+      if (allp2) P.cost_mode = 3;
+    }
+    P.log2d = 0;
+    if (pow2u) while ((1ull << P.log2d) < dim_u) ++P.log2d;
+    P.n_projs = d->sparse_mask ? round_cost((double)d->n_projs) : 0.0;
+
+    // 4. Rotation log: one int32 per accepted move since the last re-base of the checkpoint.  When it is
+    // full, the next improvement re-bases the checkpoint on the current tree (a 16 N-byte copy) and the
+    // log starts again, so its size only sets how often that happens: 32 Ki entries (128 KB per replica)
+    // are one re-base per ~2000 sweeps of the 512-leaf benchmark (a re-base stalls its wavefront: with
+    // 16 Ki entries every replica took one in the 1200-sweep bench run, -3 %).  (Round 1 gave the log an eighth of
+    // the free HBM -- 34 GB at 65536 replicas -- and hipMalloc of it took 1.4 s of every create().)
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    free_b += tnco::DevCache::get().held();  // (what destroyed handles left for this one counts as free)
+    int64_t cap = (int64_t)(free_b / 8) / (R * 4);
+    cap = std::max<int64_t>(1024, std::min<int64_t>(cap, (int64_t)1 << 15));
+    if (const char* e = std::getenv("TNCO_HIP_JLOG_CAP")) cap = std::max<int64_t>(1, std::atoll(e));  // test knob
+    cap = (cap + 15) & ~(int64_t)15;  // the sweep kernel appends in whole 16-entry (64-byte) pieces
+    P.jcap = (int32_t)cap;
+    cmark("checks, stream");
+    // 5. the per-replica arrays
+    HIP_TRY(h->alloc(&P.blocks, R * h->block_bytes()));
+    HIP_TRY(h->alloc(&P.lpar, R * n * LPS + 16));  // the sweep kernel reads 8 bytes at a leaf's record
+    HIP_TRY(h->alloc(&P.mt, R * 624));
+    HIP_TRY(h->alloc(&P.mtshadow, R * MT_SHADOW));
+    HIP_TRY(h->alloc(&P.rs, R));
+    HIP_TRY(h->alloc(&P.minlinks, R * N));
+    HIP_TRY(h->alloc(&P.jlog, R * (int64_t)P.jcap));
+    cmark("allocations");
+    return TNCO_HIP_OK;
+  }
+
+  // 6. shared tables: the leaves' legs, the output / sparse legs, what the cost path reads
+  int upload_tables() {
+    Params& P = h->P;
+    HIP_TRY(h->upload(padded(h->leafmask_w.data(), n, W), &P.leafmask));
+    HIP_TRY(h->upload(padded(h->outmask_w.data(), 1, W), &P.outmask));
+    if (d->sparse_mask) HIP_TRY(h->upload(padded(d->sparse_mask, 1, W), &P.sparse));
+    if (P.cost_mode == 1) {
+      // std::pow(size_t, size_t) -> double pow, converted to cost_type (simple.hpp:45)
+      std::vector<double> tab((size_t)W * 64 + 1);
+      for (size_t k = 0; k < tab.size(); ++k) tab[k] = round_cost(std::pow((double)dim_u, (double)k));
+      HIP_TRY(h->upload(tab, &P.ctab));
+    }
+    if (P.cost_mode < 2) return TNCO_HIP_OK;
+    // dims[p] = 2^a * odd: exponent classes (a = 1 .. max) for both modes; mode 2 also the odd parts
+    // (as cost_type) and the mask of the positions that have one (simple.hpp:51-53; sa_kernels.h seq_product)
+    int max_a = 0;
+    std::vector<int> av((size_t)I, 0);
+    std::vector<uint64_t> odd((size_t)I, 1);
+    for (int i = 0; i < I; ++i) {
+      uint64_t x = d->dims[i];
+      while ((x & 1ull) == 0) { x >>= 1; ++av[i]; }
+      odd[i] = x;
+      max_a = std::max(max_a, av[i]);
+    }
+    if (max_a > TABS_MAXCLS)
+      return fail(TNCO_HIP_ENOTIMPL, "an index dimension with a power-of-two part above 2^32 is not supported on the GPU path.");
+    std::vector<uint64_t> cls((size_t)std::max(max_a, 1) * L, 0);
+    for (int i = 0; i < I; ++i)
+      if (av[i] > 0) cls[(size_t)(av[i] - 1) * L + (i >> 6)] |= 1ull << (i & 63);
+    HIP_TRY(h->upload(cls, &P.dimclass));
+    P.n_dimclass = max_a;
+    if (P.cost_mode != 2) return TNCO_HIP_OK;
+    std::vector<double> dd((size_t)L * 64, 1.0);
+    std::vector<uint64_t> oddm((size_t)L, 0);
+    for (int i = 0; i < I; ++i) {
+      dd[i] = round_cost((double)odd[i]);
+      if (odd[i] != 1) oddm[i >> 6] |= 1ull << (i & 63);
+    }
+    HIP_TRY(h->upload(dd, &P.dimsd));
+    HIP_TRY(h->upload(oddm, &P.oddmask));
+    // a single odd part m (and exponents that fit the packed sum): chain of t factors as a table
+    uint64_t m1 = 0;
+    bool single = true;
+    for (int i = 0; i < I; ++i)
+      if (odd[i] != 1) {
+        if (m1 == 0) m1 = odd[i];
+        single &= odd[i] == m1;
+      }
+    if (single && m1 != 0 && (int64_t)max_a * W * 64 < (1 << 18) && !std::getenv("TNCO_HIP_NO_ODD_TABLE")) {
+      std::vector<double> tab((size_t)W * 64 + 1);
+      double c = 1.0;
+      const double md = round_cost((double)m1);
+      for (size_t t = 0; t < tab.size(); ++t) {
+        tab[t] = c;
+        c = round_cost(c * md);
+      }
+      HIP_TRY(h->upload(tab, &P.ctab));
+      P.odd_single = 1;
+    }
+    return TNCO_HIP_OK;
+  }
+
+  // 7. seeds -> MT state
+  int build_replicas() {
+    Params& P = h->P;
+    uint32_t* dseeds = nullptr;  // (or the positions of whole states)
+    HIP_TRY(tmp->alloc(&dseeds, R));
+    if (d->prng_states) {  // the string-seed form of the constructor (optimize/optimizer.hpp:68-71): whole states
+      HIP_TRY(hipMemcpy2D(P.mt, (size_t)624 * 4, d->prng_states, (size_t)625 * 4, (size_t)624 * 4, (size_t)R, hipMemcpyHostToDevice));
+      std::vector<uint32_t> pos((size_t)R);
+      for (int64_t r = 0; r < R; ++r) pos[(size_t)r] = d->prng_states[r * 625 + 624];
+      HIP_TRY(hipMemcpy(dseeds, pos.data(), (size_t)R * 4, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(mt_pos_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, h->stream, P.rs, dseeds, (const int64_t*)nullptr, R);
+    } else {
+      HIP_TRY(hipMemcpy(dseeds, d->seeds, (size_t)R * 4, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(mt_seed_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, h->stream, P.mt, P.rs, dseeds, R);
+    }
+    HIP_TRY(h->sync_all());
+    cmark("generator states");
+    // 8. links (+ optional explicit legs) -> node blocks and caches; the costs back, checkpoint := current tree
+    const int64_t ntrees = d->links_stride == 0 ? 1 : R;
+    int32_t* dlinks = nullptr;
+    uint64_t* dmasks = nullptr;
+    if (links_on_device && (d->links_stride == 0 || d->links_stride == 3 * (int64_t)N)) {
+      dlinks = const_cast<int32_t*>(d->links);  // (read only)
+    } else {
+      HIP_TRY(tmp->alloc(&dlinks, ntrees * 3 * N));
+      HIP_TRY(copy_rows(dlinks, 3 * (int64_t)N, d->links, d->links_stride, 3 * (int64_t)N, ntrees,
+                        links_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    }
+    if (links_on_device) {
+      int32_t* dcheck = nullptr;
+      HIP_TRY(tmp->alloc(&dcheck, ntrees));
+      hipLaunchKernelGGL(tree_check_kernel, dim3((unsigned)ntrees), dim3(64), 0, h->stream, (int32_t)N, dlinks, 3 * (int64_t)N, ntrees, dcheck);
+      HIP_TRY(hipGetLastError());
+      std::vector<int32_t> chk((size_t)ntrees);
+      HIP_TRY(hipMemcpyAsync(chk.data(), dcheck, (size_t)ntrees * 4, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h->sync_all());
+      for (int64_t r = 0; r < ntrees; ++r)
+        if (chk[r]) return fail(TNCO_HIP_EINVAL, tree_check_message(chk[r]));
+    }
+    cmark("trees checked");
+    const int64_t nmasks = d->node_masks ? (d->node_masks_stride == 0 ? 1 : R) : 0;
+    if (nmasks) {
+      HIP_TRY(tmp->alloc(&dmasks, nmasks * N * W));
+      HIP_TRY(copy_rows(dmasks, (int64_t)N * W, d->node_masks, d->node_masks_stride, (int64_t)N * W, nmasks, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(tmp->alloc(&dtotal, R));
+    HIP_TRY(tmp->alloc(&dsum, R));
+    HIP_TRY(tmp->alloc(&dstatus, R));
+    BuildArgs a{};
+    a.in_links = dlinks;
+    a.in_links_stride = d->links_stride == 0 ? 0 : 3 * (int64_t)N;
+    a.in_masks = dmasks;
+    a.in_masks_stride = (d->node_masks && d->node_masks_stride != 0) ? (int64_t)N * W : 0;
+    a.out_blocks = P.blocks; a.out_lpar = P.lpar;
+    a.scratch = reinterpret_cast<int32_t*>(P.minlinks);  // 16 B * N per replica = 4N int32
+    a.out_total = dtotal; a.out_sum = dsum; a.out_status = dstatus;
+    a.r0 = 0; a.count = R;
+    // (the second mask per node build_kernel derives the legs with)
+    if (h->hyper && !d->node_masks) HIP_TRY(tmp->alloc(&a.hyper_tmp, R * (int64_t)(n - 1) * W));
+    launch_build(h, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(h->sync_all());
+    cmark("trees -> node records");
+    if (int rc = read_costs(dstatus, R)) return rc;
+    hipLaunchKernelGGL(finish_init_kernel, dim3((unsigned)R), dim3(64), 0, h->stream, P, dsum, dtotal);
+    HIP_TRY(h->sync_all());
+    for (int64_t r = 0; r < R; ++r)
+      if (status[r]) return fail(TNCO_HIP_EINVAL, status_message(status[r]));
+    for (int64_t r = 0; r < R && !fw; ++r)  // (finite width: the costs of the sliced trees count, fw_setup)
+      if (bad_log2(total[r]) || bad_log2(sum[r])) return fail(TNCO_HIP_EINVAL, "Precision is too low.");
+    return TNCO_HIP_OK;
+  }
+
+  // 9a. The re-slice of a replica in one wavefront, its cost cache RE-PRICED (fw_wave_kernel): costs must be powers of
+  // two (uniform dims 2^k, float64, no sparse legs), a leg of a subtree decidable from the holders it contains (no
+  // hyper-indices), the headers one array per replica (split layout), a lane's share of the nodes in registers.
+  // TNCO_HIP_FW_WAVE=0: never (tests compare the two forms), =1: always where possible (else: by the fall-backs).
+  // Its holder tables, if the handle can run it.
+  int fw_wave_tables() {
+    const Params& P = h->P;
+    FwParams& F = h->F;
+    const char* wave_env = std::getenv("TNCO_HIP_FW_WAVE");
+    if (!(P.cost_mode == 0 && !P.f32 && d->sparse_mask == nullptr && P.BS == 32 && n >= 16 && n - 1 <= 64 * FWT_JMAX &&
+          F.I64 <= 4096 && fww_lds_bytes(n, fw_lanes_per_mask(), h->hyper) <= 64 * 1024 && !(wave_env && std::atoi(wave_env) == 0)))
+      return TNCO_HIP_OK;
+    constexpr int CAP = FWH_MAXH > 2 ? FWH_MAXH : 2;
+    std::vector<int32_t> cnt, who;
+    scan_holders(d->leaf_masks, n, I, W, CAP, cnt, who);
+    auto is_out = [&](int i) { return d->output_mask && ((d->output_mask[i >> 6] >> (i & 63)) & 1ull); };
+    std::vector<int32_t> hold((size_t)F.I64 * 2, -1);
+    for (int i = 0; i < I; ++i)
+      if (!(cnt[i] == 0 || cnt[i] > 2 || (cnt[i] == 2 && is_out(i))))
+        for (int k = 0; k < 2; ++k) hold[(size_t)2 * i + k] = who[(size_t)i * CAP + k];
+    HIP_TRY(h->upload(hold, &F.holder2));
+    if (h->hyper) {  // ... every holder of an index (up to FWH_MAXH), and whether it is open
+      std::vector<uint16_t> hn((size_t)F.I64 * 8, 0);
+      for (int i = 0; i < I; ++i) {
+        for (int k = 0; k < std::min(cnt[i], (int32_t)FWH_MAXH); ++k) hn[(size_t)8 * i + 1 + k] = (uint16_t)who[(size_t)i * CAP + k];
+        if (cnt[i] >= 1 && cnt[i] <= FWH_MAXH) hn[(size_t)8 * i] = (uint16_t)(cnt[i] | ((is_out(i) || cnt[i] == 1) ? 0x8000 : 0));
+      }
+      HIP_TRY(h->upload(hn, &F.holdern));
+    }
+    HIP_TRY(h->alloc(&F.slowstat, 4));
+    HIP_TRY(hipMemset(F.slowstat, 0, 32));
+    h->fw_wave_capable = true;
+#ifdef TNCO_PROFILE  // (the stage counters live in the single re-slice kernel)
+    h->fw_wave_capable = false;
+#endif
+    return TNCO_HIP_OK;
+  }
+
+  // 9b. finite width: FwParams and the per-replica arrays, the too-wide leaves, the form of the re-slice
+  // -- finite_width/greedy/optimizer.hpp:72-115
+  int fw_setup() {
+    h->fw = true;
+    FwParams& F = h->F;
+    F.width_f32 = d->width_dtype == TNCO_HIP_F32 ? 1 : 0;
+    F.max_width = F.width_f32 ? (double)(float)d->max_width : d->max_width;
+    F.log2d = uniform ? std::log2((double)dim_u) : 0.0;
+    F.log2np = d->sparse_mask ? std::log2((double)d->n_projs) : 0.0;
+    F.max_new_slices = (int64_t)std::min<uint64_t>(d->max_number_new_slices, (uint64_t)1 << 40);
+    F.I64 = 64 * L;
+    F.leaf_wide = 0;
+    if (!uniform) {
+      std::vector<double> l2((size_t)L * 64, 0.0);
+      for (int i = 0; i < I; ++i) l2[i] = std::log2((double)d->dims[i]);
+      HIP_TRY(h->upload(l2, &F.log2dims));
+    }
+    if (!F.width_f32) HIP_TRY(h->alloc(&F.width64, R * (int64_t)N));
+    HIP_TRY(h->alloc(&F.slices, R * 2 * (int64_t)L));
+    HIP_TRY(h->alloc(&F.scratch_i, R * fw_scratch_ints(N, F.I64)));
+    HIP_TRY(h->alloc(&F.scratch_d, R * 2 * (int64_t)N));
+    HIP_TRY(h->alloc(&F.status, R));
+    HIP_TRY(h->alloc(&F.nwide, R));
+    HIP_TRY(h->alloc(&F.nwfront, R));
+    HIP_TRY(hipMemset(F.status, 0, (size_t)R * 4));
+    if (int rc = fw_wave_tables()) return rc;
+    HIP_TRY(h->alloc(&F.fastflag, R));
+    HIP_TRY(hipMemset(F.fastflag, 0, (size_t)R * 4));
+    HIP_TRY(h->alloc(&F.delta_scr, R * 64));
+    // (word 0 of a replica = the change count of its last re-pricing, tnco_hip_diag_reslice_info: "none yet", whatever
+    //  a recycled block held)
+    HIP_TRY(hipMemset(F.delta_scr, 0xFF, (size_t)R * 64 * sizeof(*F.delta_scr)));
+    F.stack_cap = FW_LDSPOS;
+    if (const char* e = std::getenv("TNCO_HIP_FW_STACK")) F.stack_cap = std::max(0, std::min(FW_LDSPOS, std::atoi(e)));
+    if (d->skip_slices) HIP_TRY(h->upload(padded(d->skip_slices, 1, W), &F.skip));
+    // the leaf tensors wider than max_width (usually none: the walk of the re-slice skips the leaves then)
+    uint32_t* bits;
+    int32_t* any;
+    const int nb = (n + 31) / 32;
+    HIP_TRY(h->alloc(&bits, nb));
+    HIP_TRY(tmp->alloc(&any, 1));
+    HIP_TRY(hipMemsetAsync(bits, 0, (size_t)nb * 4, h->stream));
+    HIP_TRY(hipMemsetAsync(any, 0, 4, h->stream));
+    F.leaf_bits = bits;
+#define CALL_FWL(LL, KK) launch_fw_leaf_bits_lk<LL, KK>(h, bits, any)
+    DISPATCH_LK(h, CALL_FWL)
+#undef CALL_FWL
+    HIP_TRY(hipGetLastError());
+    int32_t a1 = 0;
+    HIP_TRY(hipMemcpyAsync(&a1, any, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h->sync_all());
+    F.leaf_wide = a1 ? 1 : 0;
+    if (F.leaf_wide) h->fw_wave_capable = false;  // (a too-wide leaf has no header to carry its width)
+    if (h->fw_wave_capable) {
+      h->fw_wave_on = true;
+      h->fw_wave_lanes = fw_lanes_per_mask();
+      // the roomier configuration (up to 1 023 too-wide tensors, 512 candidate legs) where its LDS fits; taken when the
+      // lean one leaves replicas behind for that reason (tnco_hip_run_fw), or from the start with TNCO_HIP_FW_BIG=1
+      h->fw_wave_big_ok = fww_lds_bytes(n, h->fw_wave_lanes, h->hyper, true) <= 64 * 1024;
+      const char* big_env = std::getenv("TNCO_HIP_FW_BIG");
+      h->fw_wave_big = h->fw_wave_big_ok && big_env && std::atoi(big_env) != 0;
+      h->set_wave_config();
+    }
+    F.fast_ok = h->fw_wave_on ? 1 : 0;
+    // 9c. WidthCache, initial slices (greedy, draws from the PRNG), CostCache(slices)
+    if (d->slices_stride != 0 && d->slices_stride < W) return fail(TNCO_HIP_EINVAL, "'slices_stride' is not valid.");
+    FwInitArgs a{};
+    if (d->slices) {  // rows of W words (one shared, or one per replica) -> rows of L words on the device, zero-padded
+      const int64_t rows = d->slices_stride == 0 ? 1 : R;
+      uint64_t* ds = nullptr;
+      HIP_TRY(tmp->alloc(&ds, rows * L));
+      HIP_TRY(hipMemset(ds, 0, (size_t)rows * L * 8));
+      HIP_TRY(copy_rows(ds, (int64_t)L, d->slices, std::max<int64_t>(d->slices_stride, W), (int64_t)W, rows, hipMemcpyHostToDevice));
+      a.slices_in = ds;
+      a.slices_in_stride = d->slices_stride == 0 ? 0 : L;
+    }
+    a.out_total = dtotal; a.out_sum = dsum;
+    launch_fw_init(h, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(h->sync_all());
+    if (int rc = read_costs(h->F.status, R)) return rc;
+    for (int64_t r = 0; r < R; ++r) {
+      if (status[r]) return fail(TNCO_HIP_ENOTIMPL, "finite width: candidate legs beyond the re-slice scratch (internal error).");
+      if (bad_log2(total[r]) || bad_log2(sum[r])) return fail(TNCO_HIP_EINVAL, "Precision is too low.");
+    }
+    return TNCO_HIP_OK;
+  }
+
+  // 10. The `min_ctree` / `min_slices` constructor arguments (optimize/optimizer.hpp:57-65,
+  // infinite_memory/optimizer.hpp:61-88, finite_width/greedy/optimizer.hpp:72-115): the best tree so far
+  // and its slices, min_total_cost = get_cost(min_ctree[, min_slices]), the checks of is_valid on them.
+  int restore_best() {
+    Params& P = h->P;
+    if (d->min_links) {
+      const int64_t ntrees = d->min_links_stride == 0 ? 1 : R;
+      if (d->min_links_stride != 0 && d->min_links_stride < 3 * (int64_t)N) return fail(TNCO_HIP_EINVAL, "'min_links_stride' is not valid.");
+      if (const char* e = check_trees_host(N, d->min_links, d->min_links_stride, ntrees)) return fail(TNCO_HIP_EINVAL, e);
+      int32_t* dmin = nullptr;
+      HIP_TRY(tmp->alloc(&dmin, ntrees * 3 * N));
+      HIP_TRY(copy_rows(dmin, 3 * (int64_t)N, d->min_links, d->min_links_stride, 3 * (int64_t)N, ntrees, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(set_minlinks_kernel, dim3((unsigned)R), dim3(64), 0, h->stream, P, dmin, d->min_links_stride == 0 ? (int64_t)0 : 3 * (int64_t)N);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(h->sync_all());
+    }
+    if (fw && d->min_slices) {  // row 1 of every replica's [2][L] slices record
+      const std::vector<uint64_t> rows = padded(d->min_slices, R, d->slices_stride);
+      HIP_TRY(hipMemcpy2D(h->F.slices + L, (size_t)2 * L * 8, rows.data(), (size_t)L * 8, (size_t)L * 8, (size_t)R, hipMemcpyHostToDevice));
+    }
+    const int64_t per = h->block_bytes() + (int64_t)n * 4 + (int64_t)N * 16 + 64;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(R, ((int64_t)1 << 30) / per));
+    uint8_t* tblk = nullptr; int32_t *tlpar = nullptr, *tscr = nullptr, *tbad = nullptr;
+    HIP_TRY(tmp->alloc(&tblk, chunk * h->block_bytes()));
+    HIP_TRY(tmp->alloc(&tlpar, chunk * n * LPS));
+    HIP_TRY(tmp->alloc(&tscr, chunk * 4 * N));
+    HIP_TRY(tmp->alloc(&tbad, chunk));
+    uint64_t* thy = nullptr;
+    if (h->hyper) HIP_TRY(tmp->alloc(&thy, chunk * (int64_t)(n - 1) * W));
+    std::vector<int32_t> hb((size_t)chunk);
+    for (int64_t r0 = 0; r0 < R; r0 += chunk) {
+      const int64_t cnt = std::min(chunk, R - r0);
+      BuildArgs a{};
+      a.hyper_tmp = thy;
+      a.out_blocks = tblk; a.out_lpar = tlpar; a.scratch = tscr;
+      a.out_total = dtotal; a.out_sum = dsum; a.out_status = dstatus; a.r0 = r0; a.count = cnt;
+      a.src_live = 0;
+      a.src_links = P.minlinks + r0 * (int64_t)N;
+      if (fw) { a.cost_slices = h->F.slices + L; a.cost_slices_stride = 2 * L; }
+      launch_build(h, a);
+      HIP_TRY(hipMemsetAsync(tbad, 0, (size_t)cnt * 4, h->stream));
+      if (fw) launch_fw_check(h, a, 1, 1e-5, tbad);
+      hipLaunchKernelGGL(restore_min_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, P.rs, r0, cnt, dsum);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(h->sync_all());
+      if (int rc = read_costs(dstatus, cnt)) return rc;
+      HIP_TRY(hipMemcpy(hb.data(), tbad, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+      for (int64_t q = 0; q < cnt; ++q) {
+        if (status[q]) return fail(TNCO_HIP_EINVAL, status_message(status[q]));
+        if (hb[q]) return fail(TNCO_HIP_EINVAL, "Width of the sliced minimum contraction is larger than 'max_width'.");
+        if (bad_log2(sum[q])) return fail(TNCO_HIP_EINVAL, "Precision is too low.");
+      }
+    }
+    return TNCO_HIP_OK;
+  }
+
+  // 11. the launch configuration: what choose_launch needs from the device, and what its answer needs on the device
+  int configure_launch() {
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, d->device));
+    int deg = 0;
+    for (int t = 0; t < n; ++t) {
+      int c = 0;
+      for (int w = 0; w < W; ++w) c += __builtin_popcountll(h->leafmask_w[(size_t)t * W + w]);
+      deg = std::max(deg, c);
+    }
+    LaunchIn in{n, I, W, h->K, h->log2l, h->P.log2d, R, fw, h->hyper, h->generic, d->min_links != nullptr, h->F.max_new_slices,
+                deg, prop.multiProcessorCount, device_lds_bytes(prop)};
+    // (run_seats > 0: the occupancy of the spread form.  Both forms are asked up front, also where the rule then needs one
+    //  only: a query is host arithmetic on a kernel of the handle's one inst_*.hip code object, loaded by either.)
+    if (!fw || h->F.max_new_slices == 0) { h->run_seats = 1; in.bpc_spread = run_blocks_per_cu(h); }
+    if (!fw) { h->run_seats = 0; in.bpc_full = run_blocks_per_cu(h); }
+    if (const char* e = std::getenv("TNCO_HIP_GROUPS")) in.groups_env = std::max(1, std::min((int)tnco_hip_ctx::MAX_GROUPS, std::atoi(e)));
+    LaunchCfg c = choose_launch(in);
+    if (c.lds_tree) {  // the leaves' legs for sa_lds_kernel: a table of them, or lists of 16-bit index positions
+      const int stride = c.lds_plan.leaf_stride;
+      const bool table = stride == 0;
+      std::vector<uint64_t> idx = table ? padded(h->leafmask_w.data(), n, W) : std::vector<uint64_t>((size_t)n * stride, ~0ull);
+      for (int t = 0; t < n && !table; ++t) {
+        int k = 0;
+        for (int p = 0; p < I; ++p)
+          if ((h->leafmask_w[(size_t)t * W + (p >> 6)] >> (p & 63)) & 1) {
+            uint64_t& q = idx[(size_t)t * stride + (k >> 2)];
+            q = (q & ~(0xFFFFull << (16 * (k & 3)))) | ((uint64_t)p << (16 * (k & 3)));
+            ++k;
+          }
+      }
+      HIP_TRY(h->upload(idx, &h->leaf_idx));
+      h->lds_plan = c.lds_plan;
+      if (lds_kernel_prepare(h, in.lds_bytes) != 0) {  // (the runtime refuses: the rule again, without that kernel)
+        in.lds_refused = true;
+        c = choose_launch(in);
+      }
+    }
+    static_cast<LaunchForm&>(*h) = c;
+    if (c.G > 1) {
+      for (int q = 0; q < c.G; ++q) {
+        HIP_TRY(tnco::StreamCache::get().take(&h->gstream[q], h->device));
+        HIP_TRY(hipEventCreateWithFlags(&h->gjoin[q], hipEventDisableTiming));
+      }
+      HIP_TRY(hipEventCreateWithFlags(&h->gfork, hipEventDisableTiming));
+      HIP_TRY(hipEventCreate(&h->region_a));
+      HIP_TRY(hipEventCreate(&h->region_b));
+      h->n_groups = c.G;
+    }
+    return TNCO_HIP_OK;
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -486,755 +1215,20 @@ uint64_t tnco_hip_diag_cached_bytes(void) { return (uint64_t)tnco::DevCache::get
 int tnco_hip_create(const tnco_hip_desc* d, tnco_hip_handle* out) {
   if (!d || !out) return fail(TNCO_HIP_EINVAL, "null argument.");
   *out = nullptr;
-  if (d->n_leaves < 2) return fail(TNCO_HIP_EINVAL, "Precision is too low.");  // total cost 0 -> log2 = -inf (optimizer.hpp:77-80)
-  if (d->n_inds < 0 || d->n_replicas <= 0) return fail(TNCO_HIP_EINVAL, "'n_inds' / 'n_replicas' are not valid.");
-  if (!d->leaf_masks || !d->links || (!d->seeds && !d->prng_states)) return fail(TNCO_HIP_EINVAL, "null input array.");
-  if (d->prng_states)
-    for (int64_t r = 0; r < d->n_replicas; ++r)
-      if (d->prng_states[r * 625 + 624] > 624) return fail(TNCO_HIP_EINVAL, "prng position out of range.");
-  if (d->cost_dtype != TNCO_HIP_F64 && d->cost_dtype != TNCO_HIP_F32)
-    return fail(TNCO_HIP_ENOTIMPL, "cost_type must be float64 or float32.");
-  const int n = d->n_leaves, N = 2 * n - 1, I = d->n_inds;
-  const int W = std::max(1, (I + 63) / 64);
-  if (W > 64) return fail(TNCO_HIP_ENOTIMPL, "more than 4096 indices are not supported yet.");
-  if (d->sparse_mask && d->n_projs == 0) return fail(TNCO_HIP_ERUNTIME, "'n_projs' must be a positive number.");
-  const int64_t R = d->n_replicas;
-
-  // dims (include/tnco/ctree.hpp:79-89, 121-135)
-  bool uniform = true;
-  uint64_t dim_u = d->dim_uniform;
-  if (d->dims) {
-    for (int i = 0; i < I; ++i)
-      if (d->dims[i] == 0) return fail(TNCO_HIP_EINVAL, "Dimensions must be positive numbers");
-    for (int i = 1; i < I; ++i) uniform &= d->dims[i] == d->dims[0];
-    if (I > 0 && uniform) dim_u = d->dims[0];
-    if (I == 0) uniform = false;
-  }
-  if (uniform && dim_u == 0) return fail(TNCO_HIP_EINVAL, "Dimensions must be positive numbers");
-
-  // finite width?  (tnco/app/app.py:866-870: finite max_width selects the finite_width optimizer)
-  const bool fw = std::isfinite(d->max_width);
-  if (fw) {
-    // (the greedy re-slice packs a too-wide count and a shuffled rank into 16 bits each, fw_kernels.h)
-    if (N > 65535) return fail(TNCO_HIP_ENOTIMPL, "finite width: more than 32768 tensors are not supported.");
-    if (d->max_width < 0) return fail(TNCO_HIP_ERUNTIME, "'max_width' must be a non-negative number.");
-    if (d->width_dtype != TNCO_HIP_F32 && d->width_dtype != TNCO_HIP_F64)
-      return fail(TNCO_HIP_ENOTIMPL, "finite width: width_type must be float32 or float64.");
-  }
-
-  // links already in device memory (tnco_hip_greedy_trees_device): validated there, never copied
-  bool links_on_device = false;
-  {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, d->links) == hipSuccess) {
-      if (at.type == hipMemoryTypeDevice) {
-        if (at.device != d->device) return fail(TNCO_HIP_EINVAL, "'links' are in the memory of another device.");
-        links_on_device = true;
-      }
-    } else {
-      (void)hipGetLastError();  // (plain host memory: not an error)
-    }
-  }
-  // host-side structural validation of every tree
-  if (!links_on_device) {
-    const int64_t ntrees = d->links_stride == 0 ? 1 : R;
-    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ntrees / 64 + 1, 16), std::thread::hardware_concurrency()));
-    std::vector<const char*> errs((size_t)nth, nullptr);
-    std::vector<std::thread> th;
-    for (int t = 0; t < nth; ++t)
-      th.emplace_back([&, t]() {
-        std::vector<int32_t> cp((size_t)N), cc((size_t)N);
-        for (int64_t r = t; r < ntrees && !errs[t]; r += nth) {
-          const int32_t* lk = d->links + r * d->links_stride;
-          errs[t] = tree_check(N, lk, lk + N, lk + 2 * (int64_t)N, cp, cc);
-        }
-      });
-    for (auto& x : th) x.join();
-    for (auto e : errs)
-      if (e) return fail(TNCO_HIP_EINVAL, e);
-  }
-
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (d->device < 0 || d->device >= ndev) return fail(TNCO_HIP_EINVAL, "'device' is not valid.");
-  HIP_TRY(hipSetDevice(d->device));
-
-  // TNCO_HIP_DEBUG: wall time of the steps of this call on stderr (the device drained at every mark)
-  const bool cdbg = std::getenv("TNCO_HIP_DEBUG") != nullptr;
-  auto c_t0 = std::chrono::steady_clock::now();
-  auto cmark = [&](const char* what) {
-    if (!cdbg) return;
-    (void)hipDeviceSynchronize();
-    const auto t = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "create: %-28s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(t - c_t0).count());
-    c_t0 = t;
-  };
-  tnco_hip_ctx* h = new tnco_hip_ctx();
-  struct Guard {
-    tnco_hip_ctx* h;
-    ~Guard() { delete h; }
-  } guard{h};
-  h->device = d->device;
-  HIP_TRY(tnco::StreamCache::get().take(&h->own_stream, d->device));
-  h->stream = h->own_stream;
-
-  choose_lanes(W, &h->log2l, &h->K);
-  h->L = 1 << h->log2l;
-  const int L = h->L * h->K;  // padded words per mask row in the shared tables
-
-  // hyper legs present?  (an index held by more than two of {leaves, output})
-  h->leafmask_w.assign(d->leaf_masks, d->leaf_masks + (size_t)n * W);
-  h->outmask_w.assign((size_t)W, 0);
-  if (d->output_mask) h->outmask_w.assign(d->output_mask, d->output_mask + W);
-  {
-    std::vector<int> cnt((size_t)W * 64, 0);
-    for (int t = 0; t < n; ++t)
-      for (int p = 0; p < W * 64; ++p) cnt[p] += (int)((h->leafmask_w[(size_t)t * W + (p >> 6)] >> (p & 63)) & 1);
-    bool hy = d->node_masks != nullptr;
-    for (int p = 0; p < W * 64; ++p) {
-      const int c = cnt[p] + (int)((h->outmask_w[p >> 6] >> (p & 63)) & 1);
-      if (c > 2) hy = true;
-      if (p >= I && cnt[p]) return fail(TNCO_HIP_EINVAL, "index position out of range in 'leaf_masks'.");
-    }
-    h->hyper = hy;
-  }
-  const bool f32 = d->cost_dtype == TNCO_HIP_F32;
-  const bool pow2u = uniform && (dim_u & (dim_u - 1)) == 0;
-  h->generic = !(pow2u && !d->sparse_mask && !f32);
-  // Few small trees: every replica's whole tree in LDS during a launch (sa_small.h) -- if all the replicas are resident
-  // at once (decided below, where the device is known).
-  h->small_tree = !fw && !h->hyper && !h->generic && W <= 2 && n >= 2 && n - 1 <= SMALL_MAX_INTERNAL && LPS == 1;
-#ifdef TNCO_NO_SMALL_TREE  // (the A/B library of tools/small_tree_ab.py: `make nosmall`)
-  h->small_tree = false;
-#endif
-  Params& P = h->P;
-  P.n = n; P.N = N; P.I = I; P.W = W; P.R = R;
-  P.BS = (32 + 8 * W + 31) / 32 * 32;
-  // (Networks with hyper-indices, round 5: hyper[p] = legs(p) & legs(c0) & legs(c1) is derived by the kernels from legs
-  //  they hold anyway, so no layout stores hyper legs: the blocks are those of a network without hyper-indices.)
-  // Blocks longer than a line are PACKED (a 224-byte block at 24 mask words straddles two or three 128-byte lines
-  // depending on where it starts): padding them to whole lines costs as many lines as it saves (round 3), and splitting
-  // them into headers + [partial copy | legs] records loses 5-30 % to the second dirty line per move (round 5).
-  P.WS = P.BS; P.WOFF = 32; P.RB = (int64_t)(n - 1) * P.BS;
-  if (fw) {  // split layout (sa_kernels.h, Params)
-    P.BS = 32;
-    P.WS = (8 * W + 63) / 64 * 64;
-    P.WOFF = ((n - 1) * 32 + 127) / 128 * 128;
-    P.RB = ((int64_t)P.WOFF + (int64_t)(n - 1) * P.WS + 127) / 128 * 128;
-  }
-  P.cpl = !fw && !h->hyper && !h->generic;  // (child-partial layout: sa_kernels.h)
-  P.f32 = f32; P.disable_shared = d->disable_shared_inds ? 1 : 0;
-  P.cost_mode = uniform ? (pow2u ? 0 : 1) : 2;
-  if (!uniform) {  // per-index dims, all powers of two: exponent classes only, no leg loop
-    bool allp2 = true;
-    for (int i = 0; i < I && allp2; ++i) {
-      const uint64_t x = d->dims[i];
-      allp2 = (x & (x - 1)) == 0;
-    }
-    if (allp2) P.cost_mode = 3;
-  }
-  P.log2d = 0;
-  if (pow2u) while ((1ull << P.log2d) < dim_u) ++P.log2d;
-  auto rc = [&](double x) { return f32 ? (double)(float)x : x; };
-  P.n_projs = d->sparse_mask ? rc((double)d->n_projs) : 0.0;
-
-  // Rotation log: one int32 per accepted move since the last re-base of the checkpoint.  When it is
-  // full, the next improvement re-bases the checkpoint on the current tree (a 16 N-byte copy) and the
-  // log starts again, so its size only sets how often that happens: 32 Ki entries (128 KB per replica)
-  // are one re-base per ~2000 sweeps of the 512-leaf benchmark (a re-base stalls its wavefront: with
-  // 16 Ki entries every replica took one in the 1200-sweep bench run, -3 %).  (Round 1 gave the log an eighth of
-  // the free HBM -- 34 GB at 65536 replicas -- and hipMalloc of it took 1.4 s of every create().)
-  {
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    free_b += tnco::DevCache::get().held();  // (what destroyed handles left for this one counts as free)
-    int64_t cap = (int64_t)(free_b / 8) / (R * 4);
-    cap = std::max<int64_t>(1024, std::min<int64_t>(cap, (int64_t)1 << 15));
-    if (const char* e = std::getenv("TNCO_HIP_JLOG_CAP")) cap = std::max<int64_t>(1, std::atoll(e));  // test knob
-    cap = (cap + 15) & ~(int64_t)15;  // the sweep kernel appends in whole 16-entry (64-byte) pieces
-    P.jcap = (int32_t)cap;
-  }
-
-  cmark("checks, stream");
-  HIP_TRY(h->alloc(&P.blocks, R * h->block_bytes()));
-  HIP_TRY(h->alloc(&P.lpar, R * n * LPS + 16));  // the sweep kernel reads 8 bytes at a leaf's record
-  HIP_TRY(h->alloc(&P.mt, R * 624));
-  HIP_TRY(h->alloc(&P.mtshadow, R * MT_SHADOW));
-  HIP_TRY(h->alloc(&P.rs, R));
-  HIP_TRY(h->alloc(&P.minlinks, R * N));
-  HIP_TRY(h->alloc(&P.jlog, R * (int64_t)P.jcap));
-
-  cmark("allocations");
-  // shared tables
-  {
-    std::vector<uint64_t> lm((size_t)n * L, 0), om((size_t)L, 0), sp((size_t)L, 0);
-    for (int t = 0; t < n; ++t)
-      for (int w = 0; w < W; ++w) lm[(size_t)t * L + w] = h->leafmask_w[(size_t)t * W + w];
-    for (int w = 0; w < W; ++w) om[w] = h->outmask_w[w];
-    uint64_t *dl, *dom;
-    HIP_TRY(h->alloc(&dl, (int64_t)n * L));
-    HIP_TRY(h->alloc(&dom, L));
-    HIP_TRY(hipMemcpy(dl, lm.data(), lm.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dom, om.data(), om.size() * 8, hipMemcpyHostToDevice));
-    P.leafmask = dl;
-    P.outmask = dom;
-    if (d->sparse_mask) {
-      for (int w = 0; w < W; ++w) sp[w] = d->sparse_mask[w];
-      uint64_t* dsp;
-      HIP_TRY(h->alloc(&dsp, L));
-      HIP_TRY(hipMemcpy(dsp, sp.data(), sp.size() * 8, hipMemcpyHostToDevice));
-      P.sparse = dsp;
-    }
-    if (P.cost_mode == 1) {
-      // std::pow(size_t, size_t) -> double pow, converted to cost_type (simple.hpp:45)
-      std::vector<double> tab((size_t)W * 64 + 1);
-      for (size_t k = 0; k < tab.size(); ++k) tab[k] = rc(std::pow((double)dim_u, (double)k));
-      double* dt;
-      HIP_TRY(h->alloc(&dt, (int64_t)tab.size()));
-      HIP_TRY(hipMemcpy(dt, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-      P.ctab = dt;
-    } else if (P.cost_mode == 3 || P.cost_mode == 2) {
-      // dims[p] = 2^a * odd: exponent classes (a = 1 .. max) for both modes; mode 2 also the odd parts
-      // (as cost_type) and the mask of the positions that have one (simple.hpp:51-53; sa_kernels.h seq_product)
-      int max_a = 0;
-      std::vector<int> av((size_t)I, 0);
-      std::vector<uint64_t> odd((size_t)I, 1);
-      for (int i = 0; i < I; ++i) {
-        uint64_t x = d->dims[i];
-        while ((x & 1ull) == 0) { x >>= 1; ++av[i]; }
-        odd[i] = x;
-        max_a = std::max(max_a, av[i]);
-      }
-      if (max_a > TABS_MAXCLS)
-        return fail(TNCO_HIP_ENOTIMPL, "an index dimension with a power-of-two part above 2^32 is not supported on the GPU path.");
-      std::vector<uint64_t> cls((size_t)std::max(max_a, 1) * L, 0);
-      for (int i = 0; i < I; ++i)
-        if (av[i] > 0) cls[(size_t)(av[i] - 1) * L + (i >> 6)] |= 1ull << (i & 63);
-      uint64_t* dc;
-      HIP_TRY(h->alloc(&dc, (int64_t)cls.size()));
-      HIP_TRY(hipMemcpy(dc, cls.data(), cls.size() * 8, hipMemcpyHostToDevice));
-      P.dimclass = dc;
-      P.n_dimclass = max_a;
-      if (P.cost_mode == 2) {
-        std::vector<double> dd((size_t)L * 64, 1.0);
-        std::vector<uint64_t> om((size_t)L, 0);
-        for (int i = 0; i < I; ++i) {
-          dd[i] = rc((double)odd[i]);
-          if (odd[i] != 1) om[i >> 6] |= 1ull << (i & 63);
-        }
-        double* dt;
-        uint64_t* dom2;
-        HIP_TRY(h->alloc(&dt, (int64_t)dd.size()));
-        HIP_TRY(hipMemcpy(dt, dd.data(), dd.size() * 8, hipMemcpyHostToDevice));
-        HIP_TRY(h->alloc(&dom2, (int64_t)om.size()));
-        HIP_TRY(hipMemcpy(dom2, om.data(), om.size() * 8, hipMemcpyHostToDevice));
-        P.dimsd = dt;
-        P.oddmask = dom2;
-        // a single odd part m (and exponents that fit the packed sum): chain of t factors as a table
-        uint64_t m1 = 0;
-        bool single = true;
-        for (int i = 0; i < I; ++i)
-          if (odd[i] != 1) {
-            if (m1 == 0) m1 = odd[i];
-            single &= odd[i] == m1;
-          }
-        if (single && m1 != 0 && (int64_t)max_a * W * 64 < (1 << 18) && !std::getenv("TNCO_HIP_NO_ODD_TABLE")) {
-          std::vector<double> tab((size_t)W * 64 + 1);
-          double c = 1.0;
-          const double md = rc((double)m1);
-          for (size_t t = 0; t < tab.size(); ++t) {
-            tab[t] = c;
-            c = rc(c * md);
-          }
-          double* dtab;
-          HIP_TRY(h->alloc(&dtab, (int64_t)tab.size()));
-          HIP_TRY(hipMemcpy(dtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-          P.ctab = dtab;
-          P.odd_single = 1;
-        }
-      }
-    }
-  }
-
-  cmark("shared tables");
-  TempBufs tmp;
-  // seeds -> MT state
-  if (d->prng_states) {  // the string-seed form of the constructor (optimize/optimizer.hpp:68-71): whole states
-    HIP_TRY(hipMemcpy2D(P.mt, (size_t)624 * 4, d->prng_states, (size_t)625 * 4, (size_t)624 * 4, (size_t)R, hipMemcpyHostToDevice));
-    std::vector<uint32_t> pos((size_t)R);
-    for (int64_t r = 0; r < R; ++r) pos[(size_t)r] = d->prng_states[r * 625 + 624];
-    uint32_t* dpos = nullptr;
-    HIP_TRY(tmp.alloc(&dpos, R));
-    HIP_TRY(hipMemcpy(dpos, pos.data(), (size_t)R * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(mt_pos_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, h->stream, P.rs, dpos, (const int64_t*)nullptr, R);
-    HIP_TRY(h->sync_all());
-  } else {
-    uint32_t* dseeds = nullptr;
-    HIP_TRY(tmp.alloc(&dseeds, R));
-    HIP_TRY(hipMemcpy(dseeds, d->seeds, (size_t)R * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(mt_seed_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, h->stream, P.mt, P.rs, dseeds, R);
-    HIP_TRY(h->sync_all());
-  }
-
-  cmark("generator states");
-  // links (+ optional explicit legs) -> node blocks and caches
-  {
-    const int64_t ntrees = d->links_stride == 0 ? 1 : R;
-    int32_t* dlinks = nullptr;
-    uint64_t* dmasks = nullptr;
-    double *dtotal = nullptr, *dsum = nullptr;
-    int32_t* dstatus = nullptr;
-    std::vector<double> total((size_t)R), sum((size_t)R);
-    std::vector<int32_t> status((size_t)R);
-    if (links_on_device && (d->links_stride == 0 || d->links_stride == 3 * (int64_t)N)) {
-      dlinks = const_cast<int32_t*>(d->links);  // (read only)
-    } else {
-      HIP_TRY(tmp.alloc(&dlinks, ntrees * 3 * N));
-      const hipMemcpyKind kind = links_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-      if (d->links_stride == 0 || d->links_stride == 3 * (int64_t)N)
-        HIP_TRY(hipMemcpy(dlinks, d->links, (size_t)ntrees * 3 * N * 4, kind));
-      else
-        HIP_TRY(hipMemcpy2D(dlinks, (size_t)3 * N * 4, d->links, (size_t)d->links_stride * 4, (size_t)3 * N * 4, (size_t)ntrees, kind));
-    }
-    if (links_on_device) {
-      int32_t* dcheck = nullptr;
-      HIP_TRY(tmp.alloc(&dcheck, ntrees));
-      hipLaunchKernelGGL(tree_check_kernel, dim3((unsigned)ntrees), dim3(64), 0, h->stream, (int32_t)N, dlinks, 3 * (int64_t)N, ntrees, dcheck);
-      HIP_TRY(hipGetLastError());
-      std::vector<int32_t> chk((size_t)ntrees);
-      HIP_TRY(hipMemcpyAsync(chk.data(), dcheck, (size_t)ntrees * 4, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h->sync_all());
-      for (int64_t r = 0; r < ntrees; ++r)
-        if (chk[r]) return fail(TNCO_HIP_EINVAL, tree_check_message(chk[r]));
-    }
-  cmark("trees checked");
-    const int64_t nmasks = d->node_masks ? (d->node_masks_stride == 0 ? 1 : R) : 0;
-    if (nmasks) {
-      HIP_TRY(tmp.alloc(&dmasks, nmasks * N * W));
-      if (d->node_masks_stride == 0 || d->node_masks_stride == (int64_t)N * W)
-        HIP_TRY(hipMemcpy(dmasks, d->node_masks, (size_t)nmasks * N * W * 8, hipMemcpyHostToDevice));
-      else
-        HIP_TRY(hipMemcpy2D(dmasks, (size_t)N * W * 8, d->node_masks, (size_t)d->node_masks_stride * 8, (size_t)N * W * 8, (size_t)nmasks, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(tmp.alloc(&dtotal, R));
-    HIP_TRY(tmp.alloc(&dsum, R));
-    HIP_TRY(tmp.alloc(&dstatus, R));
-    BuildArgs a{};
-    a.in_links = dlinks;
-    a.in_links_stride = d->links_stride == 0 ? 0 : 3 * (int64_t)N;
-    a.in_masks = dmasks;
-    a.in_masks_stride = (d->node_masks && d->node_masks_stride != 0) ? (int64_t)N * W : 0;
-    a.out_blocks = P.blocks; a.out_lpar = P.lpar;
-    a.scratch = reinterpret_cast<int32_t*>(P.minlinks);  // 16 B * N per replica = 4N int32
-    a.out_total = dtotal; a.out_sum = dsum; a.out_status = dstatus;
-    a.r0 = 0; a.count = R;
-    if (h->hyper && !d->node_masks) {  // (the second mask per node build_kernel derives the legs with)
-      uint64_t* dhy = nullptr;
-      HIP_TRY(tmp.alloc(&dhy, R * (int64_t)(n - 1) * W));
-      a.hyper_tmp = dhy;
-    }
-    launch_build(h, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(h->sync_all());
-  cmark("trees -> node records");
-    HIP_TRY(hipMemcpy(total.data(), dtotal, (size_t)R * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sum.data(), dsum, (size_t)R * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(status.data(), dstatus, (size_t)R * 4, hipMemcpyDeviceToHost));
-    hipLaunchKernelGGL(finish_init_kernel, dim3((unsigned)R), dim3(64), 0, h->stream, P, dsum, dtotal);
-    HIP_TRY(h->sync_all());
-    for (int64_t r = 0; r < R; ++r)
-      if (status[r]) return fail(TNCO_HIP_EINVAL, status_message(status[r]));
-    if (!fw)
-      for (int64_t r = 0; r < R; ++r)
-        if (bad_log2(total[r]) || bad_log2(sum[r])) return fail(TNCO_HIP_EINVAL, "Precision is too low.");
-  }
-
-  cmark("costs back, best trees");
-  // finite width: WidthCache, initial slices (greedy, draws from the PRNG), CostCache(slices)
-  // -- finite_width/greedy/optimizer.hpp:72-115
-  if (fw) {
-    h->fw = true;
-    FwParams& F = h->F;
-    F.width_f32 = d->width_dtype == TNCO_HIP_F32 ? 1 : 0;
-    F.max_width = F.width_f32 ? (double)(float)d->max_width : d->max_width;
-    F.log2d = uniform ? std::log2((double)dim_u) : 0.0;
-    F.log2np = d->sparse_mask ? std::log2((double)d->n_projs) : 0.0;
-    F.max_new_slices = (int64_t)std::min<uint64_t>(d->max_number_new_slices, (uint64_t)1 << 40);
-    F.I64 = 64 * L;
-    F.leaf_wide = 0;
-    if (!uniform) {
-      std::vector<double> l2((size_t)L * 64, 0.0);
-      for (int i = 0; i < I; ++i) l2[i] = std::log2((double)d->dims[i]);
-      double* dl2;
-      HIP_TRY(h->alloc(&dl2, (int64_t)l2.size()));
-      HIP_TRY(hipMemcpy(dl2, l2.data(), l2.size() * 8, hipMemcpyHostToDevice));
-      F.log2dims = dl2;
-    }
-    if (!F.width_f32) HIP_TRY(h->alloc(&F.width64, R * (int64_t)N));
-    HIP_TRY(h->alloc(&F.slices, R * 2 * (int64_t)L));
-    HIP_TRY(h->alloc(&F.scratch_i, R * fw_scratch_ints(N, F.I64)));
-    HIP_TRY(h->alloc(&F.scratch_d, R * 2 * (int64_t)N));
-    HIP_TRY(h->alloc(&F.status, R));
-    HIP_TRY(h->alloc(&F.nwide, R));
-    HIP_TRY(h->alloc(&F.nwfront, R));
-    HIP_TRY(hipMemset(F.status, 0, (size_t)R * 4));
-    // The re-slice of a replica in one wavefront, its cost cache RE-PRICED (fw_wave_kernel): costs must be powers of
-    // two (uniform dims 2^k, float64, no sparse legs), a leg of a subtree decidable from the holders it contains (no
-    // hyper-indices), the headers one array per replica (split layout), a lane's share of the nodes in registers.
-    // TNCO_HIP_FW_WAVE=0: never (tests compare the two forms), =1: always where possible (else: by the fall-backs).
-    const char* wave_env = std::getenv("TNCO_HIP_FW_WAVE");
-    const int lkw = F.I64 / 64, lanes_per_mask = lkw <= 16 ? 16 : (lkw <= 32 ? 32 : 64);
-    if (P.cost_mode == 0 && !P.f32 && d->sparse_mask == nullptr && P.BS == 32 && n >= 16 && n - 1 <= 64 * FWT_JMAX &&
-        F.I64 <= 4096 && fww_lds_bytes(n, lanes_per_mask, h->hyper) <= 64 * 1024 && !(wave_env && std::atoi(wave_env) == 0)) {
-      std::vector<int32_t> hold((size_t)F.I64 * 2, -1);
-      std::vector<int32_t> cnt((size_t)I, 0);
-      for (int t = 0; t < n; ++t)
-        for (int i = 0; i < I; ++i)
-          if ((d->leaf_masks[(size_t)t * W + (i >> 6)] >> (i & 63)) & 1ull) {
-            if (cnt[i] < 2) hold[(size_t)2 * i + cnt[i]] = t;
-            cnt[i] += 1;
-          }
-      for (int i = 0; i < I; ++i) {
-        const bool is_out = d->output_mask && ((d->output_mask[i >> 6] >> (i & 63)) & 1ull);
-        if (cnt[i] == 0 || cnt[i] > 2 || (cnt[i] == 2 && is_out)) hold[(size_t)2 * i] = hold[(size_t)2 * i + 1] = -1;
-      }
-      int32_t* dh;
-      HIP_TRY(h->alloc(&dh, (int64_t)hold.size()));
-      HIP_TRY(hipMemcpy(dh, hold.data(), hold.size() * 4, hipMemcpyHostToDevice));
-      F.holder2 = dh;
-      if (h->hyper) {  // ... every holder of an index (up to FWH_MAXH), and whether it is open
-        std::vector<uint16_t> hn((size_t)F.I64 * 8, 0);
-        std::fill(cnt.begin(), cnt.end(), 0);
-        for (int t = 0; t < n; ++t)
-          for (int i = 0; i < I; ++i)
-            if ((d->leaf_masks[(size_t)t * W + (i >> 6)] >> (i & 63)) & 1ull) {
-              if (cnt[i] < FWH_MAXH) hn[(size_t)8 * i + 1 + cnt[i]] = (uint16_t)t;
-              cnt[i] += 1;
-            }
-        for (int i = 0; i < I; ++i) {
-          const bool is_out = d->output_mask && ((d->output_mask[i >> 6] >> (i & 63)) & 1ull);
-          if (cnt[i] >= 1 && cnt[i] <= FWH_MAXH) hn[(size_t)8 * i] = (uint16_t)(cnt[i] | ((is_out || cnt[i] == 1) ? 0x8000 : 0));
-        }
-        uint16_t* dn;
-        HIP_TRY(h->alloc(&dn, (int64_t)hn.size()));
-        HIP_TRY(hipMemcpy(dn, hn.data(), hn.size() * 2, hipMemcpyHostToDevice));
-        F.holdern = dn;
-      }
-      HIP_TRY(h->alloc(&F.slowstat, 4));
-      HIP_TRY(hipMemset(F.slowstat, 0, 32));
-      h->fw_wave_capable = true;
-#ifdef TNCO_PROFILE  // (the stage counters live in the single re-slice kernel)
-      h->fw_wave_capable = false;
-#endif
-    }
-    HIP_TRY(h->alloc(&F.fastflag, R));
-    HIP_TRY(hipMemset(F.fastflag, 0, (size_t)R * 4));
-    HIP_TRY(h->alloc(&F.delta_scr, R * 64));
-    // (word 0 of a replica = the change count of its last re-pricing, tnco_hip_diag_reslice_info: "none yet", whatever
-    //  a recycled block held)
-    HIP_TRY(hipMemset(F.delta_scr, 0xFF, (size_t)R * 64 * sizeof(*F.delta_scr)));
-    F.stack_cap = FW_LDSPOS;
-    if (const char* e = std::getenv("TNCO_HIP_FW_STACK")) F.stack_cap = std::max(0, std::min(FW_LDSPOS, std::atoi(e)));
-    auto upload_mask = [&](const uint64_t* src, const uint64_t** dst) -> int {
-      std::vector<uint64_t> m((size_t)L, 0);
-      for (int w = 0; w < W; ++w) m[w] = src[w];
-      uint64_t* dm;
-      HIP_TRY(h->alloc(&dm, L));
-      HIP_TRY(hipMemcpy(dm, m.data(), m.size() * 8, hipMemcpyHostToDevice));
-      *dst = dm;
-      return TNCO_HIP_OK;
-    };
-    if (d->skip_slices)
-      if (int rc = upload_mask(d->skip_slices, &F.skip)) return rc;
-    {  // the leaf tensors wider than max_width (usually none: the walk of the re-slice skips the leaves then)
-      uint32_t* bits;
-      int32_t* any;
-      const int nb = (n + 31) / 32;
-      HIP_TRY(h->alloc(&bits, nb));
-      HIP_TRY(tmp.alloc(&any, 1));
-      HIP_TRY(hipMemsetAsync(bits, 0, (size_t)nb * 4, h->stream));
-      HIP_TRY(hipMemsetAsync(any, 0, 4, h->stream));
-      F.leaf_bits = bits;
-#define CALL_FWL(LL, KK) launch_fw_leaf_bits_lk<LL, KK>(h, bits, any)
-      DISPATCH_LK(h, CALL_FWL)
-#undef CALL_FWL
-      HIP_TRY(hipGetLastError());
-      int32_t a1 = 0;
-      HIP_TRY(hipMemcpyAsync(&a1, any, 4, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h->sync_all());
-      F.leaf_wide = a1 ? 1 : 0;
-      if (F.leaf_wide) h->fw_wave_capable = false;  // (a too-wide leaf has no header to carry its width)
-      if (h->fw_wave_capable) {
-        h->fw_wave_on = true;
-        h->fw_wave_lanes = lanes_per_mask;
-        // the roomier configuration (up to 1 023 too-wide tensors, 512 candidate legs) where its LDS fits; taken when the
-        // lean one leaves replicas behind for that reason (tnco_hip_run_fw), or from the start with TNCO_HIP_FW_BIG=1
-        h->fw_wave_big_ok = fww_lds_bytes(n, lanes_per_mask, h->hyper, true) <= 64 * 1024;
-        h->fw_wave_big = h->fw_wave_big_ok && std::getenv("TNCO_HIP_FW_BIG") && std::atoi(std::getenv("TNCO_HIP_FW_BIG")) != 0;
-        h->set_wave_config();
-      }
-      F.fast_ok = h->fw_wave_on ? 1 : 0;
-    }
-    // rows of W words (one shared, or one per replica) -> rows of L words on the device, zero-padded
-    auto upload_rows = [&](const uint64_t* src, uint64_t** dst) -> int {
-      const int64_t rows = d->slices_stride == 0 ? 1 : R;
-      uint64_t* dm;
-      HIP_TRY(tmp.alloc(&dm, rows * L));
-      HIP_TRY(hipMemset(dm, 0, (size_t)rows * L * 8));
-      HIP_TRY(hipMemcpy2D(dm, (size_t)L * 8, src, (size_t)std::max<int64_t>(d->slices_stride, W) * 8, (size_t)W * 8, (size_t)rows, hipMemcpyHostToDevice));
-      *dst = dm;
-      return TNCO_HIP_OK;
-    };
-    if (d->slices_stride != 0 && d->slices_stride < W) return fail(TNCO_HIP_EINVAL, "'slices_stride' is not valid.");
-    FwInitArgs a{};
-    if (d->slices) {
-      uint64_t* ds = nullptr;
-      if (int rc = upload_rows(d->slices, &ds)) return rc;
-      a.slices_in = ds;
-      a.slices_in_stride = d->slices_stride == 0 ? 0 : L;
-    }
-    double *dtotal = nullptr, *dsum = nullptr;
-    HIP_TRY(tmp.alloc(&dtotal, R));
-    HIP_TRY(tmp.alloc(&dsum, R));
-    a.out_total = dtotal; a.out_sum = dsum;
-    launch_fw_init(h, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(h->sync_all());
-    std::vector<double> total((size_t)R), sum((size_t)R);
-    std::vector<int32_t> st((size_t)R);
-    HIP_TRY(hipMemcpy(total.data(), dtotal, (size_t)R * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sum.data(), dsum, (size_t)R * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(st.data(), F.status, (size_t)R * 4, hipMemcpyDeviceToHost));
-    for (int64_t r = 0; r < R; ++r) {
-      if (st[r]) return fail(TNCO_HIP_ENOTIMPL, "finite width: candidate legs beyond the re-slice scratch (internal error).");
-      if (bad_log2(total[r]) || bad_log2(sum[r])) return fail(TNCO_HIP_EINVAL, "Precision is too low.");
-    }
-  }
-
-  // The `min_ctree` / `min_slices` constructor arguments (optimize/optimizer.hpp:57-65,
-  // infinite_memory/optimizer.hpp:61-88, finite_width/greedy/optimizer.hpp:72-115): the best tree so far
-  // and its slices, min_total_cost = get_cost(min_ctree[, min_slices]), the checks of is_valid on them.
-  if (d->min_links || (fw && d->min_slices)) {
-    const int64_t LKw = L;
-    if (d->min_links) {
-      const int64_t ntrees = d->min_links_stride == 0 ? 1 : R;
-      if (d->min_links_stride != 0 && d->min_links_stride < 3 * (int64_t)N) return fail(TNCO_HIP_EINVAL, "'min_links_stride' is not valid.");
-      {
-        std::vector<int32_t> cp((size_t)N), cc((size_t)N);
-        for (int64_t r = 0; r < ntrees; ++r) {
-          const int32_t* lk = d->min_links + r * d->min_links_stride;
-          if (const char* e = tree_check(N, lk, lk + N, lk + 2 * (int64_t)N, cp, cc)) return fail(TNCO_HIP_EINVAL, e);
-        }
-      }
-      int32_t* dmin = nullptr;
-      HIP_TRY(tmp.alloc(&dmin, ntrees * 3 * N));
-      if (d->min_links_stride == 0 || d->min_links_stride == 3 * (int64_t)N)
-        HIP_TRY(hipMemcpy(dmin, d->min_links, (size_t)ntrees * 3 * N * 4, hipMemcpyHostToDevice));
-      else
-        HIP_TRY(hipMemcpy2D(dmin, (size_t)3 * N * 4, d->min_links, (size_t)d->min_links_stride * 4, (size_t)3 * N * 4, (size_t)ntrees, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(set_minlinks_kernel, dim3((unsigned)R), dim3(64), 0, h->stream, P, dmin, d->min_links_stride == 0 ? (int64_t)0 : 3 * (int64_t)N);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(h->sync_all());
-      h->small_tree = false;  // (the LDS-resident kernel assumes the log starts at the checkpoint)
-    }
-    if (fw && d->min_slices) {  // row 1 of every replica's [2][L] slices record
-      std::vector<uint64_t> rows((size_t)R * LKw, 0);
-      for (int64_t r = 0; r < R; ++r)
-        for (int w = 0; w < W; ++w) rows[(size_t)r * LKw + w] = d->min_slices[r * d->slices_stride + w];
-      HIP_TRY(hipMemcpy2D(h->F.slices + LKw, (size_t)2 * LKw * 8, rows.data(), (size_t)LKw * 8, (size_t)LKw * 8, (size_t)R, hipMemcpyHostToDevice));
-    }
-    const int64_t per = h->block_bytes() + (int64_t)n * 4 + (int64_t)N * 16 + 64;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(R, ((int64_t)1 << 30) / per));
-    uint8_t* tblk = nullptr; int32_t *tlpar = nullptr, *tscr = nullptr, *tstat = nullptr, *tbad = nullptr;
-    double *ttot = nullptr, *tsum = nullptr;
-    HIP_TRY(tmp.alloc(&tblk, chunk * h->block_bytes()));
-    HIP_TRY(tmp.alloc(&tlpar, chunk * n * LPS));
-    HIP_TRY(tmp.alloc(&tscr, chunk * 4 * N));
-    HIP_TRY(tmp.alloc(&tstat, chunk));
-    HIP_TRY(tmp.alloc(&tbad, chunk));
-    HIP_TRY(tmp.alloc(&ttot, chunk));
-    HIP_TRY(tmp.alloc(&tsum, chunk));
-    uint64_t* thy = nullptr;
-    if (h->hyper) HIP_TRY(tmp.alloc(&thy, chunk * (int64_t)(n - 1) * W));
-    std::vector<int32_t> hs((size_t)chunk), hb((size_t)chunk);
-    std::vector<double> hsum((size_t)chunk);
-    for (int64_t r0 = 0; r0 < R; r0 += chunk) {
-      const int64_t cnt = std::min(chunk, R - r0);
-      BuildArgs a{};
-      a.hyper_tmp = thy;
-      a.out_blocks = tblk; a.out_lpar = tlpar; a.scratch = tscr;
-      a.out_total = ttot; a.out_sum = tsum; a.out_status = tstat; a.r0 = r0; a.count = cnt;
-      a.src_live = 0;
-      a.src_links = P.minlinks + r0 * (int64_t)N;
-      if (fw) { a.cost_slices = h->F.slices + LKw; a.cost_slices_stride = 2 * LKw; }
-      launch_build(h, a);
-      HIP_TRY(hipMemsetAsync(tbad, 0, (size_t)cnt * 4, h->stream));
-      if (fw) launch_fw_check(h, a, 1, 1e-5, tbad);
-      hipLaunchKernelGGL(restore_min_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, P.rs, r0, cnt, tsum);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(h->sync_all());
-      HIP_TRY(hipMemcpy(hs.data(), tstat, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(hb.data(), tbad, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(hsum.data(), tsum, (size_t)cnt * 8, hipMemcpyDeviceToHost));
-      for (int64_t q = 0; q < cnt; ++q) {
-        if (hs[q]) return fail(TNCO_HIP_EINVAL, status_message(hs[q]));
-        if (hb[q]) return fail(TNCO_HIP_EINVAL, "Width of the sliced minimum contraction is larger than 'max_width'.");
-        if (bad_log2(hsum[q])) return fail(TNCO_HIP_EINVAL, "Precision is too low.");
-      }
-    }
-  }
-
-  // Infinite memory: more blocks than resident ones (65536 replicas at 512 leaves: 1024 blocks, 768 resident)?  Then
-  // every step is split over two streams (host_ctx.h, tnco_hip_run), unless the last round is nearly full anyway.
-  // TNCO_HIP_GROUPS=1..4 overrides.
-  {
-    const int64_t nblocks = (R + (SWT / h->L) - 1) / (SWT / h->L);
-    int G = 1;
-    if (!fw) {
-      hipDeviceProp_t prop;
-      HIP_TRY(hipGetDeviceProperties(&prop, d->device));
-      // The LDS-resident kernel is bound by the instruction stream of one wavefront per SIMD (16 replicas; 1.35 us per
-      // move whatever the load), the HBM kernel by memory latency per replica (3.7 us) until ~50 000 replicas saturate it
-      // at 8-9e9 move-evals/s.  Up to 64 leaves a CU holds 64 LDS-resident replicas and the LDS kernel wins at every
-      // replica count (1.07e10 from 16 384 replicas on); beyond, a CU holds 32 and it wins (x2.3 ... x1.15) while two
-      // rounds of its blocks hold the replicas (profiles/r05_small_tree_ab.txt).
-#ifndef TNCO_SMALL_TREE_ALWAYS  // (the other A/B library of tools/small_tree_ab.py: `make allsmall`)
-      if (h->small_tree && n - 1 > 63 && R > 2 * (int64_t)small_replicas_per_cu(n - 1) * prop.multiProcessorCount) h->small_tree = false;
-#endif
-      if (h->small_tree) {
-        // A batch that leaves wavefront slots empty gets fewer replicas per wavefront (the spare lane groups shadow them,
-        // sa_small.h): an iteration then runs only the sections its few replicas are in -- 8.5-8.8e5 move-evals/s per
-        // replica at one per wavefront (up to 1024 replicas of <= 64 leaves), 7.5e5 at four, 6.7e5 at sixteen.
-        const int64_t slots = (int64_t)small_replicas_per_cu(n - 1) / (SMALL_TPB / 4) * prop.multiProcessorCount;
-        while (h->small_seats > 1 && (R + h->small_seats / 2 - 1) / (h->small_seats / 2) <= slots) h->small_seats /= 2;
-      }
-      // Any other tree of the fast cost path whose replicas fit the CUs' LDS at once (the latency regime of the larger
-      // networks: 512 leaves of 12 words are 58 KiB, two per CU, up to 512 replicas): sa_lds_kernel.
-      if (!h->small_tree && !h->generic && LPS == 1 && !d->min_links && n >= 2 && h->log2l == 2 && I <= 65535 &&
-          N <= 65534 && (int64_t)P.log2d * 64 * W <= 65535) {
-        int deg = 0;  // index positions per leaf at most
-        for (int t = 0; t < n; ++t) {
-          int c = 0;
-          for (int w = 0; w < W; ++w) c += __builtin_popcountll(h->leafmask_w[(size_t)t * W + w]);
-          deg = std::max(deg, c);
-        }
-        const bool table = (int64_t)n * 32 * h->K <= 16384;  // the leaf legs themselves, [n][4 K] words
-        if (table || deg <= 32) {
-          const int stride = table ? 0 : std::max(1, (deg + 3) / 4);
-          std::vector<uint64_t> idx(table ? (size_t)n * 4 * h->K : (size_t)n * stride, table ? 0ull : ~0ull);
-          for (int t = 0; t < n; ++t) {
-            if (table) {
-              for (int w = 0; w < W; ++w) idx[(size_t)t * 4 * h->K + w] = h->leafmask_w[(size_t)t * W + w];
-              continue;
-            }
-            int c = 0;
-            for (int p = 0; p < I; ++p)
-              if ((h->leafmask_w[(size_t)t * W + (p >> 6)] >> (p & 63)) & 1) {
-                uint64_t& q = idx[(size_t)t * stride + (c >> 2)];
-                q = (q & ~(0xFFFFull << (16 * (c & 3)))) | ((uint64_t)p << (16 * (c & 3)));
-                ++c;
-              }
-          }
-          const int K = h->K, ni = n - 1;
-          LdsPlan pl{};
-          pl.leaf_stride = stride;
-          pl.leaf_words = (int)idx.size();
-          pl.seat0 = (pl.leaf_words * 8 + 15) / 16 * 16;
-          pl.o_part = 8 * ni;
-          pl.o_legs = 16 * ni;
-          pl.o_lpar = pl.o_legs + 32 * K * ni;
-          pl.o_ring = pl.o_lpar + (2 * n + 7) / 8 * 8;
-          pl.o_jb = pl.o_ring + 64 * 4;
-          pl.seat_stride = (pl.o_jb + 16 * 4 + 15) / 16 * 16;
-          // Four blocks (wavefronts of up to 16 replicas) per CU -- one per SIMD -- if they hold the batch, else two, else
-          // one, and as few replicas per wavefront as spread the batch over all of them, the other lane groups shadowing
-          // (sa_small.h): per-replica move-evals/s at 128 leaves, four blocks / one block per CU: 1024 replicas 7.8 / 7.1e5,
-          // 2048: 7.4 / 6.6e5; 256 leaves, 1024: 7.6 / 7.0e5.  (Before the shadows it was the other way round: few active
-          // lanes per CU.)  x1.6 ... x2.8 the HBM kernel per replica, so a second round of blocks would lose.
-          int best = 0;
-          for (int b = 4; b >= 1 && best == 0; b >>= 1) {
-            const int seats = std::min(SMALL_TPB / 4, (device_lds_bytes(prop) / b - pl.seat0) / pl.seat_stride);
-            if (seats > 0 && (R <= (int64_t)b * seats * prop.multiProcessorCount || b == 1)) { best = b * seats; pl.seats = seats; pl.blocks_per_cu = b; }
-          }
-#ifdef TNCO_NO_SMALL_TREE
-          best = 0;
-#endif
-#ifdef TNCO_SMALL_TREE_ALWAYS
-          const bool fits = best > 0;
-#else
-          const bool fits = best > 0 && R <= (int64_t)best * prop.multiProcessorCount;
-#endif
-          if (fits) {
-            const int64_t waves = (int64_t)pl.blocks_per_cu * prop.multiProcessorCount;
-            pl.seats = (int)std::max<int64_t>(1, std::min<int64_t>(pl.seats, (R + waves - 1) / waves));
-            pl.total = pl.seat0 + pl.seats * pl.seat_stride;
-            HIP_TRY(h->alloc(&h->leaf_idx, (int64_t)idx.size()));
-            HIP_TRY(hipMemcpy(h->leaf_idx, idx.data(), idx.size() * 8, hipMemcpyHostToDevice));
-            h->lds_plan = pl;
-            h->lds_tree = lds_kernel_prepare(h, device_lds_bytes(prop)) == 0;  // (else: the HBM kernel below)
-          }
-        }
-      }
-      // A batch that leaves wavefront slots of the HBM kernel empty is spread (sa_sweep.h, SPREAD): fewer replicas per
-      // wavefront, the other lane groups shadowing them.  Per-replica move-evals/s at 512 leaves, 16 (full) / 1 / 2 / 4 / 8
-      // replicas per wavefront: 1024 replicas 3.2 / 5.3 / 4.4 / 3.8 / 3.5e5; 4096: 3.2 / - / 3.7 / 3.8 / 3.5; 8192: 3.2 / - /
-      // 2.1 / 3.2 / 3.5; 16384: 3.2 / - / - / 1.8 / 2.9 -- one replica per wavefront while that takes at most two thirds of
-      // the slots, else as few as leave ONE wavefront per SIMD (two half-filled ones lose to a full one).
-      if (!h->small_tree && !h->lds_tree) {
-        const int full = 64 / h->L;
-        h->run_seats = 1;  // (the occupancy of the spread form)
-        const int64_t wslots = (int64_t)run_blocks_per_cu(h) * prop.multiProcessorCount * (SWT / 64);
-        int seats = 1;
-        if (3 * R > 2 * wslots)
-          while (seats < full && (R + seats - 1) / seats > 4 * (int64_t)prop.multiProcessorCount) seats *= 2;
-        h->run_seats = (wslots > 0 && seats < full) ? seats : 0;
-#ifdef TNCO_NO_SMALL_TREE  // (the A/B library: the batch as it was, 64 / L replicas per wavefront)
-        h->run_seats = 0;
-#endif
-      }
-      h->run_slots = run_blocks_per_cu(h) * prop.multiProcessorCount;
-      if (h->run_slots > 0 && nblocks > h->run_slots) {
-        const double rounds = (double)nblocks / (double)h->run_slots, part = rounds - std::floor(rounds);
-        // (also with whole rounds: the blocks of a round do not end together -- the general cost path at two
-        //  wavefronts per SIMD, 1024 blocks on 512 slots: +2 ... +8 % on two streams, profiles/r03_other_configs.md)
-        if (part < 0.85) G = 2;
-      }
-    } else if (h->F.max_new_slices == 0) {
-      // finite width, a batch that leaves wavefront slots of the staged moves empty: their SPREAD form, by the rule of the
-      // infinite-memory kernel above -- the moves are 90 % of such a step (full wavefronts: 5.2 microseconds per move and
-      // replica); otherwise two halves on two streams whatever the rounds -- what overlaps then are KERNELS of different
-      // bounds (the moves wait on memory requests, get_slices and the tree kernel on LDS / instruction latency)
-      hipDeviceProp_t prop;
-      HIP_TRY(hipGetDeviceProperties(&prop, d->device));
-      const int full = 64 / h->L;
-      h->run_seats = 1;  // (the occupancy of the spread form)
-      const int64_t wslots = (int64_t)run_blocks_per_cu(h) * prop.multiProcessorCount * (SWT / 64);
-      int seats = 1;
-      if (3 * R > 2 * wslots)
-        while (seats < full && (R + seats - 1) / seats > 4 * (int64_t)prop.multiProcessorCount) seats *= 2;
-      h->run_seats = (wslots > 0 && seats < full) ? seats : 0;
-#ifdef TNCO_NO_SMALL_TREE
-      h->run_seats = 0;
-#endif
-      if (h->run_seats == 0 && nblocks >= 64) G = 2;
-    }
-    if (const char* e = std::getenv("TNCO_HIP_GROUPS")) G = std::max(1, std::min((int)tnco_hip_ctx::MAX_GROUPS, std::atoi(e)));
-    if (h->small_tree || h->lds_tree || h->run_seats > 0 || nblocks < 2 * G) G = 1;
-    if (G > 1) {
-      for (int q = 0; q < G; ++q) {
-        HIP_TRY(tnco::StreamCache::get().take(&h->gstream[q], h->device));
-        HIP_TRY(hipEventCreateWithFlags(&h->gjoin[q], hipEventDisableTiming));
-      }
-      HIP_TRY(hipEventCreateWithFlags(&h->gfork, hipEventDisableTiming));
-      HIP_TRY(hipEventCreate(&h->region_a));
-      HIP_TRY(hipEventCreate(&h->region_b));
-      h->n_groups = G;
-    }
-  }
-
-  cmark("the rest (finite width, min trees)");
-  guard.h = nullptr;
-  *out = h;
+  Create c{d};
+  if (int rc = c.check_input()) return rc;
+  if (int rc = c.open_handle()) return rc;
+  if (int rc = c.upload_tables()) return rc;
+  c.cmark("shared tables");
+  if (int rc = c.build_replicas()) return rc;
+  c.cmark("costs back, best trees");
+  if (c.fw)
+    if (int rc = c.fw_setup()) return rc;
+  if (d->min_links || (c.fw && d->min_slices))
+    if (int rc = c.restore_best()) return rc;
+  if (int rc = c.configure_launch()) return rc;
+  c.cmark("the rest (finite width, min trees)");
+  *out = c.owner.release();
   return TNCO_HIP_OK;
 }
 
