@@ -33,6 +33,12 @@ def assert_replica_equal(gpu, r, o, check_min=True):
     assert np.array_equal(gpu.prng_state(r), o.prng_state()), f"replica {r} prng"
 
 
+def expected_validate(verdicts):
+    """(n_bad, first_bad) as validate() reports them, from per-replica verdicts (true: not valid)."""
+    bad = [r for r, v in enumerate(verdicts) if v]
+    return (len(bad), bad[0] if bad else -1)
+
+
 @contextlib.contextmanager
 def padded_rows(core, **extra):
     """While active, tnco_hip_create gets the per-replica rows named in `extra` (links, node_masks, min_links, slices --

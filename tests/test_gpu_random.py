@@ -25,9 +25,7 @@ def core():
     return c
 
 
-def _expected_validate(verdicts):
-    bad = [r for r, v in enumerate(verdicts) if v]
-    return (len(bad), bad[0] if bad else -1)
+_expected_validate = H.expected_validate
 
 
 def _problem(seed, n, k, dims_kind, n_sparse):
