@@ -112,7 +112,7 @@ static __global__ __launch_bounds__(256) void gather_slices_kernel(const uint64_
 // log read 64 entries at a time by the whole wavefront); which = 0: the current tree from the node
 // blocks.  Then the post-order of include/tnco/utils.hpp:34-51 and get_contraction (:53-71) from the
 // same LDS copy.  Work area per replica (LDS when it fits, else global scratch): left[N] right[N]
-// parent[N] stack[N] visited[N].
+// parent[N] stack[N] visited[N].  (The same replay: materialize_min_kernel, sa_kernels.h; replay_rotations, tnco_hip.hip.)
 template <bool IN_LDS>
 static __global__ __launch_bounds__(64) void gather_trees_kernel(const Params P, const int64_t* ids, const int which,
                                                                  int32_t* out_links, int32_t* out_con,

@@ -30,7 +30,16 @@ struct LaunchForm {
   int run_slots = 0;  // resident blocks of the sweep kernel on this device
 };
 
-struct tnco_hip_ctx : LaunchForm {
+// in which form a tnco_hip_run_fw call re-slices, and what decides it: the rule (tnco_hip.hip, choose_fw_form) maps these to these
+struct FwFormState {
+  bool fw_wave_on = false;
+  bool fw_wave_big = false, fw_wave_big_ok = false;  // ... its roomier configuration (fw_kernels.h, BIG): in use / its LDS fits
+  int64_t fw_wave_reslices = 0;  // re-slices launched in that form since the count was read
+  int fw_single_calls = 0;        // calls in the other mode since the last probe
+  int fw_probe_wait = 4;          // ... before the next probe (doubles after a probe that failed)
+};
+
+struct tnco_hip_ctx : LaunchForm, FwFormState {
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
@@ -40,20 +49,16 @@ struct tnco_hip_ctx : LaunchForm {
   bool fw = false;  // finite-width optimizer
   // the re-slice of a replica in one wavefront (fw_wave_kernel, the cost cache re-priced) pays while few replicas fall
   // back to the full rebuild: the form of a tnco_hip_run_fw call follows the fall-backs counted during the previous one
-  bool fw_wave_capable = false, fw_wave_on = false;
+  bool fw_wave_capable = false;  // (fw_wave_on and the counters behind it: FwFormState)
   int fw_wave_maxnp = 128;  // ... candidate legs of one tensor it handles (test knob TNCO_HIP_FWS_MAXNP)
   int fw_wave_cap = 0;      // ... too-wide tensors whose legs it keeps in LDS (fww_cap; test knob TNCO_HIP_FWS_CAP)
   int fw_wave_lanes = 16;   // ... lanes per leg mask
-  bool fw_wave_big = false, fw_wave_big_ok = false;  // ... its roomier configuration (fw_kernels.h, BIG): in use / its LDS fits
   void set_wave_config() {
     fw_wave_cap = tnco::fww_cap(P.n, fw_wave_lanes, hyper, fw_wave_big);
     if (const char* e = std::getenv("TNCO_HIP_FWS_CAP")) fw_wave_cap = std::max(0, std::min(fw_wave_cap, std::atoi(e))) & ~7;  // (test knob: legs from memory)
     fw_wave_maxnp = fw_wave_big ? 512 : 128;
     if (const char* e = std::getenv("TNCO_HIP_FWS_MAXNP")) fw_wave_maxnp = std::max(0, std::min(fw_wave_maxnp, std::atoi(e)));
   }
-  int64_t fw_wave_reslices = 0;  // re-slices launched in that form since the count was read
-  int fw_single_calls = 0;        // calls in the other mode since the last probe
-  int fw_probe_wait = 4;          // ... before the next probe (doubles after a probe that failed)
   // tnco_hip_diag_fw_stats: [0] replica re-slices launched in the re-pricing form, [1] of those left to the full rebuild,
   // [2..4] why (FwParams::slowstat[1..3]), [5] replica re-slices launched in the walk + full-rebuild form
   int64_t fw_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -96,10 +101,8 @@ struct tnco_hip_ctx : LaunchForm {
   // the device's fall-back counters since the last look -> fw_stats; *slow = their total (may be NULL)
   hipError_t collect_fw_stats(unsigned long long* slow, unsigned long long* slow_wide = nullptr) {
     unsigned long long c[4] = {0, 0, 0, 0};
-    hipError_t e = hipMemcpy(c, F.slowstat, 32, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(F.slowstat, 0, 32, stream);
-    if (e != hipSuccess) return e;
+    if (hipError_t e = hipMemcpy(c, F.slowstat, 32, hipMemcpyDeviceToHost); e != hipSuccess) return e;
+    if (hipError_t e = hipMemsetAsync(F.slowstat, 0, 32, stream); e != hipSuccess) return e;
     for (int i = 0; i < 4; ++i) fw_stats[1 + i] += (int64_t)c[i];
     fw_slow_pending += c[0];
     fw_slow_wide_pending += c[1];
@@ -133,6 +136,11 @@ struct tnco_hip_ctx : LaunchForm {
     if (e == hipSuccess) *dst = p;
     return e;
   }
+  // ... and back, on the handle's stream (the caller waits: sync_all); nothing for an output the caller did not ask for
+  template <typename T>
+  hipError_t download(T* dst, const T* src, int64_t count) {
+    return dst ? hipMemcpyAsync(dst, src, (size_t)count * sizeof(T), hipMemcpyDeviceToHost, stream) : hipSuccess;
+  }
   // HIP events on the handle's stream around one kernel launch
   template <typename F>
   hipError_t timed(int kind, F&& launch) {
@@ -141,19 +149,14 @@ struct tnco_hip_ctx : LaunchForm {
       ev = free_events.back();
       free_events.pop_back();
     } else {
-      hipError_t e = hipEventCreate(&ev.a);
-      if (e != hipSuccess) return e;
-      e = hipEventCreate(&ev.b);
-      if (e != hipSuccess) return e;
+      if (hipError_t e = hipEventCreate(&ev.a); e != hipSuccess) return e;
+      if (hipError_t e = hipEventCreate(&ev.b); e != hipSuccess) return e;
     }
     ev.kind = kind;
-    hipError_t e = hipEventRecord(ev.a, stream);
-    if (e != hipSuccess) return e;
+    if (hipError_t e = hipEventRecord(ev.a, stream); e != hipSuccess) return e;
     launch();
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    e = hipEventRecord(ev.b, stream);
-    if (e != hipSuccess) return e;
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    if (hipError_t e = hipEventRecord(ev.b, stream); e != hipSuccess) return e;
     pending.push_back(ev);
     if (pending.size() > 1024) resolve_events();
     return hipSuccess;
@@ -162,24 +165,36 @@ struct tnco_hip_ctx : LaunchForm {
   hipError_t join_groups() {
     if (!groups_dirty) return hipSuccess;
     for (int q = 0; q < n_groups; ++q) {
-      hipError_t e = hipEventRecord(gjoin[q], gstream[q]);
-      if (e != hipSuccess) return e;
-      e = hipStreamWaitEvent(stream, gjoin[q], 0);
-      if (e != hipSuccess) return e;
+      if (hipError_t e = hipEventRecord(gjoin[q], gstream[q]); e != hipSuccess) return e;
+      if (hipError_t e = hipStreamWaitEvent(stream, gjoin[q], 0); e != hipSuccess) return e;
     }
     groups_dirty = false;
     if (region_open) {  // the device time of the grouped steps ends here
-      hipError_t e = hipEventRecord(region_b, stream);
-      if (e != hipSuccess) return e;
+      if (hipError_t e = hipEventRecord(region_b, stream); e != hipSuccess) return e;
       region_b_set = true;
     }
     return hipSuccess;
   }
   hipError_t sync_all() {
-    hipError_t e = join_groups();
-    if (e != hipSuccess) return e;
+    if (hipError_t e = join_groups(); e != hipSuccess) return e;
     return hipStreamSynchronize(stream);
   }
+  // the device current and the handle idle: how every entry point but the run calls begins
+  hipError_t make_idle() {
+    hipError_t e = hipSetDevice(device);
+    return e == hipSuccess ? sync_all() : e;
+  }
+  // The group streams take up after what the main stream holds (this call's betas); the timing region opens here.
+  hipError_t fork_groups() {
+    if (region_open && region_b_set) close_region();  // (a join since the last call: that stretch is complete)
+    if (hipError_t e = region_open ? hipSuccess : hipEventRecord(region_a, stream); e != hipSuccess) return e;
+    region_open = true;
+    hipError_t e = hipEventRecord(gfork, stream);
+    for (int q = 0; q < n_groups && e == hipSuccess; ++q) e = hipStreamWaitEvent(gstream[q], gfork, 0);
+    return e;
+  }
+  // per-launch work counters are 32-bit: at most (n_leaves - 1) moves per sweep
+  int64_t max_steps() const { return std::max<int64_t>(1, (int64_t)0xF0000000u / std::max(1, P.n)); }
   // closes the timing region of grouped steps (called with the groups joined and the stream idle)
   void close_region() {
     if (!region_open) return;

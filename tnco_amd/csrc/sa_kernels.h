@@ -884,7 +884,7 @@ __global__ __launch_bounds__(256) void compare_kernel(const Params P, const Buil
 
 // Best tree of every replica = checkpoint + rotations jlog[0, jmin): apply
 // Tree::swap_with_nn (include/tnco/tree.hpp:141-192) to a copy.  One thread per replica
-// (diagnostic path: validate()).
+// (diagnostic path: validate()).  The same replay: gather_trees_kernel (extract_kernels.h), replay_rotations (tnco_hip.hip).
 static __global__ void materialize_min_kernel(const Params P, Links* out, int64_t r0, int64_t count) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= count) return;

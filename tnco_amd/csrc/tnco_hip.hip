@@ -39,8 +39,7 @@ int fail(int code, const std::string& msg) {
       return fail(TNCO_HIP_ERUNTIME, std::string(#expr) + ": " + hipGetErrorString(e_));   \
   } while (0)
 
-// frees a set of temporary device buffers on scope exit
-// scratch of one call, from / back to the cache of device blocks (dev_cache.h)
+// scratch of one call, from / back to the cache of device blocks (dev_cache.h): freed on scope exit
 struct TempBufs {
   std::vector<void*> ptrs;
   std::vector<size_t> sizes;
@@ -1190,6 +1189,240 @@ struct Create {
   }
 };
 
+// ---- the run and read-back entry points: the bodies they share -------------------------------------------------------
+int check_replica(tnco_hip_handle h, int64_t r) {
+  return r < 0 || r >= h->P.R ? fail(TNCO_HIP_EINVAL, "'replica' out of range.") : TNCO_HIP_OK;
+}
+// ... every entry of a list (no list -- replicas 0 .. k-1 -- has nothing to check)
+int check_ids(tnco_hip_handle h, int64_t k, const int64_t* ids) {
+  for (int64_t i = 0; ids && i < k; ++i)
+    if (int rc = check_replica(h, ids[i])) return rc;
+  return TNCO_HIP_OK;
+}
+
+// what tnco_hip_run and tnco_hip_run_fw refuse alike (a step_offset is tnco_hip_run_fw's: it shares the betas' message)
+int check_run_args(int prob_kind, const double* betas, int64_t n_steps, int64_t step_offset = 0) {
+  if (prob_kind < 0 || prob_kind > 2) return fail(TNCO_HIP_EINVAL, "'prob_kind' is not valid.");
+  if (n_steps < 0 || (n_steps > 0 && !betas) || step_offset < 0) return fail(TNCO_HIP_EINVAL, "'betas' is not valid.");
+  return TNCO_HIP_OK;
+}
+
+// Where the nodes of replica r live (sa_kernels.h, Params): the headers of the internal nodes BS bytes apart from
+// blocks + r RB, their legs at WOFF + WS per node, the parents of the leaves in lpar, LPS words apart; a leaf has no
+// header, and its legs are the problem's (leafmask_w).  Every place as a byte offset into a downloaded image of the
+// block and as a device address; tnco_hip_get_tree, tnco_hip_get_caches and tnco_hip_diag_poke find a field here only.
+struct BlockLayout {
+  const tnco_hip_ctx* h;
+  const Params& P;
+  const int64_t r;  // the replica
+  BlockLayout(const tnco_hip_ctx* h_, int64_t r_) : h(h_), P(h_->P), r(r_) {}
+  bool internal(int64_t x) const { return x >= P.n && x < P.N; }
+  size_t header_off(int64_t x) const { return (size_t)(x - P.n) * P.BS; }
+  size_t legs_off(int64_t x) const { return (size_t)P.WOFF + (size_t)(x - P.n) * P.WS; }
+  uint8_t* block_at() const { return P.blocks + r * P.RB; }
+  uint8_t* header_at(int64_t x) const { return block_at() + header_off(x); }
+  uint8_t* legs_at(int64_t x) const { return block_at() + legs_off(x); }
+  int32_t* leaf_parent_at(int64_t i) const { return P.lpar + (r * P.n + i) * LPS; }
+  // ... and read from an image of the block
+  hipError_t fetch(std::vector<uint8_t>& img) const { return hipMemcpy(img.data(), block_at(), img.size(), hipMemcpyDeviceToHost); }  // (img: RB bytes)
+  NodeRec node(const std::vector<uint8_t>& img, int x) const {  // (a leaf, no node: zeros)
+    NodeRec hd{};
+    if (x >= P.n) std::memcpy(&hd, img.data() + header_off(x), sizeof(hd));
+    return hd;
+  }
+  const uint64_t* legs(const std::vector<uint8_t>& img, int x) const {
+    return x < P.n ? h->leafmask_w.data() + (size_t)x * P.W : reinterpret_cast<const uint64_t*>(img.data() + legs_off(x));
+  }
+};
+
+// The rotations log[0, count) applied to a tree, Tree::swap_with_nn each: best tree = checkpoint + jlog[0, jmin).
+// (The same replay on the device: materialize_min_kernel, sa_kernels.h, and gather_trees_kernel, extract_kernels.h.)
+void replay_rotations(Links* t, const int32_t* log, int count) {
+  for (int j = 0; j < count; ++j) {
+    const int D = log[j], B = t[D].parent, A = t[B].parent;
+    const int C = (t[A].left == B) ? t[A].right : t[A].left;
+    if (t[A].left != C) t[A].right = D; else t[A].left = D;
+    if (t[B].left != D) t[B].right = C; else t[B].left = C;
+    t[C].parent = B;
+    t[D].parent = A;
+  }
+}
+
+// finish the lazily generated block sequence so the 624 words are what libstdc++ holds after _M_gen_rand()
+// (random.tcc:396-430); word 624: the position
+void finish_mt_block(uint32_t* words625, const ReplicaState& rs) {
+  if (rs.mti < 624)
+    for (int k = rs.mtw; k < 624; ++k) {
+      const uint32_t y = (words625[k] & 0x80000000u) | (words625[(k + 1) % 624] & 0x7fffffffu);
+      words625[k] = words625[(k + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+    }
+  words625[624] = (uint32_t)rs.mti;
+}
+
+// fetch_rs, then a fold over the replica records: the tnco_hip_diag_* counters
+template <typename F>
+int fold_rs(tnco_hip_handle h, F&& f) {
+  std::vector<ReplicaState> rs;
+  if (int rc = fetch_rs(h, rs)) return rc;
+  for (size_t r = 0; r < rs.size(); ++r) f(r, rs[r]);
+  return TNCO_HIP_OK;
+}
+
+// sweeps up to and including the first re-slicing one (launch_fw_run: (offset + k) % every == 0); 0: no sweep re-slices
+int64_t first_reslice_prefix(int64_t offset, int64_t every) {
+  if (every <= 0) return 0;
+  const int64_t rem = offset % every;
+  return (rem == 0 ? 0 : every - rem) + 1;
+}
+
+// The wavefront form or the general one (walk + full rebuild) for this call?  The first wins while fewer than
+// ~3 % of the replicas fall back to the full rebuild (more changed indices than it re-prices: random initial
+// trees early in a schedule) -- a fall-back costs the full rebuild on top.  The previous call's kernels are
+// complete here: its fall-backs are counted, or, after 4, 8, 16 ... calls in the other form, this call probes again.
+// Plain arithmetic: the handle's form state (host_ctx.h, FwFormState) and the fall-backs of the `fw_wave_reslices`
+// re-slices counted since the last call (`slow`, of which `slow_wide` for too-wide tensors) to the state after the
+// decision.  env_big: TNCO_HIP_FW_BIG is set; env_wave: TNCO_HIP_FW_WAVE, -1 if not set.
+FwFormState choose_fw_form(FwFormState s, int64_t R, unsigned long long slow, unsigned long long slow_wide, bool env_big, int env_wave) {
+  if (s.fw_wave_reslices > 0) {
+    const bool was_on = s.fw_wave_on;
+    // (a replica that falls back costs its wavefront of fw_reslice_b_kernel the full rebuild -- sixteen replicas in lock
+    //  step: at 3 % every third wavefront.  The roomier configuration serves networks whose full rebuild is tens of times
+    //  the wavefront form: it keeps winning further out.)
+    const double lim = (s.fw_wave_big ? 0.10 : 0.03) * (double)s.fw_wave_reslices * (double)R;
+    if (!s.fw_wave_big && s.fw_wave_big_ok && (double)slow_wide >= lim && !env_big) {
+      // too many / too leggy too-wide tensors for the lean configuration: the roomier one before giving up the form
+      s.fw_wave_big = true;
+      slow -= slow_wide;
+    }
+    s.fw_wave_on = (double)slow < lim;
+    s.fw_probe_wait = s.fw_wave_on ? 4 : (was_on && s.fw_single_calls == 0 ? std::min(64, 2 * s.fw_probe_wait) : s.fw_probe_wait);
+    s.fw_wave_reslices = 0;
+    s.fw_single_calls = 0;
+  } else if (!s.fw_wave_on && ++s.fw_single_calls >= s.fw_probe_wait) {
+    s.fw_wave_on = true;
+  }
+  if (env_wave >= 0) s.fw_wave_on = env_wave != 0;  // (test knob: pin the form)
+  return s;
+}
+
+// tnco_hip_run_fw, step by step (the handle idle): the form of the call from the previous call's fall-backs ...
+int fw_choose_form(tnco_hip_handle h) {
+  if (!h->fw_wave_capable) return TNCO_HIP_OK;
+  unsigned long long slow = 0, slow_wide = 0;
+  if (h->fw_wave_reslices > 0) HIP_TRY(h->collect_fw_stats(&slow, &slow_wide));
+  const bool was_big = h->fw_wave_big;
+  const char* e = std::getenv("TNCO_HIP_FW_WAVE");
+  static_cast<FwFormState&>(*h) = choose_fw_form(*h, h->P.R, slow, slow_wide, std::getenv("TNCO_HIP_FW_BIG") != nullptr, e ? std::atoi(e) != 0 : -1);
+  if (h->fw_wave_big != was_big) h->set_wave_config();
+  h->F.fast_ok = h->fw_wave_on ? 1 : 0;
+  return TNCO_HIP_OK;
+}
+// ... its betas on the device ...
+int fw_stage_betas(tnco_hip_handle h, const double* betas, int64_t n_steps) {
+  if (n_steps > h->betas_cap) {
+    if (h->d_betas) (void)hipFree(h->d_betas);
+    h->d_betas = nullptr;
+    h->betas_cap = 0;
+    HIP_TRY(tnco::dev_malloc((void**)&h->d_betas, (size_t)n_steps * 8));
+    h->betas_cap = n_steps;
+  }
+  HIP_TRY(hipMemcpyAsync(h->d_betas, betas, (size_t)n_steps * 8, hipMemcpyHostToDevice, h->stream));
+  return TNCO_HIP_OK;
+}
+// ... and the launches
+int fw_launch(tnco_hip_handle h, int prob_kind, int64_t n_steps, int64_t update_slices_every, int64_t step_offset) {
+  const int64_t max_steps = h->max_steps();
+  if (h->n_groups > 1) HIP_TRY(h->fork_groups());  // the halves of the batch on streams of their own (GroupView), after this call's betas
+  for (int64_t s0 = 0; s0 < n_steps; s0 += max_steps) {
+    const int64_t cnt = std::min(max_steps, n_steps - s0);
+    if (h->n_groups > 1) {
+      const int64_t R = h->P.R;
+      for (int q = 0; q < h->n_groups; ++q) {
+        const int64_t r0 = R * q / h->n_groups, r1 = R * (q + 1) / h->n_groups;
+        GroupView gv(h, r0, r1 - r0, h->gstream[q]);
+        HIP_TRY(launch_fw_run(h, h->d_betas + s0, cnt, prob_kind, step_offset + s0, update_slices_every, q == 0));
+      }
+      h->groups_dirty = true;
+    } else {
+      HIP_TRY(launch_fw_run(h, h->d_betas + s0, cnt, prob_kind, step_offset + s0, update_slices_every));
+    }
+    h->launches++;
+  }
+  if (h->n_groups > 1) h->region_calls++;
+  if (h->pending.size() > 256) h->resolve_events();
+  return TNCO_HIP_OK;
+}
+
+// One field of tnco_hip_diag_poke: which bytes of the device it is, and how they read as the 64 bits the caller sees.
+struct PokeField {
+  uint8_t* at = nullptr;  // the field's device address
+  size_t nb = 8;          // ... and its size
+  bool as_float = false;  // a float32 field: `value` / `previous` are the bits of the double of the same value
+  uint64_t decode(const void* raw) const {
+    uint64_t v = 0;
+    float f;
+    int32_t x;
+    if (nb == 8) std::memcpy(&v, raw, 8);
+    else if (as_float) { std::memcpy(&f, raw, 4); const double d = (double)f; std::memcpy(&v, &d, 8); }
+    else { std::memcpy(&x, raw, 4); v = (uint64_t)(int64_t)x; }  // (a parent: -1 at the root)
+    return v;
+  }
+  void encode(uint64_t value, void* raw) const {
+    double d;
+    if (nb == 8) std::memcpy(raw, &value, 8);
+    else if (as_float) { std::memcpy(&d, &value, 8); const float f = (float)d; std::memcpy(raw, &f, 4); }
+    else { const uint32_t x = (uint32_t)value; std::memcpy(raw, &x, 4); }
+  }
+};
+// ... found, or refused: what the validator's kernels walk stays walkable (see tnco_hip_diag_poke).  What a field needs is
+// checked in one order for all of them: the layout that stores it, an internal `node`, a mask `word`.
+int poke_field(tnco_hip_handle h, int64_t r, int field, int64_t node, int64_t word, int write, uint64_t value, PokeField* f) {
+  const Params& P = h->P;
+  const int64_t n = P.n, N = P.N, LK = (int64_t)h->L * h->K;
+  const BlockLayout B(h, r);
+  const bool internal = B.internal(node);
+  uint8_t* const hdr = internal ? B.header_at(node) : nullptr;
+  uint8_t* const rs = reinterpret_cast<uint8_t*>(P.rs + r);
+  const bool own_cost = field == TNCO_HIP_POKE_CCOST || field == TNCO_HIP_POKE_PARTIAL;
+  const bool child_cost = field == TNCO_HIP_POKE_PARTIAL_LEFT || field == TNCO_HIP_POKE_PARTIAL_RIGHT;
+  const bool slices = field == TNCO_HIP_POKE_SLICES || field == TNCO_HIP_POKE_MIN_SLICES;
+  const bool in_header = own_cost || child_cost || field == TNCO_HIP_POKE_SWAP_CHILDREN || field == TNCO_HIP_POKE_WIDTH;
+  if (own_cost && P.cpl) return fail(TNCO_HIP_EINVAL, "the child-partial layout stores neither 'ccost' nor 'partial' of a node.");
+  if (child_cost && !P.cpl) return fail(TNCO_HIP_EINVAL, "only the child-partial layout stores the partial costs of a node's children.");
+  if (field == TNCO_HIP_POKE_TOTAL && !P.cpl)
+    return fail(TNCO_HIP_EINVAL, "only the child-partial layout keeps the root's partial cost in the replica record.");
+  if ((slices || field == TNCO_HIP_POKE_WIDTH) && !h->fw) return fail(TNCO_HIP_EINVAL, "handle was created without 'max_width'.");
+  if ((in_header || field == TNCO_HIP_POKE_LEGS) && !internal) return fail(TNCO_HIP_EINVAL, "'node' is not an internal node.");
+  if ((slices || field == TNCO_HIP_POKE_LEGS) && (word < 0 || word >= P.W)) return fail(TNCO_HIP_EINVAL, "'word' out of range.");
+  switch (field) {
+    case TNCO_HIP_POKE_PARENT:
+      if (node < 0 || node >= N) return fail(TNCO_HIP_EINVAL, "'node' out of range.");
+      f->at = internal ? hdr + offsetof(NodeRec, parent) : reinterpret_cast<uint8_t*>(B.leaf_parent_at(node));
+      f->nb = 4;
+      // (the root's own null parent is what a test puts back there)
+      if (write && !((int64_t)value >= n && (int64_t)value < N) && !(node == N - 1 && (int64_t)value == -1))
+        return fail(TNCO_HIP_EINVAL, "a parent must be an internal node.");
+      break;
+    case TNCO_HIP_POKE_SWAP_CHILDREN: f->at = hdr + offsetof(NodeRec, left); break;
+    case TNCO_HIP_POKE_LEGS: f->at = B.legs_at(node) + word * 8; break;
+    case TNCO_HIP_POKE_CCOST: f->at = hdr + offsetof(NodeRec, ccost); break;
+    case TNCO_HIP_POKE_PARTIAL: f->at = hdr + offsetof(NodeRec, partial); break;
+    case TNCO_HIP_POKE_PARTIAL_LEFT: f->at = hdr + offsetof(NodeRec, pleft); break;
+    case TNCO_HIP_POKE_PARTIAL_RIGHT: f->at = hdr + offsetof(NodeRec, pright); break;
+    case TNCO_HIP_POKE_TOTAL: f->at = rs + offsetof(ReplicaState, total); break;
+    case TNCO_HIP_POKE_MIN_COST: f->at = rs + offsetof(ReplicaState, min_cost); break;
+    case TNCO_HIP_POKE_JMIN: f->at = rs + offsetof(ReplicaState, jmin); f->nb = 4; break;
+    case TNCO_HIP_POKE_SLICES: f->at = reinterpret_cast<uint8_t*>(h->F.slices + r * 2 * LK + word); break;
+    case TNCO_HIP_POKE_MIN_SLICES: f->at = reinterpret_cast<uint8_t*>(h->F.slices + r * 2 * LK + LK + word); break;
+    case TNCO_HIP_POKE_WIDTH:
+      if (h->F.width_f32) { f->at = hdr + offsetof(NodeRec, pad); f->nb = 4; f->as_float = true; }
+      else f->at = reinterpret_cast<uint8_t*>(h->F.width64 + r * N + node);
+      break;
+    default: return fail(TNCO_HIP_EINVAL, "unknown 'field'.");
+  }
+  return TNCO_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1234,8 +1467,7 @@ int tnco_hip_create(const tnco_hip_desc* d, tnco_hip_handle* out) {
 
 int tnco_hip_set_stream(tnco_hip_handle h, void* s) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   h->close_region();
   h->stream = s ? (hipStream_t)s : h->own_stream;  // (a grouped handle forks from / joins into this stream)
   return TNCO_HIP_OK;
@@ -1243,15 +1475,13 @@ int tnco_hip_set_stream(tnco_hip_handle h, void* s) {
 
 int tnco_hip_sync(tnco_hip_handle h) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   return fw_runtime_status(h);
 }
 
 int tnco_hip_run(tnco_hip_handle h, int prob_kind, const double* betas, int64_t n_steps) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
-  if (prob_kind < 0 || prob_kind > 2) return fail(TNCO_HIP_EINVAL, "'prob_kind' is not valid.");
-  if (n_steps < 0 || (n_steps > 0 && !betas)) return fail(TNCO_HIP_EINVAL, "'betas' is not valid.");
+  if (int rc = check_run_args(prob_kind, betas, n_steps)) return rc;
   if (n_steps == 0) return TNCO_HIP_OK;
   if (h->fw) return fail(TNCO_HIP_EINVAL, "handle was created with 'max_width': use tnco_hip_run_fw.");
   HIP_TRY(hipSetDevice(h->device));
@@ -1276,8 +1506,7 @@ int tnco_hip_run(tnco_hip_handle h, int prob_kind, const double* betas, int64_t 
   std::memcpy(h->beta_pin + h->ring_pos, betas, (size_t)n_steps * 8);
   HIP_TRY(hipMemcpyAsync(dbetas, h->beta_pin + h->ring_pos, (size_t)n_steps * 8, hipMemcpyHostToDevice, h->stream));
   h->ring_pos += n_steps;
-  // per-launch work counters are 32-bit: at most (n_leaves - 1) moves per sweep
-  const int64_t max_steps = std::max<int64_t>(1, (int64_t)0xF0000000u / std::max(1, h->P.n));
+  const int64_t max_steps = h->max_steps();
   if (h->n_groups <= 1) {
     for (int64_t s0 = 0; s0 < n_steps; s0 += max_steps) {
       const int64_t cnt = std::min(max_steps, n_steps - s0);
@@ -1291,16 +1520,10 @@ int tnco_hip_run(tnco_hip_handle h, int prob_kind, const double* betas, int64_t 
   // stream) and -- stream order -- after its own previous launch, NOT after the other groups'.  A long call
   // is cut into slices of ~100 sweeps so that the streams interleave inside one call as they do from call
   // to call (a replica's sweeps stay in order: one stream per group).
-  if (h->region_open && h->region_b_set) h->close_region();  // (a join since the last call: that stretch is complete)
-  if (!h->region_open) {
-    HIP_TRY(hipEventRecord(h->region_a, h->stream));
-    h->region_open = true;
-  }
-  HIP_TRY(hipEventRecord(h->gfork, h->stream));
+  HIP_TRY(h->fork_groups());
   const int gpb = SWT / h->L;
   const int nblocks = (int)((h->P.R + gpb - 1) / gpb);
   const int64_t n_slices = std::max<int64_t>(1, std::max<int64_t>((n_steps + max_steps - 1) / max_steps, (n_steps + 50) / 100));
-  for (int q = 0; q < h->n_groups; ++q) HIP_TRY(hipStreamWaitEvent(h->gstream[q], h->gfork, 0));
   for (int64_t i = 0; i < n_slices; ++i) {
     const int64_t s0 = n_steps * i / n_slices, s1 = n_steps * (i + 1) / n_slices;
     if (s1 == s0) continue;
@@ -1320,8 +1543,7 @@ int tnco_hip_run_fw(tnco_hip_handle h, int prob_kind, const double* betas, int64
                     int64_t update_slices_every, int64_t step_offset) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
   if (!h->fw) return fail(TNCO_HIP_EINVAL, "handle was created without 'max_width': use tnco_hip_run.");
-  if (prob_kind < 0 || prob_kind > 2) return fail(TNCO_HIP_EINVAL, "'prob_kind' is not valid.");
-  if (n_steps < 0 || (n_steps > 0 && !betas) || step_offset < 0) return fail(TNCO_HIP_EINVAL, "'betas' is not valid.");
+  if (int rc = check_run_args(prob_kind, betas, n_steps, step_offset)) return rc;
   if (n_steps == 0) return TNCO_HIP_OK;
   if (h->fw_wave_capable && !h->fw_probed) {
     // A handle's first call: the sweeps up to its first re-slice as a call of their own, so that the rest already
@@ -1329,92 +1551,24 @@ int tnco_hip_run_fw(tnco_hip_handle h, int prob_kind, const double* betas, int64
     // of its width spent its whole first call -- ten re-slices -- in the lean configuration, every replica falling
     // back: 9.4e7 move-evals/s against 1.2e9 afterwards).
     h->fw_probed = true;
-    int64_t first = 0;  // sweeps up to and including the first re-slicing one (launch_fw_run: (offset + k) % every == 0)
-    if (update_slices_every > 0) {
-      const int64_t rem = step_offset % update_slices_every;
-      first = (rem == 0 ? 0 : update_slices_every - rem) + 1;
-    }
+    const int64_t first = first_reslice_prefix(step_offset, update_slices_every);
     if (first > 0 && n_steps > first) {
       if (int rc = tnco_hip_run_fw(h, prob_kind, betas, first, update_slices_every, step_offset)) return rc;
       return tnco_hip_run_fw(h, prob_kind, betas + first, n_steps - first, update_slices_every, step_offset + first);
     }
   }
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
-  if (h->fw_wave_capable) {
-    // The wavefront form or the general one (walk + full rebuild) for this call?  The first wins while fewer than
-    // ~3 % of the replicas fall back to the full rebuild (more changed indices than it re-prices: random initial
-    // trees early in a schedule) -- a fall-back costs the full rebuild on top.  The previous call's kernels are
-    // complete here: its fall-backs are counted, or, after 4, 8, 16 ... calls in the other form, this call probes again.
-    if (h->fw_wave_reslices > 0) {
-      unsigned long long slow = 0, slow_wide = 0;
-      HIP_TRY(h->collect_fw_stats(&slow, &slow_wide));
-      const bool was_on = h->fw_wave_on;
-      // (a replica that falls back costs its wavefront of fw_reslice_b_kernel the full rebuild -- sixteen replicas in lock
-      //  step: at 3 % every third wavefront.  The roomier configuration serves networks whose full rebuild is tens of times
-      //  the wavefront form: it keeps winning further out.)
-      const double lim = (h->fw_wave_big ? 0.10 : 0.03) * (double)h->fw_wave_reslices * (double)h->P.R;
-      if (!h->fw_wave_big && h->fw_wave_big_ok && (double)slow_wide >= lim && !std::getenv("TNCO_HIP_FW_BIG")) {
-        // too many / too leggy too-wide tensors for the lean configuration: the roomier one before giving up the form
-        h->fw_wave_big = true;
-        h->set_wave_config();
-        slow -= slow_wide;
-      }
-      h->fw_wave_on = (double)slow < lim;
-      h->fw_probe_wait = h->fw_wave_on ? 4 : (was_on && h->fw_single_calls == 0 ? std::min(64, 2 * h->fw_probe_wait) : h->fw_probe_wait);
-      h->fw_wave_reslices = 0;
-      h->fw_single_calls = 0;
-    } else if (!h->fw_wave_on && ++h->fw_single_calls >= h->fw_probe_wait) {
-      h->fw_wave_on = true;
-    }
-    if (const char* e = std::getenv("TNCO_HIP_FW_WAVE")) h->fw_wave_on = std::atoi(e) != 0;  // (test knob: pin the form)
-    h->F.fast_ok = h->fw_wave_on ? 1 : 0;
-  }
-  if (n_steps > h->betas_cap) {
-    if (h->d_betas) (void)hipFree(h->d_betas);
-    h->d_betas = nullptr;
-    h->betas_cap = 0;
-    HIP_TRY(tnco::dev_malloc((void**)&h->d_betas, (size_t)n_steps * 8));
-    h->betas_cap = n_steps;
-  }
-  HIP_TRY(hipMemcpyAsync(h->d_betas, betas, (size_t)n_steps * 8, hipMemcpyHostToDevice, h->stream));
-  const int64_t max_steps = std::max<int64_t>(1, (int64_t)0xF0000000u / std::max(1, h->P.n));
-  if (h->n_groups > 1) {  // the halves of the batch on streams of their own (GroupView), after this call's betas
-    if (h->region_open && h->region_b_set) h->close_region();
-    if (!h->region_open) {
-      HIP_TRY(hipEventRecord(h->region_a, h->stream));
-      h->region_open = true;
-    }
-    HIP_TRY(hipEventRecord(h->gfork, h->stream));
-    for (int q = 0; q < h->n_groups; ++q) HIP_TRY(hipStreamWaitEvent(h->gstream[q], h->gfork, 0));
-  }
-  for (int64_t s0 = 0; s0 < n_steps; s0 += max_steps) {
-    const int64_t cnt = std::min(max_steps, n_steps - s0);
-    if (h->n_groups > 1) {
-      const int64_t R = h->P.R;
-      for (int q = 0; q < h->n_groups; ++q) {
-        const int64_t r0 = R * q / h->n_groups, r1 = R * (q + 1) / h->n_groups;
-        GroupView gv(h, r0, r1 - r0, h->gstream[q]);
-        HIP_TRY(launch_fw_run(h, h->d_betas + s0, cnt, prob_kind, step_offset + s0, update_slices_every, q == 0));
-      }
-      h->groups_dirty = true;
-    } else {
-      HIP_TRY(launch_fw_run(h, h->d_betas + s0, cnt, prob_kind, step_offset + s0, update_slices_every));
-    }
-    h->launches++;
-  }
-  if (h->n_groups > 1) h->region_calls++;
-  if (h->pending.size() > 256) h->resolve_events();
-  return TNCO_HIP_OK;
+  HIP_TRY(h->make_idle());
+  if (int rc = fw_choose_form(h)) return rc;
+  if (int rc = fw_stage_betas(h, betas, n_steps)) return rc;
+  return fw_launch(h, prob_kind, n_steps, update_slices_every, step_offset);
 }
 
 int tnco_hip_get_slices(tnco_hip_handle h, int64_t r, uint64_t* slices, uint64_t* min_slices) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
   if (!h->fw) return fail(TNCO_HIP_EINVAL, "handle was created without 'max_width'.");
-  if (r < 0 || r >= h->P.R) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
+  if (int rc = check_replica(h, r)) return rc;
   const int LK = h->L * h->K, W = h->P.W;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   std::vector<uint64_t> s((size_t)2 * LK);
   HIP_TRY(hipMemcpy(s.data(), h->F.slices + r * 2 * (int64_t)LK, s.size() * 8, hipMemcpyDeviceToHost));
   if (slices) std::memcpy(slices, s.data(), (size_t)W * 8);
@@ -1425,21 +1579,18 @@ int tnco_hip_get_slices(tnco_hip_handle h, int64_t r, uint64_t* slices, uint64_t
 int tnco_hip_diag_reslice_info(tnco_hip_handle h, int32_t* how, int32_t* n_changed) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
   if (!h->fw || !h->fw_wave_capable) return fail(TNCO_HIP_EINVAL, "handle has no re-pricing re-slice.");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   const int64_t R = h->P.R;
   if (how) HIP_TRY(hipMemcpy(how, h->F.fastflag, (size_t)R * 4, hipMemcpyDeviceToHost));
-  if (n_changed) {  // word 0 of every replica's change list (fw_reslice_a_kernel), 512 bytes apart
-    HIP_TRY(hipMemcpy2D(n_changed, 4, h->F.delta_scr, 512, 4, (size_t)R, hipMemcpyDeviceToHost));
-  }
+  // word 0 of every replica's change list (fw_reslice_a_kernel), 512 bytes apart
+  if (n_changed) HIP_TRY(hipMemcpy2D(n_changed, 4, h->F.delta_scr, 512, 4, (size_t)R, hipMemcpyDeviceToHost));
   return TNCO_HIP_OK;
 }
 
 int tnco_hip_diag_fw_stats(tnco_hip_handle h, int64_t* out8) {
   if (!h || !out8) return fail(TNCO_HIP_EINVAL, "null argument.");
   if (!h->fw) return fail(TNCO_HIP_EINVAL, "handle was created without 'max_width'.");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   if (h->F.slowstat) HIP_TRY(h->collect_fw_stats(nullptr));
   for (int i = 0; i < 8; ++i) out8[i] = h->fw_stats[i];
   return TNCO_HIP_OK;
@@ -1447,8 +1598,7 @@ int tnco_hip_diag_fw_stats(tnco_hip_handle h, int64_t* out8) {
 
 int tnco_hip_diag_kernel_time(tnco_hip_handle h, double* ms, int64_t* launches, int reset) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   h->close_region();
   h->resolve_events();
   if (ms) *ms = h->kernel_ms;
@@ -1459,8 +1609,7 @@ int tnco_hip_diag_kernel_time(tnco_hip_handle h, double* ms, int64_t* launches, 
 
 int tnco_hip_diag_kernel_times(tnco_hip_handle h, double* ms4, int64_t* launches4, int reset) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   h->close_region();
   h->resolve_events();
   // (a finite-width handle on two streams: the AVERAGE time a stream spent in each kernel -- the streams run
@@ -1482,8 +1631,7 @@ int tnco_hip_get_costs(tnco_hip_handle h, double* total_cost, double* min_total_
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
   if (!total_cost && !min_total_cost) return TNCO_HIP_OK;
   const int64_t R = h->P.R;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   if (int rc = fw_runtime_status(h)) return rc;
   TempBufs tmp;
   double *dt = nullptr, *dm = nullptr;
@@ -1491,8 +1639,8 @@ int tnco_hip_get_costs(tnco_hip_handle h, double* total_cost, double* min_total_
   if (min_total_cost) HIP_TRY(tmp.alloc(&dm, R));
   hipLaunchKernelGGL(gather_costs_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, h->stream, h->P, dt, dm);
   HIP_TRY(hipGetLastError());
-  if (total_cost) HIP_TRY(hipMemcpyAsync(total_cost, dt, (size_t)R * 8, hipMemcpyDeviceToHost, h->stream));
-  if (min_total_cost) HIP_TRY(hipMemcpyAsync(min_total_cost, dm, (size_t)R * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h->download(total_cost, dt, R));
+  HIP_TRY(h->download(min_total_cost, dm, R));
   HIP_TRY(h->sync_all());
   return TNCO_HIP_OK;
 }
@@ -1501,12 +1649,10 @@ int tnco_hip_get_slices_many(tnco_hip_handle h, int64_t k, const int64_t* ids, u
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
   if (!h->fw) return fail(TNCO_HIP_EINVAL, "handle was created without 'max_width'.");
   if (k < 0 || (k > 0 && !ids)) return fail(TNCO_HIP_EINVAL, "null argument.");
-  for (int64_t i = 0; i < k; ++i)
-    if (ids[i] < 0 || ids[i] >= h->P.R) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
+  if (int rc = check_ids(h, k, ids)) return rc;
   if (k == 0 || (!slices && !min_slices)) return TNCO_HIP_OK;
   const int LK = h->L * h->K, W = h->P.W;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   TempBufs tmp;
   int64_t* dids = nullptr;
   uint64_t *dc = nullptr, *dm = nullptr;
@@ -1517,8 +1663,8 @@ int tnco_hip_get_slices_many(tnco_hip_handle h, int64_t k, const int64_t* ids, u
   hipLaunchKernelGGL(gather_slices_kernel, dim3((unsigned)((k * W + 255) / 256)), dim3(256), 0, h->stream, h->F.slices, LK, W,
                      dids, k, dc, dm);
   HIP_TRY(hipGetLastError());
-  if (slices) HIP_TRY(hipMemcpyAsync(slices, dc, (size_t)k * W * 8, hipMemcpyDeviceToHost, h->stream));
-  if (min_slices) HIP_TRY(hipMemcpyAsync(min_slices, dm, (size_t)k * W * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h->download(slices, dc, k * W));
+  HIP_TRY(h->download(min_slices, dm, k * W));
   HIP_TRY(h->sync_all());
   return TNCO_HIP_OK;
 }
@@ -1526,24 +1672,21 @@ int tnco_hip_get_slices_many(tnco_hip_handle h, int64_t k, const int64_t* ids, u
 int tnco_hip_get_tree(tnco_hip_handle h, int64_t r, int which, int32_t* left, int32_t* right,
                       int32_t* parent, uint64_t* masks) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
-  if (r < 0 || r >= h->P.R) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
+  if (int rc = check_replica(h, r)) return rc;
   if (!left || !right || !parent) return fail(TNCO_HIP_EINVAL, "null output array.");
-  const int n = h->P.n, N = h->P.N, W = h->P.W, BS = h->P.BS;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  const int n = h->P.n, N = h->P.N, W = h->P.W;
+  HIP_TRY(h->make_idle());
   if (which == 0) {
-    std::vector<uint8_t> blk((size_t)h->block_bytes());
-    HIP_TRY(hipMemcpy(blk.data(), h->P.blocks + r * h->block_bytes(), blk.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy2D(parent, 4, h->P.lpar + r * (int64_t)n * LPS, (size_t)LPS * 4, 4, (size_t)n,
-                        hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; ++i) { left[i] = -1; right[i] = -1; }
-    if (masks) std::memcpy(masks, h->leafmask_w.data(), (size_t)n * W * 8);
-    for (int p = n; p < N; ++p) {
-      const uint8_t* b = blk.data() + (size_t)(p - n) * BS;
-      NodeRec hd;
-      std::memcpy(&hd, b, sizeof(hd));
-      left[p] = hd.left; right[p] = hd.right; parent[p] = hd.parent;
-      if (masks) std::memcpy(masks + (size_t)p * W, blk.data() + (size_t)h->P.WOFF + (size_t)(p - n) * h->P.WS, (size_t)W * 8);
+    const BlockLayout B(h, r);
+    std::vector<uint8_t> img((size_t)h->block_bytes());
+    HIP_TRY(B.fetch(img));
+    HIP_TRY(hipMemcpy2D(parent, 4, B.leaf_parent_at(0), (size_t)LPS * 4, 4, (size_t)n, hipMemcpyDeviceToHost));
+    for (int x = 0; x < N; ++x) {
+      const NodeRec hd = B.node(img, x);
+      left[x] = x < n ? -1 : hd.left;
+      right[x] = x < n ? -1 : hd.right;
+      if (x >= n) parent[x] = hd.parent;
+      if (masks) std::memcpy(masks + (size_t)x * W, B.legs(img, x), (size_t)W * 8);
     }
   } else {
     // best tree = checkpoint + rotations jlog[0, jmin): Tree::swap_with_nn replayed on the host
@@ -1554,15 +1697,7 @@ int tnco_hip_get_tree(tnco_hip_handle h, int64_t r, int which, int32_t* left, in
     std::vector<int32_t> lg((size_t)rs.jmin);
     if (rs.jmin)
       HIP_TRY(hipMemcpy(lg.data(), h->P.jlog + r * (int64_t)h->P.jcap, (size_t)rs.jmin * 4, hipMemcpyDeviceToHost));
-    for (int32_t D : lg) {
-      const int B = t[D].parent;
-      const int A = t[B].parent;
-      const int C = (t[A].left == B) ? t[A].right : t[A].left;
-      if (t[A].left != C) t[A].right = D; else t[A].left = D;
-      if (t[B].left != D) t[B].right = C; else t[B].left = C;
-      t[C].parent = B;
-      t[D].parent = A;
-    }
+    replay_rotations(t.data(), lg.data(), (int)lg.size());
     for (int i = 0; i < N; ++i) { left[i] = t[i].left; right[i] = t[i].right; parent[i] = t[i].parent; }
     if (masks) host_derive(h, left, right, masks);
   }
@@ -1571,55 +1706,37 @@ int tnco_hip_get_tree(tnco_hip_handle h, int64_t r, int which, int32_t* left, in
 
 int tnco_hip_get_caches(tnco_hip_handle h, int64_t r, double* ccost, double* partial, uint64_t* hyper) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
-  if (r < 0 || r >= h->P.R) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
-  const int n = h->P.n, N = h->P.N, W = h->P.W, BS = h->P.BS;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
-  std::vector<uint8_t> blk((size_t)h->block_bytes());
-  HIP_TRY(hipMemcpy(blk.data(), h->P.blocks + r * h->block_bytes(), blk.size(), hipMemcpyDeviceToHost));
+  if (int rc = check_replica(h, r)) return rc;
+  const int n = h->P.n, N = h->P.N, W = h->P.W;
+  HIP_TRY(h->make_idle());
+  const BlockLayout B(h, r);
+  std::vector<uint8_t> img((size_t)h->block_bytes());
+  HIP_TRY(B.fetch(img));
   if (hyper) std::memset(hyper, 0, (size_t)N * W * 8);
-  auto node = [&](int x) {
-    NodeRec hd{};
-    if (x >= n) std::memcpy(&hd, blk.data() + (size_t)(x - n) * BS, sizeof(hd));
-    return hd;
-  };
-  double root_total = 0.0;
-  if (h->P.cpl) {
-    ReplicaState rs;
-    HIP_TRY(hipMemcpy(&rs, h->P.rs + r, sizeof(rs), hipMemcpyDeviceToHost));
-    root_total = rs.total;
-  }
+  ReplicaState rs{};  // (child-partial layout: the root's partial cost is the replica's total)
+  if (h->P.cpl) HIP_TRY(hipMemcpy(&rs, h->P.rs + r, sizeof(rs), hipMemcpyDeviceToHost));
   for (int i = 0; i < N; ++i) {
-    const NodeRec hd = node(i);
+    const NodeRec hd = B.node(img, i);
     if (i >= n && h->P.cpl) {
       // child-partial layout: the contraction cost from the legs of the children, the partial cost from the parent's slot
       if (ccost) {
-        auto legs = [&](int x) -> const uint64_t* {
-          return x < n ? h->leafmask_w.data() + (size_t)x * W
-                       : reinterpret_cast<const uint64_t*>(blk.data() + ((int64_t)h->P.WOFF + (int64_t)(x - n) * h->P.WS));
-        };
-        const uint64_t *l0 = legs(hd.left), *l1 = legs(hd.right);
+        const uint64_t *l0 = B.legs(img, hd.left), *l1 = B.legs(img, hd.right);
         int64_t pc = 0;
         for (int w = 0; w < W; ++w) pc += __builtin_popcountll(l0[w] | l1[w]);
         ccost[i] = std::ldexp(1.0, (int)std::min<int64_t>(pc * h->P.log2d, 1024));  // pow2_cost: 2^e, inf beyond 1023
       }
       if (partial) {
-        const NodeRec ph = node(hd.parent);
-        partial[i] = hd.parent < 0 ? root_total : (ph.left == i ? ph.pleft : ph.pright);
+        const NodeRec ph = B.node(img, hd.parent);
+        partial[i] = hd.parent < 0 ? rs.total : (ph.left == i ? ph.pleft : ph.pright);
       }
     } else {
       if (ccost) ccost[i] = i < n ? 0.0 : hd.ccost;
       if (partial) partial[i] = i < n ? 0.0 : hd.partial;
     }
     if (hyper && h->hyper && i >= n) {
-      {  // HyperCache (infinite_memory/utils.hpp:82-91): legs(p) & legs(c0) & legs(c1), from the stored legs
-        auto legs = [&](int x) -> const uint64_t* {
-          return x < n ? h->leafmask_w.data() + (size_t)x * W
-                       : reinterpret_cast<const uint64_t*>(blk.data() + ((int64_t)h->P.WOFF + (int64_t)(x - n) * h->P.WS));
-        };
-        const uint64_t *lp = legs(i), *l0 = legs(hd.left), *l1 = legs(hd.right);
-        for (int w = 0; w < W; ++w) hyper[(size_t)i * W + w] = lp[w] & l0[w] & l1[w];
-      }
+      // HyperCache (infinite_memory/utils.hpp:82-91): legs(p) & legs(c0) & legs(c1), from the stored legs
+      const uint64_t *lp = B.legs(img, i), *l0 = B.legs(img, hd.left), *l1 = B.legs(img, hd.right);
+      for (int w = 0; w < W; ++w) hyper[(size_t)i * W + w] = lp[w] & l0[w] & l1[w];
     }
   }
   return TNCO_HIP_OK;
@@ -1628,66 +1745,68 @@ int tnco_hip_get_caches(tnco_hip_handle h, int64_t r, double* ccost, double* par
 int tnco_hip_validate(tnco_hip_handle h, double atol, int64_t* n_bad, int64_t* first_bad) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
   const Params& P = h->P;
-  const int64_t LK = (int64_t)h->L * h->K;
+  const int64_t LK = (int64_t)h->L * h->K, R = P.R;
   const int n = P.n, N = P.N;
-  const int64_t R = P.R;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   const int64_t per = h->block_bytes() + (int64_t)n * 4 + (int64_t)N * 32 + 64;
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(R, ((int64_t)1 << 30) / per));
   TempBufs tmp;
-  uint8_t* tblk = nullptr; int32_t *tlpar = nullptr, *tscr = nullptr, *tstat = nullptr, *tbad = nullptr;
-  double *ttot = nullptr, *tsum = nullptr;
-  Links* tlinks = nullptr;
-  HIP_TRY(tmp.alloc(&tblk, chunk * h->block_bytes()));
-  HIP_TRY(tmp.alloc(&tlpar, chunk * n * LPS));
-  HIP_TRY(tmp.alloc(&tscr, chunk * 4 * N));
-  HIP_TRY(tmp.alloc(&tlinks, chunk * N));
-  HIP_TRY(tmp.alloc(&tstat, chunk));
-  HIP_TRY(tmp.alloc(&tbad, chunk));
-  HIP_TRY(tmp.alloc(&ttot, chunk));
-  HIP_TRY(tmp.alloc(&tsum, chunk));
-  uint64_t* thy = nullptr;
-  if (h->hyper) HIP_TRY(tmp.alloc(&thy, chunk * (int64_t)(n - 1) * h->P.W));
+  struct { uint8_t* blk; int32_t *lpar, *scr, *stat, *bad; double *tot, *sum; Links* links; uint64_t* hy; } t{};  // both passes' scratch
+  HIP_TRY(tmp.alloc(&t.blk, chunk * h->block_bytes()));
+  HIP_TRY(tmp.alloc(&t.lpar, chunk * n * LPS));
+  HIP_TRY(tmp.alloc(&t.scr, chunk * 4 * N));
+  HIP_TRY(tmp.alloc(&t.links, chunk * N));
+  HIP_TRY(tmp.alloc(&t.stat, chunk));
+  HIP_TRY(tmp.alloc(&t.bad, chunk));
+  HIP_TRY(tmp.alloc(&t.tot, chunk));
+  HIP_TRY(tmp.alloc(&t.sum, chunk));
+  if (h->hyper) HIP_TRY(tmp.alloc(&t.hy, chunk * (int64_t)(n - 1) * P.W));
+  // (1) current tree: rebuild everything and compare
+  auto current_tree = [&](BuildArgs& a) {
+    a.src_live = 1;
+    if (h->fw) { a.cost_slices = h->F.slices; a.cost_slices_stride = 2 * LK; }
+    launch_build(h, a);
+    launch_compare(h, a, atol, t.bad);
+    if (h->fw) launch_fw_check(h, a, 0, atol, t.bad);
+  };
+  // (2) best tree (checkpoint + rotation log): its cost must match min_total_cost
+  auto best_tree = [&](BuildArgs& a) -> int {
+    hipLaunchKernelGGL(materialize_min_kernel, dim3((unsigned)((a.count + 63) / 64)), dim3(64), 0, h->stream, P, t.links, a.r0, a.count);
+    a.src_live = 0;
+    a.src_links = t.links;
+    if (h->fw) { a.cost_slices = h->F.slices + LK; a.cost_slices_stride = 2 * LK; }
+    launch_build(h, a);
+    if (h->fw) {  // the widths of the best tree, against min_slices
+      HIP_TRY(hipMemsetAsync(t.bad, 0, (size_t)a.count * 4, h->stream));
+      launch_fw_check(h, a, 1, atol, t.bad);
+    }
+    return TNCO_HIP_OK;
+  };
   int64_t bad = 0, first = -1;
   std::vector<ReplicaState> rs;
   if (int rc = fetch_rs(h, rs)) return rc;
-  std::vector<int32_t> hb((size_t)chunk), hs((size_t)chunk);
+  std::vector<int32_t> cur_bad((size_t)chunk), best_bad((size_t)chunk, 0), hs((size_t)chunk);
   std::vector<double> hsum((size_t)chunk);
   for (int64_t r0 = 0; r0 < R; r0 += chunk) {
     const int64_t cnt = std::min(chunk, R - r0);
     BuildArgs a{};
-    a.hyper_tmp = thy;
-    a.out_blocks = tblk; a.out_lpar = tlpar; a.scratch = tscr;
-    a.out_total = ttot; a.out_sum = tsum; a.out_status = tstat; a.r0 = r0; a.count = cnt;
-    // (1) current tree: rebuild everything and compare
-    a.src_live = 1;
-    if (h->fw) { a.cost_slices = h->F.slices; a.cost_slices_stride = 2 * LK; }
-    launch_build(h, a);
-    launch_compare(h, a, atol, tbad);
-    if (h->fw) launch_fw_check(h, a, 0, atol, tbad);
+    a.hyper_tmp = t.hy;
+    a.out_blocks = t.blk; a.out_lpar = t.lpar; a.scratch = t.scr;
+    a.out_total = t.tot; a.out_sum = t.sum; a.out_status = t.stat; a.r0 = r0; a.count = cnt;
+    current_tree(a);
     HIP_TRY(h->sync_all());
-    HIP_TRY(hipMemcpy(hb.data(), tbad, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-    // (2) best tree (checkpoint + rotation log): its cost must match min_total_cost
-    hipLaunchKernelGGL(materialize_min_kernel, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, h->stream, P, tlinks, r0, cnt);
-    a.src_live = 0;
-    a.src_links = tlinks;
-    if (h->fw) { a.cost_slices = h->F.slices + LK; a.cost_slices_stride = 2 * LK; }
-    launch_build(h, a);
-    if (h->fw) {  // the widths of the best tree, against min_slices
-      HIP_TRY(hipMemsetAsync(tbad, 0, (size_t)cnt * 4, h->stream));
-      launch_fw_check(h, a, 1, atol, tbad);
+    HIP_TRY(hipMemcpy(cur_bad.data(), t.bad, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    if (int rc = best_tree(a)) return rc;
+    if (h->fw) {  // (its widths were checked too)
       HIP_TRY(h->sync_all());
-      std::vector<int32_t> hb2((size_t)cnt);
-      HIP_TRY(hipMemcpy(hb2.data(), tbad, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-      for (int64_t q = 0; q < cnt; ++q)
-        if (hb2[q]) hb[q] = hb[q] ? hb[q] : hb2[q];
+      HIP_TRY(hipMemcpy(best_bad.data(), t.bad, (size_t)cnt * 4, hipMemcpyDeviceToHost));
     }
     HIP_TRY(h->sync_all());
-    HIP_TRY(hipMemcpy(hs.data(), tstat, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hsum.data(), tsum, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hs.data(), t.stat, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hsum.data(), t.sum, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+    // the verdict on a replica: either pass found something, the best tree did not build, or its cost is not min_cost
     for (int64_t q = 0; q < cnt; ++q) {
-      const bool b = hb[q] != 0 || hs[q] != 0 || !logclose(hsum[q], rs[r0 + q].min_cost, atol);
+      const bool b = cur_bad[q] != 0 || best_bad[q] != 0 || hs[q] != 0 || !logclose(hsum[q], rs[r0 + q].min_cost, atol);
       if (b) { ++bad; if (first < 0) first = r0 + q; }
     }
   }
@@ -1697,127 +1816,37 @@ int tnco_hip_validate(tnco_hip_handle h, double atol, int64_t* n_bad, int64_t* f
 }
 
 // One field of one replica read and, with `write`, replaced from the host (the tests of tnco_hip_validate).  The
-// addresses are those the getters above decode: node headers BS bytes apart, legs at WOFF + WS per node, leaf parents
-// LPS words apart, slices / min_slices LK words each.  What the validator's kernels walk stays walkable: child links only
+// addresses are the getters' own (BlockLayout): node headers BS bytes apart, legs at WOFF + WS per node, leaf parents
+// LPS words apart; slices / min_slices LK words each.  What the validator's kernels walk stays walkable: child links only
 // change places, a parent is an internal node, jmin stays inside the journal -- see the header.
 int tnco_hip_diag_poke(tnco_hip_handle h, int64_t r, int field, int64_t node, int64_t word, int write, uint64_t value,
                        uint64_t* previous) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
-  const Params& P = h->P;
-  const int64_t n = P.n, N = P.N, W = P.W, LK = (int64_t)h->L * h->K;
-  if (r < 0 || r >= P.R) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
-  const bool internal = node >= n && node < N;
-  uint8_t* hdr = internal ? P.blocks + r * P.RB + (node - n) * (int64_t)P.BS : nullptr;
-  ReplicaState* rs = P.rs + r;
-  uint8_t* at = nullptr;  // the field's device address
-  size_t nb = 8;          // ... and its size
-  bool as_float = false;  // a float32 field: `value` / `previous` are the bits of the double of the same value
-  switch (field) {
-    case TNCO_HIP_POKE_PARENT:
-      if (node < 0 || node >= N) return fail(TNCO_HIP_EINVAL, "'node' out of range.");
-      at = internal ? hdr + offsetof(NodeRec, parent) : reinterpret_cast<uint8_t*>(P.lpar + r * n * LPS + node * LPS);
-      nb = 4;
-      // (the root's own null parent is what a test puts back there)
-      if (write && !((int64_t)value >= n && (int64_t)value < N) && !(node == N - 1 && (int64_t)value == -1))
-        return fail(TNCO_HIP_EINVAL, "a parent must be an internal node.");
-      break;
-    case TNCO_HIP_POKE_SWAP_CHILDREN:
-      if (!internal) return fail(TNCO_HIP_EINVAL, "'node' is not an internal node.");
-      at = hdr + offsetof(NodeRec, left);
-      break;
-    case TNCO_HIP_POKE_LEGS:
-      if (!internal) return fail(TNCO_HIP_EINVAL, "'node' is not an internal node.");
-      if (word < 0 || word >= W) return fail(TNCO_HIP_EINVAL, "'word' out of range.");
-      at = P.blocks + r * P.RB + P.WOFF + (node - n) * (int64_t)P.WS + word * 8;
-      break;
-    case TNCO_HIP_POKE_CCOST:
-    case TNCO_HIP_POKE_PARTIAL:
-      if (P.cpl) return fail(TNCO_HIP_EINVAL, "the child-partial layout stores neither 'ccost' nor 'partial' of a node.");
-      if (!internal) return fail(TNCO_HIP_EINVAL, "'node' is not an internal node.");
-      at = hdr + (field == TNCO_HIP_POKE_CCOST ? offsetof(NodeRec, ccost) : offsetof(NodeRec, partial));
-      break;
-    case TNCO_HIP_POKE_PARTIAL_LEFT:
-    case TNCO_HIP_POKE_PARTIAL_RIGHT:
-      if (!P.cpl) return fail(TNCO_HIP_EINVAL, "only the child-partial layout stores the partial costs of a node's children.");
-      if (!internal) return fail(TNCO_HIP_EINVAL, "'node' is not an internal node.");
-      at = hdr + (field == TNCO_HIP_POKE_PARTIAL_LEFT ? offsetof(NodeRec, pleft) : offsetof(NodeRec, pright));
-      break;
-    case TNCO_HIP_POKE_TOTAL:
-      if (!P.cpl) return fail(TNCO_HIP_EINVAL, "only the child-partial layout keeps the root's partial cost in the replica record.");
-      at = reinterpret_cast<uint8_t*>(rs) + offsetof(ReplicaState, total);
-      break;
-    case TNCO_HIP_POKE_MIN_COST:
-      at = reinterpret_cast<uint8_t*>(rs) + offsetof(ReplicaState, min_cost);
-      break;
-    case TNCO_HIP_POKE_JMIN:
-      at = reinterpret_cast<uint8_t*>(rs) + offsetof(ReplicaState, jmin);
-      nb = 4;
-      break;
-    case TNCO_HIP_POKE_SLICES:
-    case TNCO_HIP_POKE_MIN_SLICES:
-      if (!h->fw) return fail(TNCO_HIP_EINVAL, "handle was created without 'max_width'.");
-      if (word < 0 || word >= W) return fail(TNCO_HIP_EINVAL, "'word' out of range.");
-      at = reinterpret_cast<uint8_t*>(h->F.slices + r * 2 * LK + (field == TNCO_HIP_POKE_MIN_SLICES ? LK : 0) + word);
-      break;
-    case TNCO_HIP_POKE_WIDTH:
-      if (!h->fw) return fail(TNCO_HIP_EINVAL, "handle was created without 'max_width'.");
-      if (!internal) return fail(TNCO_HIP_EINVAL, "'node' is not an internal node.");
-      if (h->F.width_f32) {
-        at = hdr + offsetof(NodeRec, pad);
-        nb = 4;
-        as_float = true;
-      } else {
-        at = reinterpret_cast<uint8_t*>(h->F.width64 + r * N + node);
-      }
-      break;
-    default:
-      return fail(TNCO_HIP_EINVAL, "unknown 'field'.");
-  }
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
-  uint64_t old = 0;
+  if (int rc = check_replica(h, r)) return rc;
+  PokeField f;
+  if (int rc = poke_field(h, r, field, node, word, write, value, &f)) return rc;
+  HIP_TRY(h->make_idle());
+  uint8_t raw[8];
   if (field == TNCO_HIP_POKE_SWAP_CHILDREN) {
     if (write) {
       int32_t lr[2];
-      HIP_TRY(hipMemcpy(lr, at, 8, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(lr, f.at, 8, hipMemcpyDeviceToHost));
       std::swap(lr[0], lr[1]);
-      HIP_TRY(hipMemcpy(at, lr, 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(f.at, lr, 8, hipMemcpyHostToDevice));
     }
     if (previous) *previous = 0;
     return TNCO_HIP_OK;
   }
-  if (nb == 4) {
-    uint32_t x = 0;
-    HIP_TRY(hipMemcpy(&x, at, 4, hipMemcpyDeviceToHost));
-    if (as_float) {
-      float f;
-      std::memcpy(&f, &x, 4);
-      const double d = (double)f;
-      std::memcpy(&old, &d, 8);
-    } else {
-      old = (uint64_t)(int64_t)(int32_t)x;  // (a parent: -1 at the root)
-    }
-  } else {
-    HIP_TRY(hipMemcpy(&old, at, 8, hipMemcpyDeviceToHost));
-  }
+  HIP_TRY(hipMemcpy(raw, f.at, f.nb, hipMemcpyDeviceToHost));
+  const uint64_t old = f.decode(raw);
   if (write) {
     if (field == TNCO_HIP_POKE_JMIN) {  // every prefix of the journal's jtail entries is a sequence of legal rotations
       uint32_t jtail = 0;
-      HIP_TRY(hipMemcpy(&jtail, reinterpret_cast<uint8_t*>(rs) + offsetof(ReplicaState, jtail), 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&jtail, reinterpret_cast<uint8_t*>(h->P.rs + r) + offsetof(ReplicaState, jtail), 4, hipMemcpyDeviceToHost));
       if (value > (uint64_t)jtail) return fail(TNCO_HIP_EINVAL, "'jmin' beyond the rotations the journal holds.");
     }
-    if (nb == 4) {
-      uint32_t x = (uint32_t)value;
-      if (as_float) {
-        double d;
-        std::memcpy(&d, &value, 8);
-        const float f = (float)d;
-        std::memcpy(&x, &f, 4);
-      }
-      HIP_TRY(hipMemcpy(at, &x, 4, hipMemcpyHostToDevice));
-    } else {
-      HIP_TRY(hipMemcpy(at, &value, 8, hipMemcpyHostToDevice));
-    }
+    f.encode(value, raw);
+    HIP_TRY(hipMemcpy(f.at, raw, f.nb, hipMemcpyHostToDevice));
   }
   if (previous) *previous = old;
   return TNCO_HIP_OK;
@@ -1825,72 +1854,39 @@ int tnco_hip_diag_poke(tnco_hip_handle h, int64_t r, int field, int64_t node, in
 
 int tnco_hip_get_prng(tnco_hip_handle h, int64_t r, uint32_t* out) {
   if (!h || !out) return fail(TNCO_HIP_EINVAL, "null argument.");
-  if (r < 0 || r >= h->P.R) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  if (int rc = check_replica(h, r)) return rc;
+  HIP_TRY(h->make_idle());
   ReplicaState rs;
   HIP_TRY(hipMemcpy(&rs, h->P.rs + r, sizeof(rs), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out, h->P.mt + r * 624, 624 * 4, hipMemcpyDeviceToHost));
-  // finish the lazily generated block sequence so the 624 words are what
-  // libstdc++ holds after _M_gen_rand() (random.tcc:396-430)
-  if (rs.mti < 624) {
-    for (int k = rs.mtw; k < 624; ++k) {
-      const uint32_t y = (out[k] & 0x80000000u) | (out[(k + 1) % 624] & 0x7fffffffu);
-      out[k] = out[(k + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-    }
-  }
-  out[624] = (uint32_t)rs.mti;
+  finish_mt_block(out, rs);
   return TNCO_HIP_OK;
 }
 
 int tnco_hip_set_prng(tnco_hip_handle h, int64_t r, const uint32_t* in) {
   if (!h || !in) return fail(TNCO_HIP_EINVAL, "null argument.");
-  if (r < 0 || r >= h->P.R) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
-  if (in[624] > 624) return fail(TNCO_HIP_EINVAL, "prng position out of range.");
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
-  ReplicaState rs;
-  HIP_TRY(hipMemcpy(&rs, h->P.rs + r, sizeof(rs), hipMemcpyDeviceToHost));
-  rs.mti = (int32_t)in[624];
-  rs.mtw = 624;
-  HIP_TRY(hipMemcpy(h->P.mt + r * 624, in, 624 * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->P.rs + r, &rs, sizeof(rs), hipMemcpyHostToDevice));
-  return TNCO_HIP_OK;
+  return tnco_hip_set_prng_many(h, 1, &r, in);  // (the same refusals in the same order; the position goes through mt_pos_kernel)
 }
 
 int tnco_hip_get_prng_many(tnco_hip_handle h, int64_t k, const int64_t* ids, uint32_t* out) {
   if (!h || (k > 0 && !out)) return fail(TNCO_HIP_EINVAL, "null argument.");
   if (k < 0 || (!ids && k > h->P.R)) return fail(TNCO_HIP_EINVAL, "'k' is not valid.");
-  for (int64_t i = 0; ids && i < k; ++i)
-    if (ids[i] < 0 || ids[i] >= h->P.R) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
+  if (int rc = check_ids(h, k, ids)) return rc;
   if (k == 0) return TNCO_HIP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   std::vector<ReplicaState> rs;
   if (int rc = fetch_rs(h, rs)) return rc;
   if (!ids) {  // replicas 0 .. k-1: one strided copy
     HIP_TRY(hipMemcpy2D(out, (size_t)625 * 4, h->P.mt, (size_t)624 * 4, (size_t)624 * 4, (size_t)k, hipMemcpyDeviceToHost));
   } else {
-    for (int64_t i = 0; i < k; ++i)
-      HIP_TRY(hipMemcpyAsync(out + i * 625, h->P.mt + ids[i] * 624, 624 * 4, hipMemcpyDeviceToHost, h->stream));
+    for (int64_t i = 0; i < k; ++i) HIP_TRY(h->download(out + i * 625, h->P.mt + ids[i] * 624, 624));
     HIP_TRY(h->sync_all());
   }
-  // finish the lazily generated block sequence so the 624 words are what libstdc++ holds after
-  // _M_gen_rand() (random.tcc:396-430)
   const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(k / 256 + 1, std::min<unsigned>(16, std::thread::hardware_concurrency())));
   std::vector<std::thread> th;
   for (int t = 0; t < nth; ++t)
     th.emplace_back([&, t]() {
-      for (int64_t i = t; i < k; i += nth) {
-        const ReplicaState& x = rs[(size_t)(ids ? ids[i] : i)];
-        uint32_t* o = out + i * 625;
-        if (x.mti < 624)
-          for (int j = x.mtw; j < 624; ++j) {
-            const uint32_t y = (o[j] & 0x80000000u) | (o[(j + 1) % 624] & 0x7fffffffu);
-            o[j] = o[(j + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-          }
-        o[624] = (uint32_t)x.mti;
-      }
+      for (int64_t i = t; i < k; i += nth) finish_mt_block(out + i * 625, rs[(size_t)(ids ? ids[i] : i)]);
     });
   for (auto& x : th) x.join();
   return TNCO_HIP_OK;
@@ -1899,13 +1895,13 @@ int tnco_hip_get_prng_many(tnco_hip_handle h, int64_t k, const int64_t* ids, uin
 int tnco_hip_set_prng_many(tnco_hip_handle h, int64_t k, const int64_t* ids, const uint32_t* in) {
   if (!h || (k > 0 && !in)) return fail(TNCO_HIP_EINVAL, "null argument.");
   if (k < 0 || (!ids && k > h->P.R)) return fail(TNCO_HIP_EINVAL, "'k' is not valid.");
-  for (int64_t i = 0; i < k; ++i) {
-    if (ids && (ids[i] < 0 || ids[i] >= h->P.R)) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
+  for (int64_t i = 0; i < k; ++i) {  // (row by row: a row's replica, then its position)
+    if (ids)
+      if (int rc = check_replica(h, ids[i])) return rc;
     if (in[i * 625 + 624] > 624) return fail(TNCO_HIP_EINVAL, "prng position out of range.");
   }
   if (k == 0) return TNCO_HIP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   TempBufs tmp;
   uint32_t* dpos = nullptr;
   int64_t* dids = nullptr;
@@ -1975,8 +1971,8 @@ int tnco_hip_best(tnco_hip_handle h, int64_t k, double* costs, int64_t* replicas
   HIP_TRY(hipGetLastError());
   std::vector<unsigned long long> hc((size_t)k);
   std::vector<uint32_t> hi((size_t)k);
-  HIP_TRY(hipMemcpyAsync(hc.data(), bc[cur], (size_t)k * 8, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(hi.data(), bi[cur], (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h->download(hc.data(), bc[cur], k));
+  HIP_TRY(h->download(hi.data(), bi[cur], k));
   HIP_TRY(h->sync_all());
   for (int64_t i = 0; i < k; ++i) {
     double c;
@@ -2002,12 +1998,10 @@ int tnco_hip_get_trees(tnco_hip_handle h, int64_t k, const int64_t* ids, int whi
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
   if (k < 0 || (k > 0 && (!ids || !links))) return fail(TNCO_HIP_EINVAL, "null argument.");
   if (which != 0 && which != 1) return fail(TNCO_HIP_EINVAL, "'which' is not valid.");
-  for (int64_t i = 0; i < k; ++i)
-    if (ids[i] < 0 || ids[i] >= h->P.R) return fail(TNCO_HIP_EINVAL, "'replica' out of range.");
+  if (int rc = check_ids(h, k, ids)) return rc;
   if (k == 0) return TNCO_HIP_OK;
   const int n = h->P.n, N = h->P.N;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(h->sync_all());
+  HIP_TRY(h->make_idle());
   if (int rc = fw_runtime_status(h)) return rc;
   // in chunks, so that the device-side staging stays small whatever k
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(k, ((int64_t)256 << 20) / ((int64_t)N * 40)));
@@ -2030,10 +2024,8 @@ int tnco_hip_get_trees(tnco_hip_handle h, int64_t k, const int64_t* ids, int whi
       hipLaunchKernelGGL((gather_trees_kernel<false>), dim3((unsigned)cnt), dim3(64), 0, h->stream, h->P, dids, which,
                          dlinks, dcon, dscr);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(links + k0 * 3 * N, dlinks, (size_t)cnt * 3 * N * 4, hipMemcpyDeviceToHost, h->stream));
-    if (contraction)
-      HIP_TRY(hipMemcpyAsync(contraction + k0 * 3 * (n - 1), dcon, (size_t)cnt * 3 * (n - 1) * 4, hipMemcpyDeviceToHost,
-                             h->stream));
+    HIP_TRY(h->download(links + k0 * 3 * N, dlinks, cnt * 3 * N));
+    HIP_TRY(h->download(contraction ? contraction + k0 * 3 * (n - 1) : nullptr, dcon, cnt * 3 * (n - 1)));
     HIP_TRY(h->sync_all());
   }
   return TNCO_HIP_OK;
@@ -2042,43 +2034,34 @@ int tnco_hip_get_trees(tnco_hip_handle h, int64_t k, const int64_t* ids, int whi
 int tnco_hip_diag_counters(tnco_hip_handle h, uint64_t* moves, uint64_t* accepted, uint64_t* improved,
                           uint64_t* random_picks) {
   if (!h) return fail(TNCO_HIP_EINVAL, "null handle.");
-  std::vector<ReplicaState> rs;
-  if (int rc = fetch_rs(h, rs)) return rc;
-  uint64_t m = 0, a = 0, i = 0, q = 0;
-  for (auto& x : rs) { m += x.n_moves; a += x.n_accepted; i += x.n_improved; q += x.n_randpick; }
-  if (moves) *moves = m;
-  if (accepted) *accepted = a;
-  if (improved) *improved = i;
-  if (random_picks) *random_picks = q;
+  uint64_t c[4] = {0, 0, 0, 0}, *out[4] = {moves, accepted, improved, random_picks};
+  if (int rc = fold_rs(h, [&](size_t, const ReplicaState& x) { c[0] += x.n_moves; c[1] += x.n_accepted; c[2] += x.n_improved; c[3] += x.n_randpick; }))
+    return rc;
+  for (int k = 0; k < 4; ++k)
+    if (out[k]) *out[k] = c[k];
   return TNCO_HIP_OK;
 }
 
 int tnco_hip_diag_full_copies(tnco_hip_handle h, uint64_t* n) {
   if (!h || !n) return fail(TNCO_HIP_EINVAL, "null argument.");
-  std::vector<ReplicaState> rs;
-  if (int rc = fetch_rs(h, rs)) return rc;
   uint64_t c = 0;
-  for (auto& x : rs) c += x.n_fullcopy;
+  if (int rc = fold_rs(h, [&](size_t, const ReplicaState& x) { c += x.n_fullcopy; })) return rc;
   *n = c;
   return TNCO_HIP_OK;
 }
 
 int tnco_hip_diag_stage_cycles(tnco_hip_handle h, uint64_t* out5) {
   if (!h || !out5) return fail(TNCO_HIP_EINVAL, "null argument.");
-  std::vector<ReplicaState> rs;
-  if (int rc = fetch_rs(h, rs)) return rc;
-  for (int k = 0; k < 5; ++k) out5[k] = 0;
-  for (auto& x : rs)
-    for (int k = 0; k < 5; ++k) out5[k] += x.pad1[k];
+  uint64_t c[5] = {0, 0, 0, 0, 0};
+  if (int rc = fold_rs(h, [&](size_t, const ReplicaState& x) { for (int k = 0; k < 5; ++k) c[k] += x.pad1[k]; })) return rc;
+  std::copy(c, c + 5, out5);
   return TNCO_HIP_OK;
 }
 
 int tnco_hip_diag_moves(tnco_hip_handle h, uint64_t* out) {
   if (!h || !out) return fail(TNCO_HIP_EINVAL, "null argument.");
-  std::vector<ReplicaState> rs;
-  if (int rc = fetch_rs(h, rs)) return rc;
-  for (size_t r = 0; r < rs.size(); ++r) out[r] = rs[r].n_moves;
-  return TNCO_HIP_OK;
+  return fold_rs(h, [&](size_t r, const ReplicaState& x) { out[r] = x.n_moves; });
 }
 
 }  // extern "C"
+
