@@ -459,6 +459,16 @@ const char* tnco_hip_comm_last_error(void);
  * bit-reproducible.  Every other kernel is that of mode 0.  A finite part with |x| >= 2^128 - 2^119 has an infinite hi:
  * the elements it feeds become non-finite (the host refuses such leaves).  Works with slice batches.
  *
+ * Matrix mode (tnco_hip_contract_set_matrix; dtype codes 0..3): nothing changes in what is stored, the tables or the
+ * memory; a step of the tiled shape class (M, N >= 64, K > 32) runs on the matrix cores in the element type's own
+ * precision, a real product as v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64: an fma chain of that type, one rounding
+ * per product, nothing rounded or split on the way.  An element is summed over k in blocks of 16, ascending, and in a
+ * block in the order 0, 4, 8, 12, 1, 5, 9, 13, 2, 6, 10, 14, 3, 7, 11, 15 (the plain tiled kernel: k ascending), so the
+ * bits differ from mode off while the error bound is the same; a complex product at every such k: re += Ar Br,
+ * re += (-Ai) Bi, im += Ar Bi, im += Ai Br.  The result is stored unrounded; no atomics, a run stays bit-reproducible.
+ * Every other kernel is that of a handle without the call.  Exclusive with compute mode 1 and the path kernel; steps with
+ * row axes and storage dtypes are not supported.  Works with slice batches and hoisting.
+ *
  * Path kernel (tnco_hip_contract_set_path_kernel; dtype codes 0..3 only): with a group of G the run takes the assignments
  * in groups of up to G consecutive numbers, the first group starting at slice_start, the last one possibly partial, and a
  * group is two launches.  In the first, one workgroup per member (block b: assignment first + b) interprets the whole
@@ -553,6 +563,13 @@ int tnco_hip_contract_set_compute(tnco_hip_contract h, int32_t mode);
 /* the last run's launches of the split kernel of mode 1; they are also counted in their tiled slot of
  * tnco_hip_contract_kernel_launches (by operand layout), so the slots still sum to stats[1] as before */
 int tnco_hip_contract_split_launches(tnco_hip_contract h, int64_t* count);
+/* after create: on = 1: the runs that follow use matrix mode (above); on = 0: they do not, as on a handle on which this
+ * was never called.  EINVAL for other values, on a handle with row axes, a storage dtype, compute mode 1 or a path
+ * kernel; a handle with matrix mode on refuses compute mode 1 and a path kernel in turn */
+int tnco_hip_contract_set_matrix(tnco_hip_contract h, int32_t on);
+/* the last run's launches of the matrix kernel; they are also counted in their tiled slot of
+ * tnco_hip_contract_kernel_launches (by operand layout), so the slots still sum to stats[1] as before */
+int tnco_hip_contract_matrix_launches(tnco_hip_contract h, int64_t* count);
 /* after create, before run, once per handle: the runs that follow take `group` assignments per launch of the path
  * kernel (above).  EINVAL for a group outside [1, 1024], on a handle with row axes, a storage dtype, a slice batch or a
  * compute mode, and when a step has more than 2^24 multiply-adds (the message names the step); a handle that took this

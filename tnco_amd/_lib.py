@@ -91,7 +91,8 @@ EXPORTS = [
     "tnco_hip_contract_create", "tnco_hip_contract_run", "tnco_hip_contract_stats", "tnco_hip_contract_kernel_launches",
     "tnco_hip_contract_row_launches", "tnco_hip_contract_set_exponents", "tnco_hip_contract_exponents",
     "tnco_hip_contract_narrow_launches", "tnco_hip_contract_set_slice_batch", "tnco_hip_contract_batch_launches",
-    "tnco_hip_contract_set_compute", "tnco_hip_contract_split_launches", "tnco_hip_contract_set_path_kernel",
+    "tnco_hip_contract_set_compute", "tnco_hip_contract_split_launches", "tnco_hip_contract_set_matrix",
+    "tnco_hip_contract_matrix_launches", "tnco_hip_contract_set_path_kernel",
     "tnco_hip_contract_path_launches", "tnco_hip_contract_set_hoist", "tnco_hip_contract_destroy",
     "tnco_hip_device_name", "tnco_hip_device_count", "tnco_hip_last_error", "tnco_hip_version",
 ]
@@ -203,6 +204,8 @@ def load() -> C.CDLL:
     L.tnco_hip_contract_batch_launches.argtypes = [vp, vp]
     L.tnco_hip_contract_set_compute.argtypes = [vp, i32]
     L.tnco_hip_contract_split_launches.argtypes = [vp, vp]
+    L.tnco_hip_contract_set_matrix.argtypes = [vp, i32]
+    L.tnco_hip_contract_matrix_launches.argtypes = [vp, vp]
     L.tnco_hip_contract_set_path_kernel.argtypes = [vp, i64]
     L.tnco_hip_contract_path_launches.argtypes = [vp, vp]
     L.tnco_hip_contract_set_hoist.argtypes = [vp, vp, vp]

@@ -72,6 +72,17 @@ intermediate the elements it feeds become non-finite.  Projections are not suppo
 stays bit-equal to the unbatched run; `split_launches` of the result counts the launches of the split kernel (they
 are also counted in their tiled slot of `kernel_launches`).
 
+Matrix mode: with `compute="matrix"` (all four dtypes; exclusive with `storage`) nothing changes in what is stored
+either, and the plan's tables and `peak_device_bytes` are those of `compute=None`; the steps of the tiled shape class
+run on the matrix cores in the arrays' own precision (csrc/contract_matrix.h): a real product is one
+v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64, an fma chain of the element type with one rounding per product, and a
+complex product its four real products.  Nothing is rounded or split, so an element is within (c kt + 2) u (|A| @ |B|) of
+the exact one (u the unit roundoff of the type, c = 1 real, 2 complex), the bound of the plain kernels; the sums run in
+another order than theirs (k in blocks of 16, within a block 0, 4, 8, 12, 1, 5, ...), so the bits differ from
+`compute=None` on a tiled-class step and are equal without one.  Projections and `path_kernel` are not supported with
+it; `slice_batch` and `hoist` are, bit-equal to the run without them; `matrix_launches` of the result counts the
+launches of the matrix kernel (they are also counted in their tiled slot of `kernel_launches`).
+
 Path kernel: with `path_kernel=G` (1 to 1024; exclusive with `slice_batch`; the four plain dtypes, no `storage`, `compute`
 or `projs`) the run takes the assignments of `slice_range` in groups of up to G consecutive numbers, the first group
 starting at slice_range[0], the last one possibly partial, and a group is two launches whatever the length of the path.
@@ -122,7 +133,9 @@ DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex6
 STORAGES = {"float16": 4, "bfloat16": 6}
 SCALINGS = ("tensor",)  # per-tensor power-of-two scaling of storage mode (module docstring)
 SCALE_BITS = 14  # the largest stored magnitude of a scaled tensor lies in [2^14, 2^15]
-COMPUTES = {"bf16x3": 1}  # compute modes (module docstring) and their codes for tnco_hip_contract_set_compute
+# compute modes (module docstring).  "bf16x3": its code for tnco_hip_contract_set_compute; "matrix" has entry points of
+# its own (tnco_hip_contract_set_matrix) and no code
+COMPUTES = {"bf16x3": 1, "matrix": None}
 MAX_SLICE_BATCH = 64  # slice assignments per launch at most (csrc/contract.hip MAX_SLICE_BATCH)
 MAX_PATH_KERNEL = 1024  # path kernel: assignments per launch at most (csrc/contract_path.h MAX_PATH_GROUP)
 # path kernel: multiply-adds (H M N K) of one step at most -- one workgroup runs it.  A guard against a step that would
@@ -164,7 +177,8 @@ class ContractionResult:
     #                          the largest, of an unsliced call 1); None: unbatched
     batch_launches: int = 0  # slice_batch: launches of the kernel that folds a group's blocks into the output;
     #                          `launches` is the four counts together
-    compute: str = None  # "bf16x3": the tiled-class steps ran as three bfloat16 products on the matrix cores
+    compute: str = None  # "bf16x3": the tiled-class steps ran as three bfloat16 products on the matrix cores; "matrix":
+    #                      they ran on the matrix cores in the arrays' own precision
     split_launches: int = 0  # compute: launches of the split kernel (they are part of their tiled slot of kernel_launches)
     path_kernel: int = None  # assignments per launch of the path kernel, the effective value (`Plan.path_kernel`; of several
     #                          calls the largest, of an unsliced call 1); None: the unfused run
@@ -172,6 +186,8 @@ class ContractionResult:
     #                                into the output; `launches` is their sum and the other launch counts are zeros
     hoisted: tuple = None  # hoist=True: (steps, permutes) that ran once per call instead of once per assignment
     #                        (`Plan.hoisted`; of several calls the sums); None without the keyword
+    matrix_launches: int = 0  # compute="matrix": launches of the matrix kernel (they are part of their tiled slot of
+    #                           kernel_launches)
 
 
 @dataclass
@@ -202,7 +218,7 @@ class Plan:
     scaling: str = None  # "tensor": steps columns 14, 15 are the exponent slots of A and B (leaf t: t, step j: n_leaves + j)
     stage_refs: np.ndarray = None  # scaling: [n_steps] arena offset of a stored step's float32 staging buffer, -1 none
     slice_batch: int = None  # assignments per launch: min(what was asked for, assignments of slice_range); 1 without steps
-    compute: str = None  # "bf16x3": the tiled-class steps on the matrix cores; the tables do not depend on it
+    compute: str = None  # "bf16x3" / "matrix": the tiled-class steps on the matrix cores; the tables do not depend on it
     path_kernel: int = None  # assignments per launch of the path kernel: min(what was asked for, assignments of slice_range);
     #                          1 without steps
     hoisted: tuple = None  # hoist=True: (steps hoisted, permutes hoisted); None without the keyword
@@ -347,7 +363,7 @@ def _check_compute(compute, storage, dtype, projs=None) -> None:
         raise ValueError(f"'compute' must be None or {' or '.join(repr(s) for s in COMPUTES)}.")
     if storage is not None:
         raise ValueError("'compute' and 'storage' are exclusive.")
-    if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.complex64)):
+    if compute == "bf16x3" and np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.complex64)):
         raise TypeError(f"with 'compute' the compute dtype must be float32 or complex64, not {np.dtype(dtype)}.")
     if projs is not None:
         raise NotImplementedError("projections are not supported with 'compute'.")
@@ -906,7 +922,7 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
                 continue
             if storage is not None:
                 a = _from_storage_bits(_storage_bits(a, storage, leaves[0] not in loose), storage, a)
-            if compute is not None and leaves[0] not in loose:
+            if compute == "bf16x3" and leaves[0] not in loose:
                 _check_split_range(a)
             parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, slice_batch=effective, compute=compute,
                                            path_kernel=fused, hoisted=none_hoisted))
@@ -924,7 +940,8 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
                              narrow_launches=sum(r.narrow_launches for r in parts), slice_batch=effective,
                              batch_launches=sum(r.batch_launches for r in parts), compute=compute,
                              split_launches=sum(r.split_launches for r in parts), path_kernel=fused,
-                             path_launches=_add_counts(*(r.path_launches for r in parts)), hoisted=none_hoisted)
+                             path_launches=_add_counts(*(r.path_launches for r in parts)), hoisted=none_hoisted,
+                             matrix_launches=sum(r.matrix_launches for r in parts))
 
 
 def _add_counts(*counts) -> tuple:
@@ -940,7 +957,7 @@ def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
         leaf_exps = np.array(leaf_exps, np.int32)
     elif p.storage is not None:  # (before the device is touched: a leaf beyond the storage type's range is refused)
         leaves = [_storage_bits(a, p.storage, t not in loose) for t, a in enumerate(leaves)]
-    elif p.compute is not None:  # (before the device is touched: a leaf beyond the range of the split is refused)
+    elif p.compute == "bf16x3":  # (before the device is touched: a leaf beyond the range of the split is refused)
         for t, a in enumerate(leaves):
             if t not in loose:
                 _check_split_range(a)
@@ -986,9 +1003,11 @@ def _describe(p: Plan, device: int):
 
 def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
     from . import _lib
-    exponents, narrow, folds, splits, fused = None, 0, 0, 0, (0, 0)
+    exponents, narrow, folds, splits, fused, matrix = None, 0, 0, 0, (0, 0), 0
     try:
-        if p.compute is not None:
+        if p.compute == "matrix":
+            _lib.check(L.tnco_hip_contract_set_matrix(h, 1))
+        elif p.compute is not None:
             _lib.check(L.tnco_hip_contract_set_compute(h, COMPUTES[p.compute]))
         if p.slice_batch is not None:
             _lib.check(L.tnco_hip_contract_set_slice_batch(h, p.slice_batch))
@@ -1018,7 +1037,11 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
             count = C.c_int64()
             _lib.check(L.tnco_hip_contract_batch_launches(h, C.byref(count)))
             folds = int(count.value)
-        if p.compute is not None:
+        if p.compute == "matrix":
+            count = C.c_int64()
+            _lib.check(L.tnco_hip_contract_matrix_launches(h, C.byref(count)))
+            matrix = int(count.value)
+        elif p.compute is not None:
             count = C.c_int64()
             _lib.check(L.tnco_hip_contract_split_launches(h, C.byref(count)))
             splits = int(count.value)
@@ -1034,7 +1057,7 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
                              row_kernel_launches=tuple(int(v) for v in by_row_kernel), scaling=p.scaling,
                              exponents=exponents, narrow_launches=narrow, slice_batch=p.slice_batch, batch_launches=folds,
                              compute=p.compute, split_launches=splits, path_kernel=p.path_kernel, path_launches=fused,
-                             hoisted=p.hoisted)
+                             hoisted=p.hoisted, matrix_launches=matrix)
 
 
 def _host_layout(p: Plan, staging) -> np.ndarray:
@@ -1073,9 +1096,10 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     stage, and the components' results that enter a later call, are then scaled as leaves (`exponents`: those of the
     last call made).  slice_batch: that many slice assignments per launch in every sliced call (module docstring);
     `batch_launches` is the sum over the calls, `slice_batch` of the result the largest effective value of a component.
-    compute: "bf16x3" runs the tiled-class steps of `result.path` on the matrix cores (module docstring); the fuse stage
-    stays in plain precision; `split_launches` is the sum over the calls.  path_kernel: that many slice assignments per
-    launch of the path kernel in every call over `result.path` (module docstring); the fuse stage stays as it is;
+    compute: "bf16x3" / "matrix" runs the tiled-class steps of `result.path` on the matrix cores (module docstring); the
+    fuse stage stays on the plain kernels; `split_launches` / `matrix_launches` is the sum over the calls.
+    path_kernel: that many slice assignments per launch of the path kernel in every call over `result.path` (module
+    docstring); the fuse stage stays as it is;
     `path_launches` is the sum over the calls, `path_kernel` of the result the largest effective value of a component.
     hoist: True runs the slice-independent steps and permutes of every call over `result.path` once per call (module
     docstring); the fuse stage, unsliced, stays as it is; `hoisted` is the sum over the calls."""
@@ -1122,12 +1146,12 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
                                  fuse_macs, r.kernel_launches, r.row_kernel_launches, r.scaling, r.exponents,
                                  r.narrow_launches, r.slice_batch, r.batch_launches, r.compute, r.split_launches,
-                                 r.path_kernel, r.path_launches, r.hoisted)
+                                 r.path_kernel, r.path_launches, r.hoisted, r.matrix_launches)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
     ts, n = [tuple(x) for x in tn.ts_inds], len(tn.ts_inds)
     done, results, macs, n_slices, peak, launches, device_s = set(), [], 0, 0, 0, 0, 0.0
     by_kernel = (0,) * len(KERNEL_PATHS)
-    exponents, narrow, folds, effective, splits = None, 0, 0, None, 0
+    exponents, narrow, folds, effective, splits, matrix = None, 0, 0, None, 0, 0
     fused, fused_launches = None, (0, 0)
     hoisted = None if hoist is None else (0, 0)
     n_comp_steps = 0
@@ -1142,7 +1166,7 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         if hoist is not None:
             hoisted = _add_counts(hoisted, r.hoisted)
         exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
-        splits += r.split_launches
+        splits, matrix = splits + r.split_launches, matrix + r.matrix_launches
         if slice_batch is not None:
             effective = max(effective or 1, r.slice_batch)
         if path_kernel is not None:
@@ -1167,7 +1191,7 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
             hoisted = _add_counts(hoisted, r.hoisted)
         fused_launches = _add_counts(fused_launches, r.path_launches)
         exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
-        splits += r.split_launches
+        splits, matrix = splits + r.split_launches, matrix + r.matrix_launches
         macs, launches, peak = macs + r.macs, launches + r.launches, max(peak, r.peak_device_bytes)
         device_s += r.device_s
         by_kernel = _add_counts(by_kernel, r.kernel_launches)
@@ -1177,4 +1201,4 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     return ContractionResult(inds, array, macs, n_slices, peak, launches, device_s, fuse_macs, by_kernel,
                              scaling=scaling, exponents=exponents, narrow_launches=narrow, slice_batch=effective,
                              batch_launches=folds, compute=compute, split_launches=splits, path_kernel=fused,
-                             path_launches=fused_launches, hoisted=hoisted)
+                             path_launches=fused_launches, hoisted=hoisted, matrix_launches=matrix)

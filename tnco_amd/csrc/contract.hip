@@ -17,6 +17,10 @@
 // Compute mode bf16x3 (tnco_hip_contract_set_compute, contract_split.h): float32 / complex64 plans keep their storage and
 // run the tiled class on the matrix cores, every product as three bfloat16 products (ct_split_tiled_kernel); every other
 // kernel is the one of the plain mode.
+// Matrix mode (tnco_hip_contract_set_matrix, contract_matrix.h): plans of the four plain dtypes keep their storage and run
+// the tiled class on the matrix cores in the element type's own precision (ct_matrix_tiled_kernel: v_mfma_f32_16x16x4_f32
+// / v_mfma_f64_16x16x4_f64, nothing rounded on the way, the sums in another order than ct_gemm_tiled_kernel); every other
+// kernel is the one of the plain mode.
 // Slice batches (tnco_hip_contract_set_slice_batch): B consecutive assignments per launch.  Every kernel of the slice
 // loop has a member axis, blockIdx.z = b for assignment sid0 + b (MemberArgs): member b works in its own copy of the arena
 // (and of the exponent slots and max words), reads a leaf in place at the slice offset of its own assignment, computed on
@@ -227,6 +231,7 @@ __device__ inline void ct_store(const GemmArgs<T>& p, int64_t e, T acc) {
 }
 
 #include "contract_split.h"
+#include "contract_matrix.h"
 
 constexpr int TB = 64, TK = 16;
 
@@ -531,6 +536,8 @@ struct tnco_hip_contract_s {
   int64_t batch_launches = 0;      // launches of ct_batch_reduce_kernel in the last run
   int compute = 0;                 // tnco_hip_contract_set_compute: 0 plain, 1 bf16x3
   int64_t split_launches = 0;      // launches of ct_split_tiled_kernel in the last run
+  int matrix = 0;                  // tnco_hip_contract_set_matrix: 1: the tiled class runs ct_matrix_tiled_kernel
+  int64_t matrix_launches = 0;     // launches of ct_matrix_tiled_kernel in the last run
   int64_t path_group = 0;          // tnco_hip_contract_set_path_kernel: assignments per launch of ct_path_kernel, 0: never set
   void* d_path_stage = nullptr;    // [path_group][block_numel] of the output's type: the members' last steps
   int64_t* d_path_tables = nullptr;  // steps | first row and count of every permute group | placement of every assignment
@@ -754,7 +761,17 @@ int launch_gemm(tnco_hip_contract_s* c, const GemmArgs<T>& p, unsigned members =
   const int64_t outs = p.H * p.M * p.N;
   int path;  // slot of tnco_hip_contract_kernel_launches; the members of a batch (grid z) do not enter the choice
   constexpr bool single = std::is_same<T, float>::value || std::is_same<T, cplx<float>>::value;
-  if (p.M >= 64 && p.N >= 64 && p.K > 32 && single && c->compute == 1) {  // tiled, on the matrix cores (contract_split.h)
+  if (p.M >= 64 && p.N >= 64 && p.K > 32 && c->matrix) {  // tiled, on the matrix cores in T's precision (contract_matrix.h)
+    constexpr int BM = 32 * ct_mx<T>::TI, BNN = 32 * ct_mx<T>::TJ;
+    const int64_t tiles = p.H * ((p.M + BM - 1) / BM) * ((p.N + BNN - 1) / BNN);
+    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20), 1, members);
+    if (ak && bn) hipLaunchKernelGGL((ct_matrix_tiled_kernel<T, true, true>), grid, dim3(256), 0, c->stream, p);
+    else if (ak) hipLaunchKernelGGL((ct_matrix_tiled_kernel<T, true, false>), grid, dim3(256), 0, c->stream, p);
+    else if (bn) hipLaunchKernelGGL((ct_matrix_tiled_kernel<T, false, true>), grid, dim3(256), 0, c->stream, p);
+    else hipLaunchKernelGGL((ct_matrix_tiled_kernel<T, false, false>), grid, dim3(256), 0, c->stream, p);
+    path = 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0);
+    c->matrix_launches += 1;
+  } else if (p.M >= 64 && p.N >= 64 && p.K > 32 && single && c->compute == 1) {  // tiled, on the matrix cores (contract_split.h)
     if constexpr (single) {
       constexpr bool CP = std::is_same<T, cplx<float>>::value;
       const int64_t tiles = p.H * ((p.M + HB - 1) / HB) * ((p.N + HB - 1) / HB);
@@ -1131,7 +1148,7 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
       CT_TRY(hipMemcpyAsync(c->d_exps, c->leaf_exps.data(), c->leaf_exps.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
   }
-  c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->last_member = 0;
+  c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->matrix_launches = c->last_member = 0;
   c->path_launches[0] = c->path_launches[1] = 0;
   std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
   std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
@@ -1251,6 +1268,7 @@ int tnco_hip_contract_set_compute(tnco_hip_contract c, int32_t mode) {
   if (c->dtype != 0 && c->dtype != 2) return fail(TNCO_HIP_EINVAL, "a compute mode needs a float32 or complex64 plan.");
   if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with a compute mode.");
   if (mode && c->path_group) return fail(TNCO_HIP_EINVAL, "a compute mode is not supported with a path kernel.");
+  if (mode && c->matrix) return fail(TNCO_HIP_EINVAL, "a compute mode and matrix mode are exclusive.");
   c->compute = mode;
   return TNCO_HIP_OK;
 }
@@ -1261,6 +1279,23 @@ int tnco_hip_contract_split_launches(tnco_hip_contract c, int64_t* count) {
   return TNCO_HIP_OK;
 }
 
+int tnco_hip_contract_set_matrix(tnco_hip_contract c, int32_t on) {
+  if (!c) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (on != 0 && on != 1) return fail(TNCO_HIP_EINVAL, "'on' must be 0 or 1.");
+  if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with matrix mode.");
+  if (c->dtype > 3) return fail(TNCO_HIP_EINVAL, "matrix mode needs a plain dtype.");
+  if (c->compute) return fail(TNCO_HIP_EINVAL, "a compute mode and matrix mode are exclusive.");
+  if (c->path_group) return fail(TNCO_HIP_EINVAL, "matrix mode is not supported with a path kernel.");
+  c->matrix = on;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_matrix_launches(tnco_hip_contract c, int64_t* count) {
+  if (!c || !count) return fail(TNCO_HIP_EINVAL, "null argument.");
+  *count = c->matrix_launches;
+  return TNCO_HIP_OK;
+}
+
 int tnco_hip_contract_set_path_kernel(tnco_hip_contract c, int64_t group) {
   if (!c) return fail(TNCO_HIP_EINVAL, "null argument.");
   if (group < 1 || group > MAX_PATH_GROUP) return fail(TNCO_HIP_EINVAL, "'group' must be from 1 to 1024.");
@@ -1268,6 +1303,7 @@ int tnco_hip_contract_set_path_kernel(tnco_hip_contract c, int64_t group) {
   if (c->dtype > 3) return fail(TNCO_HIP_EINVAL, "a path kernel needs a plain dtype.");
   if (c->batch) return fail(TNCO_HIP_EINVAL, "a slice batch and a path kernel are exclusive.");
   if (c->compute) return fail(TNCO_HIP_EINVAL, "a compute mode is not supported with a path kernel.");
+  if (c->matrix) return fail(TNCO_HIP_EINVAL, "matrix mode is not supported with a path kernel.");
   if (c->path_group) return fail(TNCO_HIP_EINVAL, "the path kernel is already set.");
   if (!c->hoist_step.empty()) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with a path kernel.");
   const int64_t S = (int64_t)c->steps.size() / STEP_W;

@@ -1,12 +1,14 @@
 """Writes profiles/contract_range.txt on one GPU: what the number-range tests (tests/test_gpu_contract_range.py) measure.
 
-    python tools/range_profile.py [--out profiles/contract_range.txt]
+    python tools/range_profile.py [--out profiles/contract_range.txt] [--matrix]
 
 Per group, type and shape class the largest error / bound of one device run (every bound is stated in the module
 docstring of the test file; the tests assert a ratio of at most 1), for group D the parts that differ from the host's
 rounding per category, and the sentence on what the matrix cores do with subnormal 16-bit inputs: group A's ratios in
-the tiled class decide it, since an MFMA that read them as zero would leave the bound in every element.  Nothing is
-asserted here beyond the kernel paths: a ratio above 1 is written down as it is.
+the tiled class decide it, since an MFMA that read them as zero would leave the bound in every element.  Section G does
+the same for compute="matrix" (tests/test_gpu_contract_matrix_range.py): the float32 and float64 matrix instructions on
+subnormal operands, products and sums; `--matrix` appends that section alone to the file.  Nothing is asserted here
+beyond the kernel paths: a ratio above 1 is written down as it is.
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402  (torch's HIP runtime first: tnco_amd/_lib.py)
 
 from tests import range_cases as rc  # noqa: E402
+from tests import test_gpu_contract_matrix_range as matrix_tests  # noqa: E402
 from tests import test_gpu_contract_range as tests  # noqa: E402
 from tnco_amd import contraction as ctr  # noqa: E402
 
@@ -35,10 +38,37 @@ def per_class(runs):
     return " ".join(f"{worst[c]:10.4f}" if c in worst else f"{'-':>10}" for c in CLASSES), worst
 
 
+def matrix_section():
+    """Section G: compute="matrix" on the fills of group C, the tiled cases, per dtype and kind; and per instruction the
+    sentence on what it does with subnormal numbers."""
+    matrix_tests.MEASURE_ONLY = True
+    lines = ["", "## G: compute=\"matrix\", subnormal sums / subnormal operands, the tiled cases; bound (c kt + 2) (u |A| @ |B| + eta)",
+             f"{'dtype':>10} {'kind':>9} {'tiled':>10}"]
+    worst = {4: 0.0, 8: 0.0}
+    for dtype in matrix_tests.DTYPES:
+        for kind in rc.C_KINDS:
+            ratio = max(matrix_tests.run(ctr, c, dtype, kind) for c in rc.TILED)
+            worst[rc.real_size(dtype)] = max(worst[rc.real_size(dtype)], ratio)
+            lines.append(f"{np.dtype(dtype).name:>10} {kind:>9} {ratio:10.4f}")
+    for size, mnemonic in ((4, "v_mfma_f32_16x16x4_f32"), (8, "v_mfma_f64_16x16x4_f64")):
+        lines.append(f"subnormal numbers, {mnemonic}: " + (
+            "takes subnormal operands at their value and keeps subnormal products and sums: inside the bound of the plain "
+            "kernels, which a flushed operand or result leaves in every element" if worst[size] <= 1 else
+            f"does NOT meet the bound of the plain kernels (largest error / bound {worst[size]:.3g}): subnormal numbers are lost"))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=str(ROOT / "profiles" / "contract_range.txt"))
+    ap.add_argument("--matrix", action="store_true", help="only section G, appended to --out")
     a = ap.parse_args()
+    if a.matrix:
+        lines = [f"(the section below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})"] + matrix_section()[1:]
+        with open(a.out, "a") as f:
+            f.write("\n" + "\n".join(lines) + "\n")
+        print("\n".join(lines))
+        return
     tests.MEASURE_ONLY = True
     kinds = (("real", False), ("complex", True))
     head = f"{'tiled':>10} {'dot':>10} {'stream':>10}"
@@ -86,6 +116,7 @@ def main():
         for name, cplx in kinds:
             tests.run_e(ctr, storage, cplx)  # (asserts: a difference is an error of the widening, not a figure)
             lines.append(f"{storage:>9} {name:>8} 0 of {len(rc.all_patterns(storage))}")
+    lines += matrix_section()
     Path(a.out).write_text("\n".join(lines) + "\n")
     print("\n".join(lines))
 

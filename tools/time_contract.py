@@ -15,7 +15,9 @@ Sycamore leg with slice_batch None, 1, 8 and 64, plain, in storage mode and with
 storage="bfloat16" in one process, and the sliced Sycamore leg with compute=None and "bf16x3"); the path kernel
 (`--path-kernel`: the sliced Sycamore leg with path_kernel=None, slice_batch=64 and path_kernel 64, 256 and 1024 in one
 process); hoisting (`--hoist`: the sliced Sycamore leg with hoist=None and hoist=True, unbatched and with
-slice_batch=64, in one process).  Engine figures are its
+slice_batch=64, in one process); the matrix mode (`--matrix`: the large square step in the four dtypes with compute=None
+and compute="matrix", in float32 and complex64 also with compute="bf16x3" and storage="bfloat16", and torch, in one
+process).  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device).
 """
@@ -423,6 +425,56 @@ def compute(lines, n, depth, max_width, max_slices):
     print(lines[-1], flush=True)
 
 
+def matrix(lines, n, block=64):
+    """The matrix mode against the plain engine in the same process: the large square step in the four dtypes with
+    compute=None (the tiled LDS kernel, the yardstick) and compute="matrix" (ct_matrix_tiled_kernel); in float32 and
+    complex64 also compute="bf16x3" and storage="bfloat16"; torch.tensordot on the same operands.  Device time: the
+    minimum and the spread of three runs after a warm-up.  Every row carries the largest difference to the host product
+    in float64 / complex128 on the leading block x block of the result, relative to the largest modulus there."""
+    lines.append("")
+    lines.append(f"## matrix mode, large square step M = N = K = {n}: the arrays' own dtype on the matrix cores "
+                 "(ct_matrix_tiled_kernel: v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64) against compute=None (the tiled "
+                 "LDS kernel), the other matrix-core modes and torch.tensordot, all in one process; device seconds: the "
+                 "minimum of three runs after a warm-up, spread = (max - min) / min of the three; error: max |got - ref| / "
+                 f"max |ref| over the leading {block} x {block} block of the result, ref the host product in float64 / complex128")
+    lines.append(f"{'dtype':>10} {'mode':>18} {'device s':>9} {'spread':>7} {'TFLOP/s':>8} {'None / this':>11} {'torch / this':>12} "
+                 f"{'error':>9}")
+    rng = np.random.RandomState(7)
+    notes = []
+    for dt in (np.float32, np.float64, np.complex64, np.complex128):
+        x, y = _rand((n, n), dt, rng), _rand((n, n), dt, rng)
+        fl = FLOPS_PER_MAC[dt] * n ** 3
+        wide = np.complex128 if np.dtype(dt).kind == "c" else np.float64
+        ref = x[:block].astype(wide) @ y[:, :block].astype(wide)
+        tx, ty = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+        t_torch = _torch_time(lambda: torch.tensordot(tx, ty, dims=([1], [0])))
+        del tx, ty
+        torch.cuda.empty_cache()
+        modes = [("compute=None", dict()), ("compute=matrix", dict(compute="matrix"))]
+        if np.dtype(dt).itemsize // (2 if np.dtype(dt).kind == "c" else 1) == 4:
+            modes += [("compute=bf16x3", dict(compute="bf16x3")), ("storage=bfloat16", dict(storage="bfloat16"))]
+        t_base = spread_base = None
+        for name, kw in modes:
+            call = lambda kw=kw: ctr.contract([(0, 1)], [("i", "k"), ("k", "j")], [x, y], **kw)  # noqa: E731
+            r = call()
+            times = [call().device_s for _ in range(3)]
+            t, spread = min(times), (max(times) - min(times)) / min(times)
+            if t_base is None:
+                t_base, spread_base = t, spread
+            err = float(np.abs(r.array[:block, :block] - ref).max() / np.abs(ref).max())
+            lines.append(f"{np.dtype(dt).name:>10} {name:>18} {t:9.5f} {spread:7.3f} {fl / t / 1e12:8.1f} {t_base / t:11.2f} "
+                         f"{t_torch / t:12.2f} {err:9.2e}")
+            print(lines[-1], flush=True)
+            if name == "compute=matrix" and not t * (1 + max(spread, spread_base)) < t_base:
+                notes.append(f"  {np.dtype(dt).name}: compute=matrix is NOT faster than compute=None by more than the spread")
+            del r
+        lines.append(f"{np.dtype(dt).name:>10} {'torch.tensordot':>18} {t_torch:9.5f} {'':>7} {fl / t_torch / 1e12:8.1f} "
+                     f"{t_base / t_torch:11.2f} {1.0:12.2f} {'':>9}")
+        print(lines[-1], flush=True)
+        del ref, x, y
+    lines.extend(notes)
+
+
 def projections(lines, depth, counts, loop_max):
     """P amplitudes per call.  The network: the circuit without its 53 <x| tensors, the open wires its output and
     sparse indices.  The largest depth <= `depth` whose unsliced plan fits the free device memory at every P is used."""
@@ -495,15 +547,19 @@ def main():
     ap.add_argument("--compute", action="store_true", help="only the compute-mode leg, appended to --out")
     ap.add_argument("--path-kernel", action="store_true", help="only the path-kernel leg, appended to --out")
     ap.add_argument("--hoist", action="store_true", help="only the hoisting leg, appended to --out")
+    ap.add_argument("--matrix", action="store_true", help="only the matrix-mode leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist > 1:
-        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel and --hoist each append one leg: run "
-                 "them one after the other")
+    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix > 1:
+        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist and --matrix each append one "
+                 "leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist:  # (the other legs' sections stay as they are)
-        if a.hoist:
+    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix:  # (the other legs' sections stay as they are)
+        if a.matrix:
+            lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
+            matrix(lines, a.n)
+        elif a.hoist:
             lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
             hoist(lines, a.depth, a.max_width, min(a.max_slices, 2048))
         elif a.path_kernel:
@@ -533,6 +589,7 @@ def main():
     compute(lines, a.n, a.depth, a.max_width, a.max_slices)
     path_kernel(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     hoist(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+    matrix(lines, a.n)
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
