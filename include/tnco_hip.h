@@ -494,6 +494,20 @@ const char* tnco_hip_comm_last_error(void);
  * copy 0 and every member reads a kept tensor there; with scaling the exponent slots of copy 0 are copied to every member's
  * slots after the flagged items, in stream order.  Every step runs the kernel it runs unhoisted on the same operands, so
  * the result is bit for bit that of a handle without the call; stats[0] and the launch counts are of what ran.
+ *
+ * Indirect operands (tnco_hip_contract_set_indirect; dtype codes 0..3 only): a step operand that the plan folded is not
+ * permuted into the dense [h][m][k] / [h][k][n] order; it stays where it lies -- a leaf, also one that is not dense after
+ * slicing, read at the slice offset of the assignment, or the arena tensor an earlier step left -- and the step reads its
+ * element (h, m, k) at base + offH[h] + offM[m] + offK[k] (B: offH[h] + offK[k] + offN[n]), three int64 tables of element
+ * offsets per operand in one pool.  Both stride columns of such an operand in `steps` are 0 (create accepts that; a run
+ * of such a handle without the tables is EINVAL), and two tables say where its offsets are:
+ *   ind_steps [n_steps][6]             offsets into ind_maps of the tables of A by h, m, k and of B by h, k, n (H, M, K /
+ *                                      H, K, N entries); the three of an operand that is not folded are -1;
+ *   ind_maps  [n_maps] int64           the pool.
+ * A step with a folded operand runs a twin of the plain kernel of its shape class (contract_indirect.h), every element
+ * the same products in the same order, so the result is bit for bit that of the plan that permutes.  Works with slice
+ * batches and hoisting; steps with row axes, storage dtypes, compute mode 1, matrix mode and the path kernel are not
+ * supported.
  */
 typedef struct tnco_hip_contract_s* tnco_hip_contract;
 typedef struct tnco_hip_contract_desc {
@@ -591,6 +605,21 @@ int tnco_hip_contract_path_launches(tnco_hip_contract h, int64_t* counts);
  * writes over a kept tensor.  Reserves nothing.  A handle on which this was never called, or with no flag set, runs
  * everything per assignment */
 int tnco_hip_contract_set_hoist(tnco_hip_contract h, const int64_t* step_flags, const int64_t* perm_flags);
+/* after create, before run: the offset tables of the folded operands (above).  Validated on the host, so that no table
+ * can send a lane outside its operand: EINVAL when a table does not lie inside the pool, an entry is negative, the base
+ * plus the largest entries of an operand's three tables is not inside its leaf (at the largest slice offset) or the
+ * arena, an operand has some of its three tables but not all, a folded operand has a stride column that is not 0 or an
+ * operand without tables has both 0, or the result of the step overlaps what a folded arena operand reaches.  EINVAL,
+ * each with a text of its own, on a handle with row axes, a storage dtype, compute mode 1, matrix mode or a path kernel;
+ * a handle with tables refuses those three calls in turn.  Uploads both tables (ERUNTIME when they exceed the device's
+ * free memory; the handle then stays as it was); stats[2] counts them.  With no operand folded the handle runs as one on
+ * which this was never called */
+int tnco_hip_contract_set_indirect(tnco_hip_contract h, const int64_t* ind_steps, int64_t n_maps, const int64_t* maps);
+/* counts[TNCO_HIP_CONTRACT_N_IX_KERNELS]: the last run's launches of the kernels that read a folded operand: 0 ix_tiled,
+ * 1 ix_dot, 2 ix_stream.  They are part of stats[1] and, like the row-mapped paths, of no slot of
+ * tnco_hip_contract_kernel_launches */
+#define TNCO_HIP_CONTRACT_N_IX_KERNELS 3
+int tnco_hip_contract_indirect_launches(tnco_hip_contract h, int64_t* counts);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

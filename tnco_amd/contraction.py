@@ -110,6 +110,26 @@ kernel it runs unhoisted on the same shapes and strides, so the result is bit fo
 reads a kept tensor there).  `macs` is the sum of the hoisted steps plus assignments x the sum of the others; the launch
 counts are of what ran; `hoisted` of the plan and of the result is (steps hoisted, permutes hoisted).  Without a sliced
 index, or when nothing is slice-free, the plan and the run are those of `hoist=None`.
+
+Operands read in place: with `indirect=True` (the four plain dtypes; not with `storage`, `compute`, `path_kernel` or
+`projs`) a step operand that would be permuted into the [h][m][k] / [h][k][n] order is *folded* instead: it stays where
+it lies and the step reads its element (h, m, k) at base + offH[h] + offM[m] + offK[k] through three int64 offset tables
+(csrc/contract_indirect.h), the terms separable because h, m and k are disjoint groups of the source's axes.  An operand
+is folded when (a) its source is not slice-free under `hoist=True` -- a permute that hoisting runs once per call stays a
+permute -- and (b) its tables are no larger than the copy they replace, 8 (H + M + K) <= itemsize H M K (B: N for M).
+Everything else of a step is what the plain plan decides -- the roles, the order of the summed indices (chosen as if
+the operand were going to be permuted), the shape class, the layout of the result -- so every sum runs over the same k
+in the same order and the result is bit for bit that of `indirect=None`, with `slices`, `slice_range`, `slice_batch` and
+`hoist` too.  A folded operand keeps its kind and ref: an arena tensor stays where the step before left it and is
+released after the step; a leaf, also one that is not dense after slicing, is read at the slice offset of the
+assignment; its two stride columns in `steps` are 0.  `Plan.ind_steps` [n_steps][6] holds the offsets into the pool
+`Plan.ind_maps` of the tables of A by h, m, k and of B by h, k, n (-1: not folded); a table's entry i is the sum of digit
+x source stride over its group of axes, i linearised as the plain plan linearises the group, a leaf with the strides of
+the full array.  The folded permutes are absent from `perms`, their buffers from the arena; `peak_device_bytes` adds
+8 (ind_steps.size + ind_maps.size); `macs` is unchanged.  `indirect` of the plan and of the result is the number of
+operands folded, `indirect_launches` of the result the launches of the three kernels in INDIRECT_KERNEL_PATHS order (they
+are part of `launches` and of no slot of `kernel_launches`).  With nothing folded the plan and the run are those of
+`indirect=None`.
 """
 from __future__ import annotations
 
@@ -123,7 +143,7 @@ from .app import tn as tnmod
 
 __all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
            "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage", "SCALINGS", "scale_exponent", "scale_to_storage",
-           "MAX_SLICE_BATCH", "COMPUTES", "split_bf16", "MAX_PATH_KERNEL", "MAX_PATH_STEP_MACS"]
+           "MAX_SLICE_BATCH", "COMPUTES", "split_bf16", "MAX_PATH_KERNEL", "MAX_PATH_STEP_MACS", "INDIRECT_KERNEL_PATHS"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -152,6 +172,9 @@ LEAF_SL_W = 1 + 2 * MAX_AXES
 KERNEL_PATHS = ("gather", "tiled_km_nk", "tiled_km_kn", "tiled_mk_nk", "tiled_mk_kn", "dot", "stream")
 # the row-mapped GEMM paths (steps with a row axis) in the order tnco_hip_contract_row_launches counts them
 ROW_KERNEL_PATHS = ("rows_tiled", "rows_dot", "rows_stream")
+# the kernels that read a folded operand in place (indirect=True) in the order tnco_hip_contract_indirect_launches counts them
+INDIRECT_KERNEL_PATHS = ("ix_tiled", "ix_dot", "ix_stream")
+IND_W = 6  # ind_steps: offsets into ind_maps of the tables of A by h, m, k and of B by h, k, n; -1: the operand is not folded
 ROW_W = 5  # row_steps: R, rows of A, map of A, rows of B, map of B (a map: offset into row_maps, -1 none)
 PROJ = "proj"  # the first axis of a projected result
 ALIGN = 64  # arena offsets in elements: 64 x (4..16 B) keeps every buffer 256-byte aligned
@@ -186,6 +209,10 @@ class ContractionResult:
     #                                into the output; `launches` is their sum and the other launch counts are zeros
     hoisted: tuple = None  # hoist=True: (steps, permutes) that ran once per call instead of once per assignment
     #                        (`Plan.hoisted`; of several calls the sums); None without the keyword
+    indirect: int = None  # indirect=True: step operands read in place through offset tables instead of being permuted
+    #                       (`Plan.indirect`; of several calls the sum); None without the keyword
+    indirect_launches: tuple = (0, 0, 0)  # indirect: launches per kernel that reads a folded operand, in
+    #                                       INDIRECT_KERNEL_PATHS order; part of `launches`, of no slot of kernel_launches
     matrix_launches: int = 0  # compute="matrix": launches of the matrix kernel (they are part of their tiled slot of
     #                           kernel_launches)
 
@@ -226,6 +253,10 @@ class Plan:
     perm_hoist: np.ndarray = None  # hoist=True: [n_perms] the same per row of `perms` (within a group the hoisted rows first)
     kept: tuple = ()  # hoist=True: (arena offset, elements) of every slice-free tensor that a step of the assignments reads
     hoisted_macs: int = 0  # multiply-adds of the hoisted steps (they are part of macs_per_slice)
+    indirect: int = None  # indirect=True: the operands folded (read in place through ind_maps); None without the keyword
+    ind_steps: np.ndarray = None  # [n_steps, IND_W]; None when nothing is folded
+    ind_maps: np.ndarray = None  # int64 pool of the offset tables: entry i of a table is the sum of digit x source stride
+    #                              over the table's group of axes, i linearised as the plain plan linearises the group
 
     @property
     def n_slices(self) -> int:
@@ -254,6 +285,8 @@ class Plan:
             batch = self.path_kernel
             stage = item * batch * self.out_numel // math.prod(self.shape[self.inds.index(x)] for x in self.block_inds)
             tables += 8 * (self.steps.size + 2 * (len(self.steps) + 1) + self.slice_range[1] - self.slice_range[0])
+        if self.ind_steps is not None:
+            tables += 8 * (self.ind_steps.size + self.ind_maps.size)
         return held * (int(self.leaf_numel.sum()) + self.arena_elems * batch) + item * self.out_numel + tables + maps + \
             scale * batch + stage
 
@@ -392,6 +425,26 @@ def _check_hoist(hoist, path_kernel=None, projs=None) -> None:
         raise NotImplementedError("'hoist' is not supported with 'path_kernel'.")
     if projs is not None:
         raise NotImplementedError("projections are not supported with 'hoist'.")
+
+
+def _check_indirect(indirect, storage=None, compute=None, path_kernel=None, projs=None) -> None:
+    if indirect is None:
+        return
+    if indirect is not True:
+        raise ValueError("'indirect' must be None or True.")
+    for name, value in (("storage", storage), ("compute", compute), ("path_kernel", path_kernel)):
+        if value is not None:
+            raise NotImplementedError(f"'{name}' is not supported with 'indirect'.")
+    if projs is not None:
+        raise NotImplementedError("projections are not supported with 'indirect'.")
+
+
+def _offset_table(group, st, dims) -> np.ndarray:
+    """Entry i: the sum of digit x st[axis] over the axes of `group`, i the row-major number of the digits."""
+    t = np.zeros(1, np.int64)
+    for x in group:
+        t = (t.reshape(-1, 1) + np.arange(dims[x], dtype=np.int64) * st[x]).reshape(-1)
+    return t
 
 
 def _check_path_steps(p) -> None:
@@ -576,16 +629,17 @@ def _unique_rows(table):
 
 def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
          sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
-         hoist=None) -> Plan:
+         hoist=None, indirect=None) -> Plan:
     """The device plan of one contraction along a path that leaves one tensor (no GPU).
     `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`, `slice_batch`,
-    `compute`, `path_kernel`, `hoist`: see the module docstring."""
+    `compute`, `path_kernel`, `hoist`, `indirect`: see the module docstring."""
     _check_compute(compute, storage, dtype, projs)
     _check_storage(storage, dtype, projs)
     _check_scaling(scaling, storage)
     _check_slice_batch(slice_batch, projs)
     _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
     _check_hoist(hoist, path_kernel, projs)
+    _check_indirect(indirect, storage, compute, path_kernel, projs)
     ts_inds = [tuple(xs) for xs in ts_inds]
     shapes = [tuple(int(d) for d in s) for s in shapes]
     dims = _dims_of(ts_inds, shapes)
@@ -665,6 +719,7 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     buf_size, front, events = [], ([], []), ([], [])
     perms, rows, ops, stage = [], [], [], []
     perm_h, step_h, kept_bufs = [], [], []
+    ind_rows, ind_pool, ind_top = [], [], 0  # indirect: the rows of ind_steps, the tables of ind_maps, their length so far
 
     def new_buf(numel, at_start=False, h=False):
         buf_size.append(numel)
@@ -720,8 +775,21 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         hst = A.free and B.free  # the step is hoisted: both operands are slice-free
         step_h.append(int(hst))
         moved_from = []  # (the permutes of one step run in one launch: their sources are released after both)
-        for T, form, target in ((A, form_a, ra + h + xs + s_order), (B, form_b, rb + h + s_order + ys)):
-            if form is None:
+        ind = [-1] * IND_W
+        for side, (T, form, target) in enumerate(((A, form_a, ra + h + xs + s_order), (B, form_b, rb + h + s_order + ys))):
+            # indirect: an operand that depends on the assignment is read where it lies when its three offset tables
+            # are no larger than the copy they replace; roles, s_order and the result's layout stay as decided above
+            groups = (h, s_order, ys) if side else (h, xs, s_order)
+            if form is None and indirect is True and not T.free and \
+                    8 * sum(size(g) for g in groups) <= np.dtype(dtype).itemsize * size(target):
+                st = strides[T.leaf] if T.leaf is not None else {x: size(T.inds[q + 1:]) for q, x in enumerate(T.inds)}
+                for q, g in enumerate(groups):
+                    ind[3 * side + q] = ind_top
+                    ind_pool.append(_offset_table(g, st, dims))
+                    ind_top += len(ind_pool[-1])
+                if T.leaf is not None:  # (also a leaf that is not dense after slicing: read at its slice offset)
+                    T.kind, T.ref = LEAF, T.leaf
+            elif form is None:
                 ref = permute(T, target, -1 if T.leaf is not None else k)
                 if T.kind == ARENA:
                     moved_from.append((T.ref, T.free))
@@ -730,6 +798,7 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
             events[free].append(("free", q))
         form_a = 0 if form_a is None else form_a
         form_b = 0 if form_b is None else form_b
+        ind_rows.append(ind)
         H, M, N, K = size(h), size(xs), size(ys), size(s_order)
         z = rz + h + xs + ys
         assert not (hst and k == len(steps) - 1)  # (some leaf holds a sliced index, and the last step is above it)
@@ -766,8 +835,10 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
                         row_maps.append(m)
                 row_steps.append([R, size(ra), at[0], size(rb), at[1]])
                 op.update(R=R, folded=False, a_map=maps[0], b_map=maps[1])
-        rows.append([A.kind, A.ref, *((K, 1) if form_a == 0 else (1, M)),
-                     B.kind, B.ref, *((N, 1) if form_b == 0 else (1, K)), c_kind, c_ref, H, M, N, K,
+        if indirect is not None:
+            op.update(ind_a=ind[0] >= 0, ind_b=ind[3] >= 0)
+        rows.append([A.kind, A.ref, *((0, 0) if ind[0] >= 0 else (K, 1) if form_a == 0 else (1, M)),
+                     B.kind, B.ref, *((0, 0) if ind[3] >= 0 else (N, 1) if form_b == 0 else (1, K)), c_kind, c_ref, H, M, N, K,
                      *((A.slot, B.slot) if scaling is not None else (0, 0))])
         ops.append(op)
         for T in (A, B):
@@ -819,6 +890,11 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         p.hoisted = (int(p.step_hoist.sum()), int(perm_h.sum()))
         p.kept = tuple((offset[b], buf_size[b]) for b in kept_bufs)
         p.hoisted_macs = int(sum(int(r[10]) * int(r[11]) * int(r[12]) * int(r[13]) for r, h in zip(rows, step_h) if h))
+    if indirect is not None:  # (with nothing folded the tables are those of the plan without the keyword)
+        p.indirect = sum((row[0] >= 0) + (row[3] >= 0) for row in ind_rows)
+        if p.indirect:
+            p.ind_steps = np.array(ind_rows, np.int64).reshape(-1, IND_W)
+            p.ind_maps = np.concatenate(ind_pool).astype(np.int64)
     if projs is None:
         return p
     # the device holds the distinct rows of the final tensor; the result has one per projection, duplicates included
@@ -880,7 +956,7 @@ def _sub_output(ts_inds, leaves, output) -> frozenset:
 
 def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=None, device=None,
              sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
-             hoist=None, _intermediates=()) -> ContractionResult:
+             hoist=None, indirect=None, _intermediates=()) -> ContractionResult:
     """Contract `arrays` (numpy, in ts_inds order) along the linear `path` on the GPU; see the module docstring.
     A path that leaves several tensors gives lists in `inds` / `array` (the sliced and the projected form need one
     tensor).  `_intermediates` (contract_results): positions of arrays that are results of earlier storage-mode calls,
@@ -897,12 +973,13 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     _check_slice_batch(slice_batch, projs)
     _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
     _check_hoist(hoist, path_kernel, projs)
+    _check_indirect(indirect, storage, compute, path_kernel, projs)
     steps = _check_path(path, len(ts_inds))
     final, out = tnmod.contract(steps, ts_inds, output_inds, dims)
     if len(final) == 1:
         p = plan(steps, ts_inds, [a.shape for a in arrays], out, slices=slices, slice_range=slice_range, dtype=dtype,
                  sparse_inds=sparse_inds, projs=projs, storage=storage, scaling=scaling, slice_batch=slice_batch,
-                 compute=compute, path_kernel=path_kernel, hoist=hoist)
+                 compute=compute, path_kernel=path_kernel, hoist=hoist, indirect=indirect)
         return _run(p, arrays, device, loose)
     if slices:
         raise NotImplementedError("slices need a path that leaves one tensor.")
@@ -912,25 +989,27 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     effective = None if slice_batch is None else 1  # (every part is unsliced: one assignment)
     fused = None if path_kernel is None else 1
     none_hoisted = None if hoist is None else (0, 0)  # (every part is unsliced: nothing to hoist)
+    none_folded = None if indirect is None else 0
     for leaves, sub in _split(steps, len(ts_inds)):
         if not sub:  # a tensor the path does not touch: as the single-leaf plan gives it, rounded to storage
             a = arrays[leaves[0]].astype(dtype, copy=True)
             if scaling is not None:
                 a, e = scale_to_storage(a, storage)
                 parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, scaling=scaling, exponents=(e,),
-                                               slice_batch=effective, path_kernel=fused, hoisted=none_hoisted))
+                                               slice_batch=effective, path_kernel=fused, hoisted=none_hoisted,
+                                               indirect=none_folded))
                 continue
             if storage is not None:
                 a = _from_storage_bits(_storage_bits(a, storage, leaves[0] not in loose), storage, a)
             if compute == "bf16x3" and leaves[0] not in loose:
                 _check_split_range(a)
             parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, slice_batch=effective, compute=compute,
-                                           path_kernel=fused, hoisted=none_hoisted))
+                                           path_kernel=fused, hoisted=none_hoisted, indirect=none_folded))
             continue
         parts.append(contract(sub, [ts_inds[t] for t in leaves], [arrays[t].astype(dtype, copy=False) for t in leaves],
                               _sub_output(ts_inds, leaves, out), device=device, storage=storage, scaling=scaling,
                               slice_batch=slice_batch, compute=compute, path_kernel=path_kernel, hoist=hoist,
-                              _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
+                              indirect=indirect, _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
     assert [tuple(r.inds) for r in parts] == [tuple(f) for f in final]
     return ContractionResult([r.inds for r in parts], [r.array for r in parts], sum(r.macs for r in parts), 1,
                              max(r.peak_device_bytes for r in parts), sum(r.launches for r in parts),
@@ -941,6 +1020,8 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
                              batch_launches=sum(r.batch_launches for r in parts), compute=compute,
                              split_launches=sum(r.split_launches for r in parts), path_kernel=fused,
                              path_launches=_add_counts(*(r.path_launches for r in parts)), hoisted=none_hoisted,
+                             indirect=None if indirect is None else sum(r.indirect for r in parts),
+                             indirect_launches=_add_counts(*(r.indirect_launches for r in parts)),
                              matrix_launches=sum(r.matrix_launches for r in parts))
 
 
@@ -1004,6 +1085,7 @@ def _describe(p: Plan, device: int):
 def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
     from . import _lib
     exponents, narrow, folds, splits, fused, matrix = None, 0, 0, 0, (0, 0), 0
+    through = (0,) * len(INDIRECT_KERNEL_PATHS)
     try:
         if p.compute == "matrix":
             _lib.check(L.tnco_hip_contract_set_matrix(h, 1))
@@ -1018,6 +1100,10 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
         if p.hoisted is not None and any(p.hoisted):  # (nothing hoisted: the run of the plan without the keyword)
             flags = [np.ascontiguousarray(q, np.int64) for q in (p.step_hoist, p.perm_hoist)]
             _lib.check(L.tnco_hip_contract_set_hoist(h, *(q.ctypes.data_as(C.c_void_p) for q in flags)))
+        if p.indirect:  # (nothing folded: the run of the plan without the keyword)
+            tabs = [np.ascontiguousarray(q, np.int64) for q in (p.ind_steps, p.ind_maps)]
+            _lib.check(L.tnco_hip_contract_set_indirect(h, tabs[0].ctypes.data_as(C.c_void_p), tabs[1].size,
+                                                        tabs[1].ctypes.data_as(C.c_void_p)))
         staging = np.empty(p.out_numel, p.dtype)
         ptrs = (C.c_void_p * max(1, len(leaves)))(*[a.ctypes.data for a in leaves])
         _lib.check(L.tnco_hip_contract_run(h, ptrs, staging.ctypes.data_as(C.c_void_p)))
@@ -1049,6 +1135,10 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
             counts = np.zeros(2, np.int64)
             _lib.check(L.tnco_hip_contract_path_launches(h, counts.ctypes.data_as(C.c_void_p)))
             fused = tuple(int(v) for v in counts)
+        if p.indirect:
+            counts = np.zeros(len(INDIRECT_KERNEL_PATHS), np.int64)
+            _lib.check(L.tnco_hip_contract_indirect_launches(h, counts.ctypes.data_as(C.c_void_p)))
+            through = tuple(int(v) for v in counts)
     finally:
         L.tnco_hip_contract_destroy(h)
     array = _host_layout(p, staging)
@@ -1057,7 +1147,7 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
                              row_kernel_launches=tuple(int(v) for v in by_row_kernel), scaling=p.scaling,
                              exponents=exponents, narrow_launches=narrow, slice_batch=p.slice_batch, batch_launches=folds,
                              compute=p.compute, split_launches=splits, path_kernel=p.path_kernel, path_launches=fused,
-                             hoisted=p.hoisted, matrix_launches=matrix)
+                             hoisted=p.hoisted, indirect=p.indirect, indirect_launches=through, matrix_launches=matrix)
 
 
 def _host_layout(p: Plan, staging) -> np.ndarray:
@@ -1079,7 +1169,7 @@ def _host_layout(p: Plan, staging) -> np.ndarray:
 
 def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse_inds=None,
                      storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
-                     hoist=None) -> ContractionResult:
+                     hoist=None, indirect=None) -> ContractionResult:
     """Run a result of `Optimizer.optimize` over the arrays of the network as given.
 
     tn0: the network before pre-fusing (`load_tn(obj, fuse=None)`); arrays: in tn0.tensors order, or {name: array}
@@ -1102,13 +1192,16 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     docstring); the fuse stage stays as it is;
     `path_launches` is the sum over the calls, `path_kernel` of the result the largest effective value of a component.
     hoist: True runs the slice-independent steps and permutes of every call over `result.path` once per call (module
-    docstring); the fuse stage, unsliced, stays as it is; `hoisted` is the sum over the calls."""
+    docstring); the fuse stage, unsliced, stays as it is; `hoisted` is the sum over the calls.
+    indirect: True reads the step operands of every call over `result.path` that would be permuted per assignment in
+    place (module docstring); the fuse stage stays as it is; `indirect` and `indirect_launches` are sums over the calls."""
     _check_compute(compute, storage, np.float32, projs)
     _check_storage(storage, np.float32, projs)
     _check_scaling(scaling, storage)
     _check_slice_batch(slice_batch, projs)
     _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
     _check_hoist(hoist, path_kernel, projs)
+    _check_indirect(indirect, storage, compute, path_kernel, projs)
     if (tn0.sparse_inds or tn.sparse_inds) and projs is None:
         raise NotImplementedError("sparse indices (n_projs) have an array meaning only at given projections: "
                                   "pass projs=, an integer array [P, number of sparse indices].")
@@ -1142,11 +1235,12 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     if len(comp_paths) <= 1:  # one component to contract: the path with its slices, in one call
         r = contract(result.path, tn.ts_inds, arrays, tn.output_inds, slices=getattr(result, "slices", ()),
                      device=device, sparse_inds=sparse_inds or (), projs=projs, storage=storage, scaling=scaling,
-                     slice_batch=slice_batch, compute=compute, path_kernel=path_kernel, hoist=hoist)
+                     slice_batch=slice_batch, compute=compute, path_kernel=path_kernel, hoist=hoist, indirect=indirect)
         return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
                                  fuse_macs, r.kernel_launches, r.row_kernel_launches, r.scaling, r.exponents,
                                  r.narrow_launches, r.slice_batch, r.batch_launches, r.compute, r.split_launches,
-                                 r.path_kernel, r.path_launches, r.hoisted, r.matrix_launches)
+                                 r.path_kernel, r.path_launches, r.hoisted, indirect=r.indirect,
+                                 indirect_launches=r.indirect_launches, matrix_launches=r.matrix_launches)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
     ts, n = [tuple(x) for x in tn.ts_inds], len(tn.ts_inds)
     done, results, macs, n_slices, peak, launches, device_s = set(), [], 0, 0, 0, 0, 0.0
@@ -1154,6 +1248,7 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     exponents, narrow, folds, effective, splits, matrix = None, 0, 0, None, 0, 0
     fused, fused_launches = None, (0, 0)
     hoisted = None if hoist is None else (0, 0)
+    folded, through = None if indirect is None else 0, (0,) * len(INDIRECT_KERNEL_PATHS)
     n_comp_steps = 0
     for q, cut in zip(result.disconnected_paths, result.disconnected_slices):
         if not q:
@@ -1162,9 +1257,11 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         (leaves, sub), = [(lv, s) for lv, s in _split(_check_path(q, n), n) if s]
         r = contract(sub, [ts[t] for t in leaves], [arrays[t] for t in leaves], _sub_output(ts, leaves, tn.output_inds),
                      slices=cut, device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute,
-                     path_kernel=path_kernel, hoist=hoist)
+                     path_kernel=path_kernel, hoist=hoist, indirect=indirect)
         if hoist is not None:
             hoisted = _add_counts(hoisted, r.hoisted)
+        if indirect is not None:
+            folded, through = folded + r.indirect, _add_counts(through, r.indirect_launches)
         exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
         splits, matrix = splits + r.split_launches, matrix + r.matrix_launches
         if slice_batch is not None:
@@ -1185,10 +1282,12 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     if tail:
         r = contract(tail, state_inds, state_arrays, frozenset(tn.output_inds) & {x for xs in state_inds for x in xs},
                      device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute,
-                     path_kernel=path_kernel, hoist=hoist,
+                     path_kernel=path_kernel, hoist=hoist, indirect=indirect,
                      _intermediates=range(len(state_arrays) - len(results), len(state_arrays)))
         if hoist is not None:
             hoisted = _add_counts(hoisted, r.hoisted)
+        if indirect is not None:
+            folded, through = folded + r.indirect, _add_counts(through, r.indirect_launches)
         fused_launches = _add_counts(fused_launches, r.path_launches)
         exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
         splits, matrix = splits + r.split_launches, matrix + r.matrix_launches
@@ -1201,4 +1300,5 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     return ContractionResult(inds, array, macs, n_slices, peak, launches, device_s, fuse_macs, by_kernel,
                              scaling=scaling, exponents=exponents, narrow_launches=narrow, slice_batch=effective,
                              batch_launches=folds, compute=compute, split_launches=splits, path_kernel=fused,
-                             path_launches=fused_launches, hoisted=hoisted, matrix_launches=matrix)
+                             path_launches=fused_launches, hoisted=hoisted, indirect=folded, indirect_launches=through,
+                             matrix_launches=matrix)

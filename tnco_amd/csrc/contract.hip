@@ -36,6 +36,11 @@
 // Hoisting (tnco_hip_contract_set_hoist): the steps and permutes the plan flags -- their operands hold no sliced axis
 // anywhere below them -- run once per run, before the slice loop, as one-member launches of the same kernels; the loop
 // skips them, and a step of the loop reads what they left (a kept tensor) in arena copy 0.  No kernel knows of it.
+// Indirect operands (tnco_hip_contract_set_indirect, contract_indirect.h): a step operand that the plan folded is read
+// where it lies, element (h, m, k) at base + offH[h] + offM[m] + offK[k] through three int64 tables, by
+//   ct_ix_tiled_kernel, ct_ix_dot_kernel, ct_ix_stream_kernel
+//                          the twins of the three plain GEMM kernels, the same sums in the same order; its permute, the
+//                          launch and the arena buffer of the copy are not in the plan.  Plain dtypes only.
 // No atomics in any sum: every sum runs in one fixed order, so a run is bit-reproducible (the one atomic, the integer max
 // behind a scaled tensor's exponent, does not depend on order).
 #include "../../include/tnco_hip.h"
@@ -61,6 +66,7 @@ constexpr int PERM_W = 8 + 2 * CT_MAX_AXES;
 constexpr int STEP_W = 16;
 constexpr int LEAF_SL_W = 1 + 2 * CT_MAX_AXES;
 constexpr int ROW_W = 5;  // row_steps: R, rows of A, map of A, rows of B, map of B
+constexpr int IND_W = 6;  // ind_steps: offsets into the pool of the tables of A by h, m, k and of B by h, k, n; -1: direct
 constexpr int64_t K_LEAF = 0, K_ARENA = 1, K_OUT = 2;
 
 int fail(int code, const std::string& msg) { return tnco::set_error(code, msg); }
@@ -516,6 +522,8 @@ __global__ __launch_bounds__(256) void ct_rows_dot_kernel(RowGemmArgs<T> p) {
   }
 }
 
+#include "contract_indirect.h"
+
 }  // namespace
 
 struct tnco_hip_contract_s {
@@ -545,6 +553,12 @@ struct tnco_hip_contract_s {
   int64_t path_launches[2] = {0, 0};  // launches of ct_path_kernel and of ct_path_reduce_kernel in the last run
   std::vector<char> hoist_step, hoist_perm;  // tnco_hip_contract_set_hoist: the flags; empty: never set, or no flag set
   std::vector<char> kept_opnd;     // [n_steps][2]: the operand is a kept tensor, read in arena copy 0 by every member
+  bool folded = false;             // a step has an operand with both stride columns 0: it runs with indirect tables only
+  std::vector<int64_t> ind_steps;  // tnco_hip_contract_set_indirect: [n_steps][IND_W]; empty: never set, or nothing folded
+  std::vector<char> ind_fast;      // [n_steps][2]: lanes of the tiled kernel stage A along k / B along n
+  int64_t* d_ind = nullptr;        // ind_steps | the pool of the offset tables
+  int64_t ind_bytes = 0;           // what the tables add to `bytes`
+  int64_t by_ix[TNCO_HIP_CONTRACT_N_IX_KERNELS] = {};  // launches of the last run per indirect kernel (tnco_hip.h)
   std::vector<int64_t> hoist_count, hoist_max, rest_max;  // per permute group, at index g + 1: the flagged rows (they come
                                    // first), the largest numel among them and among the others
   int64_t last_member = 0;         // the member that ran the last assignment of the last run (its exponent slots)
@@ -681,8 +695,12 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
       for (int64_t r = 0; r < R; ++r)
         if (c->row_maps[map + r] < 0 || c->row_maps[map + r] >= rows) return "row map entry beyond the operand's rows.";
     }
-    if (!((st[2] == K && st[3] == 1) || (st[2] == 1 && st[3] == M))) return "A strides are not valid.";
-    if (!((st[6] == N && st[7] == 1) || (st[6] == 1 && st[7] == K))) return "B strides are not valid.";
+    // (0, 0): a folded operand, read through the tables of tnco_hip_contract_set_indirect, which a run then needs
+    const bool ind_a = st[2] == 0 && st[3] == 0, ind_b = st[6] == 0 && st[7] == 0;
+    if (!ind_a && !((st[2] == K && st[3] == 1) || (st[2] == 1 && st[3] == M))) return "A strides are not valid.";
+    if (!ind_b && !((st[6] == N && st[7] == 1) || (st[6] == 1 && st[7] == K))) return "B strides are not valid.";
+    if ((ind_a || ind_b) && (d->dtype > 3 || d->row_steps)) return "folded operands need a plain dtype and no row axes.";
+    c->folded |= ind_a || ind_b;
     int64_t lo[2], hi[2];
     for (int side = 0; side < 2; ++side) {
       const int64_t kind = st[4 * side], ref = st[4 * side + 1], n = rw[1 + 2 * side] * H * K * (side ? N : M);
@@ -869,6 +887,31 @@ int launch_rows_gemm(tnco_hip_contract_s* c, const RowGemmArgs<T>& p) {
   return TNCO_HIP_OK;
 }
 
+// launch_gemm for a step with a folded operand: the same thresholds, the kernels of contract_indirect.h
+template <class T>
+int launch_ix_gemm(tnco_hip_contract_s* c, const IxGemmArgs<T>& p, unsigned members = 1) {
+  const int64_t outs = p.H * p.M * p.N;
+  int path;  // slot of tnco_hip_contract_indirect_launches
+  if (p.M >= 64 && p.N >= 64 && p.K > 32) {
+    const int64_t tiles = p.H * ((p.M + TB - 1) / TB) * ((p.N + TB - 1) / TB);
+    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20), 1, members);
+    hipLaunchKernelGGL(ct_ix_tiled_kernel<T>, grid, dim3(256), 0, c->stream, p);
+    path = 0;
+  } else if (p.K >= 512 && outs <= 8192) {
+    hipLaunchKernelGGL(ct_ix_dot_kernel<T>, dim3((unsigned)outs, 1, members), dim3(256), 0, c->stream, p);
+    path = 1;
+  } else {
+    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16), 1, members);
+    hipLaunchKernelGGL(ct_ix_stream_kernel<T>, grid, dim3(256), 0, c->stream, p);
+    path = 2;
+  }
+  CT_TRY(hipGetLastError());
+  c->launches += 1;
+  c->by_ix[path] += 1;
+  c->macs += outs * p.K * members;
+  return TNCO_HIP_OK;
+}
+
 // T: the type of the sums and of the output; E: of the leaves and the arena (storage mode: st_f16 / st_bf16 or a pair)
 template <class T, class E = T>
 int run_impl(tnco_hip_contract_s* c) {
@@ -959,6 +1002,22 @@ int run_impl(tnco_hip_contract_s* c) {
         p.b_row = rw[4] < 0 && rw[3] == 1 ? 0 : p.H * p.K * p.N;
         p.beta = st[8] == K_OUT ? beta : 0;
         return launch_rows_gemm<T>(c, p);
+      }
+      const int64_t* ix = c->ind_steps.empty() ? nullptr : &c->ind_steps[k * IND_W];
+      if (ix && (ix[0] >= 0 || ix[3] >= 0)) {  // a folded operand: read in place through its tables
+        const int64_t* pool = c->d_ind + c->ind_steps.size();
+        IxGemmArgs<T> p;
+        p.A = opnd[0], p.B = opnd[1];
+        p.C = dest;
+        p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
+        p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
+        p.beta = last ? out_beta : 0;
+        p.mb = mb;
+        const bool fa = ix[0] >= 0, fb = ix[3] >= 0;
+        p.a_h = fa ? pool + ix[0] : nullptr, p.a_mo = fa ? pool + ix[1] : nullptr, p.a_ko = fa ? pool + ix[2] : nullptr;
+        p.b_h = fb ? pool + ix[3] : nullptr, p.b_ko = fb ? pool + ix[4] : nullptr, p.b_no = fb ? pool + ix[5] : nullptr;
+        p.a_kfast = c->ind_fast[2 * k], p.b_nfast = c->ind_fast[2 * k + 1];
+        return launch_ix_gemm<T>(c, p, members);
       }
       GemmArgs<T> p;
       p.A = opnd[0], p.B = opnd[1];
@@ -1130,6 +1189,8 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
 
 int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* out) {
   if (!c || !out || (!leaves && !c->leaf_numel.empty())) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (c->folded && c->ind_steps.empty())
+    return fail(TNCO_HIP_EINVAL, "the plan has folded operands: call tnco_hip_contract_set_indirect before the run.");
   CT_TRY(hipSetDevice(c->device));
   for (size_t t = 0; t < c->leaf_numel.size(); ++t) {
     if (!leaves[t]) return fail(TNCO_HIP_EINVAL, "null leaf.");
@@ -1152,6 +1213,7 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
   c->path_launches[0] = c->path_launches[1] = 0;
   std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
   std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
+  std::fill(std::begin(c->by_ix), std::end(c->by_ix), 0);
   CT_TRY(hipEventRecord(c->ev[0], c->stream));
   const bool fused = c->path_group > 0 && n_steps > 0;  // (a plan without steps runs as it does without the call)
   int rc = fused ? (c->dtype == 0 ? run_path<float>(c)
@@ -1269,6 +1331,7 @@ int tnco_hip_contract_set_compute(tnco_hip_contract c, int32_t mode) {
   if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with a compute mode.");
   if (mode && c->path_group) return fail(TNCO_HIP_EINVAL, "a compute mode is not supported with a path kernel.");
   if (mode && c->matrix) return fail(TNCO_HIP_EINVAL, "a compute mode and matrix mode are exclusive.");
+  if (mode && !c->ind_steps.empty()) return fail(TNCO_HIP_EINVAL, "a compute mode is not supported with indirect operands.");
   c->compute = mode;
   return TNCO_HIP_OK;
 }
@@ -1286,6 +1349,7 @@ int tnco_hip_contract_set_matrix(tnco_hip_contract c, int32_t on) {
   if (c->dtype > 3) return fail(TNCO_HIP_EINVAL, "matrix mode needs a plain dtype.");
   if (c->compute) return fail(TNCO_HIP_EINVAL, "a compute mode and matrix mode are exclusive.");
   if (c->path_group) return fail(TNCO_HIP_EINVAL, "matrix mode is not supported with a path kernel.");
+  if (!c->ind_steps.empty()) return fail(TNCO_HIP_EINVAL, "matrix mode is not supported with indirect operands.");
   c->matrix = on;
   return TNCO_HIP_OK;
 }
@@ -1306,6 +1370,7 @@ int tnco_hip_contract_set_path_kernel(tnco_hip_contract c, int64_t group) {
   if (c->matrix) return fail(TNCO_HIP_EINVAL, "matrix mode is not supported with a path kernel.");
   if (c->path_group) return fail(TNCO_HIP_EINVAL, "the path kernel is already set.");
   if (!c->hoist_step.empty()) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with a path kernel.");
+  if (!c->ind_steps.empty() || c->folded) return fail(TNCO_HIP_EINVAL, "a path kernel is not supported with indirect operands.");
   const int64_t S = (int64_t)c->steps.size() / STEP_W;
   for (int64_t k = 0; k < S; ++k) {
     const int64_t* st = &c->steps[k * STEP_W];
@@ -1475,6 +1540,94 @@ int tnco_hip_contract_set_hoist(tnco_hip_contract c, const int64_t* step_flags, 
   return TNCO_HIP_OK;
 }
 
+int tnco_hip_contract_set_indirect(tnco_hip_contract c, const int64_t* ind_steps, int64_t n_maps, const int64_t* maps) {
+  if (!c) return fail(TNCO_HIP_EINVAL, "null argument.");
+  const int64_t S = (int64_t)c->steps.size() / STEP_W;
+  if ((S && !ind_steps) || n_maps < 0 || (n_maps && !maps)) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with indirect operands.");
+  if (c->dtype > 3) return fail(TNCO_HIP_EINVAL, "indirect operands need a plain dtype.");
+  if (c->compute) return fail(TNCO_HIP_EINVAL, "a compute mode is not supported with indirect operands.");
+  if (c->matrix) return fail(TNCO_HIP_EINVAL, "matrix mode is not supported with indirect operands.");
+  if (c->path_group) return fail(TNCO_HIP_EINVAL, "a path kernel is not supported with indirect operands.");
+  // Every table inside the pool, every entry >= 0, and the furthest element the three tables of an operand reach inside
+  // the leaf (at the largest slice offset) or the arena: no table can send a lane outside its operand
+  std::vector<char> fast(2 * S, 0);
+  bool any = false;
+  for (int64_t k = 0; k < S; ++k) {
+    const int64_t* st = &c->steps[k * STEP_W];
+    const int64_t H = st[10], M = st[11], N = st[12], K = st[13];
+    const std::string at = "step " + std::to_string(k) + ": ";
+    for (int side = 0; side < 2; ++side) {
+      const int64_t* o = ind_steps + k * IND_W + 3 * side;
+      const int64_t ext[3] = {H, side ? K : M, side ? N : K};
+      const int64_t s0 = st[4 * side + 2], s1 = st[4 * side + 3];
+      if (o[0] == -1 && o[1] == -1 && o[2] == -1) {
+        if (s0 == 0 && s1 == 0) return fail(TNCO_HIP_EINVAL, at + "an operand with both strides 0 needs its tables.");
+        fast[2 * k + side] = s1 == 1;  // (direct: A contiguous along k, B along n, as the plain kernel stages them)
+        continue;
+      }
+      if (s0 != 0 || s1 != 0) return fail(TNCO_HIP_EINVAL, at + "both stride columns of a folded operand must be 0.");
+      const int64_t kind = st[4 * side], ref = st[4 * side + 1];
+      const int64_t room = kind == K_LEAF ? c->leaf_numel[ref] - leaf_slice_reach(c, ref) : c->arena_elems - ref;
+      int64_t reach = 0, step1[3];
+      for (int q = 0; q < 3; ++q) {
+        if (o[q] < 0 || o[q] > n_maps || ext[q] > n_maps - o[q]) return fail(TNCO_HIP_EINVAL, at + "an offset table lies outside the pool.");
+        int64_t largest = 0;
+        for (int64_t i = 0; i < ext[q]; ++i) {
+          const int64_t v = maps[o[q] + i];
+          if (v < 0) return fail(TNCO_HIP_EINVAL, at + "an offset table has a negative entry.");
+          if (v >= room) return fail(TNCO_HIP_EINVAL, at + "an offset table reaches beyond its operand.");
+          largest = std::max(largest, v);
+        }
+        reach += largest;
+        step1[q] = ext[q] > 1 ? maps[o[q] + 1] - maps[o[q]] : INT64_MAX;
+        if (step1[q] <= 0) step1[q] = INT64_MAX;
+      }
+      if (reach >= room) return fail(TNCO_HIP_EINVAL, at + "an offset table reaches beyond its operand.");
+      // (the result of the step, in the arena, apart from everything a folded arena operand reaches)
+      if (kind == K_ARENA && st[8] == K_ARENA && st[9] <= ref + reach && ref < st[9] + H * M * N)
+        return fail(TNCO_HIP_EINVAL, at + "step result overlaps a folded operand.");
+      // tiled kernel: lanes along k of A (n of B) when that table has the smaller step, the source's innermost axis
+      fast[2 * k + side] = step1[2] <= step1[1];  // (the tables of A: h, m, k; of B: h, k, n)
+      any = true;
+    }
+  }
+  if (!any) {  // nothing folded: the handle runs as one on which this was never called
+    if (c->d_ind) (void)hipFree(c->d_ind);
+    c->d_ind = nullptr, c->bytes -= c->ind_bytes, c->ind_bytes = 0;
+    c->ind_steps.clear(), c->ind_fast.clear();
+    return TNCO_HIP_OK;
+  }
+  CT_TRY(hipSetDevice(c->device));
+  CT_TRY(hipStreamSynchronize(c->stream));
+  std::vector<int64_t> image(ind_steps, ind_steps + S * IND_W);
+  image.insert(image.end(), maps, maps + n_maps);
+  const int64_t bytes = (int64_t)image.size() * 8;
+  size_t free_b = 0, total_b = 0;
+  CT_TRY(hipMemGetInfo(&free_b, &total_b));
+  if ((size_t)bytes > free_b)
+    return fail(TNCO_HIP_ERUNTIME, "the offset tables need " + std::to_string(bytes) + " bytes of device memory, " +
+                                       std::to_string(free_b) + " are free.");
+  // the new buffer first: a handle that this call fails on stays as it was
+  int64_t* d_new = nullptr;
+  if (hipMalloc((void**)&d_new, (size_t)bytes) != hipSuccess ||
+      hipMemcpyAsync(d_new, image.data(), (size_t)bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) {
+    if (d_new) (void)hipFree(d_new);
+    return fail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+  }
+  if (c->d_ind) (void)hipFree(c->d_ind);
+  c->d_ind = d_new, c->bytes += bytes - c->ind_bytes, c->ind_bytes = bytes;
+  c->ind_steps.assign(ind_steps, ind_steps + S * IND_W), c->ind_fast = fast;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_indirect_launches(tnco_hip_contract c, int64_t* counts) {
+  if (!c || !counts) return fail(TNCO_HIP_EINVAL, "null argument.");
+  std::copy(std::begin(c->by_ix), std::end(c->by_ix), counts);
+  return TNCO_HIP_OK;
+}
+
 int tnco_hip_contract_batch_launches(tnco_hip_contract c, int64_t* count) {
   if (!c || !count) return fail(TNCO_HIP_EINVAL, "null argument.");
   *count = c->batch_launches;
@@ -1485,7 +1638,7 @@ void tnco_hip_contract_destroy(tnco_hip_contract c) {
   if (!c) return;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_leaves, c->d_arena, c->d_out, (void*)c->d_tables, (void*)c->d_leaf_ptrs, (void*)c->d_row_maps,
-                  (void*)c->d_exps, c->d_batch_out, c->d_path_stage, (void*)c->d_path_tables})
+                  (void*)c->d_exps, c->d_batch_out, c->d_path_stage, (void*)c->d_path_tables, (void*)c->d_ind})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);

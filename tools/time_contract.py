@@ -17,7 +17,9 @@ storage="bfloat16" in one process, and the sliced Sycamore leg with compute=None
 process); hoisting (`--hoist`: the sliced Sycamore leg with hoist=None and hoist=True, unbatched and with
 slice_batch=64, in one process); the matrix mode (`--matrix`: the large square step in the four dtypes with compute=None
 and compute="matrix", in float32 and complex64 also with compute="bf16x3" and storage="bfloat16", and torch, in one
-process).  Engine figures are its
+process); operands read in place (`--indirect`: the sliced Sycamore leg with slice_batch None and 64, hoist None and True,
+each with indirect=None and indirect=True, and one bandwidth-bound step whose 2^26-element operand lies in reversed axis
+order, in one process).  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device).
 """
@@ -373,6 +375,82 @@ def hoist(lines, depth, max_width, max_slices):
             del r
 
 
+def indirect(lines, depth, max_width, max_slices):
+    """Operands read in place against the permutes they replace, all in this process: the sliced Sycamore amplitude of the
+    storage leg, complex64, with slice_batch None and 64, hoist None and True, each with indirect=None and indirect=True;
+    and one bandwidth-bound step, a complex64 operand of 2^26 elements whose 26 axes of dimension 2 lie in reversed order,
+    summed over four axes in its middle with a vector (the stream class).  Device time: the minimum and the spread of
+    three runs after a warm-up; every indirect result is compared bit for bit with the run without the keyword."""
+    lines.append("")
+    ts, d, o = syn.sycamore53_tn(depth=depth)
+    tn0 = tnmod.TensorNetwork([tnmod.Tensor(xs, [d] * len(xs)) for xs in ts], output_inds=o)
+    tn, res = Optimizer(method="sa", max_width=max_width, seed=0).optimize(tn0, betas=(0, 50), n_steps=200, n_runs=256)
+    r0 = res[0]
+    rng = np.random.RandomState(2)
+    n_inds = len({x for xs in ts for x in xs})
+    scale = 2.0 ** (-n_inds / (2 * len(ts)))  # (as in the storage leg: the amplitude stays near 1)
+    arrays = [(_rand(tuple(d for _ in xs), np.complex64, rng) * scale).astype(np.complex64) for xs in ts]
+    fused = ctr.contract(tn.tags["fuse_path"], tn0.ts_inds, arrays, tn0.output_inds)
+    leaves = fused.array if isinstance(fused.array, list) else [fused.array]
+    shapes = [a.shape for a in leaves]
+    p0 = ctr.plan(r0.path, tn.ts_inds, shapes, tn.output_inds, slices=r0.slices)
+    m = min(p0.n_slices, max_slices)
+    folds = {h: ctr.plan(r0.path, tn.ts_inds, shapes, tn.output_inds, slices=r0.slices, hoist=h, indirect=True)
+             for h in (None, True)}
+    lines.append(f"## indirect, sliced Sycamore-53 amplitude, depth {depth}, complex64, max_width {max_width}, cost {r0.cost}, "
+                 f"{len(r0.path)} steps and {len(p0.perms)} permutes, of which indirect=True folds {folds[None].indirect} "
+                 f"({folds[True].indirect} beside hoist=True, which runs {folds[True].hoisted[1]} once per call), offset tables "
+                 f"{folds[None].ind_maps.size} entries, assignments [0, {m}) of {p0.n_slices}: device seconds are the minimum of "
+                 "three runs after a warm-up, spread = (max - min) / min of the three; all runs in one process")
+    head = (f"{'setting':>44} {'device s':>9} {'spread':>7} {'None / this':>11} {'us / slice':>10} {'launches':>9} "
+            f"{'indirect launches':>18} {'peak bytes':>11} {'bits equal None':>15}")
+    lines.append(head)
+    notes = []
+
+    def rows(label, call_of, metric=lambda t, r: t / r.n_slices * 1e6):
+        base = t_base = spread_base = None
+        for ind in (None, True):
+            call = lambda ind=ind: call_of(ind)  # noqa: E731
+            r = call()
+            times = [call().device_s for _ in range(3)]
+            t, spread = min(times), (max(times) - min(times)) / min(times)
+            if ind is None:
+                base, t_base, spread_base = r.array, t, spread
+            same = np.array_equal(np.ravel(r.array).view(np.uint32), np.ravel(base).view(np.uint32))
+            lines.append(f"{f'{label} indirect={ind}':>44} {t:9.4f} {spread:7.3f} {t_base / t:11.2f} "
+                         f"{metric(t, r):10.2f} "
+                         f"{r.launches:9d} {str(r.indirect_launches):>18} {r.peak_device_bytes:11d} {str(bool(same)):>15}")
+            print(lines[-1], flush=True)
+            if ind and t > t_base * (1 + max(spread, spread_base)):
+                notes.append(f"  {label}: indirect=True is SLOWER than indirect=None by more than the spread")
+            del r
+
+    for B in (None, 64):
+        for h in (None, True):
+            rows(f"slice_batch={B} hoist={h}",
+                 lambda ind, B=B, h=h: ctr.contract(r0.path, tn.ts_inds, leaves, tn.output_inds, slices=r0.slices,
+                                                    slice_range=(0, m), slice_batch=B, hoist=h, indirect=ind))
+    del leaves, arrays
+    # the bandwidth-bound step: X (x25, ..., x0), 2^26 complex64, summed over x13..x10 with Y (x13, ..., x10): M = 2^22
+    # around K = 16, N = 1, the stream class; the plain plan permutes X (a read and a write of 512 MiB) before it reads
+    # the copy
+    nx, ks = 26, (13, 12, 11, 10)
+    xs = tuple(f"x{q}" for q in reversed(range(nx)))
+    ys = tuple(f"x{q}" for q in ks)
+    x, y = _rand((2,) * nx, np.complex64, rng), _rand((2,) * len(ks), np.complex64, rng)
+    q = ctr.plan([(0, 1)], [xs, ys], [x.shape, y.shape], dtype=np.complex64, indirect=True)
+    op = q.ops[0]
+    lines.append(f"## indirect, one bandwidth-bound step: X complex64, 2^{nx} elements, axes of dimension 2 in reversed "
+                 "order, "
+                 f"Z = sum over {len(ks)} axes in its middle of X Y: M N K = {op['M']} x {op['N']} x {op['K']} (stream class), "
+                 f"{q.indirect} operand folded, offset tables {q.ind_maps.size} entries; effective GB/s = (X + Z bytes) / time")
+    lines.append(head.replace("us / slice", "      GB/s"))
+    moved = x.nbytes + x.nbytes // op["K"]
+    rows("reversed 2^26", lambda ind: ctr.contract([(0, 1)], [xs, ys], [x, y], indirect=ind),
+         lambda t, r: moved / t / 1e9)
+    lines.extend(notes)
+
+
 def compute(lines, n, depth, max_width, max_slices):
     """The compute mode against the plain engine in the same process: the large square step with compute=None (the tiled
     LDS kernel, the yardstick), compute="bf16x3" (ct_split_tiled_kernel) and storage="bfloat16" (ct_mfma_tiled_kernel), and
@@ -548,15 +626,19 @@ def main():
     ap.add_argument("--path-kernel", action="store_true", help="only the path-kernel leg, appended to --out")
     ap.add_argument("--hoist", action="store_true", help="only the hoisting leg, appended to --out")
     ap.add_argument("--matrix", action="store_true", help="only the matrix-mode leg, appended to --out")
+    ap.add_argument("--indirect", action="store_true", help="only the indirect-operand leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix > 1:
-        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist and --matrix each append one "
-                 "leg: run them one after the other")
+    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect > 1:
+        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix and --indirect each "
+                 "append one leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix:  # (the other legs' sections stay as they are)
-        if a.matrix:
+    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect:  # (the other legs' sections stay as they are)
+        if a.indirect:
+            lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
+            indirect(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+        elif a.matrix:
             lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
             matrix(lines, a.n)
         elif a.hoist:
@@ -590,6 +672,7 @@ def main():
     path_kernel(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     hoist(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     matrix(lines, a.n)
+    indirect(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
