@@ -495,6 +495,22 @@ const char* tnco_hip_comm_last_error(void);
  * slots after the flagged items, in stream order.  Every step runs the kernel it runs unhoisted on the same operands, so
  * the result is bit for bit that of a handle without the call; stats[0] and the launch counts are of what ran.
  *
+ * Reuse (tnco_hip_contract_set_reuse): hoisting with as many levels as there are sliced indices.  Assignment a gives
+ * sliced index j the value (a / place[j]) % dim[j], place[j] the product of the dimensions after j, so a tensor whose
+ * leaves hold the sliced indices D has one value for all a with equal a / min place[D] (a / number of assignments when D
+ * is empty).  The plan gives every step and permute that number as its period, and an item runs at assignment a iff a
+ * is slice_start or a % period == 0.  The items of one period are a phase; at an assignment the phases that are due run
+ * one after the other, the largest period first, each as the plain loop runs an assignment: the rows of permute group -1
+ * of that period (one gather launch, sized by the largest of them), then for each step k the rows of its group of that
+ * period and the step itself when it has that period.  A tensor whose reader has a smaller period than its writer is
+ * kept: it stays where it is until its writer is due again.  A slower phase may use the room of a faster phase's kept
+ * tensors for its temporaries -- whenever it is due, every faster phase is due after it and writes them again -- which
+ * is why the phases do not interleave in path order.  With scaling the exponent slot of a kept tensor stays as written;
+ * an assignment clears the max words only.  Every step runs the kernel it runs in the plain loop on the same operands,
+ * so the result is bit for bit that of a handle without the call; stats[0] and the launch counts are of what ran.
+ * Works with storage dtypes, scaling, compute mode 1, matrix mode and indirect operands; not with row axes, slice
+ * batches, the path kernel or hoisting (which is its two-level case).
+ *
  * Indirect operands (tnco_hip_contract_set_indirect; dtype codes 0..3 only): a step operand that the plan folded is not
  * permuted into the dense [h][m][k] / [h][k][n] order; it stays where it lies -- a leaf, also one that is not dense after
  * slicing, read at the slice offset of the assignment, or the arena tensor an earlier step left -- and the step reads its
@@ -605,6 +621,16 @@ int tnco_hip_contract_path_launches(tnco_hip_contract h, int64_t* counts);
  * writes over a kept tensor.  Reserves nothing.  A handle on which this was never called, or with no flag set, runs
  * everything per assignment */
 int tnco_hip_contract_set_hoist(tnco_hip_contract h, const int64_t* step_flags, const int64_t* perm_flags);
+/* after create, before run: step_period[n_steps] and perm_period[n_perms] (in the rows' order), the period of every item
+ * (above).  EINVAL, each with a text of its own and the handle left as it was: for a period that is neither the place of
+ * a sliced index nor the number of assignments; on a handle with row axes, a path kernel, a slice batch or hoist flags
+ * (each of those calls refuses a handle with periods in turn); for a step or permute that writes the output with a
+ * period other than 1; for a permute group whose rows are not ordered by period, the largest first; for an item with a
+ * larger period than a leaf it reads allows (the smallest place of the leaf's sliced axes of a dimension above 1) or
+ * than the item that wrote its arena operand or source; and when an item writes into a kept tensor after its writer
+ * in the writer's phase, or in any faster phase.  Reserves nothing.  A handle on which this was never called, or with every period 1, runs everything
+ * per assignment */
+int tnco_hip_contract_set_reuse(tnco_hip_contract h, const int64_t* step_period, const int64_t* perm_period);
 /* after create, before run: the offset tables of the folded operands (above).  Validated on the host, so that no table
  * can send a lane outside its operand: EINVAL when a table does not lie inside the pool, an entry is negative, the base
  * plus the largest entries of an operand's three tables is not inside its leaf (at the largest slice offset) or the

@@ -93,7 +93,8 @@ EXPORTS = [
     "tnco_hip_contract_narrow_launches", "tnco_hip_contract_set_slice_batch", "tnco_hip_contract_batch_launches",
     "tnco_hip_contract_set_compute", "tnco_hip_contract_split_launches", "tnco_hip_contract_set_matrix",
     "tnco_hip_contract_matrix_launches", "tnco_hip_contract_set_path_kernel",
-    "tnco_hip_contract_path_launches", "tnco_hip_contract_set_hoist", "tnco_hip_contract_set_indirect",
+    "tnco_hip_contract_path_launches", "tnco_hip_contract_set_hoist", "tnco_hip_contract_set_reuse",
+    "tnco_hip_contract_set_indirect",
     "tnco_hip_contract_indirect_launches", "tnco_hip_contract_destroy",
     "tnco_hip_device_name", "tnco_hip_device_count", "tnco_hip_last_error", "tnco_hip_version",
 ]
@@ -210,6 +211,7 @@ def load() -> C.CDLL:
     L.tnco_hip_contract_set_path_kernel.argtypes = [vp, i64]
     L.tnco_hip_contract_path_launches.argtypes = [vp, vp]
     L.tnco_hip_contract_set_hoist.argtypes = [vp, vp, vp]
+    L.tnco_hip_contract_set_reuse.argtypes = [vp, vp, vp]
     L.tnco_hip_contract_set_indirect.argtypes = [vp, vp, i64, vp]
     L.tnco_hip_contract_indirect_launches.argtypes = [vp, vp]
     L.tnco_hip_contract_destroy.argtypes = [vp]

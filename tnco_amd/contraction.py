@@ -111,6 +111,34 @@ reads a kept tensor there).  `macs` is the sum of the hoisted steps plus assignm
 counts are of what ran; `hoisted` of the plan and of the result is (steps hoisted, permutes hoisted).  Without a sliced
 index, or when nothing is slice-free, the plan and the run are those of `hoist=None`.
 
+Reuse: with `reuse=True` (not with `hoist`, which it includes, nor with `slice_batch`, `path_kernel` or `projs`) a step or
+permute runs only at the assignments that change a sliced index below it.  With the sliced indices s_0 .. s_{L-1} in
+`Plan.slice_inds` order, place[j] the product of the dimensions after s_j and n their product, assignment a gives s_j
+the value (a // place[j]) % dim(s_j).  dep(T) is the set of sliced indices (of a dimension above 1: one of dimension 1
+never changes) held by a leaf below the tensor T, per(T) the smallest place in dep(T), n when dep(T) is empty: T has one
+value for all a with equal a // per(T).  A step has the period of its result, min(per(A), per(B)); a permute that of its
+source.  An item of period P is due at assignment a of slice_range = (lo, hi) iff a == lo or a % P == 0, so it runs
+1 + (hi - 1) // P - lo // P times.  A tensor is kept when its reader has a smaller period than its writer: its buffer is
+never released (`Plan.kept`, `Plan.kept_period`).  The items of one period are a phase.  The arena is planned on one
+allocator with the phases in order of descending period, the events of a phase in path order, its temporaries released
+and the kept buffers not; at an assignment the phases that are due run slowest first, each in path order (the rows of a
+permute group that have one period are contiguous, the slowest first: one gather launch).  Roles, summed order, shape
+class, result layout and kernel of every step are the plain plan's, so the result is bit for bit that of `reuse=None`
+under the same `slice_order`, in the four dtypes and with `slice_range`, `storage`, `scaling`, `compute` and `indirect`
+(an operand is folded iff its tables are small enough, its source is not slice-free and has the period of the step; the
+permute of a slower source stays, runs at the source's period, and its copy is kept).  With scaling the exponent slot
+of a kept tensor stays as written until its writer is due again.  `Plan.step_period` / `Plan.perm_period` are the
+periods, `macs` is the sum over the steps of runs x H M N K, `reused` of the plan and of the result is (steps, permutes)
+with a period above 1.  Without a sliced index, or when every period is 1, the plan and the run are those of
+`reuse=None`.
+
+Slice order: `slice_order=` (not with `projs`) gives the order of `Plan.slice_inds`, the slowest index first: a sequence
+that names every sliced index once, or "reuse" (needs `reuse=True`).  The slice numbers of `slice_range` and the order in
+which the assignments are summed follow it, so the bits may differ from `slice_order=None`, the default order (first
+appearance in `ts_inds`); a call stays bit-reproducible.  "reuse" places the fastest index first: of the indices not yet
+placed the one with the smallest sum of H M N K over the steps that hold it and that no faster index covers yet, of equal
+ones the later in the default order; it keeps the default order unless that one has strictly fewer multiply-adds.
+
 Operands read in place: with `indirect=True` (the four plain dtypes; not with `storage`, `compute`, `path_kernel` or
 `projs`) a step operand that would be permuted into the [h][m][k] / [h][k][n] order is *folded* instead: it stays where
 it lies and the step reads its element (h, m, k) at base + offH[h] + offM[m] + offK[k] through three int64 offset tables
@@ -135,6 +163,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from collections import defaultdict
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -209,6 +238,8 @@ class ContractionResult:
     #                                into the output; `launches` is their sum and the other launch counts are zeros
     hoisted: tuple = None  # hoist=True: (steps, permutes) that ran once per call instead of once per assignment
     #                        (`Plan.hoisted`; of several calls the sums); None without the keyword
+    reused: tuple = None  # reuse=True: (steps, permutes) that ran only at the assignments that change their slices
+    #                       (`Plan.reused`; of several calls the sums); None without the keyword
     indirect: int = None  # indirect=True: step operands read in place through offset tables instead of being permuted
     #                       (`Plan.indirect`; of several calls the sum); None without the keyword
     indirect_launches: tuple = (0, 0, 0)  # indirect: launches per kernel that reads a folded operand, in
@@ -251,12 +282,18 @@ class Plan:
     hoisted: tuple = None  # hoist=True: (steps hoisted, permutes hoisted); None without the keyword
     step_hoist: np.ndarray = None  # hoist=True: [n_steps] 1 where the step runs once per call, before the first assignment
     perm_hoist: np.ndarray = None  # hoist=True: [n_perms] the same per row of `perms` (within a group the hoisted rows first)
-    kept: tuple = ()  # hoist=True: (arena offset, elements) of every slice-free tensor that a step of the assignments reads
+    kept: tuple = ()  # hoist=True: (arena offset, elements) of every slice-free tensor that a step of the assignments reads;
+    #                   reuse=True: of every tensor whose reader has a smaller period than its writer
     hoisted_macs: int = 0  # multiply-adds of the hoisted steps (they are part of macs_per_slice)
     indirect: int = None  # indirect=True: the operands folded (read in place through ind_maps); None without the keyword
     ind_steps: np.ndarray = None  # [n_steps, IND_W]; None when nothing is folded
     ind_maps: np.ndarray = None  # int64 pool of the offset tables: entry i of a table is the sum of digit x source stride
     #                              over the table's group of axes, i linearised as the plain plan linearises the group
+    reused: tuple = None  # reuse=True: (steps, permutes) with a period above 1; None without the keyword
+    step_period: np.ndarray = None  # reuse=True: [n_steps] the step runs at assignment a iff a is the first of slice_range
+    #                                 or a % period == 0; a period is a place of a sliced index or the number of assignments
+    perm_period: np.ndarray = None  # reuse=True: [n_perms] the same per row of `perms` (within a group the slowest rows first)
+    kept_period: tuple = ()  # reuse=True: per entry of `kept` the period of the item that writes it
 
     @property
     def n_slices(self) -> int:
@@ -264,6 +301,9 @@ class Plan:
 
     @property
     def macs(self) -> int:
+        if self.step_period is not None:  # every step as often as it is due
+            return sum(_runs(int(P), *self.slice_range) * int(r[10]) * int(r[11]) * int(r[12]) * int(r[13])
+                       for P, r in zip(self.step_period, self.steps))
         return self.hoisted_macs + (self.macs_per_slice - self.hoisted_macs) * (self.slice_range[1] - self.slice_range[0])
 
     @property
@@ -425,6 +465,88 @@ def _check_hoist(hoist, path_kernel=None, projs=None) -> None:
         raise NotImplementedError("'hoist' is not supported with 'path_kernel'.")
     if projs is not None:
         raise NotImplementedError("projections are not supported with 'hoist'.")
+
+
+def _check_reuse(reuse, hoist=None, slice_batch=None, path_kernel=None, projs=None) -> None:
+    if reuse is None:
+        return
+    if reuse is not True:
+        raise ValueError("'reuse' must be None or True.")
+    if hoist is not None:
+        raise ValueError("'reuse' includes 'hoist': give one of them.")
+    for name, value in (("slice_batch", slice_batch), ("path_kernel", path_kernel)):
+        if value is not None:
+            raise NotImplementedError(f"'{name}' is not supported with 'reuse'.")
+    if projs is not None:
+        raise NotImplementedError("projections are not supported with 'reuse'.")
+
+
+SLICE_ORDER_ERROR = "'slice_order' must be None, 'reuse' or every sliced index once."
+
+
+def _check_slice_order(slice_order, reuse=None, projs=None) -> None:
+    """What can be said without the network: that a sequence names every sliced index once is checked where they are known."""
+    if slice_order is None:
+        return
+    if isinstance(slice_order, str):
+        if slice_order != "reuse":
+            raise ValueError(SLICE_ORDER_ERROR)
+        if reuse is not True:
+            raise ValueError("slice_order='reuse' needs reuse=True.")
+    else:
+        try:
+            if len(set(slice_order)) != len(tuple(slice_order)):
+                raise ValueError(SLICE_ORDER_ERROR)
+        except TypeError as e:
+            raise ValueError(SLICE_ORDER_ERROR) from e
+    if projs is not None:
+        raise NotImplementedError("projections are not supported with 'slice_order'.")
+
+
+def _named_order(slice_order, slice_inds) -> tuple:
+    """`slice_inds` in the order of the sequence `slice_order`, which must name each of them once."""
+    order = tuple(slice_order)
+    if len(order) != len(slice_inds) or set(order) != set(slice_inds):
+        raise ValueError(SLICE_ORDER_ERROR)
+    return order
+
+
+def _runs(period: int, lo: int, hi: int) -> int:
+    """The assignments a of [lo, hi) at which an item of that period is due: a == lo or a % period == 0."""
+    return 1 + (hi - 1) // period - lo // period
+
+
+def _reuse_macs(order, deps, each, dims, lo, hi) -> int:
+    """The multiply-adds of a run under reuse=True with the sliced indices in `order`: deps[k] the sliced indices below
+    step k, each[k] its H M N K."""
+    place, n = {}, 1
+    for x in reversed(order):
+        place[x], n = n, n * dims[x]
+    return sum(_runs(min((place[x] for x in d), default=n), lo, hi) * m for d, m in zip(deps, each))
+
+
+def _reuse_order(default, deps, each) -> tuple:
+    """slice_order="reuse": the fastest place first, each time the index with the least multiply-adds in the steps that
+    hold it and that no faster index covers yet; of equal ones the later of `default`."""
+    left, covered, fastest_first = list(default), set(), []
+    while left:
+        cost = {x: sum(m for k, (d, m) in enumerate(zip(deps, each)) if k not in covered and x in d) for x in left}
+        x = min(reversed(left), key=cost.get)
+        fastest_first.append(x)
+        left.remove(x)
+        covered |= {k for k, d in enumerate(deps) if x in d}
+    return tuple(reversed(fastest_first))
+
+
+def _step_deps(steps, ts_inds, sl) -> list:
+    """Per step of the path: the indices of `sl` that the leaves below its result hold."""
+    live = [frozenset(x for x in xs if x in sl) for xs in ts_inds]
+    out = []
+    for a, b in steps:
+        db, da = live.pop(b), live.pop(a)
+        live.append(da | db)
+        out.append(da | db)
+    return out
 
 
 def _check_indirect(indirect, storage=None, compute=None, path_kernel=None, projs=None) -> None:
@@ -629,10 +751,10 @@ def _unique_rows(table):
 
 def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
          sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
-         hoist=None, indirect=None) -> Plan:
+         hoist=None, indirect=None, reuse=None, slice_order=None) -> Plan:
     """The device plan of one contraction along a path that leaves one tensor (no GPU).
     `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`, `slice_batch`,
-    `compute`, `path_kernel`, `hoist`, `indirect`: see the module docstring."""
+    `compute`, `path_kernel`, `hoist`, `indirect`, `reuse`, `slice_order`: see the module docstring."""
     _check_compute(compute, storage, dtype, projs)
     _check_storage(storage, dtype, projs)
     _check_scaling(scaling, storage)
@@ -640,6 +762,20 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
     _check_hoist(hoist, path_kernel, projs)
     _check_indirect(indirect, storage, compute, path_kernel, projs)
+    _check_reuse(reuse, hoist, slice_batch, path_kernel, projs)
+    _check_slice_order(slice_order, reuse, projs)
+    if isinstance(slice_order, str):  # "reuse": the default order unless the greedy one has strictly fewer multiply-adds
+        mode = dict(slices=slices, slice_range=slice_range, dtype=dtype, storage=storage, scaling=scaling, compute=compute,
+                    indirect=indirect, reuse=reuse)
+        p = plan(path, ts_inds, shapes, output_inds, **mode)
+        dims = dict(zip(p.slice_inds, p.slice_dims))
+        deps = _step_deps(_check_path(path, len(p.leaf_numel)), [tuple(xs) for xs in ts_inds],
+                          frozenset(x for x in slices if dims[x] > 1))
+        each = [int(r[10]) * int(r[11]) * int(r[12]) * int(r[13]) for r in p.steps]
+        greedy = _reuse_order(p.slice_inds, deps, each)
+        if greedy != p.slice_inds and _reuse_macs(greedy, deps, each, dims, *p.slice_range) < p.macs:
+            p = plan(path, ts_inds, shapes, output_inds, slice_order=greedy, **mode)
+        return p
     ts_inds = [tuple(xs) for xs in ts_inds]
     shapes = [tuple(int(d) for d in s) for s in shapes]
     dims = _dims_of(ts_inds, shapes)
@@ -686,6 +822,8 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     if not sl <= set(every):
         raise ValueError("'slices' has indices not in 'ts_inds'.")
     slice_inds = tuple(x for x in every if x in sl)
+    if slice_order is not None:
+        slice_inds = _named_order(slice_order, slice_inds)
     slice_dims = tuple(dims[x] for x in slice_inds)
     n_slices = math.prod(slice_dims)
     lo, hi = (0, n_slices) if slice_range is None else (int(slice_range[0]), int(slice_range[1]))
@@ -695,6 +833,15 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         raise NotImplementedError(f"tensors with more than {MAX_AXES} axes (after slicing) are not supported.")
     size = lambda xs: math.prod(dims[x] for x in xs)  # noqa: E731
     slot = {x: k for k, x in enumerate(slice_inds)}
+    place = {x: math.prod(slice_dims[k + 1:]) for k, x in enumerate(slice_inds)}
+
+    # The period of a tensor whose leaves hold the sliced indices `dep`: it has one value for all assignments a with
+    # equal a // period.  reuse: the smallest place of `dep`, the number of assignments when `dep` is empty.  hoist is the
+    # two-level case and needs ranks only: 2 for a slice-free tensor, 1 for every other.  Without either: 1
+    def period(dep):
+        if reuse is True:
+            return min((place[x] for x in dep), default=n_slices)
+        return 2 if hoist is True and bool(sl) and not dep else 1
 
     leaf_numel = np.array([math.prod(s) for s in shapes], np.int64)
     leaf_sl = np.zeros((len(ts_inds), LEAF_SL_W), np.int64)
@@ -712,16 +859,20 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         dense = all(st[x] == size(kept[k + 1:]) for k, x in enumerate(kept))
         live.append(_Live(kept, LEAF if dense else None, t, t))
         live[-1].slot = t  # (scaling: the exponent slot; a permute keeps it)
-        live[-1].free = hoist is True and bool(sl) and not cut  # hoist: slice-free, no leaf below it holds a sliced index
+        # slice-free: no leaf below it holds a sliced index (it runs once per call; `indirect` leaves its permutes alone).
+        # reuse: a sliced index of dimension 1 has one value in every assignment and counts as not held
+        moving = frozenset(x for x in cut if dims[x] > 1) if reuse is True else frozenset(cut)
+        live[-1].dep, live[-1].per = moving, period(moving)
+        live[-1].free = bool(sl) and not moving and (hoist is True or (reuse is True and n_slices > 1))
 
-    # buffers are symbolic (numbers) until the event list is replayed on the arena.  Two phases, [1] the hoisted work
-    # of a call, [0] the work of an assignment: without `hoist` everything is in [0]
-    buf_size, front, events = [], ([], []), ([], [])
+    # buffers are symbolic (numbers) until the event list is replayed on the arena.  One phase per period, keyed by it:
+    # under `hoist` [2] the hoisted work of a call and [1] the work of an assignment, without a keyword everything in [1]
+    buf_size, front, events = [], defaultdict(list), defaultdict(list)
     perms, rows, ops, stage = [], [], [], []
-    perm_h, step_h, kept_bufs = [], [], []
+    perm_per, step_per, kept_bufs, kept_per = [], [], [], []
     ind_rows, ind_pool, ind_top = [], [], 0  # indirect: the rows of ind_steps, the tables of ind_maps, their length so far
 
-    def new_buf(numel, at_start=False, h=False):
+    def new_buf(numel, at_start=False, h=1):
         buf_size.append(numel)
         (front if at_start else events)[h].append(("alloc", len(buf_size) - 1))
         return len(buf_size) - 1
@@ -733,8 +884,9 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         else:
             skind, sref = ARENA, src.ref
             st = {x: size(src.inds[k + 1:]) for k, x in enumerate(src.inds)}
-        h = src.free and dst_kind == ARENA  # (hoisted: the source is slice-free)
-        perm_h.append(int(h))
+        h = src.per if dst_kind == ARENA else 1  # (a permute has the period of its source)
+        assert h == src.per or src.per == 1  # (what is copied to the output depends on every sliced index)
+        perm_per.append(h)
         dst = new_buf(numel, at_start=group < 0, h=h) if dst_kind == ARENA else 0
         row = [skind, sref, dst_kind, dst, len(layout), numel, group, 0] + [0] * (2 * MAX_AXES)
         row[8:8 + len(layout)] = [dims[x] for x in layout]
@@ -772,15 +924,15 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
             if best is None or moved < best[0]:
                 best = (moved, s_order, fa[0] if fa else None, fb[0] if fb else None)
         _, s_order, form_a, form_b = best
-        hst = A.free and B.free  # the step is hoisted: both operands are slice-free
-        step_h.append(int(hst))
+        hst = min(A.per, B.per)  # the period of the step (hoist: 2, it is hoisted, when both operands are slice-free)
+        step_per.append(hst)
         moved_from = []  # (the permutes of one step run in one launch: their sources are released after both)
         ind = [-1] * IND_W
         for side, (T, form, target) in enumerate(((A, form_a, ra + h + xs + s_order), (B, form_b, rb + h + s_order + ys))):
             # indirect: an operand that depends on the assignment is read where it lies when its three offset tables
             # are no larger than the copy they replace; roles, s_order and the result's layout stay as decided above
             groups = (h, s_order, ys) if side else (h, xs, s_order)
-            if form is None and indirect is True and not T.free and \
+            if form is None and indirect is True and not T.free and T.per == hst and \
                     8 * sum(size(g) for g in groups) <= np.dtype(dtype).itemsize * size(target):
                 st = strides[T.leaf] if T.leaf is not None else {x: size(T.inds[q + 1:]) for q, x in enumerate(T.inds)}
                 for q, g in enumerate(groups):
@@ -792,16 +944,16 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
             elif form is None:
                 ref = permute(T, target, -1 if T.leaf is not None else k)
                 if T.kind == ARENA:
-                    moved_from.append((T.ref, T.free))
+                    moved_from.append((T.ref, T.per))
                 T.inds, T.kind, T.ref, T.leaf = target, ARENA, ref, None
-        for q, free in moved_from:  # (a hoisted permute releases its source in the hoisted phase)
-            events[free].append(("free", q))
+        for q, per in moved_from:  # (a permute releases its source in its own phase)
+            events[per].append(("free", q))
         form_a = 0 if form_a is None else form_a
         form_b = 0 if form_b is None else form_b
         ind_rows.append(ind)
         H, M, N, K = size(h), size(xs), size(ys), size(s_order)
         z = rz + h + xs + ys
-        assert not (hst and k == len(steps) - 1)  # (some leaf holds a sliced index, and the last step is above it)
+        assert not (hst > 1 and k == len(steps) - 1)  # (the last step is above every leaf that holds a sliced index)
         c_kind, c_ref = (OUT, 0) if k == len(steps) - 1 else (ARENA, new_buf(size(z), h=hst))
         if scaling is not None:
             # a stored result is summed into a float32 staging buffer (2 storage elements per element) and narrowed
@@ -842,17 +994,23 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
                      *((A.slot, B.slot) if scaling is not None else (0, 0))])
         ops.append(op)
         for T in (A, B):
-            if T.kind == ARENA and T.free and not hst:  # kept: written once, read by every assignment, never released
+            if T.kind == ARENA and T.per > hst:  # kept: its reader runs more often than its writer; never released
                 kept_bufs.append(T.ref)
+                kept_per.append(T.per)
             elif T.kind == ARENA:
                 events[hst].append(("free", T.ref))
         live.append(_Live(z, ARENA, c_ref))
         live[-1].slot = len(ts_inds) + k
-        live[-1].free = hst
+        live[-1].dep, live[-1].per, live[-1].free = A.dep | B.dep, hst, A.free and B.free
 
-    # the hoisted phase first; the assignments then run on top of what it left, the kept buffers
+    # One allocator, the phases in order of descending period (hoist: the hoisted phase first), the events of a phase
+    # in path order; a phase's temporaries are released, the kept buffers never.  Why that is sound when the phases run
+    # slowest first at every assignment at which they are due: a slower phase's temporaries may lie where a faster
+    # phase's kept buffers lie, because whenever the slower phase is due every faster one is due after it (the periods
+    # divide one another) and rewrites them.  They never lie on a slower phase's kept buffers, which are still allocated
+    # when the faster phase is planned
     arena, offset = _Arena(), {}
-    for what, buf in front[1] + events[1] + front[0] + events[0]:
+    for what, buf in (ev for P in sorted(set(front) | set(events), reverse=True) for ev in front[P] + events[P]):
         if what == "alloc":
             offset[buf] = arena.alloc(buf_size[buf])
         else:
@@ -867,10 +1025,11 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
             if row[at] == ARENA:
                 row[at + 1] = offset[row[at + 1]]
     perm_tab = np.array(perms, np.int64).reshape(-1, PERM_W)
-    perm_h = np.array(perm_h, np.int64)
-    # slice-start gathers (group -1) first; within a group the hoisted rows first
-    order = np.argsort(2 * perm_tab[:, 6] - perm_h, kind="stable")
-    perm_tab, perm_h = perm_tab[order], perm_h[order]
+    perm_per = np.array(perm_per, np.int64).reshape(-1)
+    # slice-start gathers (group -1) first; within a group the rows of one period together, the slowest (hoisted) first
+    order = np.lexsort((-perm_per, perm_tab[:, 6]))
+    perm_tab, perm_per = perm_tab[order], perm_per[order]
+    step_per = np.array(step_per, np.int64).reshape(-1)
     step_tab = np.array(rows, np.int64).reshape(-1, STEP_W)
     macs = int(sum(int(r[10]) * int(r[11]) * int(r[12]) * int(r[13]) for r in rows))
     p = Plan(dtype=np.dtype(dtype), inds=final, shape=tuple(dims[x] for x in final), slice_inds=slice_inds,
@@ -886,10 +1045,15 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         _check_path_steps(p)
         p.path_kernel = min(int(path_kernel), hi - lo) if steps else 1
     if hoist is not None:  # (without a hoisted step or permute the tables are those of the plan without the keyword)
-        p.step_hoist, p.perm_hoist = np.array(step_h, np.int64), perm_h
-        p.hoisted = (int(p.step_hoist.sum()), int(perm_h.sum()))
+        p.step_hoist, p.perm_hoist = (step_per == 2).astype(np.int64), (perm_per == 2).astype(np.int64)
+        p.hoisted = (int(p.step_hoist.sum()), int(p.perm_hoist.sum()))
         p.kept = tuple((offset[b], buf_size[b]) for b in kept_bufs)
-        p.hoisted_macs = int(sum(int(r[10]) * int(r[11]) * int(r[12]) * int(r[13]) for r, h in zip(rows, step_h) if h))
+        p.hoisted_macs = int(sum(int(r[10]) * int(r[11]) * int(r[12]) * int(r[13]) for r, h in zip(rows, p.step_hoist) if h))
+    if reuse is not None:  # (when every period is 1 the tables are those of the plan without the keyword)
+        p.step_period, p.perm_period = step_per, perm_per
+        p.reused = (int((step_per > 1).sum()), int((perm_per > 1).sum()))
+        p.kept = tuple((offset[b], buf_size[b]) for b in kept_bufs)
+        p.kept_period = tuple(kept_per)
     if indirect is not None:  # (with nothing folded the tables are those of the plan without the keyword)
         p.indirect = sum((row[0] >= 0) + (row[3] >= 0) for row in ind_rows)
         if p.indirect:
@@ -956,7 +1120,7 @@ def _sub_output(ts_inds, leaves, output) -> frozenset:
 
 def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=None, device=None,
              sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
-             hoist=None, indirect=None, _intermediates=()) -> ContractionResult:
+             hoist=None, indirect=None, reuse=None, slice_order=None, _intermediates=()) -> ContractionResult:
     """Contract `arrays` (numpy, in ts_inds order) along the linear `path` on the GPU; see the module docstring.
     A path that leaves several tensors gives lists in `inds` / `array` (the sliced and the projected form need one
     tensor).  `_intermediates` (contract_results): positions of arrays that are results of earlier storage-mode calls,
@@ -974,12 +1138,15 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
     _check_hoist(hoist, path_kernel, projs)
     _check_indirect(indirect, storage, compute, path_kernel, projs)
+    _check_reuse(reuse, hoist, slice_batch, path_kernel, projs)
+    _check_slice_order(slice_order, reuse, projs)
     steps = _check_path(path, len(ts_inds))
     final, out = tnmod.contract(steps, ts_inds, output_inds, dims)
     if len(final) == 1:
         p = plan(steps, ts_inds, [a.shape for a in arrays], out, slices=slices, slice_range=slice_range, dtype=dtype,
                  sparse_inds=sparse_inds, projs=projs, storage=storage, scaling=scaling, slice_batch=slice_batch,
-                 compute=compute, path_kernel=path_kernel, hoist=hoist, indirect=indirect)
+                 compute=compute, path_kernel=path_kernel, hoist=hoist, indirect=indirect, reuse=reuse,
+                 slice_order=slice_order)
         return _run(p, arrays, device, loose)
     if slices:
         raise NotImplementedError("slices need a path that leaves one tensor.")
@@ -990,6 +1157,9 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     fused = None if path_kernel is None else 1
     none_hoisted = None if hoist is None else (0, 0)  # (every part is unsliced: nothing to hoist)
     none_folded = None if indirect is None else 0
+    none_reused = None if reuse is None else (0, 0)  # (every part is unsliced: every item runs once)
+    if slice_order is not None and not isinstance(slice_order, str):
+        _named_order(slice_order, ())
     for leaves, sub in _split(steps, len(ts_inds)):
         if not sub:  # a tensor the path does not touch: as the single-leaf plan gives it, rounded to storage
             a = arrays[leaves[0]].astype(dtype, copy=True)
@@ -997,19 +1167,21 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
                 a, e = scale_to_storage(a, storage)
                 parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, scaling=scaling, exponents=(e,),
                                                slice_batch=effective, path_kernel=fused, hoisted=none_hoisted,
-                                               indirect=none_folded))
+                                               indirect=none_folded, reused=none_reused))
                 continue
             if storage is not None:
                 a = _from_storage_bits(_storage_bits(a, storage, leaves[0] not in loose), storage, a)
             if compute == "bf16x3" and leaves[0] not in loose:
                 _check_split_range(a)
             parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, slice_batch=effective, compute=compute,
-                                           path_kernel=fused, hoisted=none_hoisted, indirect=none_folded))
+                                           path_kernel=fused, hoisted=none_hoisted, indirect=none_folded,
+                                           reused=none_reused))
             continue
         parts.append(contract(sub, [ts_inds[t] for t in leaves], [arrays[t].astype(dtype, copy=False) for t in leaves],
                               _sub_output(ts_inds, leaves, out), device=device, storage=storage, scaling=scaling,
                               slice_batch=slice_batch, compute=compute, path_kernel=path_kernel, hoist=hoist,
-                              indirect=indirect, _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
+                              indirect=indirect, reuse=reuse,
+                              _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
     assert [tuple(r.inds) for r in parts] == [tuple(f) for f in final]
     return ContractionResult([r.inds for r in parts], [r.array for r in parts], sum(r.macs for r in parts), 1,
                              max(r.peak_device_bytes for r in parts), sum(r.launches for r in parts),
@@ -1022,7 +1194,7 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
                              path_launches=_add_counts(*(r.path_launches for r in parts)), hoisted=none_hoisted,
                              indirect=None if indirect is None else sum(r.indirect for r in parts),
                              indirect_launches=_add_counts(*(r.indirect_launches for r in parts)),
-                             matrix_launches=sum(r.matrix_launches for r in parts))
+                             matrix_launches=sum(r.matrix_launches for r in parts), reused=none_reused)
 
 
 def _add_counts(*counts) -> tuple:
@@ -1100,6 +1272,9 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
         if p.hoisted is not None and any(p.hoisted):  # (nothing hoisted: the run of the plan without the keyword)
             flags = [np.ascontiguousarray(q, np.int64) for q in (p.step_hoist, p.perm_hoist)]
             _lib.check(L.tnco_hip_contract_set_hoist(h, *(q.ctypes.data_as(C.c_void_p) for q in flags)))
+        if p.reused is not None and any(p.reused):  # (every period 1: the run of the plan without the keyword)
+            periods = [np.ascontiguousarray(q, np.int64) for q in (p.step_period, p.perm_period)]
+            _lib.check(L.tnco_hip_contract_set_reuse(h, *(q.ctypes.data_as(C.c_void_p) for q in periods)))
         if p.indirect:  # (nothing folded: the run of the plan without the keyword)
             tabs = [np.ascontiguousarray(q, np.int64) for q in (p.ind_steps, p.ind_maps)]
             _lib.check(L.tnco_hip_contract_set_indirect(h, tabs[0].ctypes.data_as(C.c_void_p), tabs[1].size,
@@ -1147,7 +1322,8 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
                              row_kernel_launches=tuple(int(v) for v in by_row_kernel), scaling=p.scaling,
                              exponents=exponents, narrow_launches=narrow, slice_batch=p.slice_batch, batch_launches=folds,
                              compute=p.compute, split_launches=splits, path_kernel=p.path_kernel, path_launches=fused,
-                             hoisted=p.hoisted, indirect=p.indirect, indirect_launches=through, matrix_launches=matrix)
+                             hoisted=p.hoisted, indirect=p.indirect, indirect_launches=through, matrix_launches=matrix,
+                             reused=p.reused)
 
 
 def _host_layout(p: Plan, staging) -> np.ndarray:
@@ -1169,7 +1345,7 @@ def _host_layout(p: Plan, staging) -> np.ndarray:
 
 def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse_inds=None,
                      storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
-                     hoist=None, indirect=None) -> ContractionResult:
+                     hoist=None, indirect=None, reuse=None, slice_order=None) -> ContractionResult:
     """Run a result of `Optimizer.optimize` over the arrays of the network as given.
 
     tn0: the network before pre-fusing (`load_tn(obj, fuse=None)`); arrays: in tn0.tensors order, or {name: array}
@@ -1194,7 +1370,11 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     hoist: True runs the slice-independent steps and permutes of every call over `result.path` once per call (module
     docstring); the fuse stage, unsliced, stays as it is; `hoisted` is the sum over the calls.
     indirect: True reads the step operands of every call over `result.path` that would be permuted per assignment in
-    place (module docstring); the fuse stage stays as it is; `indirect` and `indirect_launches` are sums over the calls."""
+    place (module docstring); the fuse stage stays as it is; `indirect` and `indirect_launches` are sums over the calls.
+    reuse: True runs every step and permute of every call over `result.path` only at the assignments that change the slices
+    below it (module docstring); the fuse stage, unsliced, stays as it is; `reused` is the sum over the calls.
+    slice_order: the order of the sliced indices, slowest first (module docstring): "reuse" for every sliced call, or a
+    sequence that names every index of `result.slices` once (of several components: each takes its own, in that order)."""
     _check_compute(compute, storage, np.float32, projs)
     _check_storage(storage, np.float32, projs)
     _check_scaling(scaling, storage)
@@ -1202,6 +1382,8 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
     _check_hoist(hoist, path_kernel, projs)
     _check_indirect(indirect, storage, compute, path_kernel, projs)
+    _check_reuse(reuse, hoist, slice_batch, path_kernel, projs)
+    _check_slice_order(slice_order, reuse, projs)
     if (tn0.sparse_inds or tn.sparse_inds) and projs is None:
         raise NotImplementedError("sparse indices (n_projs) have an array meaning only at given projections: "
                                   "pass projs=, an integer array [P, number of sparse indices].")
@@ -1235,12 +1417,13 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     if len(comp_paths) <= 1:  # one component to contract: the path with its slices, in one call
         r = contract(result.path, tn.ts_inds, arrays, tn.output_inds, slices=getattr(result, "slices", ()),
                      device=device, sparse_inds=sparse_inds or (), projs=projs, storage=storage, scaling=scaling,
-                     slice_batch=slice_batch, compute=compute, path_kernel=path_kernel, hoist=hoist, indirect=indirect)
+                     slice_batch=slice_batch, compute=compute, path_kernel=path_kernel, hoist=hoist, indirect=indirect,
+                     reuse=reuse, slice_order=slice_order)
         return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
                                  fuse_macs, r.kernel_launches, r.row_kernel_launches, r.scaling, r.exponents,
                                  r.narrow_launches, r.slice_batch, r.batch_launches, r.compute, r.split_launches,
                                  r.path_kernel, r.path_launches, r.hoisted, indirect=r.indirect,
-                                 indirect_launches=r.indirect_launches, matrix_launches=r.matrix_launches)
+                                 indirect_launches=r.indirect_launches, matrix_launches=r.matrix_launches, reused=r.reused)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
     ts, n = [tuple(x) for x in tn.ts_inds], len(tn.ts_inds)
     done, results, macs, n_slices, peak, launches, device_s = set(), [], 0, 0, 0, 0, 0.0
@@ -1249,6 +1432,10 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     fused, fused_launches = None, (0, 0)
     hoisted = None if hoist is None else (0, 0)
     folded, through = None if indirect is None else 0, (0,) * len(INDIRECT_KERNEL_PATHS)
+    reused = None if reuse is None else (0, 0)
+    named = slice_order is not None and not isinstance(slice_order, str)
+    if named:  # every index of every component's set, once
+        _named_order(slice_order, tuple(dict.fromkeys(x for cut in result.disconnected_slices for x in cut)))
     n_comp_steps = 0
     for q, cut in zip(result.disconnected_paths, result.disconnected_slices):
         if not q:
@@ -1257,7 +1444,10 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         (leaves, sub), = [(lv, s) for lv, s in _split(_check_path(q, n), n) if s]
         r = contract(sub, [ts[t] for t in leaves], [arrays[t] for t in leaves], _sub_output(ts, leaves, tn.output_inds),
                      slices=cut, device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute,
-                     path_kernel=path_kernel, hoist=hoist, indirect=indirect)
+                     path_kernel=path_kernel, hoist=hoist, indirect=indirect, reuse=reuse,
+                     slice_order=[x for x in slice_order if x in set(cut)] if named else slice_order)
+        if reuse is not None:
+            reused = _add_counts(reused, r.reused)
         if hoist is not None:
             hoisted = _add_counts(hoisted, r.hoisted)
         if indirect is not None:
@@ -1282,8 +1472,10 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     if tail:
         r = contract(tail, state_inds, state_arrays, frozenset(tn.output_inds) & {x for xs in state_inds for x in xs},
                      device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute,
-                     path_kernel=path_kernel, hoist=hoist, indirect=indirect,
+                     path_kernel=path_kernel, hoist=hoist, indirect=indirect, reuse=reuse,
                      _intermediates=range(len(state_arrays) - len(results), len(state_arrays)))
+        if reuse is not None:
+            reused = _add_counts(reused, r.reused)
         if hoist is not None:
             hoisted = _add_counts(hoisted, r.hoisted)
         if indirect is not None:
@@ -1301,4 +1493,4 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
                              scaling=scaling, exponents=exponents, narrow_launches=narrow, slice_batch=effective,
                              batch_launches=folds, compute=compute, split_launches=splits, path_kernel=fused,
                              path_launches=fused_launches, hoisted=hoisted, indirect=folded, indirect_launches=through,
-                             matrix_launches=matrix)
+                             matrix_launches=matrix, reused=reused)

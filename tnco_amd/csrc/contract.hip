@@ -50,6 +50,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <iterator>
 #include <string>
 #include <type_traits>
@@ -561,6 +562,10 @@ struct tnco_hip_contract_s {
   int64_t by_ix[TNCO_HIP_CONTRACT_N_IX_KERNELS] = {};  // launches of the last run per indirect kernel (tnco_hip.h)
   std::vector<int64_t> hoist_count, hoist_max, rest_max;  // per permute group, at index g + 1: the flagged rows (they come
                                    // first), the largest numel among them and among the others
+  std::vector<int64_t> reuse_step;  // tnco_hip_contract_set_reuse: the steps' periods; empty: never set, or every period 1
+  std::vector<int64_t> reuse_phase;  // the distinct periods, the largest first: the phases of an assignment in running order
+  std::vector<int64_t> reuse_first, reuse_count, reuse_max;  // per phase q and permute group g, at q (n_steps + 1) + g + 1: the
+                                   // first row of that period, how many there are (they are contiguous), their largest numel
   int64_t last_member = 0;         // the member that ran the last assignment of the last run (its exponent slots)
   int64_t base_bytes = 0;          // `bytes` as create reserved them
   std::vector<int32_t> exps_image;  // the leaves' exponents, once per member
@@ -743,16 +748,23 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
 }
 
 template <class D, class SI = D, bool half = false, bool scaled = false>
-int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t out_off, int64_t members = 0, bool hoisted = false) {
-  // a handle with hoisting: the flagged rows of the group (hoisted) or the others; without: every row
+int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t out_off, int64_t members = 0, bool hoisted = false,
+                   int64_t phase = -1) {
+  // a handle with hoisting: the flagged rows of the group (hoisted) or the others; with periods: the rows of the group
+  // that have the period of `phase`; without either: every row
   const bool split = !c->hoist_count.empty();
   const int64_t nh = split ? c->hoist_count[group + 1] : 0;
-  const int64_t n = hoisted ? nh : c->group_count[group + 1] - nh;
+  const int64_t at = phase < 0 ? 0 : phase * ((int64_t)c->group_first.size()) + group + 1;
+  const int64_t n = phase >= 0 ? c->reuse_count[at] : hoisted ? nh : c->group_count[group + 1] - nh;
   if (!n) return TNCO_HIP_OK;
-  const int64_t largest = !split ? c->group_max[group + 1] : hoisted ? c->hoist_max[group + 1] : c->rest_max[group + 1];
+  const int64_t largest = phase >= 0 ? c->reuse_max[at]
+                          : !split   ? c->group_max[group + 1]
+                          : hoisted  ? c->hoist_max[group + 1]
+                                     : c->rest_max[group + 1];
+  const int64_t first = phase >= 0 ? c->reuse_first[at] : c->group_first[group + 1] + (hoisted ? 0 : nh);
   const int64_t P = (int64_t)c->perms.size() / PERM_W;
   GatherArgs g;
-  g.rows = c->d_tables + (c->group_first[group + 1] + (hoisted ? 0 : nh)) * PERM_W;
+  g.rows = c->d_tables + first * PERM_W;
   g.leaf_sl = c->d_tables + P * PERM_W;
   g.slice_place = g.leaf_sl + c->leaf_sl.size();
   g.slice_dims = g.slice_place + c->place.size();
@@ -933,6 +945,7 @@ int run_impl(tnco_hip_contract_s* c) {
   }
   const int64_t arena_bytes = batched ? c->arena_elems * (int64_t)sizeof(E) : 0;
   const bool hoisting = !c->hoist_step.empty() && S > 0;
+  const bool reusing = !c->reuse_step.empty() && S > 0;  // (such a handle has no batch and no hoist flags)
   // Step k of the path.  bat: as members launches of a batch starting at assignment sid (the last step to the batch
   // staging buffer), else one unbatched launch: an assignment's, or a hoisted step's (which reads no sliced leaf and
   // works in arena copy 0)
@@ -1060,8 +1073,25 @@ int run_impl(tnco_hip_contract_s* c) {
     // scaling: the max words of every step are cleared at the start of an assignment (of a batch: of all its members),
     // in stream order after the narrowing passes of the one before
     if (half && c->scaling && S) CT_TRY(hipMemsetAsync(c->d_amax, 0, (size_t)(S * per) * sizeof(uint32_t), c->stream));
-    int rc = half && S == 0 ? (c->scaling ? launch_gathers<T, E, half, half>(c, -1, sid, out_off) : launch_gathers<T, E, half>(c, -1, sid, out_off))
-                            : launch_gathers<W, W, half>(c, -1, sid, out_off, batched ? n : 0);
+    int rc = TNCO_HIP_OK;
+    if (reusing) {
+      // Every phase that is due at this assignment, the slowest first, each in path order.  (Not path order across the
+      // phases: a slower phase's temporaries may lie where a faster phase keeps a tensor, which that phase, due whenever
+      // the slower one is, then writes again.)  The step that writes the output has period 1: beta and the block are
+      // those of the plain loop
+      for (int64_t q = 0; q < (int64_t)c->reuse_phase.size(); ++q) {
+        const int64_t period = c->reuse_phase[q];
+        if (sid != c->start && sid % period) continue;
+        if ((rc = launch_gathers<W, W, half>(c, -1, sid, out_off, 0, false, q))) return rc;
+        for (int64_t k = 0; k < S; ++k) {
+          if ((rc = launch_gathers<W, W, half>(c, k, sid, out_off, 0, false, q))) return rc;
+          if (c->reuse_step[k] == period && (rc = run_step(k, sid, false, 1, beta, out_off))) return rc;
+        }
+      }
+      continue;
+    }
+    rc = half && S == 0 ? (c->scaling ? launch_gathers<T, E, half, half>(c, -1, sid, out_off) : launch_gathers<T, E, half>(c, -1, sid, out_off))
+                        : launch_gathers<W, W, half>(c, -1, sid, out_off, batched ? n : 0);
     if (rc) return rc;
     for (int64_t k = 0; k < S; ++k) {
       if ((rc = launch_gathers<W, W, half>(c, k, sid, out_off, batched ? n : 0))) return rc;
@@ -1284,6 +1314,7 @@ int tnco_hip_contract_set_slice_batch(tnco_hip_contract c, int64_t batch) {
   if (batch < 1 || batch > MAX_SLICE_BATCH) return fail(TNCO_HIP_EINVAL, "'batch' must be from 1 to 64.");
   if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with a slice batch.");
   if (c->path_group) return fail(TNCO_HIP_EINVAL, "a slice batch and a path kernel are exclusive.");
+  if (!c->reuse_step.empty()) return fail(TNCO_HIP_EINVAL, "a slice batch is not supported with reuse periods.");
   const size_t n_steps = c->steps.size() / STEP_W, n_slots = c->leaf_numel.size() + n_steps;
   if (!n_steps) {  // a single leaf gathered into the output: runs as it does without a batch, nothing to reserve
     c->batch = batch;
@@ -1370,6 +1401,7 @@ int tnco_hip_contract_set_path_kernel(tnco_hip_contract c, int64_t group) {
   if (c->matrix) return fail(TNCO_HIP_EINVAL, "matrix mode is not supported with a path kernel.");
   if (c->path_group) return fail(TNCO_HIP_EINVAL, "the path kernel is already set.");
   if (!c->hoist_step.empty()) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with a path kernel.");
+  if (!c->reuse_step.empty()) return fail(TNCO_HIP_EINVAL, "a path kernel is not supported with reuse periods.");
   if (!c->ind_steps.empty() || c->folded) return fail(TNCO_HIP_EINVAL, "a path kernel is not supported with indirect operands.");
   const int64_t S = (int64_t)c->steps.size() / STEP_W;
   for (int64_t k = 0; k < S; ++k) {
@@ -1443,6 +1475,7 @@ int tnco_hip_contract_set_hoist(tnco_hip_contract c, const int64_t* step_flags, 
   if ((S && !step_flags) || (P && !perm_flags)) return fail(TNCO_HIP_EINVAL, "null argument.");
   if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with hoisting.");
   if (c->path_group) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with a path kernel.");
+  if (!c->reuse_step.empty()) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with reuse periods: they include it.");
   bool any = false;
   for (int64_t k = 0; k < S; ++k) {
     if (step_flags[k] != 0 && step_flags[k] != 1) return fail(TNCO_HIP_EINVAL, "a hoist flag must be 0 or 1.");
@@ -1537,6 +1570,143 @@ int tnco_hip_contract_set_hoist(tnco_hip_contract c, const int64_t* step_flags, 
   if (e) return fail(TNCO_HIP_EINVAL, e);
   c->hoist_step.assign(step_flags, step_flags + S), c->hoist_perm.assign(perm_flags, perm_flags + P);
   c->kept_opnd = kept_opnd, c->hoist_count = count, c->hoist_max = max_h, c->rest_max = max_rest;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_set_reuse(tnco_hip_contract c, const int64_t* step_period, const int64_t* perm_period) {
+  if (!c) return fail(TNCO_HIP_EINVAL, "null argument.");
+  const int64_t S = (int64_t)c->steps.size() / STEP_W, P = (int64_t)c->perms.size() / PERM_W;
+  if ((S && !step_period) || (P && !perm_period)) return fail(TNCO_HIP_EINVAL, "null argument.");
+  // a period: the place of a sliced index, or the number of assignments (what no sliced index reaches)
+  int64_t n_slices = 1;
+  for (int64_t d : c->slice_dims) n_slices *= d;
+  auto is_period = [&](int64_t v) { return v == n_slices || std::find(c->place.begin(), c->place.end(), v) != c->place.end(); };
+  bool any = false;
+  for (int64_t k = 0; k < S; ++k) {
+    if (!is_period(step_period[k])) return fail(TNCO_HIP_EINVAL, "a period must be the place of a sliced index or the number of assignments.");
+    any |= step_period[k] != 1;
+  }
+  for (int64_t r = 0; r < P; ++r) {
+    if (!is_period(perm_period[r])) return fail(TNCO_HIP_EINVAL, "a period must be the place of a sliced index or the number of assignments.");
+    any |= perm_period[r] != 1;
+  }
+  if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with reuse periods.");
+  if (c->path_group) return fail(TNCO_HIP_EINVAL, "a path kernel is not supported with reuse periods.");
+  if (c->batch) return fail(TNCO_HIP_EINVAL, "a slice batch is not supported with reuse periods.");
+  if (!c->hoist_step.empty()) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with reuse periods: they include it.");
+  if (!any) {  // every item at every assignment: the handle runs as one on which this was never called
+    c->reuse_step.clear(), c->reuse_phase.clear();
+    c->reuse_first.clear(), c->reuse_count.clear(), c->reuse_max.clear();
+    return TNCO_HIP_OK;
+  }
+  for (int64_t k = 0; k < S; ++k)
+    if (c->steps[k * STEP_W + 8] == K_OUT && step_period[k] != 1) return fail(TNCO_HIP_EINVAL, "the step that writes the output must have period 1.");
+  for (int64_t r = 0; r < P; ++r) {
+    const int64_t* row = &c->perms[r * PERM_W];
+    if (row[2] == K_OUT && perm_period[r] != 1) return fail(TNCO_HIP_EINVAL, "the permute that writes the output must have period 1.");
+    if (r && row[6] == row[6 - PERM_W] && perm_period[r] > perm_period[r - 1])
+      return fail(TNCO_HIP_EINVAL, "the rows of a permute group must be ordered by period, the largest first.");
+  }
+  // what a leaf allows an item that reads it: the smallest place of its sliced axes, the number of assignments without one
+  // (an axis of dimension 1 has one value in every assignment and allows everything)
+  auto leaf_period = [&](int64_t leaf) {
+    const int64_t* ls = &c->leaf_sl[leaf * LEAF_SL_W];
+    int64_t per = n_slices;
+    for (int j = 0; j < (int)ls[0]; ++j)
+      if (c->slice_dims[ls[1 + j]] > 1) per = std::min(per, c->place[ls[1 + j]]);
+    return per;
+  };
+  for (int64_t r = 0; r < P; ++r) {
+    const int64_t* row = &c->perms[r * PERM_W];
+    if (row[0] == K_LEAF && perm_period[r] > leaf_period(row[1])) return fail(TNCO_HIP_EINVAL, "a permute is slower than a sliced leaf it reads allows.");
+  }
+  for (int64_t k = 0; k < S; ++k)
+    for (int side = 0; side < 2; ++side) {
+      const int64_t* st = &c->steps[k * STEP_W];
+      if (st[4 * side] == K_LEAF && step_period[k] > leaf_period(st[4 * side + 1]))
+        return fail(TNCO_HIP_EINVAL, "a step is slower than a sliced leaf it reads allows.");
+    }
+  // Replay the path: who wrote what an item reads.  A write: [lo, hi) of the arena and the period of its item, in path
+  // order; read: an item has consumed it (every tensor has one reader) or nothing reads it (a staging buffer)
+  struct Write {
+    int64_t lo, hi, period;
+    char read;
+  };
+  struct Kept {
+    int64_t lo, hi;
+    size_t writer;
+  };
+  std::vector<Write> writes;
+  std::vector<Kept> kept;
+  // The write an item of that period reads at ref, -1: none, and marks it read.  The phases run one after the other, so
+  // an item sees the latest write of its own phase there, or else what the nearest slower phase kept; a write of a faster
+  // phase is returned last, for the caller to refuse.  This rests on one property of a sound arena, which the check of
+  // the kept tensors below enforces for what matters: when an item reads at ref, at most one unread write of its own
+  // phase starts there (a buffer is written, read, and only then given to the next tensor of the phase), and a kept
+  // tensor shares its start with no write of its own or a faster phase
+  auto writer_of = [&](int64_t ref, int64_t period) -> int64_t {
+    int64_t best = -1;
+    for (int64_t w = (int64_t)writes.size() - 1; w >= 0; --w) {
+      if (writes[w].lo != ref || writes[w].read) continue;
+      if (writes[w].period == period) {
+        best = w;
+        break;
+      }
+      const bool slower = writes[w].period > period;
+      if (best < 0 || (slower && (writes[best].period < period || writes[w].period < writes[best].period))) best = w;
+    }
+    if (best >= 0) writes[best].read = 1;
+    return best;
+  };
+  const char* e = nullptr;
+  auto source = [&](int64_t ref, int64_t period, int64_t numel, const char* slower) {
+    const int64_t w = writer_of(ref, period);
+    if (w < 0) return;
+    if (writes[w].period < period) e = slower;
+    if (writes[w].period > period) kept.push_back(Kept{ref, ref + numel, (size_t)w});
+  };
+  const int64_t G = S + 1;
+  std::vector<int64_t> phase;  // the distinct periods, the largest first
+  for (int64_t k = 0; k < S; ++k) phase.push_back(step_period[k]);
+  for (int64_t r = 0; r < P; ++r) phase.push_back(perm_period[r]);
+  std::sort(phase.begin(), phase.end(), std::greater<int64_t>());
+  phase.erase(std::unique(phase.begin(), phase.end()), phase.end());
+  std::vector<int64_t> first(phase.size() * G, 0), count(phase.size() * G, 0), largest(phase.size() * G, 0);
+  auto perm_rows = [&](int64_t g) {  // the rows of permute group g
+    for (int64_t r = c->group_first[g + 1], n = 0; n < c->group_count[g + 1] && !e; ++r, ++n) {
+      const int64_t* row = &c->perms[r * PERM_W];
+      const int64_t per = perm_period[r];
+      if (row[0] == K_ARENA) source(row[1], per, row[5], "a permute is slower than the item that wrote its source.");
+      if (row[2] == K_ARENA) writes.push_back(Write{row[3], row[3] + row[5], per, 0});
+      const int64_t at = (std::find(phase.begin(), phase.end(), per) - phase.begin()) * G + g + 1;
+      if (!count[at]++) first[at] = r;
+      largest[at] = std::max(largest[at], row[5]);
+    }
+  };
+  perm_rows(-1);
+  for (int64_t k = 0; k < S && !e; ++k) {
+    perm_rows(k);
+    const int64_t* st = &c->steps[k * STEP_W];
+    const int64_t H = st[10], M = st[11], N = st[12], K = st[13], nc = H * M * N;
+    for (int side = 0; side < 2 && !e; ++side)
+      if (st[4 * side] == K_ARENA) source(st[4 * side + 1], step_period[k], H * K * (side ? N : M), "a step is slower than the item that wrote its operand.");
+    if (st[8] == K_ARENA) {
+      writes.push_back(Write{st[9], st[9] + nc, step_period[k], 0});
+      if (c->scaling) writes.push_back(Write{c->stage_refs[k], c->stage_refs[k] + 2 * nc, step_period[k], 1});
+    }
+  }
+  if (e) return fail(TNCO_HIP_EINVAL, e);
+  // a kept tensor stays until its writer is due again: no item of its writer's phase writes into it after the writer, and
+  // no item of a faster phase at all (a slower phase may: whenever it is due, the writer is due after it)
+  for (size_t q = 0; q < kept.size(); ++q) {
+    const Write& own = writes[kept[q].writer];
+    for (size_t w = 0; w < writes.size(); ++w)
+      if (w != kept[q].writer && (writes[w].period < own.period || (writes[w].period == own.period && w > kept[q].writer)) &&
+          writes[w].lo < kept[q].hi && kept[q].lo < writes[w].hi)
+        return fail(TNCO_HIP_EINVAL, "a kept tensor is written over.");
+  }
+  c->reuse_step.assign(step_period, step_period + S);
+  c->reuse_phase = phase, c->reuse_first = first, c->reuse_count = count, c->reuse_max = largest;
   return TNCO_HIP_OK;
 }
 

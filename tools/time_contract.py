@@ -19,7 +19,9 @@ slice_batch=64, in one process); the matrix mode (`--matrix`: the large square s
 and compute="matrix", in float32 and complex64 also with compute="bf16x3" and storage="bfloat16", and torch, in one
 process); operands read in place (`--indirect`: the sliced Sycamore leg with slice_batch None and 64, hoist None and True,
 each with indirect=None and indirect=True, and one bandwidth-bound step whose 2^26-element operand lies in reversed axis
-order, in one process).  Engine figures are its
+order, in one process); reuse (`--reuse`: the sliced Sycamore leg, unbatched, with hoist=None, hoist=True, reuse=True,
+reuse=True with slice_order="reuse", and that with indirect=True, and the same five on a deeper network whose assignments
+take milliseconds, every ratio against hoist=True, in one process).  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device).
 """
@@ -375,6 +377,91 @@ def hoist(lines, depth, max_width, max_slices):
             del r
 
 
+REUSE_SETTINGS = (("hoist=None", dict()), ("hoist=True", dict(hoist=True)), ("reuse=True", dict(reuse=True)),
+                  ("reuse=True slice_order=reuse", dict(reuse=True, slice_order="reuse")),
+                  ("reuse=True slice_order=reuse indirect=True", dict(reuse=True, slice_order="reuse", indirect=True)))
+# the arithmetic-bound leg of --reuse: (depth, max_width) in the order they are tried, and what an assignment must take
+REUSE_BIG = ((10, 18), (12, 20), (12, 22), (14, 24))
+REUSE_BIG_MS = 1.0
+
+
+def _sliced_sycamore(depth, max_width):
+    """(tn, the first result of the finite-width optimization, the leaves after the fuse stage): the sliced Sycamore
+    amplitude of the storage leg, complex64."""
+    ts, d, o = syn.sycamore53_tn(depth=depth)
+    tn0 = tnmod.TensorNetwork([tnmod.Tensor(xs, [d] * len(xs)) for xs in ts], output_inds=o)
+    tn, res = Optimizer(method="sa", max_width=max_width, seed=0).optimize(tn0, betas=(0, 50), n_steps=200, n_runs=256)
+    rng = np.random.RandomState(2)
+    n_inds = len({x for xs in ts for x in xs})
+    scale = 2.0 ** (-n_inds / (2 * len(ts)))  # (as in the storage leg: the amplitude stays near 1)
+    arrays = [(_rand(tuple(d for _ in xs), np.complex64, rng) * scale).astype(np.complex64) for xs in ts]
+    fused = ctr.contract(tn.tags["fuse_path"], tn0.ts_inds, arrays, tn0.output_inds)
+    return tn, res[0], fused.array if isinstance(fused.array, list) else [fused.array]
+
+
+def _reuse_rows(lines, tn, r0, leaves, m):
+    """The five settings of REUSE_SETTINGS on assignments [0, m), unbatched; every ratio against hoist=True."""
+    shapes = [a.shape for a in leaves]
+    lines.append(f"{'setting':>44} {'device s':>9} {'spread':>7} {'hoist=True / this':>17} {'ms / slice':>10} {'launches':>9} "
+                 f"{'MACs':>15} {'MACs / plain':>12} {'peak bytes':>12} {'reused':>10} {'kept':>5} {'bits equal plain, same order':>28}")
+    run = lambda **kw: ctr.contract(r0.path, tn.ts_inds, leaves, tn.output_inds, slices=r0.slices, slice_range=(0, m), **kw)  # noqa: E731
+    rows, notes, plain_macs = [], [], None
+    for name, kw in REUSE_SETTINGS:
+        p = ctr.plan(r0.path, tn.ts_inds, shapes, tn.output_inds, slices=r0.slices, slice_range=(0, m), dtype=np.complex64, **kw)
+        r = run(**kw)
+        times = [run(**kw).device_s for _ in range(3)]
+        t, spread = min(times), (max(times) - min(times)) / min(times)
+        # bits: against the run without reuse / hoist under the same order of the sliced indices
+        base = run(slice_order=p.slice_inds, **{k: v for k, v in kw.items() if k == "indirect"})
+        same = np.array_equal(np.ravel(r.array).view(np.uint32), np.ravel(base.array).view(np.uint32))
+        plain_macs = r.macs if plain_macs is None else plain_macs
+        rows.append((name, t, spread, r, p, same))
+        del base
+    t_hoist, s_hoist = rows[1][1], rows[1][2]
+    for name, t, spread, r, p, same in rows:
+        lines.append(f"{name:>44} {t:9.4f} {spread:7.3f} {t_hoist / t:17.2f} {t / m * 1e3:10.4f} {r.launches:9d} {r.macs:15d} "
+                     f"{r.macs / plain_macs:12.3f} {r.peak_device_bytes:12d} {str(r.reused):>10} {len(p.kept):5d} {str(bool(same)):>28}")
+        print(lines[-1], flush=True)
+        if name.startswith("reuse") and not t * (1 + max(spread, s_hoist)) < t_hoist:
+            notes.append(f"  {name}: NOT faster than hoist=True by more than the spread")
+    lines.extend(notes)
+
+
+def reuse(lines, depth, max_width, max_slices):
+    """Steps that run only when their slices change, all in this process, unbatched: (a) the sliced Sycamore amplitude of
+    the storage leg, launch-bound; (b) the first network of REUSE_BIG whose assignment takes REUSE_BIG_MS milliseconds or
+    more under hoist=True (measured here on 8 assignments), on its first 64 assignments.  Device time: the minimum and
+    the spread of three runs after a warm-up; the baseline of every ratio is hoist=True."""
+    lines.append("")
+    tn, r0, leaves = _sliced_sycamore(depth, max_width)
+    n = 2 ** len(r0.slices)
+    m = min(n, max_slices)
+    lines.append(f"## reuse (a), sliced Sycamore-53 amplitude, depth {depth}, complex64, max_width {max_width}, cost {r0.cost}, "
+                 f"{len(r0.path)} steps, {len(r0.slices)} sliced indices, assignments [0, {m}) of {n}, unbatched: device seconds "
+                 "are the minimum of three runs after a warm-up, spread = (max - min) / min of the three; all runs in one process")
+    _reuse_rows(lines, tn, r0, leaves, m)
+    del leaves
+    for big_depth, big_width in REUSE_BIG:
+        tn, r0, leaves = _sliced_sycamore(big_depth, big_width)
+        n = 2 ** len(r0.slices)
+        probe = ctr.contract(r0.path, tn.ts_inds, leaves, tn.output_inds, slices=r0.slices, slice_range=(0, min(n, 8)), hoist=True)
+        probe = ctr.contract(r0.path, tn.ts_inds, leaves, tn.output_inds, slices=r0.slices, slice_range=(0, min(n, 8)), hoist=True)
+        ms = probe.device_s / min(n, 8) * 1e3
+        lines.append(f"(depth {big_depth}, max_width {big_width}: {len(r0.slices)} sliced indices, {ms:.3f} ms per assignment under "
+                     f"hoist=True on the first {min(n, 8)})")
+        print(lines[-1], flush=True)
+        if ms >= REUSE_BIG_MS or (big_depth, big_width) == REUSE_BIG[-1]:
+            break
+        del leaves
+    m = min(n, 64)
+    chosen = (f"the first of {REUSE_BIG} whose assignment takes {REUSE_BIG_MS} ms or more" if ms >= REUSE_BIG_MS else
+              f"the last of {REUSE_BIG}: NONE of them takes {REUSE_BIG_MS} ms per assignment, this one {ms:.3f} ms")
+    lines.append(f"## reuse (b), sliced Sycamore-53 amplitude, depth {big_depth}, complex64, max_width {big_width}, cost {r0.cost}, "
+                 f"{len(r0.path)} steps, {len(r0.slices)} sliced indices, assignments [0, {m}) of {n}, unbatched: {chosen}; "
+                 f"the range covers the {int(np.log2(m))} fastest sliced indices of each order only")
+    _reuse_rows(lines, tn, r0, leaves, m)
+
+
 def indirect(lines, depth, max_width, max_slices):
     """Operands read in place against the permutes they replace, all in this process: the sliced Sycamore amplitude of the
     storage leg, complex64, with slice_batch None and 64, hoist None and True, each with indirect=None and indirect=True;
@@ -627,15 +714,19 @@ def main():
     ap.add_argument("--hoist", action="store_true", help="only the hoisting leg, appended to --out")
     ap.add_argument("--matrix", action="store_true", help="only the matrix-mode leg, appended to --out")
     ap.add_argument("--indirect", action="store_true", help="only the indirect-operand leg, appended to --out")
+    ap.add_argument("--reuse", action="store_true", help="only the reuse leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect > 1:
-        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix and --indirect each "
+    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect + a.reuse > 1:
+        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix, --indirect and --reuse each "
                  "append one leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect:  # (the other legs' sections stay as they are)
-        if a.indirect:
+    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect or a.reuse:  # (the other legs' sections stay as they are)
+        if a.reuse:
+            lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
+            reuse(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+        elif a.indirect:
             lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
             indirect(lines, a.depth, a.max_width, min(a.max_slices, 2048))
         elif a.matrix:
@@ -673,6 +764,7 @@ def main():
     hoist(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     matrix(lines, a.n)
     indirect(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+    reuse(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
