@@ -14,10 +14,11 @@ import pytest
 
 from tests import hoist_cases as hc
 from tests import mode_cases as mc
+from tests import schedule_cases as sc
 from tnco_amd import contraction as ctr
 
 TABLES = ("leaf_numel", "leaf_sl", "perms", "steps")
-ALL = [(n, hc.case(n)) for n in hc.NAMES] + [(i, c) for i, c in zip(mc.IDS, mc.CASES)]
+ALL = [(n, hc.case(n)) for n in hc.NAMES] + [(i, c) for i, c in zip(sc.IDS, sc.CASES)]  # (mode_cases.CASES and EXTRA)
 
 
 def same_plan(p, q):

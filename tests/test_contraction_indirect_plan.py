@@ -7,12 +7,13 @@ import pytest
 
 from tests import indirect_cases as ic
 from tests import mode_cases as mc
+from tests import schedule_cases as sc
 from tnco_amd import contraction as ctr
 
 TABLES = ("leaf_numel", "leaf_sl", "perms", "steps")
 ONE = [(f"{n}-{f}", ic.case(n, f)) for n, f in ic.ONE_STEP]
 CHAINS = list(ic.CHAINS.items())
-MODE = [(i, c) for i, c in zip(mc.IDS, mc.CASES)]
+MODE = [(i, c) for i, c in zip(sc.IDS, sc.CASES)]  # (mode_cases.CASES and EXTRA)
 ALL = ONE + CHAINS + MODE
 ids = lambda rows: [n for n, _ in rows]  # noqa: E731
 

@@ -4,10 +4,12 @@
     python tools/fuzz_contract.py --seeds 3000:3400
 
 For every seed of the range the generator of tests/mode_cases.py gives a network (or none, when the seed's network is
-beyond the caps of a case); it is replayed by the numpy interpreter in its own dtype against the plain bound and then run
-on the device in every mode with the checks of tests/test_gpu_contract_modes.py (`check_case`).  One process.  The run
-stops at the first mismatch or exception and prints the case as a line that can be pasted into `mode_cases`; at the end
-it prints the largest error / bound per mode.  Not part of the suite.
+beyond the caps of a case); it is replayed by the numpy interpreter in its own dtype against the plain bound, its plans
+under `hoist=True`, `reuse=True` (three orders of the sliced indices) and `indirect=True` are replayed on a NaN-poisoned
+arena by the interpreters of those features' plan tests, and then it is run on the device in every mode with the checks of
+tests/test_gpu_contract_modes.py and in every schedule with those of tests/test_gpu_contract_schedules.py (the two
+`check_case`).  One process.  The run stops at the first mismatch or exception and prints the case as a line that can be
+pasted into `mode_cases`; at the end it prints the largest error / bound per mode.  Not part of the suite.
 """
 import argparse
 import sys
@@ -26,10 +28,25 @@ def main():
     lo, hi = (int(v) for v in args.seeds.split(":"))
     from tests import mode_cases as mc
     from tests.test_contraction_plan import _interpret
-    ctr = check_case = None
+    from tests import indirect_cases as ic
+    from tests import schedule_cases as sc
+    from tests.test_contraction_reuse_plan import interpret as interpret_reuse
+    ctr = check_case = check_schedules = None
     if not args.cpu_only:
         from tests.test_gpu_contract_modes import check_case
+        from tests.test_gpu_contract_schedules import check_case as check_schedules
         from tnco_amd import contraction as ctr
+
+    def schedules_replayed(case):
+        """The plans of the schedule tests on one flat arena that is NaN wherever nothing valid lies, in double precision."""
+        P = sc.Plans(case)
+        wide = [np.asarray(a, np.complex128 if np.iscomplexobj(a) else np.float64) for a in mc.fill(case)]
+        runs = [(q, ic.interpret(q, wide)) for q in (P.hoist, P.indirect, P.indirect_hoist)]
+        runs += [(q, interpret_reuse(case, q, wide)) for q in list(P.reuse.values()) + list(P.indirect_reuse.values())]
+        for q, got in runs:
+            ref, mag = mc.reference(case, q, wide)
+            assert not np.isnan(got).any(), "a schedule reads a buffer that nothing valid is in"
+            assert (np.abs(got - ref) <= 1e-12 * mc.kt(q) * mag).all(), "the replay of a schedule is not the einsum"
     worst, ran = {}, 0
     for seed in range(lo, hi):
         case = mc.generate(seed)
@@ -43,8 +60,10 @@ def main():
             bound = mc.plain_bound(case, p, mag)
             assert (err <= bound).all(), "the replay of the tables leaves the plain bound"
             ratios = {"replay": float(np.divide(err, bound, out=np.zeros_like(err), where=bound > 0).max())}
+            schedules_replayed(case)
             if check_case is not None:
                 ratios.update(check_case(ctr, case, out=lambda line: None))
+                ratios.update({f"schedules {k}": v for k, v in check_schedules(ctr, case, out=lambda line: None).items()})
         except Exception as e:  # noqa: BLE001 -- whatever it is, the case is what is wanted
             print(f"seed {seed}: {type(e).__name__}: {e}\n{case.paste()}")
             return 1
