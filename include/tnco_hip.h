@@ -488,12 +488,21 @@ const char* tnco_hip_comm_last_error(void);
  * below them holds a sliced axis -- is flagged by the plan and runs once per run, before the first assignment, instead of
  * once per assignment: first the flagged rows of permute group -1, then for each step k the flagged rows of its permute
  * group and the step itself when it is flagged, as one-member launches of the kernels the loop would launch.  The loop
- * over the assignments skips what is flagged.  A flagged item reads leaves without sliced axes and arena tensors that
+ * over the assignments skips what is flagged.  The flags are the two-period case of the schedule that Reuse (below)
+ * describes, and one loop runs both: a flagged item has the period that is due at slice_start only (the number of
+ * assignments), every other item has period 1, so the flagged items are the slow phase of the first assignment.
+ * A flagged item reads leaves without sliced axes and arena tensors that
  * flagged items wrote, and writes the arena; what an unflagged step reads of it (a kept tensor) stays where it is for the
  * whole run, and the plan places nothing an assignment writes over it.  With a slice batch the flagged items work in arena
  * copy 0 and every member reads a kept tensor there; with scaling the exponent slots of copy 0 are copied to every member's
  * slots after the flagged items, in stream order.  Every step runs the kernel it runs unhoisted on the same operands, so
  * the result is bit for bit that of a handle without the call; stats[0] and the launch counts are of what ran.
+ * The flags are refused in three places where the equal periods are not.  (a) A flagged item must not read a leaf with
+ * any sliced axis; a period only counts the axes of a dimension above 1.  (b) A flagged step must not read an arena
+ * tensor that no item wrote.  (c) A permute and the item that wrote its source carry the same flag; periods let a permute
+ * be faster than its source, which is then kept.  (c) is what makes a slice batch sound, which flags accept and periods
+ * do not: only a step operand can be marked as kept and read in arena copy 0 by every member, so an unflagged permute of a
+ * kept tensor would read the arena copy of its own member, where nothing wrote it.
  *
  * Reuse (tnco_hip_contract_set_reuse): hoisting with as many levels as there are sliced indices.  Assignment a gives
  * sliced index j the value (a / place[j]) % dim[j], place[j] the product of the dimensions after j, so a tensor whose
@@ -618,7 +627,10 @@ int tnco_hip_contract_path_launches(tnco_hip_contract h, int64_t* counts);
  * output or has an operand with a sliced axis or an arena operand that an unflagged item wrote, for a flagged permute
  * that writes the output or whose source has a sliced axis or was written by an unflagged item, for an unflagged permute
  * whose source a flagged item wrote, for a permute group whose flagged rows do not come first, and when an unflagged item
- * writes over a kept tensor.  Reserves nothing.  A handle on which this was never called, or with no flag set, runs
+ * writes over a kept tensor.  The flags are checked as the periods of tnco_hip_contract_set_reuse are, a flag as the
+ * number of assignments and no flag as 1, with the three further refusals listed under Hoisting above (a sliced axis of
+ * dimension 1, an arena operand that nothing wrote, a permute that is faster than its source), which keep a flagged
+ * handle fit for a slice batch.  Reserves nothing.  A handle on which this was never called, or with no flag set, runs
  * everything per assignment */
 int tnco_hip_contract_set_hoist(tnco_hip_contract h, const int64_t* step_flags, const int64_t* perm_flags);
 /* after create, before run: step_period[n_steps] and perm_period[n_perms] (in the rows' order), the period of every item

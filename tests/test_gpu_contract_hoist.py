@@ -144,6 +144,64 @@ def test_nothing_to_hoist_runs_as_without_the_keyword(ctr):
     assert one.hoisted == (0, 0) and np.array_equal(bits(one.array), bits(ctr.contract([], [case.ts_inds[2]], [a], slices=("u",)).array))
 
 
+@pytest.mark.parametrize("dtype", ("float32", "complex128"))
+@pytest.mark.parametrize("name", ("kept-first-stream-7-9-11", "arena-permute", "leaf-permute", "chain"))
+def test_hoist_flags_are_the_two_period_schedule(ctr, name, dtype):
+    """Through the ABI: the plan's flags given to tnco_hip_contract_set_hoist, and given to tnco_hip_contract_set_reuse as
+    periods (the number of assignments for a flag, 1 for none), run the same launches on the same bytes.  What the flags
+    refuse beyond the periods stays: an unflagged permute of a kept tensor."""
+    from tnco_amd import _lib
+    L = _lib.load()
+    i64 = lambda v: np.ascontiguousarray(v, np.int64)  # noqa: E731
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    case = hc.case(name, dtype)
+    p = case.plan(hoist=True)
+    assert p.hoisted == hc.TABLE[name][1]
+    flags = (i64(p.step_hoist), i64(p.perm_hoist))
+    reads = [(st[0], st[1]) for st, f in zip(p.steps, flags[0]) if f] + [(st[4], st[5]) for st, f in zip(p.steps, flags[0]) if f]
+    reads += [(row[0], row[1]) for row, f in zip(p.perms, flags[1]) if f]
+    if any(kind == ctr.LEAF and p.leaf_sl[ref][0] != 0 for kind, ref in reads):
+        pytest.skip("a hoisted item reads a leaf whose sliced axes have dimension 1: flags refuse it, periods do not")
+    n = int(np.prod(list(hc.SLICE_DIMS.values())))
+    assert n == hc.N_ASSIGNMENTS == case.n_assignments()
+    periods = tuple(np.where(f == 1, n, 1).astype(np.int64) for f in flags)
+    arrays = [np.ascontiguousarray(a, p.dtype) for a in mc.fill(case)]
+    leaves = (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+    def handle():
+        d, keep = ctr._describe(p, 0)
+        h = C.c_void_p()
+        _lib.check(L.tnco_hip_contract_create(C.byref(d), C.byref(h)))
+        del keep
+        return h
+
+    def run(h):
+        out, stats, counts = np.empty(p.out_numel, p.dtype), np.zeros(4, np.int64), np.zeros(len(ctr.KERNEL_PATHS), np.int64)
+        _lib.check(L.tnco_hip_contract_run(h, leaves, ptr(out)))
+        _lib.check(L.tnco_hip_contract_stats(h, ptr(stats)))
+        _lib.check(L.tnco_hip_contract_kernel_launches(h, ptr(counts)))
+        return out, int(stats[0]), int(stats[1]), tuple(counts.tolist())
+
+    by_flags, by_periods = handle(), handle()
+    try:
+        _lib.check(L.tnco_hip_contract_set_hoist(by_flags, ptr(flags[0]), ptr(flags[1])))
+        _lib.check(L.tnco_hip_contract_set_reuse(by_periods, ptr(periods[0]), ptr(periods[1])))
+        a, b = run(by_flags), run(by_periods)
+        assert np.array_equal(bits(a[0]), bits(b[0])), f"{name} {dtype}: the bytes differ"
+        assert a[1] == b[1] == p.macs and a[2] == b[2] == sum(a[3]) and a[3] == b[3], (name, dtype, a[1:], b[1:])
+        via = ctr.contract(list(case.path), case.ts_inds, arrays, case.output_inds, slices=case.slices, hoist=True)
+        assert np.array_equal(bits(a[0]), bits(via.array)) and a[3] == via.kernel_launches, (name, dtype)
+        if name == "arena-permute":  # the permute of the kept tensor, unflagged: its source stays kept under periods
+            assert flags[1].tolist() == [1] and p.perms[0][0] == ctr.ARENA
+            assert L.tnco_hip_contract_set_hoist(by_flags, ptr(flags[0]), ptr(i64([0]))) == _lib.EINVAL
+            assert L.tnco_hip_last_error() == b"a permute and the item that writes its source must both be hoisted or both not."
+            assert run(by_flags)[1:] == a[1:]  # (the refusal leaves the flags as they were)
+            assert L.tnco_hip_contract_set_reuse(by_periods, ptr(periods[0]), ptr(i64([1]))) == _lib.OK
+    finally:
+        L.tnco_hip_contract_destroy(by_flags)
+        L.tnco_hip_contract_destroy(by_periods)
+
+
 def test_the_setter_validates_the_flags(ctr):
     """Through the ABI: flags that do not describe slice-independent work are refused, and so are handles with row axes
     or a path kernel."""

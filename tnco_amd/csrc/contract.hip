@@ -33,9 +33,12 @@
 // workgroup per assignment interpreting the whole path in its own copy of the arena (ct_path_kernel), and
 //   ct_path_reduce_kernel  folds the group's blocks into the output as ct_batch_reduce_kernel does;
 // two launches per group, the sums in the order of the unfused kernels: bit-equal to the loop above.
-// Hoisting (tnco_hip_contract_set_hoist): the steps and permutes the plan flags -- their operands hold no sliced axis
-// anywhere below them -- run once per run, before the slice loop, as one-member launches of the same kernels; the loop
-// skips them, and a step of the loop reads what they left (a kept tensor) in arena copy 0.  No kernel knows of it.
+// The schedule (Schedule, make_schedule): every step and permute has a period and is due at assignment a iff a is the first
+// of the run or a % period == 0; the slice loop runs the phases (the items of one period) that are due, the slowest first.
+// Every period 1: the plain loop.  Reuse periods (tnco_hip_contract_set_reuse): the plan's.  Hoisting
+// (tnco_hip_contract_set_hoist): the steps and permutes the plan flags -- their operands hold no sliced axis anywhere
+// below them -- have the period that is due once per run, as one-member launches of the same kernels; a step of period 1
+// reads what they left (a kept tensor) in arena copy 0.  No kernel knows of it.
 // Indirect operands (tnco_hip_contract_set_indirect, contract_indirect.h): a step operand that the plan folded is read
 // where it lies, element (h, m, k) at base + offH[h] + offM[m] + offK[k] through three int64 tables, by
 //   ct_ix_tiled_kernel, ct_ix_dot_kernel, ct_ix_stream_kernel
@@ -527,11 +530,23 @@ __global__ __launch_bounds__(256) void ct_rows_dot_kernel(RowGemmArgs<T> p) {
 
 }  // namespace
 
+// The schedule of the slice loop.  Every step and permute has a period: it is due at assignment a of [lo, hi) iff a == lo
+// or a % period == 0.  Every period 1: the plain loop; hoist flags: the number of assignments for a flagged item, 1 for
+// the others; reuse periods: as given.
+struct Schedule {
+  enum Set { NEVER, HOIST, REUSE } set = NEVER;  // the setter the periods came from; NEVER: none, or one that left every period 1
+  std::vector<int64_t> step_period;  // [n_steps]
+  std::vector<int64_t> phase;        // the distinct periods, the largest first: the phases of an assignment in running order
+  std::vector<int64_t> first, count, largest;  // per phase q and permute group g, at q (n_steps + 1) + g + 1: the first row of
+                                     // that period, how many there are (they are contiguous), their largest numel
+  std::vector<char> kept_opnd;       // [n_steps][2]: the operand is a kept tensor, read in arena copy 0 by every member
+};
+
 struct tnco_hip_contract_s {
   int device = 0, dtype = 0;
   size_t elem = 4, out_elem = 4;  // bytes of an element of the leaves and the arena / of the output (storage mode: not the same)
   std::vector<int64_t> leaf_numel, leaf_off, leaf_sl, perms, steps, slice_dims, place, block;
-  std::vector<int64_t> group_first, group_count, group_max;  // perm rows of group g at index g + 1
+  std::vector<int64_t> group_first, group_count;  // perm rows of group g at index g + 1
   std::vector<int64_t> row_steps;  // [n_steps][ROW_W], empty: no step has a row axis
   std::vector<int32_t> row_maps;
   int scaling = 0;                 // per-tensor scaling of a storage dtype (tnco_hip.h)
@@ -552,20 +567,13 @@ struct tnco_hip_contract_s {
   int64_t* d_path_tables = nullptr;  // steps | first row and count of every permute group | placement of every assignment
   std::vector<int64_t> path_image;   // the host copy of d_path_tables
   int64_t path_launches[2] = {0, 0};  // launches of ct_path_kernel and of ct_path_reduce_kernel in the last run
-  std::vector<char> hoist_step, hoist_perm;  // tnco_hip_contract_set_hoist: the flags; empty: never set, or no flag set
-  std::vector<char> kept_opnd;     // [n_steps][2]: the operand is a kept tensor, read in arena copy 0 by every member
+  Schedule sched;                  // which items an assignment runs (make_schedule); create: every item at every one
   bool folded = false;             // a step has an operand with both stride columns 0: it runs with indirect tables only
   std::vector<int64_t> ind_steps;  // tnco_hip_contract_set_indirect: [n_steps][IND_W]; empty: never set, or nothing folded
   std::vector<char> ind_fast;      // [n_steps][2]: lanes of the tiled kernel stage A along k / B along n
   int64_t* d_ind = nullptr;        // ind_steps | the pool of the offset tables
   int64_t ind_bytes = 0;           // what the tables add to `bytes`
   int64_t by_ix[TNCO_HIP_CONTRACT_N_IX_KERNELS] = {};  // launches of the last run per indirect kernel (tnco_hip.h)
-  std::vector<int64_t> hoist_count, hoist_max, rest_max;  // per permute group, at index g + 1: the flagged rows (they come
-                                   // first), the largest numel among them and among the others
-  std::vector<int64_t> reuse_step;  // tnco_hip_contract_set_reuse: the steps' periods; empty: never set, or every period 1
-  std::vector<int64_t> reuse_phase;  // the distinct periods, the largest first: the phases of an assignment in running order
-  std::vector<int64_t> reuse_first, reuse_count, reuse_max;  // per phase q and permute group g, at q (n_steps + 1) + g + 1: the
-                                   // first row of that period, how many there are (they are contiguous), their largest numel
   int64_t last_member = 0;         // the member that ran the last assignment of the last run (its exponent slots)
   int64_t base_bytes = 0;          // `bytes` as create reserved them
   std::vector<int32_t> exps_image;  // the leaves' exponents, once per member
@@ -649,7 +657,7 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
     c->leaf_off[t + 1] = c->leaf_off[t] + ((c->leaf_numel[t] + 63) / 64) * 64;
   }
   // permutes: sizes, reach of the source, room at the destination; rows sorted by group
-  c->group_first.assign(S + 1, 0), c->group_count.assign(S + 1, 0), c->group_max.assign(S + 1, 0);
+  c->group_first.assign(S + 1, 0), c->group_count.assign(S + 1, 0);
   int64_t prev_group = -1;
   for (int64_t r = 0; r < P; ++r) {
     const int64_t* row = &c->perms[r * PERM_W];
@@ -657,7 +665,7 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
     if (nd < 0 || nd > CT_MAX_AXES || g < -1 || g >= S || g < prev_group) return "permute table is not valid.";
     if (g != prev_group || r == 0) c->group_first[g + 1] = r;
     prev_group = g;
-    c->group_count[g + 1] += 1, c->group_max[g + 1] = std::max(c->group_max[g + 1], numel);
+    c->group_count[g + 1] += 1;
     int64_t prod = 1, reach = 0;
     for (int k = 0; k < nd; ++k) {
       if (row[8 + k] < 1 || row[8 + CT_MAX_AXES + k] < 0) return "permute table is not valid.";
@@ -747,21 +755,12 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
   return nullptr;
 }
 
+// the rows of permute group `group` that have the period of phase `phase`, in one launch
 template <class D, class SI = D, bool half = false, bool scaled = false>
-int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t sid, int64_t out_off, int64_t members = 0, bool hoisted = false,
-                   int64_t phase = -1) {
-  // a handle with hoisting: the flagged rows of the group (hoisted) or the others; with periods: the rows of the group
-  // that have the period of `phase`; without either: every row
-  const bool split = !c->hoist_count.empty();
-  const int64_t nh = split ? c->hoist_count[group + 1] : 0;
-  const int64_t at = phase < 0 ? 0 : phase * ((int64_t)c->group_first.size()) + group + 1;
-  const int64_t n = phase >= 0 ? c->reuse_count[at] : hoisted ? nh : c->group_count[group + 1] - nh;
+int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t phase, int64_t sid, int64_t out_off, int64_t members = 0) {
+  const int64_t at = phase * (int64_t)c->group_first.size() + group + 1;
+  const int64_t n = c->sched.count[at], largest = c->sched.largest[at], first = c->sched.first[at];
   if (!n) return TNCO_HIP_OK;
-  const int64_t largest = phase >= 0 ? c->reuse_max[at]
-                          : !split   ? c->group_max[group + 1]
-                          : hoisted  ? c->hoist_max[group + 1]
-                                     : c->rest_max[group + 1];
-  const int64_t first = phase >= 0 ? c->reuse_first[at] : c->group_first[group + 1] + (hoisted ? 0 : nh);
   const int64_t P = (int64_t)c->perms.size() / PERM_W;
   GatherArgs g;
   g.rows = c->d_tables + first * PERM_W;
@@ -944,11 +943,10 @@ int run_impl(tnco_hip_contract_s* c) {
     mb0.exp_step = (int)(L + S), mb0.amax_step = (int)S;
   }
   const int64_t arena_bytes = batched ? c->arena_elems * (int64_t)sizeof(E) : 0;
-  const bool hoisting = !c->hoist_step.empty() && S > 0;
-  const bool reusing = !c->reuse_step.empty() && S > 0;  // (such a handle has no batch and no hoist flags)
+  const Schedule& sc = c->sched;
   // Step k of the path.  bat: as members launches of a batch starting at assignment sid (the last step to the batch
-  // staging buffer), else one unbatched launch: an assignment's, or a hoisted step's (which reads no sliced leaf and
-  // works in arena copy 0)
+  // staging buffer), else one unbatched launch: an assignment's, or a step's of a period above 1 (which works in arena
+  // copy 0)
   auto run_step = [&](int64_t k, int64_t sid, bool bat, unsigned members, int beta, int64_t out_off) -> int {
     int rc;
     const int64_t* st = &c->steps[k * STEP_W];
@@ -960,7 +958,7 @@ int run_impl(tnco_hip_contract_s* c) {
       const int64_t kind = st[4 * side], ref = st[4 * side + 1];
       if (kind != K_LEAF) {  // (of a batch: each member's own arena; a kept tensor: copy 0 for every member)
         opnd[side] = arena + ref;
-        (side ? mb.b_step : mb.a_step) = hoisting && c->kept_opnd[2 * k + side] ? 0 : member_bytes;
+        (side ? mb.b_step : mb.a_step) = sc.kept_opnd[2 * k + side] ? 0 : member_bytes;
         continue;
       }
       // a leaf read in place: at the slice offset of the assignment, which a member of a batch adds for its own
@@ -1042,20 +1040,6 @@ int run_impl(tnco_hip_contract_s* c) {
       return launch_gemm<T>(c, p, members);
     }
   };
-  if (hoisting) {  // what does not depend on the assignment: once, in path order, in arena copy 0
-    int rc;
-    if (half && c->scaling) CT_TRY(hipMemsetAsync(c->d_amax, 0, (size_t)S * sizeof(uint32_t), c->stream));
-    if ((rc = launch_gathers<W, W, half>(c, -1, c->start, 0, 0, true))) return rc;
-    for (int64_t k = 0; k < S; ++k) {
-      if ((rc = launch_gathers<W, W, half>(c, k, c->start, 0, 0, true))) return rc;
-      if (c->hoist_step[k] && (rc = run_step(k, c->start, false, 1, 0, 0))) return rc;
-    }
-    // scaling in a batch: every member reads the exponents of the kept tensors in its own copy of the slots (the
-    // assignments clear the max words only, d_amax, never a slot)
-    if (half && c->scaling && batched)
-      for (int64_t b = 1; b < c->batch; ++b)
-        CT_TRY(hipMemcpyAsync(c->d_exps + b * (L + S), c->d_exps, (size_t)(L + S) * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-  }
   for (int64_t sid = c->start; sid < c->stop; sid += per) {
     const int64_t n = std::min(per, c->stop - sid);  // members of this launch
     const unsigned members = (unsigned)n;
@@ -1073,30 +1057,26 @@ int run_impl(tnco_hip_contract_s* c) {
     // scaling: the max words of every step are cleared at the start of an assignment (of a batch: of all its members),
     // in stream order after the narrowing passes of the one before
     if (half && c->scaling && S) CT_TRY(hipMemsetAsync(c->d_amax, 0, (size_t)(S * per) * sizeof(uint32_t), c->stream));
-    int rc = TNCO_HIP_OK;
-    if (reusing) {
-      // Every phase that is due at this assignment, the slowest first, each in path order.  (Not path order across the
-      // phases: a slower phase's temporaries may lie where a faster phase keeps a tensor, which that phase, due whenever
-      // the slower one is, then writes again.)  The step that writes the output has period 1: beta and the block are
-      // those of the plain loop
-      for (int64_t q = 0; q < (int64_t)c->reuse_phase.size(); ++q) {
-        const int64_t period = c->reuse_phase[q];
-        if (sid != c->start && sid % period) continue;
-        if ((rc = launch_gathers<W, W, half>(c, -1, sid, out_off, 0, false, q))) return rc;
-        for (int64_t k = 0; k < S; ++k) {
-          if ((rc = launch_gathers<W, W, half>(c, k, sid, out_off, 0, false, q))) return rc;
-          if (c->reuse_step[k] == period && (rc = run_step(k, sid, false, 1, beta, out_off))) return rc;
-        }
+    // Every phase that is due at this assignment, the slowest first, each in path order.  (Not path order across the
+    // phases: a slower phase's temporaries may lie where a faster phase keeps a tensor, which that phase, due whenever
+    // the slower one is, then writes again.)  A phase of a period above 1 is one unbatched launch per item in arena copy
+    // 0; the phase of period 1, which holds the step that writes the output, is the batch when the handle has one
+    for (int64_t q = 0; q < (int64_t)sc.phase.size(); ++q) {
+      const int64_t period = sc.phase[q];
+      if (sid != c->start && sid % period) continue;
+      const bool bat = batched && period == 1;
+      // scaling in a batch: every member reads the exponents of the kept tensors in its own copy of the slots (the
+      // assignments clear the max words only, d_amax, never a slot)
+      if (half && c->scaling && bat && q && sid == c->start)
+        for (int64_t b = 1; b < c->batch; ++b)
+          CT_TRY(hipMemcpyAsync(c->d_exps + b * (L + S), c->d_exps, (size_t)(L + S) * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+      int rc = half && S == 0 ? (c->scaling ? launch_gathers<T, E, half, half>(c, -1, q, sid, out_off) : launch_gathers<T, E, half>(c, -1, q, sid, out_off))
+                              : launch_gathers<W, W, half>(c, -1, q, sid, out_off, bat ? n : 0);
+      if (rc) return rc;
+      for (int64_t k = 0; k < S; ++k) {
+        if ((rc = launch_gathers<W, W, half>(c, k, q, sid, out_off, bat ? n : 0))) return rc;
+        if (sc.step_period[k] == period && (rc = run_step(k, sid, bat, bat ? members : 1, beta, out_off))) return rc;
       }
-      continue;
-    }
-    rc = half && S == 0 ? (c->scaling ? launch_gathers<T, E, half, half>(c, -1, sid, out_off) : launch_gathers<T, E, half>(c, -1, sid, out_off))
-                        : launch_gathers<W, W, half>(c, -1, sid, out_off, batched ? n : 0);
-    if (rc) return rc;
-    for (int64_t k = 0; k < S; ++k) {
-      if ((rc = launch_gathers<W, W, half>(c, k, sid, out_off, batched ? n : 0))) return rc;
-      if (hoisting && c->hoist_step[k]) continue;
-      if ((rc = run_step(k, sid, batched, members, beta, out_off))) return rc;
     }
     if (batched) {  // the members' blocks into the output, in assignment order
       const dim3 grid((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048));
@@ -1148,6 +1128,154 @@ int run_path(tnco_hip_contract_s* c) {
   return TNCO_HIP_OK;
 }
 
+int64_t n_assignments(const tnco_hip_contract_s* c) {
+  int64_t n = 1;
+  for (int64_t d : c->slice_dims) n *= d;
+  return n;
+}
+
+// What tnco_hip_contract_set_hoist refuses beyond tnco_hip_contract_set_reuse (hoist), and the wording of each setter for
+// the checks they share.
+struct ScheduleRules {
+  bool hoist;
+  const char *out_step, *out_perm, *order, *leaf_perm, *leaf_step, *perm_source, *step_source;
+};
+const ScheduleRules HOIST_RULES = {true,
+                                   "a hoisted step must write the arena.",
+                                   "a hoisted permute must write the arena.",
+                                   "the hoisted rows of a permute group must come first.",
+                                   "a hoisted permute reads a leaf with a sliced axis.",
+                                   "a hoisted step reads a leaf with a sliced axis.",
+                                   "a permute and the item that writes its source must both be hoisted or both not.",
+                                   "a hoisted step reads an arena tensor that no hoisted item wrote."};
+const ScheduleRules REUSE_RULES = {false,
+                                   "the step that writes the output must have period 1.",
+                                   "the permute that writes the output must have period 1.",
+                                   "the rows of a permute group must be ordered by period, the largest first.",
+                                   "a permute is slower than a sliced leaf it reads allows.",
+                                   "a step is slower than a sliced leaf it reads allows.",
+                                   "a permute is slower than the item that wrote its source.",
+                                   "a step is slower than the item that wrote its operand."};
+
+// The schedule of the periods given (each one valid: a place, the number of assignments, or what set_hoist makes of a
+// flag) into *s, or the text of what is wrong with them: nothing may be due less often than what it reads changes, and
+// what a slower item left for a faster one must still be there when that one runs.
+const char* make_schedule(const tnco_hip_contract_s* c, const int64_t* step_period, const int64_t* perm_period, const ScheduleRules& t,
+                          Schedule* s) {
+  const int64_t S = (int64_t)c->steps.size() / STEP_W, P = (int64_t)c->perms.size() / PERM_W, G = S + 1;
+  for (int64_t k = 0; k < S; ++k)
+    if (c->steps[k * STEP_W + 8] == K_OUT && step_period[k] != 1) return t.out_step;
+  for (int64_t r = 0; r < P; ++r) {
+    const int64_t* row = &c->perms[r * PERM_W];
+    if (row[2] == K_OUT && perm_period[r] != 1) return t.out_perm;
+    if (r && row[6] == row[6 - PERM_W] && perm_period[r] > perm_period[r - 1]) return t.order;
+  }
+  // what a leaf allows an item that reads it: the smallest place of its sliced axes, everything without one (an axis of
+  // dimension 1 has one value in every assignment and allows everything; not so for hoist flags, which take a leaf with
+  // any sliced axis to change with the assignment)
+  auto leaf_period = [&](int64_t leaf) {
+    const int64_t* ls = &c->leaf_sl[leaf * LEAF_SL_W];
+    int64_t per = t.hoist && ls[0] ? 1 : INT64_MAX;
+    for (int j = 0; j < (int)ls[0]; ++j)
+      if (c->slice_dims[ls[1 + j]] > 1) per = std::min(per, c->place[ls[1 + j]]);
+    return per;
+  };
+  for (int64_t r = 0; r < P; ++r) {
+    const int64_t* row = &c->perms[r * PERM_W];
+    if (row[0] == K_LEAF && perm_period[r] > leaf_period(row[1])) return t.leaf_perm;
+  }
+  for (int64_t k = 0; k < S; ++k)
+    for (int side = 0; side < 2; ++side) {
+      const int64_t* st = &c->steps[k * STEP_W];
+      if (st[4 * side] == K_LEAF && step_period[k] > leaf_period(st[4 * side + 1])) return t.leaf_step;
+    }
+  // Replay the path: who wrote what an item reads.  A write: [lo, hi) of the arena and the period of its item, in path
+  // order; read: an item has consumed it (every tensor has one reader) or nothing reads it (a staging buffer)
+  struct Write {
+    int64_t lo, hi, period;
+    char read;
+  };
+  struct Kept {
+    int64_t lo, hi;
+    size_t writer;
+  };
+  std::vector<Write> writes;
+  std::vector<Kept> kept;
+  // The write an item of that period reads at ref, -1: none, and marks it read.  The phases run one after the other, so
+  // an item sees the latest write of its own phase there, or else what the nearest slower phase kept; a write of a faster
+  // phase is returned last, for the caller to refuse.  This rests on one property of a sound arena, which the check of
+  // the kept tensors below enforces for what matters: when an item reads at ref, at most one unread write of its own
+  // phase starts there (a buffer is written, read, and only then given to the next tensor of the phase), and a kept
+  // tensor shares its start with no write of its own or a faster phase
+  auto writer_of = [&](int64_t ref, int64_t period) -> int64_t {
+    int64_t best = -1;
+    for (int64_t w = (int64_t)writes.size() - 1; w >= 0; --w) {
+      if (writes[w].lo != ref || writes[w].read) continue;
+      if (writes[w].period == period) {
+        best = w;
+        break;
+      }
+      const bool slower = writes[w].period > period;
+      if (best < 0 || (slower && (writes[best].period < period || writes[w].period < writes[best].period))) best = w;
+    }
+    if (best >= 0) writes[best].read = 1;
+    return best;
+  };
+  const char* e = nullptr;
+  // An item of that period reads [ref, ref + numel) of the arena: refused when a faster item wrote it; kept, and true, when
+  // a slower one did.  Hoist flags refuse more: a flagged item that reads what no item wrote, and a permute of a kept
+  // tensor (kept_opnd covers step operands only: in a slice batch such a permute would read the arena copy of its member)
+  auto source = [&](int64_t ref, int64_t period, int64_t numel, bool perm) {
+    const int64_t w = writer_of(ref, period);
+    const bool slower = w >= 0 && writes[w].period > period;
+    if (w < 0 ? t.hoist && period > 1 : writes[w].period < period || (slower && t.hoist && perm)) e = perm ? t.perm_source : t.step_source;
+    else if (slower) kept.push_back(Kept{ref, ref + numel, (size_t)w});
+    return slower && !e;
+  };
+  s->step_period.assign(step_period, step_period + S);
+  s->kept_opnd.assign(2 * S, 0);
+  std::vector<int64_t>& phase = s->phase;
+  phase.assign(step_period, step_period + S);
+  phase.insert(phase.end(), perm_period, perm_period + P);
+  std::sort(phase.begin(), phase.end(), std::greater<int64_t>());
+  phase.erase(std::unique(phase.begin(), phase.end()), phase.end());
+  s->first.assign(phase.size() * G, 0), s->count.assign(phase.size() * G, 0), s->largest.assign(phase.size() * G, 0);
+  auto perm_rows = [&](int64_t g) {  // the rows of permute group g
+    for (int64_t r = c->group_first[g + 1], n = 0; n < c->group_count[g + 1] && !e; ++r, ++n) {
+      const int64_t* row = &c->perms[r * PERM_W];
+      const int64_t per = perm_period[r];
+      if (row[0] == K_ARENA) source(row[1], per, row[5], true);
+      if (row[2] == K_ARENA) writes.push_back(Write{row[3], row[3] + row[5], per, 0});
+      const int64_t at = (std::find(phase.begin(), phase.end(), per) - phase.begin()) * G + g + 1;
+      if (!s->count[at]++) s->first[at] = r;
+      s->largest[at] = std::max(s->largest[at], row[5]);
+    }
+  };
+  perm_rows(-1);
+  for (int64_t k = 0; k < S && !e; ++k) {
+    perm_rows(k);
+    const int64_t* st = &c->steps[k * STEP_W];
+    const int64_t H = st[10], M = st[11], N = st[12], K = st[13], nc = H * M * N;
+    for (int side = 0; side < 2 && !e; ++side)
+      if (st[4 * side] == K_ARENA) s->kept_opnd[2 * k + side] = source(st[4 * side + 1], step_period[k], H * K * (side ? N : M), false);
+    if (st[8] == K_ARENA) {
+      writes.push_back(Write{st[9], st[9] + nc, step_period[k], 0});
+      if (c->scaling) writes.push_back(Write{c->stage_refs[k], c->stage_refs[k] + 2 * nc, step_period[k], 1});
+    }
+  }
+  if (e) return e;
+  // a kept tensor stays until its writer is due again: no item of its writer's phase writes into it after the writer, and
+  // no item of a faster phase at all (a slower phase may: whenever it is due, the writer is due after it)
+  for (size_t q = 0; q < kept.size(); ++q) {
+    const Write& own = writes[kept[q].writer];
+    for (size_t w = 0; w < writes.size(); ++w)
+      if (w != kept[q].writer && (writes[w].period < own.period || (writes[w].period == own.period && w > kept[q].writer)) &&
+          writes[w].lo < kept[q].hi && kept[q].lo < writes[w].hi)
+        return "a kept tensor is written over.";
+  }
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1160,6 +1288,8 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
     delete c;
     return fail(TNCO_HIP_EINVAL, e);
   }
+  const std::vector<int64_t> ones(std::max(c->steps.size() / STEP_W, c->perms.size() / PERM_W), 1);
+  (void)make_schedule(c, ones.data(), ones.data(), REUSE_RULES, &c->sched);  // every period 1: nothing there to refuse
   static const size_t elem[8] = {4, 8, 8, 16, 2, 4, 2, 4}, out_elem[8] = {4, 8, 8, 16, 4, 8, 4, 8};
   c->dtype = d->dtype, c->elem = elem[d->dtype], c->out_elem = out_elem[d->dtype], c->device = d->device;
   int ndev = 0;
@@ -1314,7 +1444,7 @@ int tnco_hip_contract_set_slice_batch(tnco_hip_contract c, int64_t batch) {
   if (batch < 1 || batch > MAX_SLICE_BATCH) return fail(TNCO_HIP_EINVAL, "'batch' must be from 1 to 64.");
   if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with a slice batch.");
   if (c->path_group) return fail(TNCO_HIP_EINVAL, "a slice batch and a path kernel are exclusive.");
-  if (!c->reuse_step.empty()) return fail(TNCO_HIP_EINVAL, "a slice batch is not supported with reuse periods.");
+  if (c->sched.set == Schedule::REUSE) return fail(TNCO_HIP_EINVAL, "a slice batch is not supported with reuse periods.");
   const size_t n_steps = c->steps.size() / STEP_W, n_slots = c->leaf_numel.size() + n_steps;
   if (!n_steps) {  // a single leaf gathered into the output: runs as it does without a batch, nothing to reserve
     c->batch = batch;
@@ -1400,8 +1530,8 @@ int tnco_hip_contract_set_path_kernel(tnco_hip_contract c, int64_t group) {
   if (c->compute) return fail(TNCO_HIP_EINVAL, "a compute mode is not supported with a path kernel.");
   if (c->matrix) return fail(TNCO_HIP_EINVAL, "matrix mode is not supported with a path kernel.");
   if (c->path_group) return fail(TNCO_HIP_EINVAL, "the path kernel is already set.");
-  if (!c->hoist_step.empty()) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with a path kernel.");
-  if (!c->reuse_step.empty()) return fail(TNCO_HIP_EINVAL, "a path kernel is not supported with reuse periods.");
+  if (c->sched.set == Schedule::HOIST) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with a path kernel.");
+  if (c->sched.set == Schedule::REUSE) return fail(TNCO_HIP_EINVAL, "a path kernel is not supported with reuse periods.");
   if (!c->ind_steps.empty() || c->folded) return fail(TNCO_HIP_EINVAL, "a path kernel is not supported with indirect operands.");
   const int64_t S = (int64_t)c->steps.size() / STEP_W;
   for (int64_t k = 0; k < S; ++k) {
@@ -1475,101 +1605,21 @@ int tnco_hip_contract_set_hoist(tnco_hip_contract c, const int64_t* step_flags, 
   if ((S && !step_flags) || (P && !perm_flags)) return fail(TNCO_HIP_EINVAL, "null argument.");
   if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with hoisting.");
   if (c->path_group) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with a path kernel.");
-  if (!c->reuse_step.empty()) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with reuse periods: they include it.");
+  if (c->sched.set == Schedule::REUSE) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with reuse periods: they include it.");
+  // a flagged item: the period that is due at the first assignment of a run only (a single assignment: any above 1)
+  const int64_t once = std::max<int64_t>(n_assignments(c), 2);
+  std::vector<int64_t> step_period(S), perm_period(P);
   bool any = false;
-  for (int64_t k = 0; k < S; ++k) {
-    if (step_flags[k] != 0 && step_flags[k] != 1) return fail(TNCO_HIP_EINVAL, "a hoist flag must be 0 or 1.");
-    any |= step_flags[k] == 1;
+  for (int64_t i = 0; i < S + P; ++i) {
+    const int64_t f = i < S ? step_flags[i] : perm_flags[i - S];
+    if (f != 0 && f != 1) return fail(TNCO_HIP_EINVAL, "a hoist flag must be 0 or 1.");
+    (i < S ? step_period[i] : perm_period[i - S]) = f ? once : 1;
+    any |= f == 1;
   }
-  for (int64_t r = 0; r < P; ++r) {
-    if (perm_flags[r] != 0 && perm_flags[r] != 1) return fail(TNCO_HIP_EINVAL, "a hoist flag must be 0 or 1.");
-    any |= perm_flags[r] == 1;
-  }
-  if (!any) {  // nothing to hoist: the handle runs as one on which this was never called
-    c->hoist_step.clear(), c->hoist_perm.clear(), c->kept_opnd.clear();
-    c->hoist_count.clear(), c->hoist_max.clear(), c->rest_max.clear();
-    return TNCO_HIP_OK;
-  }
-  // Replay the path: who wrote what an item reads.  A write: [lo, hi) of the arena and the flag of its item, in path
-  // order; read: an item has consumed it (every tensor has one reader) or nothing reads it (a staging buffer)
-  struct Write {
-    int64_t lo, hi;
-    char flag, read;
-  };
-  struct Kept {
-    int64_t lo, hi;
-    size_t writer;
-  };
-  std::vector<Write> writes;
-  std::vector<Kept> kept;
-  std::vector<char> kept_opnd(2 * S, 0);
-  std::vector<int64_t> count(S + 1, 0), max_h(S + 1, 0), max_rest(S + 1, 0);
-  // The write an item reads at ref, -1: none.  The hoisted items run before every other one, so a hoisted item sees
-  // the latest hoisted write there; another item the latest write of its own kind, or else what a hoisted one left
-  auto writer_of = [&](int64_t ref, char flag) -> int64_t {
-    for (char want : {flag, (char)1})
-      for (int64_t w = (int64_t)writes.size() - 1; w >= 0; --w)
-        if (writes[w].lo == ref && writes[w].flag == want && !writes[w].read) {
-          writes[w].read = 1;
-          return w;
-        }
-    return -1;
-  };
-  auto free_leaf = [&](int64_t leaf) { return c->leaf_sl[leaf * LEAF_SL_W] == 0; };
-  auto perm_rows = [&](int64_t g) -> const char* {  // the rows of permute group g
-    for (int64_t r = c->group_first[g + 1], n = 0; n < c->group_count[g + 1]; ++r, ++n) {
-      const int64_t* row = &c->perms[r * PERM_W];
-      const char f = (char)perm_flags[r];
-      if (f && n && !perm_flags[r - 1]) return "the hoisted rows of a permute group must come first.";
-      if (row[0] == K_LEAF) {
-        if (f && !free_leaf(row[1])) return "a hoisted permute reads a leaf with a sliced axis.";
-      } else {
-        const int64_t w = writer_of(row[1], f);
-        if ((w >= 0 && writes[w].flag) != (bool)f) return "a permute and the item that writes its source must both be hoisted or both not.";
-      }
-      if (f && row[2] != K_ARENA) return "a hoisted permute must write the arena.";
-      if (row[2] == K_ARENA) writes.push_back(Write{row[3], row[3] + row[5], f, 0});
-      count[g + 1] += f;
-      int64_t& largest = (f ? max_h : max_rest)[g + 1];
-      largest = std::max(largest, row[5]);
-    }
-    return nullptr;
-  };
-  const char* e = perm_rows(-1);
-  for (int64_t k = 0; k < S && !e; ++k) {
-    if ((e = perm_rows(k))) break;
-    const int64_t* st = &c->steps[k * STEP_W];
-    const char f = (char)step_flags[k];
-    const int64_t H = st[10], M = st[11], N = st[12], K = st[13], nc = H * M * N;
-    for (int side = 0; side < 2 && !e; ++side) {
-      const int64_t kind = st[4 * side], ref = st[4 * side + 1];
-      if (kind == K_LEAF) {
-        if (f && !free_leaf(ref)) e = "a hoisted step reads a leaf with a sliced axis.";
-        continue;
-      }
-      const int64_t w = writer_of(ref, f);
-      const bool from_hoisted = w >= 0 && writes[w].flag;
-      if (f && !from_hoisted) e = "a hoisted step reads an arena tensor that no hoisted item wrote.";
-      if (!f && from_hoisted) {
-        kept_opnd[2 * k + side] = 1;
-        kept.push_back(Kept{ref, ref + H * K * (side ? N : M), (size_t)w});
-      }
-    }
-    if (e) break;
-    if (f && st[8] != K_ARENA) e = "a hoisted step must write the arena.";
-    if (st[8] == K_ARENA) {
-      writes.push_back(Write{st[9], st[9] + nc, f, 0});
-      if (c->scaling) writes.push_back(Write{c->stage_refs[k], c->stage_refs[k] + 2 * nc, f, 1});
-    }
-  }
-  // a kept tensor stays for the whole run: no assignment writes into it, and no hoisted item after the one that wrote it
-  for (size_t q = 0; q < kept.size() && !e; ++q)
-    for (size_t w = 0; w < writes.size() && !e; ++w)
-      if (w != kept[q].writer && (!writes[w].flag || w > kept[q].writer) && writes[w].lo < kept[q].hi && kept[q].lo < writes[w].hi)
-        e = "a kept tensor is written over.";
-  if (e) return fail(TNCO_HIP_EINVAL, e);
-  c->hoist_step.assign(step_flags, step_flags + S), c->hoist_perm.assign(perm_flags, perm_flags + P);
-  c->kept_opnd = kept_opnd, c->hoist_count = count, c->hoist_max = max_h, c->rest_max = max_rest;
+  Schedule s;
+  if (const char* e = make_schedule(c, step_period.data(), perm_period.data(), HOIST_RULES, &s)) return fail(TNCO_HIP_EINVAL, e);
+  s.set = any ? Schedule::HOIST : Schedule::NEVER;  // (nothing to hoist: the handle runs as one on which this was never called)
+  c->sched = std::move(s);
   return TNCO_HIP_OK;
 }
 
@@ -1578,135 +1628,22 @@ int tnco_hip_contract_set_reuse(tnco_hip_contract c, const int64_t* step_period,
   const int64_t S = (int64_t)c->steps.size() / STEP_W, P = (int64_t)c->perms.size() / PERM_W;
   if ((S && !step_period) || (P && !perm_period)) return fail(TNCO_HIP_EINVAL, "null argument.");
   // a period: the place of a sliced index, or the number of assignments (what no sliced index reaches)
-  int64_t n_slices = 1;
-  for (int64_t d : c->slice_dims) n_slices *= d;
-  auto is_period = [&](int64_t v) { return v == n_slices || std::find(c->place.begin(), c->place.end(), v) != c->place.end(); };
+  const int64_t n_slices = n_assignments(c);
   bool any = false;
-  for (int64_t k = 0; k < S; ++k) {
-    if (!is_period(step_period[k])) return fail(TNCO_HIP_EINVAL, "a period must be the place of a sliced index or the number of assignments.");
-    any |= step_period[k] != 1;
-  }
-  for (int64_t r = 0; r < P; ++r) {
-    if (!is_period(perm_period[r])) return fail(TNCO_HIP_EINVAL, "a period must be the place of a sliced index or the number of assignments.");
-    any |= perm_period[r] != 1;
+  for (int64_t i = 0; i < S + P; ++i) {
+    const int64_t v = i < S ? step_period[i] : perm_period[i - S];
+    if (v != n_slices && std::find(c->place.begin(), c->place.end(), v) == c->place.end())
+      return fail(TNCO_HIP_EINVAL, "a period must be the place of a sliced index or the number of assignments.");
+    any |= v != 1;
   }
   if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with reuse periods.");
   if (c->path_group) return fail(TNCO_HIP_EINVAL, "a path kernel is not supported with reuse periods.");
   if (c->batch) return fail(TNCO_HIP_EINVAL, "a slice batch is not supported with reuse periods.");
-  if (!c->hoist_step.empty()) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with reuse periods: they include it.");
-  if (!any) {  // every item at every assignment: the handle runs as one on which this was never called
-    c->reuse_step.clear(), c->reuse_phase.clear();
-    c->reuse_first.clear(), c->reuse_count.clear(), c->reuse_max.clear();
-    return TNCO_HIP_OK;
-  }
-  for (int64_t k = 0; k < S; ++k)
-    if (c->steps[k * STEP_W + 8] == K_OUT && step_period[k] != 1) return fail(TNCO_HIP_EINVAL, "the step that writes the output must have period 1.");
-  for (int64_t r = 0; r < P; ++r) {
-    const int64_t* row = &c->perms[r * PERM_W];
-    if (row[2] == K_OUT && perm_period[r] != 1) return fail(TNCO_HIP_EINVAL, "the permute that writes the output must have period 1.");
-    if (r && row[6] == row[6 - PERM_W] && perm_period[r] > perm_period[r - 1])
-      return fail(TNCO_HIP_EINVAL, "the rows of a permute group must be ordered by period, the largest first.");
-  }
-  // what a leaf allows an item that reads it: the smallest place of its sliced axes, the number of assignments without one
-  // (an axis of dimension 1 has one value in every assignment and allows everything)
-  auto leaf_period = [&](int64_t leaf) {
-    const int64_t* ls = &c->leaf_sl[leaf * LEAF_SL_W];
-    int64_t per = n_slices;
-    for (int j = 0; j < (int)ls[0]; ++j)
-      if (c->slice_dims[ls[1 + j]] > 1) per = std::min(per, c->place[ls[1 + j]]);
-    return per;
-  };
-  for (int64_t r = 0; r < P; ++r) {
-    const int64_t* row = &c->perms[r * PERM_W];
-    if (row[0] == K_LEAF && perm_period[r] > leaf_period(row[1])) return fail(TNCO_HIP_EINVAL, "a permute is slower than a sliced leaf it reads allows.");
-  }
-  for (int64_t k = 0; k < S; ++k)
-    for (int side = 0; side < 2; ++side) {
-      const int64_t* st = &c->steps[k * STEP_W];
-      if (st[4 * side] == K_LEAF && step_period[k] > leaf_period(st[4 * side + 1]))
-        return fail(TNCO_HIP_EINVAL, "a step is slower than a sliced leaf it reads allows.");
-    }
-  // Replay the path: who wrote what an item reads.  A write: [lo, hi) of the arena and the period of its item, in path
-  // order; read: an item has consumed it (every tensor has one reader) or nothing reads it (a staging buffer)
-  struct Write {
-    int64_t lo, hi, period;
-    char read;
-  };
-  struct Kept {
-    int64_t lo, hi;
-    size_t writer;
-  };
-  std::vector<Write> writes;
-  std::vector<Kept> kept;
-  // The write an item of that period reads at ref, -1: none, and marks it read.  The phases run one after the other, so
-  // an item sees the latest write of its own phase there, or else what the nearest slower phase kept; a write of a faster
-  // phase is returned last, for the caller to refuse.  This rests on one property of a sound arena, which the check of
-  // the kept tensors below enforces for what matters: when an item reads at ref, at most one unread write of its own
-  // phase starts there (a buffer is written, read, and only then given to the next tensor of the phase), and a kept
-  // tensor shares its start with no write of its own or a faster phase
-  auto writer_of = [&](int64_t ref, int64_t period) -> int64_t {
-    int64_t best = -1;
-    for (int64_t w = (int64_t)writes.size() - 1; w >= 0; --w) {
-      if (writes[w].lo != ref || writes[w].read) continue;
-      if (writes[w].period == period) {
-        best = w;
-        break;
-      }
-      const bool slower = writes[w].period > period;
-      if (best < 0 || (slower && (writes[best].period < period || writes[w].period < writes[best].period))) best = w;
-    }
-    if (best >= 0) writes[best].read = 1;
-    return best;
-  };
-  const char* e = nullptr;
-  auto source = [&](int64_t ref, int64_t period, int64_t numel, const char* slower) {
-    const int64_t w = writer_of(ref, period);
-    if (w < 0) return;
-    if (writes[w].period < period) e = slower;
-    if (writes[w].period > period) kept.push_back(Kept{ref, ref + numel, (size_t)w});
-  };
-  const int64_t G = S + 1;
-  std::vector<int64_t> phase;  // the distinct periods, the largest first
-  for (int64_t k = 0; k < S; ++k) phase.push_back(step_period[k]);
-  for (int64_t r = 0; r < P; ++r) phase.push_back(perm_period[r]);
-  std::sort(phase.begin(), phase.end(), std::greater<int64_t>());
-  phase.erase(std::unique(phase.begin(), phase.end()), phase.end());
-  std::vector<int64_t> first(phase.size() * G, 0), count(phase.size() * G, 0), largest(phase.size() * G, 0);
-  auto perm_rows = [&](int64_t g) {  // the rows of permute group g
-    for (int64_t r = c->group_first[g + 1], n = 0; n < c->group_count[g + 1] && !e; ++r, ++n) {
-      const int64_t* row = &c->perms[r * PERM_W];
-      const int64_t per = perm_period[r];
-      if (row[0] == K_ARENA) source(row[1], per, row[5], "a permute is slower than the item that wrote its source.");
-      if (row[2] == K_ARENA) writes.push_back(Write{row[3], row[3] + row[5], per, 0});
-      const int64_t at = (std::find(phase.begin(), phase.end(), per) - phase.begin()) * G + g + 1;
-      if (!count[at]++) first[at] = r;
-      largest[at] = std::max(largest[at], row[5]);
-    }
-  };
-  perm_rows(-1);
-  for (int64_t k = 0; k < S && !e; ++k) {
-    perm_rows(k);
-    const int64_t* st = &c->steps[k * STEP_W];
-    const int64_t H = st[10], M = st[11], N = st[12], K = st[13], nc = H * M * N;
-    for (int side = 0; side < 2 && !e; ++side)
-      if (st[4 * side] == K_ARENA) source(st[4 * side + 1], step_period[k], H * K * (side ? N : M), "a step is slower than the item that wrote its operand.");
-    if (st[8] == K_ARENA) {
-      writes.push_back(Write{st[9], st[9] + nc, step_period[k], 0});
-      if (c->scaling) writes.push_back(Write{c->stage_refs[k], c->stage_refs[k] + 2 * nc, step_period[k], 1});
-    }
-  }
-  if (e) return fail(TNCO_HIP_EINVAL, e);
-  // a kept tensor stays until its writer is due again: no item of its writer's phase writes into it after the writer, and
-  // no item of a faster phase at all (a slower phase may: whenever it is due, the writer is due after it)
-  for (size_t q = 0; q < kept.size(); ++q) {
-    const Write& own = writes[kept[q].writer];
-    for (size_t w = 0; w < writes.size(); ++w)
-      if (w != kept[q].writer && (writes[w].period < own.period || (writes[w].period == own.period && w > kept[q].writer)) &&
-          writes[w].lo < kept[q].hi && kept[q].lo < writes[w].hi)
-        return fail(TNCO_HIP_EINVAL, "a kept tensor is written over.");
-  }
-  c->reuse_step.assign(step_period, step_period + S);
-  c->reuse_phase = phase, c->reuse_first = first, c->reuse_count = count, c->reuse_max = largest;
+  if (c->sched.set == Schedule::HOIST) return fail(TNCO_HIP_EINVAL, "hoisting is not supported with reuse periods: they include it.");
+  Schedule s;
+  if (const char* e = make_schedule(c, step_period, perm_period, REUSE_RULES, &s)) return fail(TNCO_HIP_EINVAL, e);
+  s.set = any ? Schedule::REUSE : Schedule::NEVER;  // (every period 1: the handle runs as one on which this was never called)
+  c->sched = std::move(s);
   return TNCO_HIP_OK;
 }
 
