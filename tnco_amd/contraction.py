@@ -164,7 +164,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from collections import defaultdict
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -302,8 +302,7 @@ class Plan:
     @property
     def macs(self) -> int:
         if self.step_period is not None:  # every step as often as it is due
-            return sum(_runs(int(P), *self.slice_range) * int(r[10]) * int(r[11]) * int(r[12]) * int(r[13])
-                       for P, r in zip(self.step_period, self.steps))
+            return sum(_runs(int(P), *self.slice_range) * _step_macs(r) for P, r in zip(self.step_period, self.steps))
         return self.hoisted_macs + (self.macs_per_slice - self.hoisted_macs) * (self.slice_range[1] - self.slice_range[0])
 
     @property
@@ -314,16 +313,16 @@ class Plan:
         maps = 0 if self.row_maps is None else 4 * self.row_maps.size + 8 * self.row_steps.size
         # scaling: an int32 exponent per leaf and step, a max word per step
         scale = 0 if self.scaling is None else 4 * (self.leaf_numel.size + 2 * len(self.steps))
-        # a slice batch: an arena and the scale words per member, and a block of the output per member as staging
+        # a slice batch or a path kernel: an arena and the scale words per member, and a block of the output per member
+        # as staging
+        members = self.slice_batch if self.path_kernel is None else self.path_kernel
         batch, stage = 1, 0
-        if self.slice_batch is not None and len(self.steps):
-            batch = self.slice_batch
+        if members is not None and len(self.steps):
+            batch = members
             stage = item * batch * self.out_numel // math.prod(self.shape[self.inds.index(x)] for x in self.block_inds)
-        # a path kernel: an arena and a block of the output as staging per member, and the tables that are new on the
-        # device: the steps, the first row and the count of every permute group, the placement of every assignment
+        # a path kernel: also the tables that are new on the device: the steps, the first row and the count of every
+        # permute group, the placement of every assignment
         if self.path_kernel is not None and len(self.steps):
-            batch = self.path_kernel
-            stage = item * batch * self.out_numel // math.prod(self.shape[self.inds.index(x)] for x in self.block_inds)
             tables += 8 * (self.steps.size + 2 * (len(self.steps) + 1) + self.slice_range[1] - self.slice_range[0])
         if self.ind_steps is not None:
             tables += 8 * (self.ind_steps.size + self.ind_maps.size)
@@ -400,107 +399,87 @@ def _storage_itemsize(dtype) -> int:
     return 4 if np.dtype(dtype).kind == "c" else 2
 
 
-def _check_storage(storage, dtype, projs=None) -> None:
-    if storage is None:
-        return
-    if storage not in STORAGES:
-        raise ValueError(f"'storage' must be None, {' or '.join(repr(s) for s in STORAGES)}.")
-    if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.complex64)):
-        raise TypeError(f"with 'storage' the compute dtype must be float32 or complex64, not {np.dtype(dtype)}.")
-    if projs is not None:
-        raise NotImplementedError("projections are not supported with 'storage'.")
-
-
-def _check_scaling(scaling, storage) -> None:
-    if scaling is None:
-        return
-    if not isinstance(scaling, str) or scaling not in SCALINGS:
-        raise ValueError("'scaling' must be None or 'tensor'.")
-    if storage is None:
-        raise ValueError("'scaling' needs 'storage'.")
-
-
-def _check_slice_batch(slice_batch, projs=None) -> None:
-    if slice_batch is None:
-        return
-    if isinstance(slice_batch, bool) or not isinstance(slice_batch, int) or not 1 <= slice_batch <= MAX_SLICE_BATCH:
-        raise ValueError(f"'slice_batch' must be None or an integer from 1 to {MAX_SLICE_BATCH}.")
-    if projs is not None:
-        raise NotImplementedError("projections are not supported with 'slice_batch'.")
-
-
-def _check_compute(compute, storage, dtype, projs=None) -> None:
-    if compute is None:
-        return
-    if not isinstance(compute, str) or compute not in COMPUTES:
-        raise ValueError(f"'compute' must be None or {' or '.join(repr(s) for s in COMPUTES)}.")
-    if storage is not None:
-        raise ValueError("'compute' and 'storage' are exclusive.")
-    if compute == "bf16x3" and np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.complex64)):
-        raise TypeError(f"with 'compute' the compute dtype must be float32 or complex64, not {np.dtype(dtype)}.")
-    if projs is not None:
-        raise NotImplementedError("projections are not supported with 'compute'.")
-
-
-def _check_path_kernel(path_kernel, slice_batch=None, storage=None, compute=None, projs=None) -> None:
-    if path_kernel is None:
-        return
-    if isinstance(path_kernel, bool) or not isinstance(path_kernel, int) or not 1 <= path_kernel <= MAX_PATH_KERNEL:
-        raise ValueError(f"'path_kernel' must be None or an integer from 1 to {MAX_PATH_KERNEL}.")
-    if slice_batch is not None:
-        raise ValueError("'path_kernel' and 'slice_batch' are exclusive.")
-    for name, value in (("storage", storage), ("compute", compute)):
-        if value is not None:
-            raise NotImplementedError(f"'{name}' is not supported with 'path_kernel'.")
-    if projs is not None:
-        raise NotImplementedError("projections are not supported with 'path_kernel'.")
-
-
-def _check_hoist(hoist, path_kernel=None, projs=None) -> None:
-    if hoist is None:
-        return
-    if hoist is not True:
-        raise ValueError("'hoist' must be None or True.")
-    if path_kernel is not None:
-        raise NotImplementedError("'hoist' is not supported with 'path_kernel'.")
-    if projs is not None:
-        raise NotImplementedError("projections are not supported with 'hoist'.")
-
-
-def _check_reuse(reuse, hoist=None, slice_batch=None, path_kernel=None, projs=None) -> None:
-    if reuse is None:
-        return
-    if reuse is not True:
-        raise ValueError("'reuse' must be None or True.")
-    if hoist is not None:
-        raise ValueError("'reuse' includes 'hoist': give one of them.")
-    for name, value in (("slice_batch", slice_batch), ("path_kernel", path_kernel)):
-        if value is not None:
-            raise NotImplementedError(f"'{name}' is not supported with 'reuse'.")
-    if projs is not None:
-        raise NotImplementedError("projections are not supported with 'reuse'.")
-
-
 SLICE_ORDER_ERROR = "'slice_order' must be None, 'reuse' or every sliced index once."
+_F32 = (np.dtype(np.float32), np.dtype(np.complex64))
 
 
-def _check_slice_order(slice_order, reuse=None, projs=None) -> None:
+def _is_count(most):
+    return lambda v: not isinstance(v, bool) and isinstance(v, int) and 1 <= v <= most
+
+
+def _is_order(v) -> bool:
     """What can be said without the network: that a sequence names every sliced index once is checked where they are known."""
-    if slice_order is None:
-        return
-    if isinstance(slice_order, str):
-        if slice_order != "reuse":
-            raise ValueError(SLICE_ORDER_ERROR)
-        if reuse is not True:
-            raise ValueError("slice_order='reuse' needs reuse=True.")
-    else:
-        try:
-            if len(set(slice_order)) != len(tuple(slice_order)):
-                raise ValueError(SLICE_ORDER_ERROR)
-        except TypeError as e:
-            raise ValueError(SLICE_ORDER_ERROR) from e
-    if projs is not None:
-        raise NotImplementedError("projections are not supported with 'slice_order'.")
+    if isinstance(v, str):
+        return v == "reuse"
+    try:
+        return len(set(v)) == len(tuple(v))
+    except TypeError as e:
+        raise ValueError(SLICE_ORDER_ERROR) from e
+
+
+def _given(*names, text="'{0}' is not supported with '{1}'.", error=NotImplementedError):
+    """Rules of the keyword `names[0]`: it is refused when one of the others is given ({0} the other, {1} the keyword)."""
+    return tuple((lambda o, dtype, x=x: getattr(o, x) is not None, error, text.format(x, names[0])) for x in names[1:])
+
+
+# The option keywords in the order they are checked.  Of each: the test of a value that is not None, what the value must
+# be (ValueError otherwise), and the rules that follow, first match: (refused when, exception, message; {dtype}: the
+# compute dtype).  The last rule of every keyword is not listed: no projections.
+_RULES = {
+    "compute": (lambda v: isinstance(v, str) and v in COMPUTES, "None or " + " or ".join(repr(s) for s in COMPUTES),
+                _given("compute", "storage", text="'{1}' and '{0}' are exclusive.", error=ValueError) +
+                ((lambda o, dtype: o.compute == "bf16x3" and dtype not in _F32, TypeError,
+                  "with 'compute' the compute dtype must be float32 or complex64, not {dtype}."),)),
+    "storage": (lambda v: v in STORAGES, "None, " + " or ".join(repr(s) for s in STORAGES),
+                ((lambda o, dtype: dtype not in _F32, TypeError,
+                  "with 'storage' the compute dtype must be float32 or complex64, not {dtype}."),)),
+    "scaling": (lambda v: isinstance(v, str) and v in SCALINGS, "None or 'tensor'",
+                ((lambda o, dtype: o.storage is None, ValueError, "'scaling' needs 'storage'."),)),
+    "slice_batch": (_is_count(MAX_SLICE_BATCH), f"None or an integer from 1 to {MAX_SLICE_BATCH}", ()),
+    "path_kernel": (_is_count(MAX_PATH_KERNEL), f"None or an integer from 1 to {MAX_PATH_KERNEL}",
+                    _given("path_kernel", "slice_batch", text="'{1}' and '{0}' are exclusive.", error=ValueError) +
+                    _given("path_kernel", "storage", "compute")),
+    "hoist": (lambda v: v is True, "None or True", _given("hoist", "path_kernel", text="'{1}' is not supported with '{0}'.")),
+    "indirect": (lambda v: v is True, "None or True", _given("indirect", "storage", "compute", "path_kernel")),
+    "reuse": (lambda v: v is True, "None or True",
+              _given("reuse", "hoist", text="'{1}' includes '{0}': give one of them.", error=ValueError) +
+              _given("reuse", "slice_batch", "path_kernel")),
+    "slice_order": (_is_order, "None, 'reuse' or every sliced index once",
+                    ((lambda o, dtype: isinstance(o.slice_order, str) and o.reuse is not True, ValueError,
+                      "slice_order='reuse' needs reuse=True."),)),
+}
+
+
+@dataclass(frozen=True)
+class _Options:
+    """The option keywords of `plan`, `contract` and `contract_results` (module docstring), as one call was given them."""
+    storage: object = None
+    scaling: object = None
+    slice_batch: object = None
+    compute: object = None
+    path_kernel: object = None
+    hoist: object = None
+    indirect: object = None
+    reuse: object = None
+    slice_order: object = None
+
+    def check(self, dtype, projs=None) -> None:
+        """Raises what _RULES refuses of the keywords, for arrays of the compute dtype `dtype` and the projections `projs`."""
+        dtype = np.dtype(dtype)
+        for name, (is_valid, must_be, rules) in _RULES.items():
+            if getattr(self, name) is None:
+                continue
+            if not is_valid(getattr(self, name)):
+                raise ValueError(f"'{name}' must be {must_be}.")
+            for refused, error, text in rules:
+                if refused(self, dtype):
+                    raise error(text.format(dtype=dtype))
+            if projs is not None:
+                raise NotImplementedError(f"projections are not supported with '{name}'.")
+
+    def keywords(self, **other) -> dict:
+        """The record as the keywords of a call, those of `other` in place of its own."""
+        return {**vars(self), **other}
 
 
 def _named_order(slice_order, slice_inds) -> tuple:
@@ -509,6 +488,11 @@ def _named_order(slice_order, slice_inds) -> tuple:
     if len(order) != len(slice_inds) or set(order) != set(slice_inds):
         raise ValueError(SLICE_ORDER_ERROR)
     return order
+
+
+def _step_macs(row) -> int:
+    """H M N K of a row of `Plan.steps`."""
+    return int(row[10]) * int(row[11]) * int(row[12]) * int(row[13])
 
 
 def _runs(period: int, lo: int, hi: int) -> int:
@@ -547,18 +531,6 @@ def _step_deps(steps, ts_inds, sl) -> list:
         live.append(da | db)
         out.append(da | db)
     return out
-
-
-def _check_indirect(indirect, storage=None, compute=None, path_kernel=None, projs=None) -> None:
-    if indirect is None:
-        return
-    if indirect is not True:
-        raise ValueError("'indirect' must be None or True.")
-    for name, value in (("storage", storage), ("compute", compute), ("path_kernel", path_kernel)):
-        if value is not None:
-            raise NotImplementedError(f"'{name}' is not supported with 'indirect'.")
-    if projs is not None:
-        raise NotImplementedError("projections are not supported with 'indirect'.")
 
 
 def _offset_table(group, st, dims) -> np.ndarray:
@@ -614,8 +586,7 @@ def _storage_bits(a, storage, check=True) -> np.ndarray:
     """A float32 / complex64 array in storage layout: uint16 of the same shape (complex: one more axis of 2, re and
     im).  ValueError when a finite value is not finite in the storage type; with check=False it becomes inf, as an
     intermediate does on the device."""
-    a = np.ascontiguousarray(a)
-    parts = a.reshape(-1).view(np.float32).reshape(a.shape + (2,)) if a.dtype.kind == "c" else a.astype(np.float32, copy=False)
+    parts = _parts(a)
     if storage == "float16":
         with np.errstate(over="ignore"):
             half = parts.astype(np.float16)
@@ -632,7 +603,7 @@ def round_to_storage(a, storage) -> np.ndarray:
     """`a` (float32 / complex64) with every part rounded to `storage` as the engine rounds a leaf: same dtype and
     shape.  ValueError as the engine raises it."""
     a = np.asarray(a)
-    _check_storage(storage, a.dtype)
+    _Options(storage=storage).check(a.dtype)
     return _from_storage_bits(_storage_bits(a, storage), storage, a)
 
 
@@ -669,7 +640,7 @@ def scale_to_storage(a, storage):
     a = np.asarray(a)
     if storage not in STORAGES:
         raise ValueError(f"'storage' must be {' or '.join(repr(s) for s in STORAGES)}.")
-    _check_storage(storage, a.dtype)
+    _Options(storage=storage).check(a.dtype)
     bits, e = _scaled_bits(a, storage)
     like = np.empty(bits.shape, np.float32)
     with np.errstate(over="ignore"):
@@ -755,26 +726,19 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     """The device plan of one contraction along a path that leaves one tensor (no GPU).
     `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`, `slice_batch`,
     `compute`, `path_kernel`, `hoist`, `indirect`, `reuse`, `slice_order`: see the module docstring."""
-    _check_compute(compute, storage, dtype, projs)
-    _check_storage(storage, dtype, projs)
-    _check_scaling(scaling, storage)
-    _check_slice_batch(slice_batch, projs)
-    _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
-    _check_hoist(hoist, path_kernel, projs)
-    _check_indirect(indirect, storage, compute, path_kernel, projs)
-    _check_reuse(reuse, hoist, slice_batch, path_kernel, projs)
-    _check_slice_order(slice_order, reuse, projs)
+    options = _Options(storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute, path_kernel=path_kernel,
+                       hoist=hoist, indirect=indirect, reuse=reuse, slice_order=slice_order)
+    options.check(dtype, projs)
     if isinstance(slice_order, str):  # "reuse": the default order unless the greedy one has strictly fewer multiply-adds
-        mode = dict(slices=slices, slice_range=slice_range, dtype=dtype, storage=storage, scaling=scaling, compute=compute,
-                    indirect=indirect, reuse=reuse)
-        p = plan(path, ts_inds, shapes, output_inds, **mode)
+        mode = dict(slices=slices, slice_range=slice_range, dtype=dtype)
+        p = plan(path, ts_inds, shapes, output_inds, **mode, **options.keywords(slice_order=None))
         dims = dict(zip(p.slice_inds, p.slice_dims))
         deps = _step_deps(_check_path(path, len(p.leaf_numel)), [tuple(xs) for xs in ts_inds],
                           frozenset(x for x in slices if dims[x] > 1))
-        each = [int(r[10]) * int(r[11]) * int(r[12]) * int(r[13]) for r in p.steps]
+        each = [_step_macs(r) for r in p.steps]
         greedy = _reuse_order(p.slice_inds, deps, each)
         if greedy != p.slice_inds and _reuse_macs(greedy, deps, each, dims, *p.slice_range) < p.macs:
-            p = plan(path, ts_inds, shapes, output_inds, slice_order=greedy, **mode)
+            p = plan(path, ts_inds, shapes, output_inds, **mode, **options.keywords(slice_order=greedy))
         return p
     ts_inds = [tuple(xs) for xs in ts_inds]
     shapes = [tuple(int(d) for d in s) for s in shapes]
@@ -1031,7 +995,7 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     perm_tab, perm_per = perm_tab[order], perm_per[order]
     step_per = np.array(step_per, np.int64).reshape(-1)
     step_tab = np.array(rows, np.int64).reshape(-1, STEP_W)
-    macs = int(sum(int(r[10]) * int(r[11]) * int(r[12]) * int(r[13]) for r in rows))
+    macs = int(sum(_step_macs(r) for r in rows))
     p = Plan(dtype=np.dtype(dtype), inds=final, shape=tuple(dims[x] for x in final), slice_inds=slice_inds,
              slice_dims=slice_dims, block_inds=tuple(x for x in slice_inds if x in final), leaf_numel=leaf_numel,
              leaf_sl=leaf_sl, perms=perm_tab, steps=step_tab, arena_elems=arena.peak, out_numel=size(final),
@@ -1044,15 +1008,14 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     if path_kernel is not None:  # (the tables are those of the unfused plan; projections were refused above)
         _check_path_steps(p)
         p.path_kernel = min(int(path_kernel), hi - lo) if steps else 1
+    p.kept = tuple((offset[b], buf_size[b]) for b in kept_bufs)  # (without hoist and reuse every period is 1: none)
     if hoist is not None:  # (without a hoisted step or permute the tables are those of the plan without the keyword)
         p.step_hoist, p.perm_hoist = (step_per == 2).astype(np.int64), (perm_per == 2).astype(np.int64)
         p.hoisted = (int(p.step_hoist.sum()), int(p.perm_hoist.sum()))
-        p.kept = tuple((offset[b], buf_size[b]) for b in kept_bufs)
-        p.hoisted_macs = int(sum(int(r[10]) * int(r[11]) * int(r[12]) * int(r[13]) for r, h in zip(rows, p.step_hoist) if h))
+        p.hoisted_macs = int(sum(_step_macs(r) for r, h in zip(rows, p.step_hoist) if h))
     if reuse is not None:  # (when every period is 1 the tables are those of the plan without the keyword)
         p.step_period, p.perm_period = step_per, perm_per
         p.reused = (int((step_per > 1).sum()), int((perm_per > 1).sum()))
-        p.kept = tuple((offset[b], buf_size[b]) for b in kept_bufs)
         p.kept_period = tuple(kept_per)
     if indirect is not None:  # (with nothing folded the tables are those of the plan without the keyword)
         p.indirect = sum((row[0] >= 0) + (row[3] >= 0) for row in ind_rows)
@@ -1065,8 +1028,7 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     p.sparse_inds, p.leaf_rows = sparse, leaf_rows
     p.row_steps = np.array(row_steps, np.int64).reshape(-1, ROW_W)
     p.row_maps = np.concatenate(row_maps + [np.zeros(0, np.int32)]).astype(np.int32)
-    p.macs_per_slice = int(sum(int(w[0]) * int(r[10]) * int(r[11]) * int(r[12]) * int(r[13])
-                               for w, r in zip(row_steps, rows)))
+    p.macs_per_slice = int(sum(int(w[0]) * _step_macs(r) for w, r in zip(row_steps, rows)))
     rest = tuple(x for x in full_final if x not in col)
     if sparse:
         p.out_rows = (dims[final[0]], _unique_rows(projs)[1])
@@ -1131,74 +1093,68 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     arrays = [np.asarray(a) for a in arrays]
     dims = _dims_of(ts_inds, [a.shape for a in arrays])
     dtype = _compute_dtype(arrays)
-    _check_compute(compute, storage, dtype, projs)
-    _check_storage(storage, dtype, projs)
-    _check_scaling(scaling, storage)
-    _check_slice_batch(slice_batch, projs)
-    _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
-    _check_hoist(hoist, path_kernel, projs)
-    _check_indirect(indirect, storage, compute, path_kernel, projs)
-    _check_reuse(reuse, hoist, slice_batch, path_kernel, projs)
-    _check_slice_order(slice_order, reuse, projs)
+    options = _Options(storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute, path_kernel=path_kernel,
+                       hoist=hoist, indirect=indirect, reuse=reuse, slice_order=slice_order)
+    options.check(dtype, projs)
     steps = _check_path(path, len(ts_inds))
     final, out = tnmod.contract(steps, ts_inds, output_inds, dims)
     if len(final) == 1:
         p = plan(steps, ts_inds, [a.shape for a in arrays], out, slices=slices, slice_range=slice_range, dtype=dtype,
-                 sparse_inds=sparse_inds, projs=projs, storage=storage, scaling=scaling, slice_batch=slice_batch,
-                 compute=compute, path_kernel=path_kernel, hoist=hoist, indirect=indirect, reuse=reuse,
-                 slice_order=slice_order)
+                 sparse_inds=sparse_inds, projs=projs, **options.keywords())
         return _run(p, arrays, device, loose)
     if slices:
         raise NotImplementedError("slices need a path that leaves one tensor.")
     if projs is not None or tuple(sparse_inds):
         raise NotImplementedError("projections need a path that leaves one tensor.")
     parts = []
-    effective = None if slice_batch is None else 1  # (every part is unsliced: one assignment)
-    fused = None if path_kernel is None else 1
-    none_hoisted = None if hoist is None else (0, 0)  # (every part is unsliced: nothing to hoist)
-    none_folded = None if indirect is None else 0
-    none_reused = None if reuse is None else (0, 0)  # (every part is unsliced: every item runs once)
     if slice_order is not None and not isinstance(slice_order, str):
         _named_order(slice_order, ())
+    # every part is unsliced: one assignment, nothing to hoist, nothing folded, every item runs once
+    unsliced = dict(slice_batch=None if slice_batch is None else 1, path_kernel=None if path_kernel is None else 1,
+                    hoisted=None if hoist is None else (0, 0), indirect=None if indirect is None else 0,
+                    reused=None if reuse is None else (0, 0))
     for leaves, sub in _split(steps, len(ts_inds)):
         if not sub:  # a tensor the path does not touch: as the single-leaf plan gives it, rounded to storage
-            a = arrays[leaves[0]].astype(dtype, copy=True)
+            a, e = arrays[leaves[0]].astype(dtype, copy=True), None
             if scaling is not None:
                 a, e = scale_to_storage(a, storage)
-                parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, scaling=scaling, exponents=(e,),
-                                               slice_batch=effective, path_kernel=fused, hoisted=none_hoisted,
-                                               indirect=none_folded, reused=none_reused))
-                continue
-            if storage is not None:
+            elif storage is not None:
                 a = _from_storage_bits(_storage_bits(a, storage, leaves[0] not in loose), storage, a)
-            if compute == "bf16x3" and leaves[0] not in loose:
+            elif compute == "bf16x3" and leaves[0] not in loose:
                 _check_split_range(a)
-            parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, slice_batch=effective, compute=compute,
-                                           path_kernel=fused, hoisted=none_hoisted, indirect=none_folded,
-                                           reused=none_reused))
+            parts.append(ContractionResult(ts_inds[leaves[0]], a, 0, 1, 0, scaling=scaling, compute=compute,
+                                           exponents=None if e is None else (e,), **unsliced))
             continue
         parts.append(contract(sub, [ts_inds[t] for t in leaves], [arrays[t].astype(dtype, copy=False) for t in leaves],
-                              _sub_output(ts_inds, leaves, out), device=device, storage=storage, scaling=scaling,
-                              slice_batch=slice_batch, compute=compute, path_kernel=path_kernel, hoist=hoist,
-                              indirect=indirect, reuse=reuse,
+                              _sub_output(ts_inds, leaves, out), device=device, **options.keywords(slice_order=None),
                               _intermediates=[k for k, t in enumerate(leaves) if t in loose]))
     assert [tuple(r.inds) for r in parts] == [tuple(f) for f in final]
-    return ContractionResult([r.inds for r in parts], [r.array for r in parts], sum(r.macs for r in parts), 1,
-                             max(r.peak_device_bytes for r in parts), sum(r.launches for r in parts),
-                             kernel_launches=_add_counts(*(r.kernel_launches for r in parts)),
-                             row_kernel_launches=_add_counts(*(r.row_kernel_launches for r in parts)), scaling=scaling,
-                             exponents=None if scaling is None else [r.exponents for r in parts],
-                             narrow_launches=sum(r.narrow_launches for r in parts), slice_batch=effective,
-                             batch_launches=sum(r.batch_launches for r in parts), compute=compute,
-                             split_launches=sum(r.split_launches for r in parts), path_kernel=fused,
-                             path_launches=_add_counts(*(r.path_launches for r in parts)), hoisted=none_hoisted,
-                             indirect=None if indirect is None else sum(r.indirect for r in parts),
-                             indirect_launches=_add_counts(*(r.indirect_launches for r in parts)),
-                             matrix_launches=sum(r.matrix_launches for r in parts), reused=none_reused)
+    return _sum_results(parts, inds=[r.inds for r in parts], array=[r.array for r in parts], n_slices=1,
+                        exponents=None if scaling is None else [r.exponents for r in parts])
 
 
-def _add_counts(*counts) -> tuple:
-    return tuple(sum(c) for c in zip(*counts))
+def _sum_results(parts, **given) -> ContractionResult:
+    """The results of several calls as one.  `given`: inds, array, n_slices, exponents and fuse_macs, which are the
+    caller's to say.  Of the others the counters are sums and `peak_device_bytes` the largest; `slice_batch` and
+    `path_kernel` are the largest, `hoisted`, `reused` and `indirect` the sums, over the parts that have one, None when
+    none has; `scaling` and `compute` are what the parts have in common."""
+    def add(name):  # None is no part of a sum; tuples are added element by element
+        values = [v for v in (getattr(r, name) for r in parts) if v is not None]
+        if not values:
+            return None
+        return tuple(sum(c) for c in zip(*values)) if isinstance(values[0], tuple) else sum(values)
+
+    def common(name):
+        (value,) = {getattr(r, name) for r in parts}
+        return value
+
+    sums = ("macs", "launches", "device_s", "kernel_launches", "row_kernel_launches", "narrow_launches", "batch_launches",
+            "split_launches", "path_launches", "hoisted", "reused", "indirect", "indirect_launches", "matrix_launches")
+    return ContractionResult(peak_device_bytes=max(r.peak_device_bytes for r in parts),
+                             slice_batch=max((r.slice_batch for r in parts if r.slice_batch is not None), default=None),
+                             path_kernel=max((r.path_kernel for r in parts if r.path_kernel is not None), default=None),
+                             scaling=common("scaling"), compute=common("compute"), **{name: add(name) for name in sums},
+                             **given)
 
 
 def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
@@ -1256,74 +1212,56 @@ def _describe(p: Plan, device: int):
 
 def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
     from . import _lib
-    exponents, narrow, folds, splits, fused, matrix = None, 0, 0, 0, (0, 0), 0
-    through = (0,) * len(INDIRECT_KERNEL_PATHS)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    i64 = lambda a: None if a is None else np.ascontiguousarray(a, np.int64)  # noqa: E731
+    matrix, split = p.compute == "matrix", p.compute not in (None, "matrix")
     try:
-        if p.compute == "matrix":
-            _lib.check(L.tnco_hip_contract_set_matrix(h, 1))
-        elif p.compute is not None:
-            _lib.check(L.tnco_hip_contract_set_compute(h, COMPUTES[p.compute]))
-        if p.slice_batch is not None:
-            _lib.check(L.tnco_hip_contract_set_slice_batch(h, p.slice_batch))
-        if p.path_kernel is not None:
-            _lib.check(L.tnco_hip_contract_set_path_kernel(h, p.path_kernel))
-        if p.scaling is not None:
-            _lib.check(L.tnco_hip_contract_set_exponents(h, leaf_exps.ctypes.data_as(C.c_void_p)))
-        if p.hoisted is not None and any(p.hoisted):  # (nothing hoisted: the run of the plan without the keyword)
-            flags = [np.ascontiguousarray(q, np.int64) for q in (p.step_hoist, p.perm_hoist)]
-            _lib.check(L.tnco_hip_contract_set_hoist(h, *(q.ctypes.data_as(C.c_void_p) for q in flags)))
-        if p.reused is not None and any(p.reused):  # (every period 1: the run of the plan without the keyword)
-            periods = [np.ascontiguousarray(q, np.int64) for q in (p.step_period, p.perm_period)]
-            _lib.check(L.tnco_hip_contract_set_reuse(h, *(q.ctypes.data_as(C.c_void_p) for q in periods)))
-        if p.indirect:  # (nothing folded: the run of the plan without the keyword)
-            tabs = [np.ascontiguousarray(q, np.int64) for q in (p.ind_steps, p.ind_maps)]
-            _lib.check(L.tnco_hip_contract_set_indirect(h, tabs[0].ctypes.data_as(C.c_void_p), tabs[1].size,
-                                                        tabs[1].ctypes.data_as(C.c_void_p)))
+        # (is it on, entry point, arguments), in an order the library takes.  Nothing hoisted, every period 1 or nothing
+        # folded: the run of the plan without the keyword
+        setters = (
+            (matrix, L.tnco_hip_contract_set_matrix, (1,)),
+            (split, L.tnco_hip_contract_set_compute, (COMPUTES.get(p.compute),)),
+            (p.slice_batch is not None, L.tnco_hip_contract_set_slice_batch, (p.slice_batch,)),
+            (p.path_kernel is not None, L.tnco_hip_contract_set_path_kernel, (p.path_kernel,)),
+            (p.scaling is not None, L.tnco_hip_contract_set_exponents, (leaf_exps,)),
+            (p.hoisted is not None and any(p.hoisted), L.tnco_hip_contract_set_hoist, (i64(p.step_hoist), i64(p.perm_hoist))),
+            (p.reused is not None and any(p.reused), L.tnco_hip_contract_set_reuse, (i64(p.step_period), i64(p.perm_period))),
+            (p.indirect, L.tnco_hip_contract_set_indirect, (i64(p.ind_steps), np.size(p.ind_maps), i64(p.ind_maps))))
+        # (is it on, entry point, length, field of the result)
+        counters = (
+            (True, L.tnco_hip_contract_kernel_launches, len(KERNEL_PATHS), "kernel_launches"),
+            (True, L.tnco_hip_contract_row_launches, len(ROW_KERNEL_PATHS), "row_kernel_launches"),
+            (p.scaling is not None, L.tnco_hip_contract_narrow_launches, 1, "narrow_launches"),
+            (p.slice_batch is not None, L.tnco_hip_contract_batch_launches, 1, "batch_launches"),
+            (matrix, L.tnco_hip_contract_matrix_launches, 1, "matrix_launches"),
+            (split, L.tnco_hip_contract_split_launches, 1, "split_launches"),
+            (p.path_kernel is not None, L.tnco_hip_contract_path_launches, 2, "path_launches"),
+            (p.indirect, L.tnco_hip_contract_indirect_launches, len(INDIRECT_KERNEL_PATHS), "indirect_launches"))
+        exponents, counted = None, {}
+        for on, entry, args in setters:
+            if on:
+                _lib.check(entry(h, *(ptr(a) if isinstance(a, np.ndarray) else a for a in args)))
         staging = np.empty(p.out_numel, p.dtype)
         ptrs = (C.c_void_p * max(1, len(leaves)))(*[a.ctypes.data for a in leaves])
-        _lib.check(L.tnco_hip_contract_run(h, ptrs, staging.ctypes.data_as(C.c_void_p)))
+        _lib.check(L.tnco_hip_contract_run(h, ptrs, ptr(staging)))
         stats = np.zeros(4, np.int64)
-        _lib.check(L.tnco_hip_contract_stats(h, stats.ctypes.data_as(C.c_void_p)))
-        by_kernel = np.zeros(len(KERNEL_PATHS), np.int64)
-        _lib.check(L.tnco_hip_contract_kernel_launches(h, by_kernel.ctypes.data_as(C.c_void_p)))
-        by_row_kernel = np.zeros(len(ROW_KERNEL_PATHS), np.int64)
-        _lib.check(L.tnco_hip_contract_row_launches(h, by_row_kernel.ctypes.data_as(C.c_void_p)))
+        _lib.check(L.tnco_hip_contract_stats(h, ptr(stats)))
         if p.scaling is not None:
             slots = np.zeros(len(leaves) + len(p.steps), np.int32)
-            _lib.check(L.tnco_hip_contract_exponents(h, slots.ctypes.data_as(C.c_void_p)))
-            count = C.c_int64()
-            _lib.check(L.tnco_hip_contract_narrow_launches(h, C.byref(count)))
-            exponents, narrow = tuple(int(v) for v in slots), int(count.value)
-        if p.slice_batch is not None:
-            count = C.c_int64()
-            _lib.check(L.tnco_hip_contract_batch_launches(h, C.byref(count)))
-            folds = int(count.value)
-        if p.compute == "matrix":
-            count = C.c_int64()
-            _lib.check(L.tnco_hip_contract_matrix_launches(h, C.byref(count)))
-            matrix = int(count.value)
-        elif p.compute is not None:
-            count = C.c_int64()
-            _lib.check(L.tnco_hip_contract_split_launches(h, C.byref(count)))
-            splits = int(count.value)
-        if p.path_kernel is not None:
-            counts = np.zeros(2, np.int64)
-            _lib.check(L.tnco_hip_contract_path_launches(h, counts.ctypes.data_as(C.c_void_p)))
-            fused = tuple(int(v) for v in counts)
-        if p.indirect:
-            counts = np.zeros(len(INDIRECT_KERNEL_PATHS), np.int64)
-            _lib.check(L.tnco_hip_contract_indirect_launches(h, counts.ctypes.data_as(C.c_void_p)))
-            through = tuple(int(v) for v in counts)
+            _lib.check(L.tnco_hip_contract_exponents(h, ptr(slots)))
+            exponents = tuple(int(v) for v in slots)
+        for on, entry, length, name in counters:
+            if on:
+                counts = np.zeros(length, np.int64)
+                _lib.check(entry(h, ptr(counts)))
+                counted[name] = int(counts[0]) if length == 1 else tuple(int(v) for v in counts)
     finally:
         L.tnco_hip_contract_destroy(h)
     array = _host_layout(p, staging)
     return ContractionResult(p.inds, array, int(stats[0]), p.slice_range[1] - p.slice_range[0], int(stats[2]),
-                             int(stats[1]), float(stats[3]) * 1e-9, kernel_launches=tuple(int(v) for v in by_kernel),
-                             row_kernel_launches=tuple(int(v) for v in by_row_kernel), scaling=p.scaling,
-                             exponents=exponents, narrow_launches=narrow, slice_batch=p.slice_batch, batch_launches=folds,
-                             compute=p.compute, split_launches=splits, path_kernel=p.path_kernel, path_launches=fused,
-                             hoisted=p.hoisted, indirect=p.indirect, indirect_launches=through, matrix_launches=matrix,
-                             reused=p.reused)
+                             int(stats[1]), float(stats[3]) * 1e-9, scaling=p.scaling, exponents=exponents,
+                             slice_batch=p.slice_batch, compute=p.compute, path_kernel=p.path_kernel, hoisted=p.hoisted,
+                             reused=p.reused, indirect=p.indirect, **counted)
 
 
 def _host_layout(p: Plan, staging) -> np.ndarray:
@@ -1375,15 +1313,9 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     below it (module docstring); the fuse stage, unsliced, stays as it is; `reused` is the sum over the calls.
     slice_order: the order of the sliced indices, slowest first (module docstring): "reuse" for every sliced call, or a
     sequence that names every index of `result.slices` once (of several components: each takes its own, in that order)."""
-    _check_compute(compute, storage, np.float32, projs)
-    _check_storage(storage, np.float32, projs)
-    _check_scaling(scaling, storage)
-    _check_slice_batch(slice_batch, projs)
-    _check_path_kernel(path_kernel, slice_batch, storage, compute, projs)
-    _check_hoist(hoist, path_kernel, projs)
-    _check_indirect(indirect, storage, compute, path_kernel, projs)
-    _check_reuse(reuse, hoist, slice_batch, path_kernel, projs)
-    _check_slice_order(slice_order, reuse, projs)
+    options = _Options(storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute, path_kernel=path_kernel,
+                       hoist=hoist, indirect=indirect, reuse=reuse, slice_order=slice_order)
+    options.check(np.float32, projs)  # (before the network is looked at; the arrays' dtype: below)
     if (tn0.sparse_inds or tn.sparse_inds) and projs is None:
         raise NotImplementedError("sparse indices (n_projs) have an array meaning only at given projections: "
                                   "pass projs=, an integer array [P, number of sparse indices].")
@@ -1402,8 +1334,7 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         except KeyError as e:
             raise ValueError("'ts_inds' is not consistent with 'arrays'.") from e
     arrays = [np.asarray(a) for a in arrays]
-    _check_compute(compute, storage, _compute_dtype(arrays))
-    _check_storage(storage, _compute_dtype(arrays))
+    options.check(_compute_dtype(arrays))  # (what compute and storage say of the dtype; the rest passed above)
     fuse_macs = 0
     if tn.tags.get("fuse_path"):
         fused = contract(tn.tags["fuse_path"], tn0.ts_inds, arrays, tn0.output_inds, device=device)
@@ -1416,23 +1347,11 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     comp_paths = [list(q) for q in getattr(result, "disconnected_paths", ()) if q]
     if len(comp_paths) <= 1:  # one component to contract: the path with its slices, in one call
         r = contract(result.path, tn.ts_inds, arrays, tn.output_inds, slices=getattr(result, "slices", ()),
-                     device=device, sparse_inds=sparse_inds or (), projs=projs, storage=storage, scaling=scaling,
-                     slice_batch=slice_batch, compute=compute, path_kernel=path_kernel, hoist=hoist, indirect=indirect,
-                     reuse=reuse, slice_order=slice_order)
-        return ContractionResult(r.inds, r.array, r.macs, r.n_slices, r.peak_device_bytes, r.launches, r.device_s,
-                                 fuse_macs, r.kernel_launches, r.row_kernel_launches, r.scaling, r.exponents,
-                                 r.narrow_launches, r.slice_batch, r.batch_launches, r.compute, r.split_launches,
-                                 r.path_kernel, r.path_launches, r.hoisted, indirect=r.indirect,
-                                 indirect_launches=r.indirect_launches, matrix_launches=r.matrix_launches, reused=r.reused)
+                     device=device, sparse_inds=sparse_inds or (), projs=projs, **options.keywords())
+        return replace(r, fuse_macs=fuse_macs)
     # several: each component with its own slices, then the remaining steps of the merged path over their results
     ts, n = [tuple(x) for x in tn.ts_inds], len(tn.ts_inds)
-    done, results, macs, n_slices, peak, launches, device_s = set(), [], 0, 0, 0, 0, 0.0
-    by_kernel = (0,) * len(KERNEL_PATHS)
-    exponents, narrow, folds, effective, splits, matrix = None, 0, 0, None, 0, 0
-    fused, fused_launches = None, (0, 0)
-    hoisted = None if hoist is None else (0, 0)
-    folded, through = None if indirect is None else 0, (0,) * len(INDIRECT_KERNEL_PATHS)
-    reused = None if reuse is None else (0, 0)
+    done, results = set(), []
     named = slice_order is not None and not isinstance(slice_order, str)
     if named:  # every index of every component's set, once
         _named_order(slice_order, tuple(dict.fromkeys(x for cut in result.disconnected_slices for x in cut)))
@@ -1443,54 +1362,24 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         n_comp_steps += len(q)
         (leaves, sub), = [(lv, s) for lv, s in _split(_check_path(q, n), n) if s]
         r = contract(sub, [ts[t] for t in leaves], [arrays[t] for t in leaves], _sub_output(ts, leaves, tn.output_inds),
-                     slices=cut, device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute,
-                     path_kernel=path_kernel, hoist=hoist, indirect=indirect, reuse=reuse,
-                     slice_order=[x for x in slice_order if x in set(cut)] if named else slice_order)
-        if reuse is not None:
-            reused = _add_counts(reused, r.reused)
-        if hoist is not None:
-            hoisted = _add_counts(hoisted, r.hoisted)
-        if indirect is not None:
-            folded, through = folded + r.indirect, _add_counts(through, r.indirect_launches)
-        exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
-        splits, matrix = splits + r.split_launches, matrix + r.matrix_launches
-        if slice_batch is not None:
-            effective = max(effective or 1, r.slice_batch)
-        if path_kernel is not None:
-            fused, fused_launches = max(fused or 1, r.path_kernel), _add_counts(fused_launches, r.path_launches)
+                     slices=cut, device=device,
+                     **options.keywords(slice_order=[x for x in slice_order if x in set(cut)] if named else slice_order))
         done |= set(leaves)
         results.append(r)
-        macs, n_slices, launches = macs + r.macs, n_slices + r.n_slices, launches + r.launches
-        peak, device_s = max(peak, r.peak_device_bytes), device_s + r.device_s
-        by_kernel = _add_counts(by_kernel, r.kernel_launches)
     state_inds = [ts[t] for t in range(n) if t not in done] + [tuple(r.inds) for r in results]
     state_arrays = [arrays[t] for t in range(n) if t not in done] + [r.array for r in results]
     expect = tnmod.contract(_check_path(result.path[:n_comp_steps], n), ts, tn.output_inds)[0]
     if [tuple(x) for x in expect] != state_inds:
         raise ValueError("'path' is not valid.")
     tail = result.path[n_comp_steps:]
-    if tail:
+    calls = list(results)
+    if tail:  # (unsliced: it adds no slice assignments; its slice_batch and path_kernel are 1)
         r = contract(tail, state_inds, state_arrays, frozenset(tn.output_inds) & {x for xs in state_inds for x in xs},
-                     device=device, storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute,
-                     path_kernel=path_kernel, hoist=hoist, indirect=indirect, reuse=reuse,
+                     device=device, **options.keywords(slice_order=None),
                      _intermediates=range(len(state_arrays) - len(results), len(state_arrays)))
-        if reuse is not None:
-            reused = _add_counts(reused, r.reused)
-        if hoist is not None:
-            hoisted = _add_counts(hoisted, r.hoisted)
-        if indirect is not None:
-            folded, through = folded + r.indirect, _add_counts(through, r.indirect_launches)
-        fused_launches = _add_counts(fused_launches, r.path_launches)
-        exponents, narrow, folds = r.exponents, narrow + r.narrow_launches, folds + r.batch_launches
-        splits, matrix = splits + r.split_launches, matrix + r.matrix_launches
-        macs, launches, peak = macs + r.macs, launches + r.launches, max(peak, r.peak_device_bytes)
-        device_s += r.device_s
-        by_kernel = _add_counts(by_kernel, r.kernel_launches)
+        calls.append(r)
         inds, array = r.inds, r.array
     else:
         inds, array = (state_inds[0], state_arrays[0]) if len(state_inds) == 1 else (state_inds, state_arrays)
-    return ContractionResult(inds, array, macs, n_slices, peak, launches, device_s, fuse_macs, by_kernel,
-                             scaling=scaling, exponents=exponents, narrow_launches=narrow, slice_batch=effective,
-                             batch_launches=folds, compute=compute, split_launches=splits, path_kernel=fused,
-                             path_launches=fused_launches, hoisted=hoisted, indirect=folded, indirect_launches=through,
-                             matrix_launches=matrix, reused=reused)
+    return _sum_results(calls, inds=inds, array=array, n_slices=sum(r.n_slices for r in results),
+                        exponents=calls[-1].exponents, fuse_macs=fuse_macs)
