@@ -64,8 +64,23 @@ def _networks():
     return out
 
 
-def _interpret(p, arrays):
-    """The device semantics of the tables, in numpy: what csrc/contract.hip does, element by element."""
+def _gather(row, src, base):
+    """The elements a row of `perms` moves, in the order of its destination: src[base + sum of digit x stride]."""
+    P = ctr.MAX_AXES
+    nd = int(row[4])
+    shape, strides = row[8:8 + nd], row[8 + P:8 + P + nd]
+    idx = np.full(tuple(shape), base, np.int64)
+    for ax in range(nd):
+        sh = [1] * nd
+        sh[ax] = int(shape[ax])
+        idx = idx + (np.arange(shape[ax]) * strides[ax]).reshape(sh)
+    return src[idx.ravel()].copy()
+
+
+def _interpret(p, arrays, gather=_gather, store=None):
+    """The device semantics of the tables, in numpy: what csrc/contract.hip does, element by element.  `gather`: what a
+    row of `perms` moves (tests/test_contraction_gather_plan.py plants its defects there); `store`: what a step leaves
+    in the arena of its flat result z, as store(k, z) (storage modes round there; None: z itself)."""
     P = ctr.MAX_AXES
     leaves = [np.ascontiguousarray(a, p.dtype).ravel() for a in arrays]
     arena = np.zeros(max(p.arena_elems, 1), p.dtype)
@@ -90,15 +105,8 @@ def _interpret(p, arrays):
         for k in [-1] + list(range(len(p.steps))):
             writes = []  # (the rows of a group are one launch: every row reads before any row writes)
             for row in p.perms[p.perms[:, 6] == k]:
-                nd, numel = int(row[4]), int(row[5])
-                shape, strides = row[8:8 + nd], row[8 + P:8 + P + nd]
                 src, base = (leaves[row[1]], leaf_off(int(row[1]), sid)) if row[0] == ctr.LEAF else (arena, int(row[1]))
-                idx = np.full(tuple(shape), base, np.int64)
-                for ax in range(nd):
-                    sh = [1] * nd
-                    sh[ax] = int(shape[ax])
-                    idx = idx + (np.arange(shape[ax]) * strides[ax]).reshape(sh)
-                writes.append((row, src[idx.ravel()].copy()))
+                writes.append((row, gather(row, src, base)))
             for row, vals in writes:
                 if row[2] == ctr.ARENA:
                     arena[row[3]:row[3] + int(row[5])] = vals
@@ -122,7 +130,7 @@ def _interpret(p, arrays):
                 sl = slice(blk * block_numel, (blk + 1) * block_numel)
                 out[sl] = out[sl] + z if beta else z
             else:
-                arena[st[9]:st[9] + z.size] = z
+                arena[st[9]:st[9] + z.size] = z if store is None else store(k, z)
     rest = tuple(x for x in p.inds if x not in set(p.slice_inds))
     held = p.block_inds + rest
     arr = out.reshape(tuple(p.shape[p.inds.index(x)] for x in held))
