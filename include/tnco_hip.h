@@ -533,6 +533,11 @@ const char* tnco_hip_comm_last_error(void);
  * the same products in the same order, so the result is bit for bit that of the plan that permutes.  Works with slice
  * batches and hoisting; steps with row axes, storage dtypes, compute mode 1, matrix mode and the path kernel are not
  * supported.
+ *
+ * Wide accumulation (tnco_hip_contract_set_accumulate; float32 / complex64 outputs: dtype codes 0, 2 and 4..7): the
+ * blocks of the slice assignments, each computed as without the call, are summed in float64 / complex128 in assignment
+ * order and rounded once into the output (contract_accumulate.h; the call's own comment below has the definition).  Works
+ * with everything above except row axes.
  */
 typedef struct tnco_hip_contract_s* tnco_hip_contract;
 typedef struct tnco_hip_contract_desc {
@@ -658,6 +663,27 @@ int tnco_hip_contract_set_indirect(tnco_hip_contract h, const int64_t* ind_steps
  * tnco_hip_contract_kernel_launches */
 #define TNCO_HIP_CONTRACT_N_IX_KERNELS 3
 int tnco_hip_contract_indirect_launches(tnco_hip_contract h, int64_t* counts);
+/* after create, before run: the runs that follow sum the blocks of the slice assignments in float64 (mode 1) or as a
+ * handle on which this was never called (mode 0).  Mode 1: every assignment computes its block of the output as before,
+ * the same kernels on the same shapes in the same k order, always with beta 0 and into a staging block (the batch
+ * staging buffer, the path kernel's, or unbatched a block reserved here).  The blocks go in assignment order, each part
+ * (re, im) on its own, into an accumulator of float64 / complex128 with one element per output element: the first block
+ * that reaches an output block is placed, widened exactly, every later one added with one float64 addition.  After the
+ * last assignment the accumulator is rounded once, to nearest even, into the output; blocks the run does not reach stay
+ * zero.  No atomics, the order fixed: the result does not depend on a slice batch, the path kernel, hoist flags, periods
+ * or indirect operands, and where every output block is visited once it is that of mode 0.  A plan without steps sums
+ * nothing: it runs as in mode 0 and nothing is reserved.
+ * EINVAL, each with a text of its own and the handle left as it was: a mode other than 0 and 1; dtype codes 1 and 3 (the
+ * output must be float32 / complex64: codes 0, 2 and the storage dtypes); a handle with row axes.  Reserves the
+ * accumulator and, without a slice batch and a path kernel, the staging block (ERUNTIME when they exceed the device's
+ * free memory; the handle then stays as it was); stats[2] counts them.  May come before or after the other set calls: a
+ * slice batch or a path kernel set later releases the staging block */
+int tnco_hip_contract_set_accumulate(tnco_hip_contract h, int32_t mode);
+/* counts[2]: the last run's launches of the kernels that fold blocks into the accumulator (one per assignment, per group
+ * of a slice batch or of the path kernel) and of the kernel that rounds it into the output (one per run); zeros in mode
+ * 0.  They are part of stats[1]; the folds are also counted by tnco_hip_contract_batch_launches (with a path kernel: in
+ * slot 1 of tnco_hip_contract_path_launches), the rounding by tnco_hip_contract_narrow_launches */
+int tnco_hip_contract_accumulate_launches(tnco_hip_contract h, int64_t* counts);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

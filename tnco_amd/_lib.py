@@ -95,7 +95,8 @@ EXPORTS = [
     "tnco_hip_contract_matrix_launches", "tnco_hip_contract_set_path_kernel",
     "tnco_hip_contract_path_launches", "tnco_hip_contract_set_hoist", "tnco_hip_contract_set_reuse",
     "tnco_hip_contract_set_indirect",
-    "tnco_hip_contract_indirect_launches", "tnco_hip_contract_destroy",
+    "tnco_hip_contract_indirect_launches", "tnco_hip_contract_set_accumulate", "tnco_hip_contract_accumulate_launches",
+    "tnco_hip_contract_destroy",
     "tnco_hip_device_name", "tnco_hip_device_count", "tnco_hip_last_error", "tnco_hip_version",
 ]
 
@@ -214,6 +215,8 @@ def load() -> C.CDLL:
     L.tnco_hip_contract_set_reuse.argtypes = [vp, vp, vp]
     L.tnco_hip_contract_set_indirect.argtypes = [vp, vp, i64, vp]
     L.tnco_hip_contract_indirect_launches.argtypes = [vp, vp]
+    L.tnco_hip_contract_set_accumulate.argtypes = [vp, i32]
+    L.tnco_hip_contract_accumulate_launches.argtypes = [vp, vp]
     L.tnco_hip_contract_destroy.argtypes = [vp]
     L.tnco_hip_contract_destroy.restype = None
     L.tnco_hip_device_name.argtypes = [C.c_int, vp, C.c_int]

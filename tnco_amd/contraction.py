@@ -158,6 +158,25 @@ the full array.  The folded permutes are absent from `perms`, their buffers from
 operands folded, `indirect_launches` of the result the launches of the three kernels in INDIRECT_KERNEL_PATHS order (they
 are part of `launches` and of no slot of `kernel_launches`).  With nothing folded the plan and the run are those of
 `indirect=None`.
+
+Wide accumulation: with `accumulate="float64"` (float32 / complex64 arrays, every mode whose output is one of them:
+`storage`, `scaling`, `compute` too; not with `projs`) the sum over slice assignments runs in float64.  Every assignment
+computes its float32 / complex64 block of the output exactly as without the keyword -- the kernels, the shapes, the k
+order; the block is the one the plain run would place with beta 0 -- into a staging block, and the blocks are added in
+assignment order, each part (re, im) on its own, into a device accumulator of float64 / complex128 with one element per
+output element (csrc/contract_accumulate.h): the first block that reaches an output block is placed, widened exactly,
+every later one is added with one IEEE float64 addition.  After the last assignment of `slice_range` the accumulator is
+rounded once, to nearest even, into the output; blocks that `slice_range` does not reach stay zero.  With b_0, b_1, ...
+the blocks that hit one output block, r = float32(((float64(b_0) + float64(b_1)) + float64(b_2)) + ...).  Nothing is
+atomic and the order is fixed, so a call stays bit-reproducible; r does not depend on `slice_batch`, `path_kernel`,
+`hoist`, `indirect` or `reuse` under one `slice_order`; where every output block is visited once -- an unsliced call, a
+sliced index that the result holds -- r is the bytes of `accumulate=None`.  The plan's tables do not change.  Device
+memory grows by the accumulator, 2 itemsize out_numel, and, when neither `slice_batch` nor `path_kernel` is given, by a
+staging block of itemsize block_numel (`Plan.peak_device_bytes`).  The folds are counted in `batch_launches` (unbatched:
+one per assignment; with `slice_batch` one per group, as without the keyword), with `path_kernel` in `path_launches[1]`;
+the one launch that rounds the accumulator is counted in `narrow_launches`; all of them are part of `launches`.  `array`
+keeps the arrays' dtype.  A plan without steps places blocks and sums nothing: it takes the keyword, reserves nothing and
+runs as without it.
 """
 from __future__ import annotations
 
@@ -172,7 +191,8 @@ from .app import tn as tnmod
 
 __all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
            "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage", "SCALINGS", "scale_exponent", "scale_to_storage",
-           "MAX_SLICE_BATCH", "COMPUTES", "split_bf16", "MAX_PATH_KERNEL", "MAX_PATH_STEP_MACS", "INDIRECT_KERNEL_PATHS"]
+           "MAX_SLICE_BATCH", "COMPUTES", "split_bf16", "MAX_PATH_KERNEL", "MAX_PATH_STEP_MACS", "INDIRECT_KERNEL_PATHS",
+           "ACCUMULATES"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -181,6 +201,7 @@ DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex6
 # of include/tnco_hip.h is STORAGES[name] + (1 when complex)
 STORAGES = {"float16": 4, "bfloat16": 6}
 SCALINGS = ("tensor",)  # per-tensor power-of-two scaling of storage mode (module docstring)
+ACCUMULATES = ("float64",)  # the sum over slice assignments in a wider type (module docstring)
 SCALE_BITS = 14  # the largest stored magnitude of a scaled tensor lies in [2^14, 2^15]
 # compute modes (module docstring).  "bf16x3": its code for tnco_hip_contract_set_compute; "matrix" has entry points of
 # its own (tnco_hip_contract_set_matrix) and no code
@@ -294,6 +315,8 @@ class Plan:
     #                                 or a % period == 0; a period is a place of a sliced index or the number of assignments
     perm_period: np.ndarray = None  # reuse=True: [n_perms] the same per row of `perms` (within a group the slowest rows first)
     kept_period: tuple = ()  # reuse=True: per entry of `kept` the period of the item that writes it
+    accumulate: str = None  # "float64": the blocks of the assignments are summed in float64 / complex128 and rounded once; the
+    #                         tables do not depend on it
 
     @property
     def n_slices(self) -> int:
@@ -326,8 +349,13 @@ class Plan:
             tables += 8 * (self.steps.size + 2 * (len(self.steps) + 1) + self.slice_range[1] - self.slice_range[0])
         if self.ind_steps is not None:
             tables += 8 * (self.ind_steps.size + self.ind_maps.size)
+        # accumulate: the wide accumulator, and unbatched a staging block of its own; a plan without steps sums nothing
+        wide = 0
+        if self.accumulate is not None and len(self.steps):
+            block = self.out_numel // math.prod(self.shape[self.inds.index(x)] for x in self.block_inds)
+            wide = 2 * item * self.out_numel + (item * block if members is None else 0)
         return held * (int(self.leaf_numel.sum()) + self.arena_elems * batch) + item * self.out_numel + tables + maps + \
-            scale * batch + stage
+            scale * batch + stage + wide
 
 
 class _Arena:
@@ -447,6 +475,9 @@ _RULES = {
     "slice_order": (_is_order, "None, 'reuse' or every sliced index once",
                     ((lambda o, dtype: isinstance(o.slice_order, str) and o.reuse is not True, ValueError,
                       "slice_order='reuse' needs reuse=True."),)),
+    "accumulate": (lambda v: isinstance(v, str) and v in ACCUMULATES, "None or 'float64'",
+                   ((lambda o, dtype: dtype not in _F32, TypeError,
+                     "with 'accumulate' the compute dtype must be float32 or complex64, not {dtype}."),)),
 }
 
 
@@ -462,6 +493,7 @@ class _Options:
     indirect: object = None
     reuse: object = None
     slice_order: object = None
+    accumulate: object = None
 
     def check(self, dtype, projs=None) -> None:
         """Raises what _RULES refuses of the keywords, for arrays of the compute dtype `dtype` and the projections `projs`."""
@@ -722,12 +754,12 @@ def _unique_rows(table):
 
 def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
          sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
-         hoist=None, indirect=None, reuse=None, slice_order=None) -> Plan:
+         hoist=None, indirect=None, reuse=None, slice_order=None, accumulate=None) -> Plan:
     """The device plan of one contraction along a path that leaves one tensor (no GPU).
     `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`, `slice_batch`,
-    `compute`, `path_kernel`, `hoist`, `indirect`, `reuse`, `slice_order`: see the module docstring."""
+    `compute`, `path_kernel`, `hoist`, `indirect`, `reuse`, `slice_order`, `accumulate`: see the module docstring."""
     options = _Options(storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute, path_kernel=path_kernel,
-                       hoist=hoist, indirect=indirect, reuse=reuse, slice_order=slice_order)
+                       hoist=hoist, indirect=indirect, reuse=reuse, slice_order=slice_order, accumulate=accumulate)
     options.check(dtype, projs)
     if isinstance(slice_order, str):  # "reuse": the default order unless the greedy one has strictly fewer multiply-adds
         mode = dict(slices=slices, slice_range=slice_range, dtype=dtype)
@@ -999,7 +1031,7 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
     p = Plan(dtype=np.dtype(dtype), inds=final, shape=tuple(dims[x] for x in final), slice_inds=slice_inds,
              slice_dims=slice_dims, block_inds=tuple(x for x in slice_inds if x in final), leaf_numel=leaf_numel,
              leaf_sl=leaf_sl, perms=perm_tab, steps=step_tab, arena_elems=arena.peak, out_numel=size(final),
-             macs_per_slice=macs, slice_range=(lo, hi), ops=ops, storage=storage, compute=compute)
+             macs_per_slice=macs, slice_range=(lo, hi), ops=ops, storage=storage, compute=compute, accumulate=accumulate)
     if scaling is not None:
         p.scaling = scaling
         p.stage_refs = np.array([offset[b] if b >= 0 else -1 for b in stage], np.int64)
@@ -1082,7 +1114,7 @@ def _sub_output(ts_inds, leaves, output) -> frozenset:
 
 def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=None, device=None,
              sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
-             hoist=None, indirect=None, reuse=None, slice_order=None, _intermediates=()) -> ContractionResult:
+             hoist=None, indirect=None, reuse=None, slice_order=None, accumulate=None, _intermediates=()) -> ContractionResult:
     """Contract `arrays` (numpy, in ts_inds order) along the linear `path` on the GPU; see the module docstring.
     A path that leaves several tensors gives lists in `inds` / `array` (the sliced and the projected form need one
     tensor).  `_intermediates` (contract_results): positions of arrays that are results of earlier storage-mode calls,
@@ -1094,7 +1126,7 @@ def contract(path, ts_inds, arrays, output_inds=None, *, slices=(), slice_range=
     dims = _dims_of(ts_inds, [a.shape for a in arrays])
     dtype = _compute_dtype(arrays)
     options = _Options(storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute, path_kernel=path_kernel,
-                       hoist=hoist, indirect=indirect, reuse=reuse, slice_order=slice_order)
+                       hoist=hoist, indirect=indirect, reuse=reuse, slice_order=slice_order, accumulate=accumulate)
     options.check(dtype, projs)
     steps = _check_path(path, len(ts_inds))
     final, out = tnmod.contract(steps, ts_inds, output_inds, dims)
@@ -1215,6 +1247,7 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     i64 = lambda a: None if a is None else np.ascontiguousarray(a, np.int64)  # noqa: E731
     matrix, split = p.compute == "matrix", p.compute not in (None, "matrix")
+    wide = p.accumulate is not None
     try:
         # (is it on, entry point, arguments), in an order the library takes.  Nothing hoisted, every period 1 or nothing
         # folded: the run of the plan without the keyword
@@ -1226,13 +1259,14 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
             (p.scaling is not None, L.tnco_hip_contract_set_exponents, (leaf_exps,)),
             (p.hoisted is not None and any(p.hoisted), L.tnco_hip_contract_set_hoist, (i64(p.step_hoist), i64(p.perm_hoist))),
             (p.reused is not None and any(p.reused), L.tnco_hip_contract_set_reuse, (i64(p.step_period), i64(p.perm_period))),
-            (p.indirect, L.tnco_hip_contract_set_indirect, (i64(p.ind_steps), np.size(p.ind_maps), i64(p.ind_maps))))
+            (p.indirect, L.tnco_hip_contract_set_indirect, (i64(p.ind_steps), np.size(p.ind_maps), i64(p.ind_maps))),
+            (wide, L.tnco_hip_contract_set_accumulate, (1,)))
         # (is it on, entry point, length, field of the result)
         counters = (
             (True, L.tnco_hip_contract_kernel_launches, len(KERNEL_PATHS), "kernel_launches"),
             (True, L.tnco_hip_contract_row_launches, len(ROW_KERNEL_PATHS), "row_kernel_launches"),
-            (p.scaling is not None, L.tnco_hip_contract_narrow_launches, 1, "narrow_launches"),
-            (p.slice_batch is not None, L.tnco_hip_contract_batch_launches, 1, "batch_launches"),
+            (p.scaling is not None or wide, L.tnco_hip_contract_narrow_launches, 1, "narrow_launches"),
+            (p.slice_batch is not None or wide, L.tnco_hip_contract_batch_launches, 1, "batch_launches"),
             (matrix, L.tnco_hip_contract_matrix_launches, 1, "matrix_launches"),
             (split, L.tnco_hip_contract_split_launches, 1, "split_launches"),
             (p.path_kernel is not None, L.tnco_hip_contract_path_launches, 2, "path_launches"),
@@ -1283,7 +1317,7 @@ def _host_layout(p: Plan, staging) -> np.ndarray:
 
 def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse_inds=None,
                      storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
-                     hoist=None, indirect=None, reuse=None, slice_order=None) -> ContractionResult:
+                     hoist=None, indirect=None, reuse=None, slice_order=None, accumulate=None) -> ContractionResult:
     """Run a result of `Optimizer.optimize` over the arrays of the network as given.
 
     tn0: the network before pre-fusing (`load_tn(obj, fuse=None)`); arrays: in tn0.tensors order, or {name: array}
@@ -1312,9 +1346,11 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
     reuse: True runs every step and permute of every call over `result.path` only at the assignments that change the slices
     below it (module docstring); the fuse stage, unsliced, stays as it is; `reused` is the sum over the calls.
     slice_order: the order of the sliced indices, slowest first (module docstring): "reuse" for every sliced call, or a
-    sequence that names every index of `result.slices` once (of several components: each takes its own, in that order)."""
+    sequence that names every index of `result.slices` once (of several components: each takes its own, in that order).
+    accumulate: "float64" sums the slice assignments of every call over `result.path` in float64 (module docstring); the
+    fuse stage, unsliced, runs without it; `batch_launches`, `path_launches` and `narrow_launches` count its launches."""
     options = _Options(storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute, path_kernel=path_kernel,
-                       hoist=hoist, indirect=indirect, reuse=reuse, slice_order=slice_order)
+                       hoist=hoist, indirect=indirect, reuse=reuse, slice_order=slice_order, accumulate=accumulate)
     options.check(np.float32, projs)  # (before the network is looked at; the arrays' dtype: below)
     if (tn0.sparse_inds or tn.sparse_inds) and projs is None:
         raise NotImplementedError("sparse indices (n_projs) have an array meaning only at given projections: "

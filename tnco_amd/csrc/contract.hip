@@ -44,6 +44,12 @@
 //   ct_ix_tiled_kernel, ct_ix_dot_kernel, ct_ix_stream_kernel
 //                          the twins of the three plain GEMM kernels, the same sums in the same order; its permute, the
 //                          launch and the arena buffer of the copy are not in the plan.  Plain dtypes only.
+// Wide accumulation (tnco_hip_contract_set_accumulate, contract_accumulate.h; float32 / complex64 outputs): the step that
+// writes the output always writes with beta 0 to a staging block (unbatched: one of its own) and the fold goes into a
+// float64 / complex128 accumulator, placed or added in assignment order by
+//   ct_acc_reduce_kernel, ct_acc_path_reduce_kernel  the twins of the two reduce kernels, and
+//   ct_acc_narrow_kernel   rounds the accumulator into the output once, after the last assignment.
+// Every other kernel, shape, k order and block is that of the run without the call.
 // No atomics in any sum: every sum runs in one fixed order, so a run is bit-reproducible (the one atomic, the integer max
 // behind a scaled tensor's exponent, does not depend on order).
 #include "../../include/tnco_hip.h"
@@ -400,6 +406,7 @@ __global__ __launch_bounds__(256) void ct_batch_reduce_kernel(T* out, const T* s
 }
 
 #include "contract_path.h"
+#include "contract_accumulate.h"
 
 // A step with a row axis: row r of the result reads row a_map[r] of A and row b_map[r] of B.  A null map with a row
 // stride: row r itself; a row stride of 0: the operand has one row, read for every r.
@@ -574,6 +581,10 @@ struct tnco_hip_contract_s {
   int64_t* d_ind = nullptr;        // ind_steps | the pool of the offset tables
   int64_t ind_bytes = 0;           // what the tables add to `bytes`
   int64_t by_ix[TNCO_HIP_CONTRACT_N_IX_KERNELS] = {};  // launches of the last run per indirect kernel (tnco_hip.h)
+  int accumulate = 0;              // tnco_hip_contract_set_accumulate: 1: the sum over assignments in float64
+  void* d_acc = nullptr;           // [out_numel] of the wide type: the accumulator
+  void* d_acc_stage = nullptr;     // [block_numel] of the output's type: the block of an unbatched assignment
+  int64_t acc_launches[2] = {0, 0};  // fold launches and narrowing launches of the last run
   int64_t last_member = 0;         // the member that ran the last assignment of the last run (its exponent slots)
   int64_t base_bytes = 0;          // `bytes` as create reserved them
   std::vector<int32_t> exps_image;  // the leaves' exponents, once per member
@@ -923,6 +934,19 @@ int launch_ix_gemm(tnco_hip_contract_s* c, const IxGemmArgs<T>& p, unsigned memb
   return TNCO_HIP_OK;
 }
 
+// wide accumulation, after the last assignment of a run: the accumulator rounded once into the output
+template <class T>
+int narrow_accumulator(tnco_hip_contract_s* c) {
+  const dim3 grid((unsigned)std::min<int64_t>((c->out_numel + 255) / 256, 2048));
+  hipLaunchKernelGGL(ct_acc_narrow_kernel<T>, grid, dim3(256), 0, c->stream, (T*)c->d_out, (const ct_wide_t<T>*)c->d_acc,
+                     c->out_numel);
+  CT_TRY(hipGetLastError());
+  c->launches += 1;
+  c->narrow_launches += 1;
+  c->acc_launches[1] += 1;
+  return TNCO_HIP_OK;
+}
+
 // T: the type of the sums and of the output; E: of the leaves and the arena (storage mode: st_f16 / st_bf16 or a pair)
 template <class T, class E = T>
 int run_impl(tnco_hip_contract_s* c) {
@@ -934,6 +958,9 @@ int run_impl(tnco_hip_contract_s* c) {
   // a batch: up to c->batch assignments per launch, each in its own arena; a plan without steps runs as it does unbatched
   const bool batched = c->batch > 0 && S > 0;
   const int64_t per = batched ? c->batch : 1;
+  // wide accumulation: the folds go into the accumulator; a plan without steps places blocks only and runs as it is
+  constexpr bool single = std::is_same<T, float>::value || std::is_same<T, cplx<float>>::value;
+  const bool wide = single && c->accumulate && S > 0;
   E* arena = (E*)c->d_arena;
   T* out = (T*)c->d_out;
   const int64_t* d_leaf_sl = c->d_tables + c->perms.size();
@@ -967,8 +994,9 @@ int run_impl(tnco_hip_contract_s* c) {
     }
     // batched: the last step writes every member's block, with beta 0, to the batch staging buffer
     const bool last = st[8] == K_OUT;
-    T* out_dest = bat ? (T*)c->d_batch_out : out + out_off;
-    const int out_beta = bat ? 0 : beta;
+    // (wide accumulation, unbatched: the same, one block, to the staging block of the accumulator)
+    T* out_dest = bat ? (T*)c->d_batch_out : wide ? (T*)c->d_acc_stage : out + out_off;
+    const int out_beta = bat || wide ? 0 : beta;
     if (bat) mb.c_step = last ? c->block_numel * (int64_t)sizeof(T) : arena_bytes;
     if constexpr (half) {
       HalfGemmArgs<E> p;
@@ -1078,14 +1106,24 @@ int run_impl(tnco_hip_contract_s* c) {
         if (sc.step_period[k] == period && (rc = run_step(k, sid, bat, bat ? members : 1, beta, out_off))) return rc;
       }
     }
-    if (batched) {  // the members' blocks into the output, in assignment order
+    if (batched || wide) {  // the members' blocks into the output (the accumulator), in assignment order
       const dim3 grid((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048));
-      hipLaunchKernelGGL(ct_batch_reduce_kernel<T>, grid, dim3(256), 0, c->stream, out, (const T*)c->d_batch_out, c->block_numel,
-                         (int)n, pl);
+      if constexpr (single) {
+        if (wide)
+          hipLaunchKernelGGL(ct_acc_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (ct_wide_t<T>*)c->d_acc,
+                             (const T*)(batched ? c->d_batch_out : c->d_acc_stage), c->block_numel, (int)n, pl);
+      }
+      if (!wide)
+        hipLaunchKernelGGL(ct_batch_reduce_kernel<T>, grid, dim3(256), 0, c->stream, out, (const T*)c->d_batch_out, c->block_numel,
+                           (int)n, pl);
       CT_TRY(hipGetLastError());
       c->launches += 1;
       c->batch_launches += 1;
+      c->acc_launches[0] += wide;
     }
+  }
+  if constexpr (single) {
+    if (wide) return narrow_accumulator<T>(c);
   }
   return TNCO_HIP_OK;
 }
@@ -1095,6 +1133,8 @@ int run_impl(tnco_hip_contract_s* c) {
 template <class T>
 int run_path(tnco_hip_contract_s* c) {
   const int64_t S = (int64_t)c->steps.size() / STEP_W, P = (int64_t)c->perms.size() / PERM_W;
+  constexpr bool single = std::is_same<T, float>::value || std::is_same<T, cplx<float>>::value;
+  const bool wide = single && c->accumulate;  // the folds go into the accumulator (run_path: a plan with steps)
   PathArgs a;
   a.perms = c->d_tables;
   a.leaf_sl = c->d_tables + P * PERM_W;
@@ -1118,12 +1158,22 @@ int run_path(tnco_hip_contract_s* c) {
     hipLaunchKernelGGL(ct_path_kernel<T>, dim3((unsigned)n), dim3(PATH_LANES), 0, c->stream, a);
     CT_TRY(hipGetLastError());
     const dim3 grid((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048));
-    hipLaunchKernelGGL(ct_path_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (T*)c->d_out, (const T*)c->d_path_stage,
-                       c->block_numel, (int)n, d_place + (sid - c->start));
+    if constexpr (single) {
+      if (wide)
+        hipLaunchKernelGGL(ct_acc_path_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (ct_wide_t<T>*)c->d_acc,
+                           (const T*)c->d_path_stage, c->block_numel, (int)n, d_place + (sid - c->start));
+    }
+    if (!wide)
+      hipLaunchKernelGGL(ct_path_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (T*)c->d_out, (const T*)c->d_path_stage,
+                         c->block_numel, (int)n, d_place + (sid - c->start));
     CT_TRY(hipGetLastError());
     c->launches += 2;
     c->path_launches[0] += 1, c->path_launches[1] += 1;
+    c->acc_launches[0] += wide;
     c->macs += per_slice * n;
+  }
+  if constexpr (single) {
+    if (wide) return narrow_accumulator<T>(c);
   }
   return TNCO_HIP_OK;
 }
@@ -1276,6 +1326,20 @@ const char* make_schedule(const tnco_hip_contract_s* c, const int64_t* step_peri
   return nullptr;
 }
 
+// What wide accumulation adds to stats[2] in mode `mode`: the accumulator, and the staging block of an unbatched run (a
+// batch and the path kernel stage in their own buffers).  A plan without steps sums nothing and reserves nothing.
+int64_t accumulate_bytes(const tnco_hip_contract_s* c, int mode) {
+  if (!mode || c->steps.empty()) return 0;
+  const bool own_stage = !c->batch && !c->path_group;
+  return (int64_t)c->out_elem * (2 * c->out_numel + (own_stage ? c->block_numel : 0));
+}
+
+// a slice batch or a path kernel set after tnco_hip_contract_set_accumulate: the members' staging buffer takes its place
+void drop_accumulate_stage(tnco_hip_contract_s* c) {
+  if (c->d_acc_stage) (void)hipFree(c->d_acc_stage);
+  c->d_acc_stage = nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1359,6 +1423,7 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
   }
   CT_TRY(hipMemsetAsync(c->d_out, 0, (size_t)c->out_numel * c->out_elem, c->stream));
   const size_t n_steps = c->steps.size() / STEP_W;
+  if (c->d_acc) CT_TRY(hipMemsetAsync(c->d_acc, 0, (size_t)c->out_numel * 2 * c->out_elem, c->stream));
   if (c->scaling && !c->leaf_exps.empty()) {
     if (c->batch && n_steps) {  // every member's copy of the slots starts with the same leaf exponents
       const size_t n_slots = c->leaf_exps.size() + n_steps;
@@ -1370,7 +1435,7 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
     }
   }
   c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->matrix_launches = c->last_member = 0;
-  c->path_launches[0] = c->path_launches[1] = 0;
+  c->path_launches[0] = c->path_launches[1] = c->acc_launches[0] = c->acc_launches[1] = 0;
   std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
   std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
   std::fill(std::begin(c->by_ix), std::end(c->by_ix), 0);
@@ -1400,7 +1465,7 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
 
 int tnco_hip_contract_stats(tnco_hip_contract c, int64_t* stats) {
   if (!c || !stats) return fail(TNCO_HIP_EINVAL, "null argument.");
-  stats[0] = c->macs, stats[1] = c->launches, stats[2] = c->bytes, stats[3] = c->device_ns;
+  stats[0] = c->macs, stats[1] = c->launches, stats[2] = c->bytes + accumulate_bytes(c, c->accumulate), stats[3] = c->device_ns;
   return TNCO_HIP_OK;
 }
 
@@ -1480,6 +1545,7 @@ int tnco_hip_contract_set_slice_batch(tnco_hip_contract c, int64_t batch) {
   for (void* p : {c->d_arena, c->d_batch_out, c->scaling ? (void*)c->d_exps : nullptr})
     if (p) (void)hipFree(p);
   c->d_arena = d_arena, c->d_batch_out = d_stage;
+  drop_accumulate_stage(c);
   if (c->scaling) c->d_exps = (int32_t*)d_exps, c->d_amax = (uint32_t*)(c->d_exps + B * n_slots);
   c->batch = batch, c->bytes = bytes;
   return TNCO_HIP_OK;
@@ -1589,6 +1655,7 @@ int tnco_hip_contract_set_path_kernel(tnco_hip_contract c, int64_t group) {
   }
   if (c->d_arena) (void)hipFree(c->d_arena);
   c->d_arena = d_arena, c->d_path_stage = d_stage, c->d_path_tables = (int64_t*)d_tab;
+  drop_accumulate_stage(c);
   c->path_group = group, c->bytes = bytes;
   return TNCO_HIP_OK;
 }
@@ -1735,6 +1802,40 @@ int tnco_hip_contract_indirect_launches(tnco_hip_contract c, int64_t* counts) {
   return TNCO_HIP_OK;
 }
 
+int tnco_hip_contract_set_accumulate(tnco_hip_contract c, int32_t mode) {
+  if (!c) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (mode != 0 && mode != 1) return fail(TNCO_HIP_EINVAL, "'mode' must be 0 (off) or 1 (float64).");
+  if (c->dtype == 1 || c->dtype == 3) return fail(TNCO_HIP_EINVAL, "wide accumulation needs a float32 or complex64 output.");
+  if (!c->row_steps.empty() || !c->row_maps.empty()) return fail(TNCO_HIP_EINVAL, "row axes are not supported with wide accumulation.");
+  CT_TRY(hipSetDevice(c->device));
+  CT_TRY(hipStreamSynchronize(c->stream));
+  // the new buffers first: a handle that this call fails on stays as it was
+  void *d_acc = nullptr, *d_stage = nullptr;
+  if (const int64_t bytes = accumulate_bytes(c, mode)) {
+    size_t free_b = 0, total_b = 0;
+    CT_TRY(hipMemGetInfo(&free_b, &total_b));
+    const int64_t had = accumulate_bytes(c, c->accumulate);
+    if (bytes > had && (size_t)(bytes - had) > free_b)
+      return fail(TNCO_HIP_ERUNTIME, "the accumulator needs " + std::to_string(bytes - had) + " bytes of device memory, " +
+                                         std::to_string(free_b) + " are free.");
+    const size_t acc = (size_t)c->out_numel * 2 * c->out_elem, stage = (size_t)(bytes - (int64_t)acc);
+    if (hipMalloc(&d_acc, acc) != hipSuccess || (stage && hipMalloc(&d_stage, stage) != hipSuccess)) {
+      if (d_acc) (void)hipFree(d_acc);
+      return fail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+    }
+  }
+  if (c->d_acc) (void)hipFree(c->d_acc);
+  drop_accumulate_stage(c);
+  c->d_acc = d_acc, c->d_acc_stage = d_stage, c->accumulate = mode;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_accumulate_launches(tnco_hip_contract c, int64_t* counts) {
+  if (!c || !counts) return fail(TNCO_HIP_EINVAL, "null argument.");
+  counts[0] = c->acc_launches[0], counts[1] = c->acc_launches[1];
+  return TNCO_HIP_OK;
+}
+
 int tnco_hip_contract_batch_launches(tnco_hip_contract c, int64_t* count) {
   if (!c || !count) return fail(TNCO_HIP_EINVAL, "null argument.");
   *count = c->batch_launches;
@@ -1745,7 +1846,8 @@ void tnco_hip_contract_destroy(tnco_hip_contract c) {
   if (!c) return;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_leaves, c->d_arena, c->d_out, (void*)c->d_tables, (void*)c->d_leaf_ptrs, (void*)c->d_row_maps,
-                  (void*)c->d_exps, c->d_batch_out, c->d_path_stage, (void*)c->d_path_tables, (void*)c->d_ind})
+                  (void*)c->d_exps, c->d_batch_out, c->d_path_stage, (void*)c->d_path_tables, (void*)c->d_ind, c->d_acc,
+                  c->d_acc_stage})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);

@@ -21,7 +21,9 @@ process); operands read in place (`--indirect`: the sliced Sycamore leg with sli
 each with indirect=None and indirect=True, and one bandwidth-bound step whose 2^26-element operand lies in reversed axis
 order, in one process); reuse (`--reuse`: the sliced Sycamore leg, unbatched, with hoist=None, hoist=True, reuse=True,
 reuse=True with slice_order="reuse", and that with indirect=True, and the same five on a deeper network whose assignments
-take milliseconds, every ratio against hoist=True, in one process).  Engine figures are its
+take milliseconds, every ratio against hoist=True, in one process); the wide accumulation (`--accumulate`: the sliced
+Sycamore leg with accumulate=None and "float64", unbatched, with slice_batch=64 and hoist=True, and with path_kernel=1024,
+and the error of each against the same plan in complex128, in one process).  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device).
 """
@@ -462,6 +464,46 @@ def reuse(lines, depth, max_width, max_slices):
     _reuse_rows(lines, tn, r0, leaves, m)
 
 
+ACCUMULATE_SETTINGS = (("unbatched", dict()), ("slice_batch=64 hoist=True", dict(slice_batch=64, hoist=True)),
+                       ("path_kernel=1024", dict(path_kernel=1024)))
+
+
+def accumulate(lines, depth, max_width, max_slices):
+    """The sum over assignments in float64 on the sliced Sycamore amplitude of the storage leg, complex64, all in this
+    process: accumulate=None against "float64", unbatched, with slice_batch=64 and hoist=True, and with path_kernel=1024:
+    device time (the minimum and the spread of three runs after a warm-up), launches, peak bytes, and the relative error
+    by norm of both against the same plan run on the engine in complex128."""
+    lines.append("")
+    tn, r0, leaves = _sliced_sycamore(depth, max_width)
+    n = 2 ** len(r0.slices)
+    m = min(n, max_slices)
+    run = lambda arrays=leaves, **kw: ctr.contract(r0.path, tn.ts_inds, arrays, tn.output_inds, slices=r0.slices,  # noqa: E731
+                                                   slice_range=(0, m), **kw)
+    ref = run([a.astype(np.complex128) for a in leaves]).array
+    norm = float(np.linalg.norm(np.ravel(ref)))
+    lines.append(f"## accumulate, sliced Sycamore-53 amplitude, depth {depth}, complex64, max_width {max_width}, cost {r0.cost}, "
+                 f"{len(r0.path)} steps, assignments [0, {m}) of {n}: device seconds are the minimum of three runs after a "
+                 "warm-up, spread = (max - min) / min of the three; error = |result - ref| / |ref| by norm, ref the same plan "
+                 "run in complex128; all runs in one process")
+    lines.append(f"{'setting':>26} {'accumulate':>10} {'device s':>9} {'spread':>7} {'this / None':>11} {'launches':>9} "
+                 f"{'peak bytes':>11} {'error':>10} {'bits equal unbatched':>20}")
+    first = {}
+    for name, kw in ACCUMULATE_SETTINGS:
+        t_none = None
+        for acc in (None, "float64"):
+            r = run(accumulate=acc, **kw)
+            times = [run(accumulate=acc, **kw).device_s for _ in range(3)]
+            t = min(times)
+            t_none = t if acc is None else t_none
+            base = first.setdefault(acc, r.array)
+            same = np.array_equal(np.ravel(r.array).view(np.uint32), np.ravel(base).view(np.uint32))
+            err = float(np.linalg.norm(np.ravel(r.array.astype(np.complex128) - ref))) / norm
+            lines.append(f"{name:>26} {str(acc):>10} {t:9.4f} {(max(times) - t) / t:7.3f} {t / t_none:11.3f} {r.launches:9d} "
+                         f"{r.peak_device_bytes:11d} {err:10.3e} {str(bool(same)):>20}")
+            print(lines[-1], flush=True)
+            del r
+
+
 def indirect(lines, depth, max_width, max_slices):
     """Operands read in place against the permutes they replace, all in this process: the sliced Sycamore amplitude of the
     storage leg, complex64, with slice_batch None and 64, hoist None and True, each with indirect=None and indirect=True;
@@ -715,15 +757,19 @@ def main():
     ap.add_argument("--matrix", action="store_true", help="only the matrix-mode leg, appended to --out")
     ap.add_argument("--indirect", action="store_true", help="only the indirect-operand leg, appended to --out")
     ap.add_argument("--reuse", action="store_true", help="only the reuse leg, appended to --out")
+    ap.add_argument("--accumulate", action="store_true", help="only the wide-accumulation leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect + a.reuse > 1:
-        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix, --indirect and --reuse each "
+    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect + a.reuse + a.accumulate > 1:
+        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix, --indirect, --reuse and --accumulate each "
                  "append one leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect or a.reuse:  # (the other legs' sections stay as they are)
-        if a.reuse:
+    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect or a.reuse or a.accumulate:  # (the other legs' sections stay as they are)
+        if a.accumulate:
+            lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
+            accumulate(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+        elif a.reuse:
             lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
             reuse(lines, a.depth, a.max_width, min(a.max_slices, 2048))
         elif a.indirect:
@@ -765,6 +811,7 @@ def main():
     matrix(lines, a.n)
     indirect(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     reuse(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+    accumulate(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
