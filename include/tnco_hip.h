@@ -684,6 +684,40 @@ int tnco_hip_contract_set_accumulate(tnco_hip_contract h, int32_t mode);
  * 0.  They are part of stats[1]; the folds are also counted by tnco_hip_contract_batch_launches (with a path kernel: in
  * slot 1 of tnco_hip_contract_path_launches), the rounding by tnco_hip_contract_narrow_launches */
 int tnco_hip_contract_accumulate_launches(tnco_hip_contract h, int64_t* counts);
+/* Resident use: one handle, many runs, leaves and result in host or in device memory.  tnco_hip_contract_run is "load
+ * every leaf from the host, then run what is loaded"; the two halves are entry points of their own.
+ *
+ * A caller's device pointer is touched by kernels only.  A process that uses PyTorch holds two HIP runtimes, PyTorch's
+ * bundled one and the one this library links, and memory that one of them allocated is unknown to the other: a copy, a
+ * memset or an attribute query on it fails or worse.  So no API call of this library's runtime ever gets such a pointer:
+ * it is an argument of ct_ingest_kernel / ct_emit_kernel (csrc/contract_io.h) and nothing else.  Two things follow.  The
+ * library cannot tell what a device pointer can reach: the caller checks that dims and strides stay inside its
+ * allocation.  And the two sides are ordered by full synchronisation, not by events: the caller's work on the memory has
+ * finished before the call (for PyTorch: torch.cuda.synchronize), and each of these entry points synchronises the
+ * handle's stream before it returns.
+ *
+ * load_leaf: leaf `leaf` of the plan from `src`, ndim <= 32 axes of `dims`.  where 0: host memory, C-contiguous
+ * (strides == NULL), src_dtype the handle's dtype code (a storage code: storage layout), copied as tnco_hip_contract_run
+ * copies it.  where 1: device memory, `strides` in elements, >= 0, 0 allowed (an expanded axis), NULL: C-contiguous;
+ * src_dtype 0..3 the handle's dtype or one that widens to it exactly (float32 -> float64, complex64, complex128;
+ * float64 -> complex128; complex64 -> complex128; a real source gives an imaginary part of +0.0).  A loaded leaf stays
+ * until it is loaded again or the handle is destroyed.  EINVAL, each with a text of its own and the handle left as it
+ * was: a null pointer; a leaf number outside the plan; `where` not 0 or 1; ndim outside [0, 32]; a dimension below 1; a
+ * negative stride; dims whose product is not the leaf's leaf_numel; a host leaf of another dtype or with strides; a
+ * device leaf on a handle with a storage dtype (4..7) or scaling; a src_dtype that does not widen to the handle's. */
+int tnco_hip_contract_load_leaf(tnco_hip_contract h, int64_t leaf, const void* src, int32_t where, int32_t src_dtype,
+                                int64_t ndim, const int64_t* dims, const int64_t* strides);
+/* runs as tnco_hip_contract_run does once the leaves are in place.  where 0: `out` is host memory and gets the raw output
+ * buffer, out_numel elements, [block axes][the other axes]; ndim, dims and dst_strides are not read.  where 1: `out` is
+ * device memory; dims are those of the output buffer's axes in its own order, dst_strides (in elements) where each of
+ * them goes in `out`.  EINVAL: a null pointer; `where` not 0 or 1; folded operands without their tables (as run); with
+ * where 1 a handle with row axes, ndim outside [0, 32], a dimension below 1, a negative stride or one of 0 on an axis
+ * longer than 1, dims whose product is not out_numel; a leaf that was never loaded (the text names the first one). */
+int tnco_hip_contract_run_loaded(tnco_hip_contract h, void* out, int32_t where, int64_t ndim, const int64_t* dims,
+                                 const int64_t* dst_strides);
+/* counts[2]: launches of ct_ingest_kernel and of ct_emit_kernel since the handle was created; they are no part of
+ * stats[1] or of any other counter, and the kernels reserve nothing: stats[2] does not change */
+int tnco_hip_contract_io_launches(tnco_hip_contract h, int64_t* counts);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

@@ -177,6 +177,15 @@ one per assignment; with `slice_batch` one per group, as without the keyword), w
 the one launch that rounds the accumulator is counted in `narrow_launches`; all of them are part of `launches`.  `array`
 keeps the arrays' dtype.  A plan without steps places blocks and sums nothing: it takes the keyword, reserves nothing and
 runs as without it.
+
+Resident use: `contract` plans, creates a device handle, copies every leaf in, runs, copies the output back, lays it out
+on the host and destroys the handle, every call.  A `Contractor` holds one plan and one handle for many runs: leaves can
+be bound and stay on the device, arrays can be torch tensors on the device (any strides >= 0; the plan's dtype or one that
+widens to it exactly) and the result can be written into a tensor (csrc/contract_io.h: ct_ingest_kernel copies a
+tensor into the handle's leaf buffer, ct_emit_kernel the output buffer into the tensor in the result's axis order).  A
+tensor's pointer is a kernel argument only -- torch's HIP runtime is not the one the library links, and memory of the one
+is unknown to the other -- and the two sides are ordered by full synchronisation.  The result is that of `contract` for
+the same arrays and keywords, byte for byte.
 """
 from __future__ import annotations
 
@@ -192,7 +201,7 @@ from .app import tn as tnmod
 __all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
            "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage", "SCALINGS", "scale_exponent", "scale_to_storage",
            "MAX_SLICE_BATCH", "COMPUTES", "split_bf16", "MAX_PATH_KERNEL", "MAX_PATH_STEP_MACS", "INDIRECT_KERNEL_PATHS",
-           "ACCUMULATES"]
+           "ACCUMULATES", "Contractor", "merge_axes", "check_extent"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -1189,30 +1198,42 @@ def _sum_results(parts, **given) -> ContractionResult:
                              **given)
 
 
+def _host_leaf(p: Plan, t: int, a, loose: bool = False):
+    """(leaf t as the handle takes it from host memory, its exponent under scaling, else None): contiguous in the plan's
+    dtype; with scaling scaled and rounded to storage; with storage rounded, a value beyond its range refused (not of a
+    `loose` leaf); with compute="bf16x3" checked against the range of the split; with projections restricted to its rows."""
+    a, e = np.ascontiguousarray(a, dtype=p.dtype), None
+    if p.scaling is not None:  # one exponent per leaf; nothing finite is beyond the range
+        a, e = _scaled_bits(a, p.storage)
+    elif p.storage is not None:
+        a = _storage_bits(a, p.storage, not loose)
+    elif p.compute == "bf16x3" and not loose:
+        _check_split_range(a)
+    if p.leaf_rows and p.leaf_rows[t] is not None:  # [rows][the other axes]: the leaf at the distinct projections of its sparse indices
+        axes, values = p.leaf_rows[t]
+        a = np.ascontiguousarray(np.moveaxis(a, axes, range(len(axes)))[tuple(values.T)])
+    return a, e
+
+
 def _run(p: Plan, arrays, device, loose=frozenset()) -> ContractionResult:
     from . import _lib, parallel
-    leaves = [np.ascontiguousarray(a, dtype=p.dtype) for a in arrays]
-    leaf_exps = None
-    if p.scaling is not None:  # one exponent per leaf; nothing finite is beyond the range
-        leaves, leaf_exps = (list(q) for q in zip(*(_scaled_bits(a, p.storage) for a in leaves)))
-        leaf_exps = np.array(leaf_exps, np.int32)
-    elif p.storage is not None:  # (before the device is touched: a leaf beyond the storage type's range is refused)
-        leaves = [_storage_bits(a, p.storage, t not in loose) for t, a in enumerate(leaves)]
-    elif p.compute == "bf16x3":  # (before the device is touched: a leaf beyond the range of the split is refused)
-        for t, a in enumerate(leaves):
-            if t not in loose:
-                _check_split_range(a)
+    # (before the device is touched: a leaf beyond the range of the storage type or of the split is refused)
+    leaves, leaf_exps = zip(*(_host_leaf(p, t, a, t in loose) for t, a in enumerate(arrays))) if arrays else ((), ())
+    leaf_exps = np.array(leaf_exps, np.int32) if p.scaling is not None else None
     L = _lib.load()
     device = parallel.local_device() if device is None else int(device)
-    for t, rows in enumerate(p.leaf_rows):
-        if rows is not None:  # [rows][the other axes]: the leaf at the distinct projections of its sparse indices
-            axes, values = rows
-            leaves[t] = np.ascontiguousarray(np.moveaxis(leaves[t], axes, range(len(axes)))[tuple(values.T)])
+    h = _create(L, p, device)
+    return _run_handle(L, h, p, list(leaves), leaf_exps)
+
+
+def _create(L, p: Plan, device: int):
+    """A new handle of the plan on that device."""
+    from . import _lib
     d, keep = _describe(p, device)
     h = C.c_void_p()
     _lib.check(L.tnco_hip_contract_create(C.byref(d), C.byref(h)))
     del keep  # (the tables are copied by create)
-    return _run_handle(L, h, p, leaves, leaf_exps)
+    return h
 
 
 def _describe(p: Plan, device: int):
@@ -1244,58 +1265,73 @@ def _describe(p: Plan, device: int):
 
 def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
     from . import _lib
+    try:
+        _set_modes(L, h, p)
+        if p.scaling is not None:
+            _lib.check(L.tnco_hip_contract_set_exponents(h, leaf_exps.ctypes.data_as(C.c_void_p)))
+        staging = np.empty(p.out_numel, p.dtype)
+        ptrs = (C.c_void_p * max(1, len(leaves)))(*[a.ctypes.data for a in leaves])
+        _lib.check(L.tnco_hip_contract_run(h, ptrs, staging.ctypes.data_as(C.c_void_p)))
+        fields = _read_counters(L, h, p)
+    finally:
+        L.tnco_hip_contract_destroy(h)
+    return ContractionResult(p.inds, _host_layout(p, staging), **fields)
+
+
+def _set_modes(L, h, p: Plan) -> None:
+    """The set calls of the plan's keywords on a new handle (the leaves' exponents of scaling apart: they belong to the arrays)."""
+    from . import _lib
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     i64 = lambda a: None if a is None else np.ascontiguousarray(a, np.int64)  # noqa: E731
     matrix, split = p.compute == "matrix", p.compute not in (None, "matrix")
+    # (is it on, entry point, arguments), in an order the library takes.  Nothing hoisted, every period 1 or nothing
+    # folded: the run of the plan without the keyword
+    setters = (
+        (matrix, L.tnco_hip_contract_set_matrix, (1,)),
+        (split, L.tnco_hip_contract_set_compute, (COMPUTES.get(p.compute),)),
+        (p.slice_batch is not None, L.tnco_hip_contract_set_slice_batch, (p.slice_batch,)),
+        (p.path_kernel is not None, L.tnco_hip_contract_set_path_kernel, (p.path_kernel,)),
+        (p.hoisted is not None and any(p.hoisted), L.tnco_hip_contract_set_hoist, (i64(p.step_hoist), i64(p.perm_hoist))),
+        (p.reused is not None and any(p.reused), L.tnco_hip_contract_set_reuse, (i64(p.step_period), i64(p.perm_period))),
+        (p.indirect, L.tnco_hip_contract_set_indirect, (i64(p.ind_steps), np.size(p.ind_maps), i64(p.ind_maps))),
+        (p.accumulate is not None, L.tnco_hip_contract_set_accumulate, (1,)))
+    for on, entry, args in setters:
+        if on:
+            _lib.check(entry(h, *(ptr(a) if isinstance(a, np.ndarray) else a for a in args)))
+
+
+def _read_counters(L, h, p: Plan) -> dict:
+    """The fields of a ContractionResult that the handle knows after a run: every one but `inds` and `array`."""
+    from . import _lib
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    matrix, split = p.compute == "matrix", p.compute not in (None, "matrix")
     wide = p.accumulate is not None
-    try:
-        # (is it on, entry point, arguments), in an order the library takes.  Nothing hoisted, every period 1 or nothing
-        # folded: the run of the plan without the keyword
-        setters = (
-            (matrix, L.tnco_hip_contract_set_matrix, (1,)),
-            (split, L.tnco_hip_contract_set_compute, (COMPUTES.get(p.compute),)),
-            (p.slice_batch is not None, L.tnco_hip_contract_set_slice_batch, (p.slice_batch,)),
-            (p.path_kernel is not None, L.tnco_hip_contract_set_path_kernel, (p.path_kernel,)),
-            (p.scaling is not None, L.tnco_hip_contract_set_exponents, (leaf_exps,)),
-            (p.hoisted is not None and any(p.hoisted), L.tnco_hip_contract_set_hoist, (i64(p.step_hoist), i64(p.perm_hoist))),
-            (p.reused is not None and any(p.reused), L.tnco_hip_contract_set_reuse, (i64(p.step_period), i64(p.perm_period))),
-            (p.indirect, L.tnco_hip_contract_set_indirect, (i64(p.ind_steps), np.size(p.ind_maps), i64(p.ind_maps))),
-            (wide, L.tnco_hip_contract_set_accumulate, (1,)))
-        # (is it on, entry point, length, field of the result)
-        counters = (
-            (True, L.tnco_hip_contract_kernel_launches, len(KERNEL_PATHS), "kernel_launches"),
-            (True, L.tnco_hip_contract_row_launches, len(ROW_KERNEL_PATHS), "row_kernel_launches"),
-            (p.scaling is not None or wide, L.tnco_hip_contract_narrow_launches, 1, "narrow_launches"),
-            (p.slice_batch is not None or wide, L.tnco_hip_contract_batch_launches, 1, "batch_launches"),
-            (matrix, L.tnco_hip_contract_matrix_launches, 1, "matrix_launches"),
-            (split, L.tnco_hip_contract_split_launches, 1, "split_launches"),
-            (p.path_kernel is not None, L.tnco_hip_contract_path_launches, 2, "path_launches"),
-            (p.indirect, L.tnco_hip_contract_indirect_launches, len(INDIRECT_KERNEL_PATHS), "indirect_launches"))
-        exponents, counted = None, {}
-        for on, entry, args in setters:
-            if on:
-                _lib.check(entry(h, *(ptr(a) if isinstance(a, np.ndarray) else a for a in args)))
-        staging = np.empty(p.out_numel, p.dtype)
-        ptrs = (C.c_void_p * max(1, len(leaves)))(*[a.ctypes.data for a in leaves])
-        _lib.check(L.tnco_hip_contract_run(h, ptrs, ptr(staging)))
-        stats = np.zeros(4, np.int64)
-        _lib.check(L.tnco_hip_contract_stats(h, ptr(stats)))
-        if p.scaling is not None:
-            slots = np.zeros(len(leaves) + len(p.steps), np.int32)
-            _lib.check(L.tnco_hip_contract_exponents(h, ptr(slots)))
-            exponents = tuple(int(v) for v in slots)
-        for on, entry, length, name in counters:
-            if on:
-                counts = np.zeros(length, np.int64)
-                _lib.check(entry(h, ptr(counts)))
-                counted[name] = int(counts[0]) if length == 1 else tuple(int(v) for v in counts)
-    finally:
-        L.tnco_hip_contract_destroy(h)
-    array = _host_layout(p, staging)
-    return ContractionResult(p.inds, array, int(stats[0]), p.slice_range[1] - p.slice_range[0], int(stats[2]),
-                             int(stats[1]), float(stats[3]) * 1e-9, scaling=p.scaling, exponents=exponents,
-                             slice_batch=p.slice_batch, compute=p.compute, path_kernel=p.path_kernel, hoisted=p.hoisted,
-                             reused=p.reused, indirect=p.indirect, **counted)
+    # (is it on, entry point, length, field of the result)
+    counters = (
+        (True, L.tnco_hip_contract_kernel_launches, len(KERNEL_PATHS), "kernel_launches"),
+        (True, L.tnco_hip_contract_row_launches, len(ROW_KERNEL_PATHS), "row_kernel_launches"),
+        (p.scaling is not None or wide, L.tnco_hip_contract_narrow_launches, 1, "narrow_launches"),
+        (p.slice_batch is not None or wide, L.tnco_hip_contract_batch_launches, 1, "batch_launches"),
+        (matrix, L.tnco_hip_contract_matrix_launches, 1, "matrix_launches"),
+        (split, L.tnco_hip_contract_split_launches, 1, "split_launches"),
+        (p.path_kernel is not None, L.tnco_hip_contract_path_launches, 2, "path_launches"),
+        (p.indirect, L.tnco_hip_contract_indirect_launches, len(INDIRECT_KERNEL_PATHS), "indirect_launches"))
+    exponents, counted = None, {}
+    stats = np.zeros(4, np.int64)
+    _lib.check(L.tnco_hip_contract_stats(h, ptr(stats)))
+    if p.scaling is not None:
+        slots = np.zeros(len(p.leaf_numel) + len(p.steps), np.int32)
+        _lib.check(L.tnco_hip_contract_exponents(h, ptr(slots)))
+        exponents = tuple(int(v) for v in slots)
+    for on, entry, length, name in counters:
+        if on:
+            counts = np.zeros(length, np.int64)
+            _lib.check(entry(h, ptr(counts)))
+            counted[name] = int(counts[0]) if length == 1 else tuple(int(v) for v in counts)
+    return dict(macs=int(stats[0]), n_slices=p.slice_range[1] - p.slice_range[0], peak_device_bytes=int(stats[2]),
+                launches=int(stats[1]), device_s=float(stats[3]) * 1e-9, scaling=p.scaling, exponents=exponents,
+                slice_batch=p.slice_batch, compute=p.compute, path_kernel=p.path_kernel, hoisted=p.hoisted,
+                reused=p.reused, indirect=p.indirect, **counted)
 
 
 def _host_layout(p: Plan, staging) -> np.ndarray:
@@ -1419,3 +1455,334 @@ def contract_results(tn0, arrays, tn, result, *, device=None, projs=None, sparse
         inds, array = (state_inds[0], state_arrays[0]) if len(state_inds) == 1 else (state_inds, state_arrays)
     return _sum_results(calls, inds=inds, array=array, n_slices=sum(r.n_slices for r in results),
                         exponents=calls[-1].exponents, fuse_macs=fuse_macs)
+
+
+def merge_axes(shape, strides) -> tuple:
+    """(dims, strides) of the same elements in the same order with as few axes as it takes: axes of dimension 1 dropped,
+    neighbours merged where the outer stride is the inner stride times the inner dimension (so two expanded neighbours,
+    both of stride 0, merge too).  Strides in elements.  A 0-d or one-element array gives ((), ()).  ValueError for a
+    negative stride, NotImplementedError when more than MAX_AXES axes are left."""
+    dims, steps = [], []
+    for d, s in zip(shape, strides):
+        d, s = int(d), int(s)
+        if d == 1:
+            continue
+        if s < 0:
+            raise ValueError("a tensor with a negative stride is not supported.")
+        if dims and steps[-1] == s * d:
+            dims[-1], steps[-1] = dims[-1] * d, s
+        else:
+            dims.append(d)
+            steps.append(s)
+    if len(dims) > MAX_AXES:
+        raise NotImplementedError(f"a tensor with more than {MAX_AXES} axes that do not merge is not supported.")
+    return tuple(dims), tuple(steps)
+
+
+def check_extent(offset: int, dims, strides, storage_elems: int) -> None:
+    """ValueError unless every element that `dims` and `strides` (>= 0, in elements) reach from `offset` lies inside a
+    storage of `storage_elems` elements."""
+    last = int(offset) + sum((int(d) - 1) * int(s) for d, s in zip(dims, strides))
+    if offset < 0 or last >= storage_elems:
+        raise ValueError(f"a tensor reaches element {last} of a storage of {storage_elems} elements.")
+
+
+def _c_strides(shape) -> tuple:
+    out, n = [], 1
+    for d in reversed(shape):
+        out.append(n)
+        n *= int(d)
+    return tuple(reversed(out))
+
+
+def _is_tensor(a) -> bool:
+    import sys
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(a, torch.Tensor)
+
+
+def _torch_dtypes() -> dict:
+    import torch
+    return {torch.float32: np.dtype(np.float32), torch.float64: np.dtype(np.float64),
+            torch.complex64: np.dtype(np.complex64), torch.complex128: np.dtype(np.complex128)}
+
+
+def _check_plain(a, what: str) -> None:
+    """ValueError unless the numbers of the tensor `a` are those its memory holds, at shape, strides and storage offset:
+    that is all a kernel is told of it.  A lazily conjugated or negated tensor (`t.conj()`, torch's conjugate and negative
+    bits) shares memory and strides with the tensor it came from, and a layout that is not strided has no strides."""
+    import torch
+    if a.layout != torch.strided:
+        raise ValueError(f"{what} has the layout {a.layout}: only strided tensors are supported.")
+    if a.is_conj():
+        raise ValueError(f"{what} is lazily conjugated (is_conj()): pass tensor.resolve_conj().")
+    if a.is_neg():
+        raise ValueError(f"{what} is lazily negated (is_neg()): pass tensor.resolve_neg().")
+
+
+# the exact widenings of csrc/contract_io.h besides the identity: source -> what it may become
+_WIDENS = {np.dtype(np.float32): (np.dtype(np.float64), np.dtype(np.complex64), np.dtype(np.complex128)),
+           np.dtype(np.float64): (np.dtype(np.complex128),), np.dtype(np.complex64): (np.dtype(np.complex128),),
+           np.dtype(np.complex128): ()}
+_SPLIT_LIMIT = float(np.array(0x7F7F8000, np.uint32).view(np.float32))  # 2^128 - 2^119: its bfloat16 is infinite
+
+
+class Contractor:
+    """One planned contraction that is run many times: the plan is made once, the device handle lives until close(), leaves
+    may stay on the device between runs (`bind`), and arrays may be numpy arrays or torch tensors on `device`.
+
+        with Contractor(path, ts_inds, shapes, output_inds, dtype=np.complex64, slices=cut, path_kernel=64) as c:
+            c.bind({0: a0, 3: t3})        # loaded now; they stay
+            r = c.run({1: a1, 2: a2})     # the other leaves, for this run
+            r = c.run(out=t)              # every leaf bound or given before: into the caller's tensor
+
+    The constructor takes what `plan` takes (`shapes`, not arrays) and refuses what it refuses; `plan` is that Plan.  It does
+    not touch the device: the handle is created at the first `bind` or `run`.  `run` returns the ContractionResult that
+    `contract` returns for the same path, arrays and keywords, `array` byte for byte (`device_s` is measured per run).
+    A numpy array must cast safely to the plan's dtype; a torch tensor must be on `device`, of any strides >= 0, of the
+    plan's dtype or one that widens to it exactly (float32 -> float64, complex64, complex128; float64, complex64 ->
+    complex128).  The arrays of one run are all numpy or all torch (bound leaves may be of either kind); `array` of the result
+    is of the kind of `out` when
+    that is given, else of the call's arrays, numpy without any.  `out`: C-contiguous, of the result's shape and dtype.
+    Torch operands and a torch `out` are not supported with `storage`, `scaling` or `projs`, which prepare leaves and
+    result on the host; numpy arrays are.  A torch tensor's memory is read and written by kernels only, after
+    torch.cuda.synchronize(device); what a tensor's strides reach is checked against its storage before its pointer is used,
+    and a tensor that is lazily conjugated or negated (`t.conj()`) or not strided is refused (ValueError: pass
+    `t.resolve_conj()`), since the kernels see its memory, not those bits."""
+
+    def __init__(self, path, ts_inds, shapes, output_inds=None, *, dtype=np.float64, slices=(), slice_range=None, device=None,
+                 sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
+                 hoist=None, indirect=None, reuse=None, slice_order=None, accumulate=None):
+        from . import parallel
+        shapes = [tuple(int(d) for d in s) for s in shapes]
+        self.plan = plan(path, ts_inds, shapes, output_inds, slices=slices, slice_range=slice_range, dtype=dtype,
+                         sparse_inds=sparse_inds, projs=projs, storage=storage, scaling=scaling, slice_batch=slice_batch,
+                         compute=compute, path_kernel=path_kernel, hoist=hoist, indirect=indirect, reuse=reuse,
+                         slice_order=slice_order, accumulate=accumulate)
+        self.device = parallel.local_device() if device is None else int(device)
+        self._shapes = shapes
+        self._host_only = next((name for name, v in (("storage", storage), ("scaling", scaling), ("projs", projs))
+                                if v is not None), None)
+        self._lib, self._h, self._closed = None, None, False
+        self._bound = set()
+        self._exps = np.zeros(len(shapes), np.int32)  # scaling: the exponents of the leaves the handle holds
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def close(self) -> None:
+        """Destroys the handle; the object refuses every use afterwards.  Closing twice is fine."""
+        if self._h is not None:
+            self._lib.tnco_hip_contract_destroy(self._h)
+        self._h, self._closed = None, True
+
+    @property
+    def io_launches(self) -> tuple:
+        """(launches of the ingest kernel, of the emit kernel) since the handle was created."""
+        self._check_open()
+        if self._h is None:
+            return (0, 0)
+        from . import _lib
+        counts = np.zeros(2, np.int64)
+        _lib.check(self._lib.tnco_hip_contract_io_launches(self._h, counts.ctypes.data_as(C.c_void_p)))
+        return (int(counts[0]), int(counts[1]))
+
+    def bind(self, leaves) -> None:
+        """Loads the leaves {leaf number: array} now; they stay until bound again or until close()."""
+        self._check_open()
+        given, _ = self._check_arrays(leaves, one_kind=False)
+        # numpy arrays and tensors may come together here; every check of both kinds before anything is loaded
+        kinds = [(kind, self._prepare({t: a for t, a in given.items() if _is_tensor(a) == kind}, kind)) for kind in (False, True)]
+        for kind, ready in kinds:
+            self._bound -= set(ready)  # (a leaf is bound once it is loaded, not while a failed load may have left it half written)
+            self._load(ready, kind)
+            self._bound |= set(ready)
+
+    def run(self, arrays=None, *, out=None) -> ContractionResult:
+        """Runs the plan over the bound leaves and `arrays`: a sequence with every leaf, or {leaf number: array} with the
+        leaves that are not bound.  The given leaves are for this run: the next run needs them again.  A bound leaf may be
+        given too: the run takes the given one, and the leaf is bound no longer."""
+        from . import _lib
+        self._check_open()
+        p = self.plan
+        given, torch_in = self._check_arrays({} if arrays is None else arrays)
+        torch_out = _is_tensor(out)
+        if torch_out and self._host_only:
+            raise NotImplementedError(f"a torch tensor as 'out' is not supported with '{self._host_only}'.")
+        ready = self._prepare(given, torch_in)
+        if out is not None:
+            self._check_out(out, torch_out)
+        missing = [t for t in range(len(self._shapes)) if t not in self._bound and t not in ready]
+        if missing:
+            raise ValueError(f"leaf {missing[0]} is neither bound nor given.")
+        to_device = torch_out or (out is None and torch_in)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        L, h = self._handle()
+        # before anything is loaded: a bound leaf that a run is given another array for is no longer the one the handle
+        # holds, also when the run fails half way
+        self._bound -= set(ready)
+        if not torch_in and not to_device and len(ready) == len(self._shapes):  # as contract(): one call, one wait
+            self._note_exponents(ready)
+            staging = np.empty(p.out_numel, p.dtype)
+            ptrs = (C.c_void_p * max(1, len(ready)))(*[ready[t][0].ctypes.data for t in range(len(ready))])
+            _lib.check(L.tnco_hip_contract_run(h, ptrs, ptr(staging)))
+        else:
+            self._load(ready, torch_in)
+            if to_device:
+                import torch
+                if out is None:
+                    kind = next(k for k, v in _torch_dtypes().items() if v == p.dtype)
+                    out = torch.empty(p.shape, dtype=kind, device=f"cuda:{self.device}")
+                rest = tuple(x for x in p.inds if x not in set(p.slice_inds))
+                held = p.block_inds + rest  # the output buffer's axes; where each of them goes in the result
+                at = [p.inds.index(x) for x in held]
+                steps = _c_strides(p.shape)
+                dims, strides = merge_axes([p.shape[q] for q in at], [steps[q] for q in at])
+                torch.cuda.synchronize(self.device)
+                i64 = lambda v: ptr(np.array(v, np.int64)) if v else None  # noqa: E731
+                _lib.check(L.tnco_hip_contract_run_loaded(h, C.c_void_p(out.data_ptr()), 1, len(dims), i64(dims), i64(strides)))
+            else:
+                staging = np.empty(p.out_numel, p.dtype)
+                _lib.check(L.tnco_hip_contract_run_loaded(h, ptr(staging), 0, 0, None, None))
+        fields = _read_counters(L, h, p)
+        if to_device:
+            return ContractionResult(p.inds, out, **fields)
+        array = _host_layout(p, staging)
+        if out is not None:
+            np.copyto(out, array)
+            array = out
+        return ContractionResult(p.inds, array, **fields)
+
+    # -- the checks; none of them touches the device through this library
+
+    def _check_open(self) -> None:
+        if self._closed:
+            raise ValueError("the Contractor is closed.")
+
+    def _check_arrays(self, arrays, one_kind=True):
+        """({leaf number: array}, whether they are torch tensors); one_kind: they must be all numpy or all torch."""
+        n = len(self._shapes)
+        if isinstance(arrays, dict):
+            given = dict(arrays)
+            for t in given:
+                if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t < n:
+                    raise ValueError(f"{t!r} is not a leaf of the plan (0 to {n - 1}).")
+            given = {int(t): a for t, a in given.items()}
+        else:
+            given = dict(enumerate(arrays))
+            if len(given) != n:
+                raise ValueError("'ts_inds' is not consistent with 'arrays'.")
+        kinds = {_is_tensor(a) for a in given.values()}
+        if len(kinds) > 1 and one_kind:
+            raise TypeError("the arrays of one run must be all numpy arrays or all torch tensors.")
+        torch_in = True in kinds
+        if torch_in and self._host_only:
+            raise NotImplementedError(f"torch tensors are not supported with '{self._host_only}'.")
+        return given, torch_in
+
+    def _prepare(self, given, torch_in) -> dict:
+        """{leaf number: what _load takes}, in leaf order: a numpy leaf as (array as the handle takes it, exponent), a
+        tensor as (tensor, dtype code, dims, strides)."""
+        p, ready = self.plan, {}
+        for t in sorted(given):
+            a = given[t]
+            if not torch_in:
+                a = np.asarray(a)
+                if tuple(a.shape) != self._shapes[t]:
+                    raise ValueError("'ts_inds' is not consistent with 'arrays'.")
+                if not np.can_cast(a.dtype, p.dtype, "safe"):
+                    raise TypeError(f"an array of dtype {a.dtype} does not cast safely to {p.dtype}.")
+                ready[t] = _host_leaf(p, t, a)
+                continue
+            if tuple(a.shape) != self._shapes[t]:
+                raise ValueError("'ts_inds' is not consistent with 'arrays'.")
+            src = _torch_dtypes().get(a.dtype)
+            if src is None or not (src == p.dtype or p.dtype in _WIDENS[src]):
+                raise TypeError(f"a tensor of dtype {a.dtype} does not widen exactly to {p.dtype}.")
+            _check_plain(a, "a tensor")
+            if a.device.type != "cuda" or a.device.index != self.device:
+                raise ValueError(f"a tensor is on {a.device}, not on cuda:{self.device}.")
+            dims, strides = merge_axes(a.shape, a.stride())
+            check_extent(a.storage_offset(), dims, strides, a.untyped_storage().nbytes() // a.element_size())
+            ready[t] = (a, DTYPES[src], dims, strides)
+        if torch_in and p.compute == "bf16x3":
+            import torch
+            for a, *_ in ready.values():
+                x = (torch.view_as_real(a) if a.is_complex() else a).abs()
+                if bool((torch.isfinite(x) & (x >= _SPLIT_LIMIT)).any()):
+                    raise ValueError("an array has finite values beyond the range of the bfloat16 split (|x| >= 2^128 - 2^119).")
+        return ready
+
+    def _check_out(self, out, torch_out) -> None:
+        p = self.plan
+        shape = tuple(p.shape)
+        if torch_out:
+            if _torch_dtypes().get(out.dtype) != p.dtype:
+                raise TypeError(f"'out' must be of dtype {p.dtype}, not {out.dtype}.")
+            _check_plain(out, "'out'")
+            if out.device.type != "cuda" or out.device.index != self.device:
+                raise ValueError(f"'out' is on {out.device}, not on cuda:{self.device}.")
+            if tuple(out.shape) != shape or not out.is_contiguous():
+                raise ValueError(f"'out' must be C-contiguous and of shape {shape}.")
+            check_extent(out.storage_offset(), out.shape, _c_strides(out.shape), out.untyped_storage().nbytes() // out.element_size())
+            return
+        if not isinstance(out, np.ndarray):
+            raise TypeError("'out' must be a numpy array or a torch tensor.")
+        if out.dtype != p.dtype:
+            raise TypeError(f"'out' must be of dtype {p.dtype}, not {out.dtype}.")
+        if tuple(out.shape) != shape or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError(f"'out' must be C-contiguous and of shape {shape}.")
+
+    # -- the device
+
+    def _handle(self):
+        if self._h is None:
+            from . import _lib
+            L = _lib.load()
+            h = _create(L, self.plan, self.device)
+            try:
+                _set_modes(L, h, self.plan)
+            except Exception:
+                L.tnco_hip_contract_destroy(h)
+                raise
+            self._lib, self._h = L, h
+        return self._lib, self._h
+
+    def _note_exponents(self, ready) -> None:
+        from . import _lib
+        if self.plan.scaling is None:
+            return
+        for t, (_a, e) in ready.items():
+            self._exps[t] = e
+        _lib.check(self._lib.tnco_hip_contract_set_exponents(self._h, self._exps.ctypes.data_as(C.c_void_p)))
+
+    def _load(self, ready, torch_in) -> None:
+        from . import _lib
+        if not ready:
+            return
+        L, h = self._handle()
+        p = self.plan
+        if not torch_in:
+            code = DTYPES[p.dtype] if p.storage is None else STORAGES[p.storage] + (p.dtype.kind == "c")
+            self._note_exponents(ready)
+            for t, (a, _e) in ready.items():
+                n = np.array([p.leaf_numel[t]], np.int64)
+                _lib.check(L.tnco_hip_contract_load_leaf(h, t, a.ctypes.data_as(C.c_void_p), 0, code, 1,
+                                                         n.ctypes.data_as(C.c_void_p), None))
+            return
+        import torch
+        torch.cuda.synchronize(self.device)
+        for t, (a, code, dims, strides) in ready.items():
+            d, s = np.array(dims, np.int64), np.array(strides, np.int64)
+            _lib.check(L.tnco_hip_contract_load_leaf(h, t, C.c_void_p(a.data_ptr()), 1, code, len(dims),
+                                                     d.ctypes.data_as(C.c_void_p) if len(dims) else None,
+                                                     s.ctypes.data_as(C.c_void_p) if len(dims) else None))

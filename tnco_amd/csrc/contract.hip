@@ -50,6 +50,10 @@
 //   ct_acc_reduce_kernel, ct_acc_path_reduce_kernel  the twins of the two reduce kernels, and
 //   ct_acc_narrow_kernel   rounds the accumulator into the output once, after the last assignment.
 // Every other kernel, shape, k order and block is that of the run without the call.
+// Resident use (tnco_hip_contract_load_leaf, tnco_hip_contract_run_loaded; contract_io.h): a run is "load every leaf, then
+// run what is loaded", and the halves are entry points of their own; a leaf or the result may lie in a caller's device
+// memory, which only
+//   ct_ingest_kernel, ct_emit_kernel  ever touch (a caller's pointer may belong to another HIP runtime in the process).
 // No atomics in any sum: every sum runs in one fixed order, so a run is bit-reproducible (the one atomic, the integer max
 // behind a scaled tensor's exponent, does not depend on order).
 #include "../../include/tnco_hip.h"
@@ -534,6 +538,7 @@ __global__ __launch_bounds__(256) void ct_rows_dot_kernel(RowGemmArgs<T> p) {
 }
 
 #include "contract_indirect.h"
+#include "contract_io.h"
 
 }  // namespace
 
@@ -600,6 +605,8 @@ struct tnco_hip_contract_s {
   int64_t macs = 0, launches = 0, bytes = 0, device_ns = 0;
   int64_t by_kernel[TNCO_HIP_CONTRACT_N_KERNELS] = {};  // launches of the last run per kernel path (tnco_hip.h)
   int64_t by_row_kernel[TNCO_HIP_CONTRACT_N_ROW_KERNELS] = {};  // the same of the row-mapped paths
+  std::vector<char> loaded;        // [n_leaves]: the leaf buffer holds a leaf (tnco_hip_contract_load_leaf, tnco_hip_contract_run)
+  int64_t io_launches[2] = {0, 0};  // launches of ct_ingest_kernel and of ct_emit_kernel since create
 };
 
 namespace {
@@ -1340,6 +1347,117 @@ void drop_accumulate_stage(tnco_hip_contract_s* c) {
   c->d_acc_stage = nullptr;
 }
 
+// a host leaf (C-contiguous, in the handle's element type) into its leaf buffer, on the handle's stream; the caller
+// synchronises
+int load_host_leaf(tnco_hip_contract_s* c, int64_t t, const void* src) {
+  CT_TRY(hipMemcpyAsync(c->d_leaves + c->leaf_off[t] * c->elem, src, (size_t)c->leaf_numel[t] * c->elem, hipMemcpyHostToDevice,
+                        c->stream));
+  c->loaded[t] = 1;
+  return TNCO_HIP_OK;
+}
+
+// dtype code `from` is `to`, or one of the five exact widenings of contract_io.h
+bool io_widens(int from, int to) {
+  return from == to || (from == 0 && to >= 1) || (from == 1 && to == 3) || (from == 2 && to == 3);
+}
+
+template <class D, class S>
+void launch_ingest_as(tnco_hip_contract_s* c, void* dst, const void* src, int64_t numel, const IoAxes& ax) {
+  hipLaunchKernelGGL((ct_ingest_kernel<D, S>), dim3(io_blocks(numel, sizeof(D), ax.nd < 0)), dim3(256), 0, c->stream, (D*)dst,
+                     (const S*)src, numel, ax);
+}
+
+// `src`, a caller's device memory of dtype code `from`, into `dst` of the handle's dtype (io_widens holds)
+int launch_ingest(tnco_hip_contract_s* c, void* dst, const void* src, int from, int64_t numel, const IoAxes& ax) {
+  using F = float;
+  using Dd = double;
+  using CF = cplx<float>;
+  using CD = cplx<double>;
+  switch (c->dtype * 4 + from) {
+    case 0: launch_ingest_as<F, F>(c, dst, src, numel, ax); break;
+    case 4: launch_ingest_as<Dd, F>(c, dst, src, numel, ax); break;
+    case 5: launch_ingest_as<Dd, Dd>(c, dst, src, numel, ax); break;
+    case 8: launch_ingest_as<CF, F>(c, dst, src, numel, ax); break;
+    case 10: launch_ingest_as<CF, CF>(c, dst, src, numel, ax); break;
+    case 12: launch_ingest_as<CD, F>(c, dst, src, numel, ax); break;
+    case 13: launch_ingest_as<CD, Dd>(c, dst, src, numel, ax); break;
+    case 14: launch_ingest_as<CD, CF>(c, dst, src, numel, ax); break;
+    case 15: launch_ingest_as<CD, CD>(c, dst, src, numel, ax); break;
+    default: return fail(TNCO_HIP_EINVAL, "'src_dtype' does not widen to the plan's dtype.");
+  }
+  CT_TRY(hipGetLastError());
+  c->io_launches[0] += 1;
+  return TNCO_HIP_OK;
+}
+
+template <class T>
+void launch_emit_as(tnco_hip_contract_s* c, void* dst, const IoAxes& ax) {
+  hipLaunchKernelGGL(ct_emit_kernel<T>, dim3(io_blocks(c->out_numel, sizeof(T), ax.nd < 0)), dim3(256), 0, c->stream, (T*)dst,
+                     (const T*)c->d_out, c->out_numel, ax);
+}
+
+// the output buffer into `dst`, a caller's device memory of the output's type (a storage dtype: float32 / complex64)
+int launch_emit(tnco_hip_contract_s* c, void* dst, const IoAxes& ax) {
+  switch (c->dtype) {
+    case 1: launch_emit_as<double>(c, dst, ax); break;
+    case 3: launch_emit_as<cplx<double>>(c, dst, ax); break;
+    case 2: case 5: case 7: launch_emit_as<cplx<float>>(c, dst, ax); break;
+    default: launch_emit_as<float>(c, dst, ax);
+  }
+  CT_TRY(hipGetLastError());
+  c->io_launches[1] += 1;
+  return TNCO_HIP_OK;
+}
+
+// The run over the leaves that the leaf buffers hold, from the zeroing of the output on.  emit == nullptr: `out` is host
+// memory and gets the raw output buffer; otherwise `out` is a caller's device memory and ct_emit_kernel writes it
+int run_loaded(tnco_hip_contract_s* c, void* out, const IoAxes* emit) {
+  CT_TRY(hipMemsetAsync(c->d_out, 0, (size_t)c->out_numel * c->out_elem, c->stream));
+  const size_t n_steps = c->steps.size() / STEP_W;
+  if (c->d_acc) CT_TRY(hipMemsetAsync(c->d_acc, 0, (size_t)c->out_numel * 2 * c->out_elem, c->stream));
+  if (c->scaling && !c->leaf_exps.empty()) {
+    if (c->batch && n_steps) {  // every member's copy of the slots starts with the same leaf exponents
+      const size_t n_slots = c->leaf_exps.size() + n_steps;
+      c->exps_image.assign((size_t)c->batch * n_slots, 0);
+      for (int64_t b = 0; b < c->batch; ++b) std::copy(c->leaf_exps.begin(), c->leaf_exps.end(), c->exps_image.begin() + b * n_slots);
+      CT_TRY(hipMemcpyAsync(c->d_exps, c->exps_image.data(), c->exps_image.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    } else {
+      CT_TRY(hipMemcpyAsync(c->d_exps, c->leaf_exps.data(), c->leaf_exps.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+  }
+  c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->matrix_launches = c->last_member = 0;
+  c->path_launches[0] = c->path_launches[1] = c->acc_launches[0] = c->acc_launches[1] = 0;
+  std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
+  std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
+  std::fill(std::begin(c->by_ix), std::end(c->by_ix), 0);
+  CT_TRY(hipEventRecord(c->ev[0], c->stream));
+  const bool fused = c->path_group > 0 && n_steps > 0;  // (a plan without steps runs as it does without the call)
+  int rc = fused ? (c->dtype == 0 ? run_path<float>(c)
+                    : c->dtype == 1 ? run_path<double>(c)
+                    : c->dtype == 2 ? run_path<cplx<float>>(c)
+                                    : run_path<cplx<double>>(c))
+           : c->dtype == 0 ? run_impl<float>(c)
+           : c->dtype == 1 ? run_impl<double>(c)
+           : c->dtype == 2 ? run_impl<cplx<float>>(c)
+           : c->dtype == 3 ? run_impl<cplx<double>>(c)
+           : c->dtype == 4 ? run_impl<float, st_f16>(c)
+           : c->dtype == 5 ? run_impl<cplx<float>, cplx<st_f16>>(c)
+           : c->dtype == 6 ? run_impl<float, st_bf16>(c)
+                           : run_impl<cplx<float>, cplx<st_bf16>>(c);
+  if (rc) return rc;
+  CT_TRY(hipEventRecord(c->ev[1], c->stream));
+  if (emit) {
+    if (int rc2 = launch_emit(c, out, *emit)) return rc2;
+  } else {
+    CT_TRY(hipMemcpyAsync(out, c->d_out, (size_t)c->out_numel * c->out_elem, hipMemcpyDeviceToHost, c->stream));
+  }
+  CT_TRY(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  CT_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+  c->device_ns = (int64_t)((double)ms * 1e6);
+  return TNCO_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1356,6 +1474,7 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
   (void)make_schedule(c, ones.data(), ones.data(), REUSE_RULES, &c->sched);  // every period 1: nothing there to refuse
   static const size_t elem[8] = {4, 8, 8, 16, 2, 4, 2, 4}, out_elem[8] = {4, 8, 8, 16, 4, 8, 4, 8};
   c->dtype = d->dtype, c->elem = elem[d->dtype], c->out_elem = out_elem[d->dtype], c->device = d->device;
+  c->loaded.assign(c->leaf_numel.size(), 0);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || d->device < 0 || d->device >= ndev) {
     delete c;
@@ -1418,48 +1537,70 @@ int tnco_hip_contract_run(tnco_hip_contract c, const void* const* leaves, void* 
   CT_TRY(hipSetDevice(c->device));
   for (size_t t = 0; t < c->leaf_numel.size(); ++t) {
     if (!leaves[t]) return fail(TNCO_HIP_EINVAL, "null leaf.");
-    CT_TRY(hipMemcpyAsync(c->d_leaves + c->leaf_off[t] * c->elem, leaves[t], (size_t)c->leaf_numel[t] * c->elem,
-                          hipMemcpyHostToDevice, c->stream));
+    if (int rc = load_host_leaf(c, (int64_t)t, leaves[t])) return rc;
   }
-  CT_TRY(hipMemsetAsync(c->d_out, 0, (size_t)c->out_numel * c->out_elem, c->stream));
-  const size_t n_steps = c->steps.size() / STEP_W;
-  if (c->d_acc) CT_TRY(hipMemsetAsync(c->d_acc, 0, (size_t)c->out_numel * 2 * c->out_elem, c->stream));
-  if (c->scaling && !c->leaf_exps.empty()) {
-    if (c->batch && n_steps) {  // every member's copy of the slots starts with the same leaf exponents
-      const size_t n_slots = c->leaf_exps.size() + n_steps;
-      c->exps_image.assign((size_t)c->batch * n_slots, 0);
-      for (int64_t b = 0; b < c->batch; ++b) std::copy(c->leaf_exps.begin(), c->leaf_exps.end(), c->exps_image.begin() + b * n_slots);
-      CT_TRY(hipMemcpyAsync(c->d_exps, c->exps_image.data(), c->exps_image.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    } else {
-      CT_TRY(hipMemcpyAsync(c->d_exps, c->leaf_exps.data(), c->leaf_exps.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    }
+  return run_loaded(c, out, nullptr);
+}
+
+int tnco_hip_contract_load_leaf(tnco_hip_contract c, int64_t leaf, const void* src, int32_t where, int32_t src_dtype,
+                                int64_t ndim, const int64_t* dims, const int64_t* strides) {
+  if (!c || !src) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (leaf < 0 || leaf >= (int64_t)c->leaf_numel.size()) return fail(TNCO_HIP_EINVAL, "'leaf' is not a leaf of the plan.");
+  if (where != 0 && where != 1) return fail(TNCO_HIP_EINVAL, "'where' must be 0 (host) or 1 (device).");
+  IoAxes ax;
+  bool contiguous = false;
+  if (const char* e = io_axes(ndim, dims, strides, c->leaf_numel[leaf], "dims do not multiply to the leaf's elements.", &ax, &contiguous))
+    return fail(TNCO_HIP_EINVAL, e);
+  if (where == 0) {
+    if (src_dtype != c->dtype) return fail(TNCO_HIP_EINVAL, "a host leaf must have the plan's dtype.");
+    if (strides) return fail(TNCO_HIP_EINVAL, "a host leaf must be C-contiguous: 'strides' must be NULL.");
+    CT_TRY(hipSetDevice(c->device));
+    if (int rc = load_host_leaf(c, leaf, src)) return rc;
+    CT_TRY(hipStreamSynchronize(c->stream));
+    return TNCO_HIP_OK;
   }
-  c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->matrix_launches = c->last_member = 0;
-  c->path_launches[0] = c->path_launches[1] = c->acc_launches[0] = c->acc_launches[1] = 0;
-  std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
-  std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
-  std::fill(std::begin(c->by_ix), std::end(c->by_ix), 0);
-  CT_TRY(hipEventRecord(c->ev[0], c->stream));
-  const bool fused = c->path_group > 0 && n_steps > 0;  // (a plan without steps runs as it does without the call)
-  int rc = fused ? (c->dtype == 0 ? run_path<float>(c)
-                    : c->dtype == 1 ? run_path<double>(c)
-                    : c->dtype == 2 ? run_path<cplx<float>>(c)
-                                    : run_path<cplx<double>>(c))
-           : c->dtype == 0 ? run_impl<float>(c)
-           : c->dtype == 1 ? run_impl<double>(c)
-           : c->dtype == 2 ? run_impl<cplx<float>>(c)
-           : c->dtype == 3 ? run_impl<cplx<double>>(c)
-           : c->dtype == 4 ? run_impl<float, st_f16>(c)
-           : c->dtype == 5 ? run_impl<cplx<float>, cplx<st_f16>>(c)
-           : c->dtype == 6 ? run_impl<float, st_bf16>(c)
-                           : run_impl<cplx<float>, cplx<st_bf16>>(c);
-  if (rc) return rc;
-  CT_TRY(hipEventRecord(c->ev[1], c->stream));
-  CT_TRY(hipMemcpyAsync(out, c->d_out, (size_t)c->out_numel * c->out_elem, hipMemcpyDeviceToHost, c->stream));
+  if (c->dtype > 3 || c->scaling)
+    return fail(TNCO_HIP_EINVAL, "a device leaf is not supported with a storage dtype or scaling.");
+  if (src_dtype < 0 || src_dtype > 3 || !io_widens(src_dtype, c->dtype))
+    return fail(TNCO_HIP_EINVAL, "'src_dtype' does not widen to the plan's dtype.");
+  CT_TRY(hipSetDevice(c->device));
+  if (contiguous) {  // one axis; of the plan's dtype: the vector path
+    ax.nd = src_dtype == c->dtype ? -1 : 1;
+    ax.dim[0] = c->leaf_numel[leaf], ax.stride[0] = 1;
+  }
+  if (int rc = launch_ingest(c, c->d_leaves + c->leaf_off[leaf] * c->elem, src, src_dtype, c->leaf_numel[leaf], ax)) return rc;
   CT_TRY(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  CT_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-  c->device_ns = (int64_t)((double)ms * 1e6);
+  c->loaded[leaf] = 1;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_run_loaded(tnco_hip_contract c, void* out, int32_t where, int64_t ndim, const int64_t* dims,
+                                 const int64_t* dst_strides) {
+  if (!c || !out) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (where != 0 && where != 1) return fail(TNCO_HIP_EINVAL, "'where' must be 0 (host) or 1 (device).");
+  if (c->folded && c->ind_steps.empty())
+    return fail(TNCO_HIP_EINVAL, "the plan has folded operands: call tnco_hip_contract_set_indirect before the run.");
+  IoAxes ax;
+  if (where == 1) {
+    if (!c->row_steps.empty() || !c->row_maps.empty())
+      return fail(TNCO_HIP_EINVAL, "a device result is not supported with row axes.");
+    if (ndim && !dst_strides) return fail(TNCO_HIP_EINVAL, "null argument.");
+    bool contiguous = false;
+    if (const char* e = io_axes(ndim, dims, dst_strides, c->out_numel, "dims do not multiply to the output's elements.", &ax, &contiguous))
+      return fail(TNCO_HIP_EINVAL, e);
+    for (int k = 0; k < ax.nd; ++k)
+      if (ax.dim[k] > 1 && ax.stride[k] == 0) return fail(TNCO_HIP_EINVAL, "a destination stride is 0.");
+    if (contiguous) ax.nd = -1;
+  }
+  for (size_t t = 0; t < c->loaded.size(); ++t)
+    if (!c->loaded[t]) return fail(TNCO_HIP_EINVAL, "leaf " + std::to_string(t) + " was never loaded.");
+  CT_TRY(hipSetDevice(c->device));
+  return run_loaded(c, out, where == 1 ? &ax : nullptr);
+}
+
+int tnco_hip_contract_io_launches(tnco_hip_contract c, int64_t* counts) {
+  if (!c || !counts) return fail(TNCO_HIP_EINVAL, "null argument.");
+  counts[0] = c->io_launches[0], counts[1] = c->io_launches[1];
   return TNCO_HIP_OK;
 }
 

@@ -23,9 +23,12 @@ order, in one process); reuse (`--reuse`: the sliced Sycamore leg, unbatched, wi
 reuse=True with slice_order="reuse", and that with indirect=True, and the same five on a deeper network whose assignments
 take milliseconds, every ratio against hoist=True, in one process); the wide accumulation (`--accumulate`: the sliced
 Sycamore leg with accumulate=None and "float64", unbatched, with slice_batch=64 and hoist=True, and with path_kernel=1024,
-and the error of each against the same plan in complex128, in one process).  Engine figures are its
+and the error of each against the same plan in complex128, in one process); the resident use (`--resident`: wall time
+per call of contract() and of one Contractor run with numpy arrays, with every leaf bound from numpy, and with every leaf
+bound from torch tensors and the result written into a tensor, on the sliced Sycamore leg under path_kernel=1024 and on
+the bandwidth-bound step of the indirect leg, in one process).  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
-operands stay on the device).
+operands stay on the device); the resident leg measures what that leaves out.
 """
 from __future__ import annotations
 
@@ -580,6 +583,79 @@ def indirect(lines, depth, max_width, max_slices):
     lines.extend(notes)
 
 
+def resident(lines, depth, max_width, max_slices, reps=5):
+    """What a call costs around its kernels: wall time per call (time.perf_counter, the device synchronised on both sides)
+    of contract() and of three ways to use one Contractor, device_s next to it; per setting the minimum of `reps` calls
+    after a warm-up and their spread, all settings in this process.  Two legs: the sliced Sycamore amplitude of the
+    path-kernel leg under path_kernel=1024, and the bandwidth-bound step of the indirect leg (X of 2^26 complex64)."""
+    lines.append("")
+    notes = []
+
+    def leg(title, path, ts, leaves, output, kw):
+        lines.append(title)
+        lines.append(f"{'setting':>46} {'wall s':>10} {'spread':>7} {'contract() / this':>17} {'device s':>10} {'io launches':>12} {'same bytes':>10}")
+        shapes = [a.shape for a in leaves]
+        tensors = [torch.from_numpy(a).cuda() for a in leaves]
+        rows, base = [], None
+        with ctr.Contractor(path, ts, shapes, output, dtype=np.complex64, **kw) as c:
+            out = torch.empty(tuple(c.plan.shape), dtype=torch.complex64, device="cuda")
+
+            def bound_numpy():
+                return c.run()
+
+            def bound_torch():
+                return c.run(out=out)
+
+            settings = (("contract()", None, lambda: ctr.contract(path, ts, leaves, output, **kw)),
+                        ("Contractor.run(numpy arrays)", None, lambda: c.run(leaves)),
+                        ("Contractor.run(), leaves bound from numpy", lambda: c.bind(dict(enumerate(leaves))), bound_numpy),
+                        ("Contractor.run(out=tensor), bound from torch", lambda: c.bind(dict(enumerate(tensors))), bound_torch))
+            for name, before, call in settings:
+                if before is not None:
+                    before()
+                r = call()  # warm-up
+                times, dev = [], []
+                for _ in range(reps):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    r = call()
+                    torch.cuda.synchronize()
+                    times.append(time.perf_counter() - t0)
+                    dev.append(r.device_s)
+                got = r.array if isinstance(r.array, np.ndarray) else r.array.cpu().numpy()
+                if base is None:
+                    base = got
+                same = np.array_equal(np.ravel(got).view(np.uint32), np.ravel(base).view(np.uint32))
+                rows.append((name, min(times), (max(times) - min(times)) / min(times), min(dev), c.io_launches, same))
+        t_base, s_base = rows[0][1], rows[0][2]
+        for name, t, spread, dev, io, same in rows:
+            lines.append(f"{name:>46} {t:10.6f} {spread:7.3f} {t_base / t:17.2f} {dev:10.6f} {str(io):>12} {str(same):>10}")
+            print(lines[-1], flush=True)
+            if t > t_base * (1 + max(spread, s_base)):
+                notes.append(f"  {name}: SLOWER per call than contract() by more than the larger of the two spreads")
+        del tensors, out
+
+    tn, r0, leaves = _sliced_sycamore(depth, max_width)
+    p = ctr.plan(r0.path, tn.ts_inds, [a.shape for a in leaves], tn.output_inds, slices=r0.slices)
+    m = min(p.n_slices, max_slices)
+    leg(f"## resident, sliced Sycamore-53 amplitude, depth {depth}, complex64, max_width {max_width}, cost {r0.cost}, "
+        f"{len(leaves)} leaves, {len(r0.path)} steps, assignments [0, {m}) of {p.n_slices}, path_kernel=1024: wall seconds per call "
+        f"(perf_counter, device synchronised on both sides), the minimum of {reps} calls after a warm-up, spread = (max - min) / min; "
+        "device s: the minimum device_s of the same calls; all settings in one process",
+        r0.path, tn.ts_inds, leaves, tn.output_inds, dict(slices=r0.slices, slice_range=(0, m), path_kernel=1024))
+    del leaves
+    rng = np.random.RandomState(2)
+    nx, ks = 26, (13, 12, 11, 10)
+    xs = tuple(f"x{q}" for q in reversed(range(nx)))
+    ys = tuple(f"x{q}" for q in ks)
+    x, y = _rand((2,) * nx, np.complex64, rng), _rand((2,) * len(ks), np.complex64, rng)
+    lines.append("")
+    leg(f"## resident, one bandwidth-bound step: X complex64, 2^{nx} elements ({x.nbytes >> 20} MiB), axes of dimension 2 in "
+        f"reversed order, Z = sum over {len(ks)} axes in its middle of X Y, indirect=True: the same columns",
+        [(0, 1)], [xs, ys], [x, y], None, dict(indirect=True))
+    lines.extend(notes)
+
+
 def compute(lines, n, depth, max_width, max_slices):
     """The compute mode against the plain engine in the same process: the large square step with compute=None (the tiled
     LDS kernel, the yardstick), compute="bf16x3" (ct_split_tiled_kernel) and storage="bfloat16" (ct_mfma_tiled_kernel), and
@@ -758,15 +834,19 @@ def main():
     ap.add_argument("--indirect", action="store_true", help="only the indirect-operand leg, appended to --out")
     ap.add_argument("--reuse", action="store_true", help="only the reuse leg, appended to --out")
     ap.add_argument("--accumulate", action="store_true", help="only the wide-accumulation leg, appended to --out")
+    ap.add_argument("--resident", action="store_true", help="only the resident (Contractor) leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect + a.reuse + a.accumulate > 1:
-        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix, --indirect, --reuse and --accumulate each "
+    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect + a.reuse + a.accumulate + a.resident > 1:
+        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix, --indirect, --reuse, --accumulate and --resident each "
                  "append one leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect or a.reuse or a.accumulate:  # (the other legs' sections stay as they are)
-        if a.accumulate:
+    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect or a.reuse or a.accumulate or a.resident:  # (the other legs' sections stay as they are)
+        if a.resident:
+            lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
+            resident(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+        elif a.accumulate:
             lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
             accumulate(lines, a.depth, a.max_width, min(a.max_slices, 2048))
         elif a.reuse:
@@ -812,6 +892,7 @@ def main():
     indirect(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     reuse(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     accumulate(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+    resident(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
