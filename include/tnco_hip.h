@@ -718,6 +718,43 @@ int tnco_hip_contract_run_loaded(tnco_hip_contract h, void* out, int32_t where, 
 /* counts[2]: launches of ct_ingest_kernel and of ct_emit_kernel since the handle was created; they are no part of
  * stats[1] or of any other counter, and the kernels reserve nothing: stats[2] does not change */
 int tnco_hip_contract_io_launches(tnco_hip_contract h, int64_t* counts);
+/* Leaf sets: many runs of one plan that differ in a few leaves, in one call (csrc/contract_sets.h).  On a handle with a
+ * path kernel a member of a launch is a pair (leaf set i, assignment a), numbered set-major: with A = slice_stop -
+ * slice_start, member m = i A + (a - slice_start).  A leaf that differs between the sets is loaded as a stack
+ * [n_sets][leaf_numel] into a buffer of the handle's own, apart from the leaf's single buffer, which stays as it is; every
+ * other leaf is read from its single buffer by every set.  The members run in groups of `group` consecutive ones, two
+ * launches per group, and the output of set i is bit for bit that of tnco_hip_contract_run_loaded over leaf set i: the
+ * blocks of a set are folded in ascending assignment order with the placement and beta bits of the path kernel's table.
+ *
+ * load_leaf_sets: tnco_hip_contract_load_leaf for a stack: the product of `dims` is n_sets leaf_numel, the elements in C
+ * order of the dims are set 0, set 1, ...; where, src_dtype and strides as there (a stride of 0 on a set axis gives equal
+ * sets).  A caller's device pointer is touched by ct_ingest_kernel only.  The stack stays until the next
+ * tnco_hip_contract_run_sets has read it, or until the leaf's stack is loaded again; its buffer grows to the largest
+ * n_sets loaded and stays until destroy (ERUNTIME when it exceeds the device's free memory; the handle then stays as it
+ * was); stats[2] counts it.  EINVAL, each with a text of its own and the handle left as it was: a null pointer; a leaf
+ * number outside the plan; n_sets < 1 or too large for 64-bit offsets; a handle with row axes, without a path kernel,
+ * with wide accumulation or without steps; and what load_leaf refuses of where, ndim, dims, strides and src_dtype. */
+int tnco_hip_contract_load_leaf_sets(tnco_hip_contract h, int64_t leaf, int64_t n_sets, const void* src, int32_t where,
+                                     int32_t src_dtype, int64_t ndim, const int64_t* dims, const int64_t* strides);
+/* runs the n_sets sets: a leaf whose stack holds n_sets sets is read from it at set stride leaf_numel, every other leaf
+ * must be loaded and is read from its single buffer at set stride 0; min(group, n_sets A) members per launch.  where 0:
+ * `out` is host memory and gets n_sets raw output buffers back to back, [n_sets][out_numel]; ndim, dims and dst_strides
+ * are not read.  where 1: `out` is device memory, written by ct_emit_kernel with the set axis as one more axis: dims are
+ * those of [n_sets][the output buffer's axes] in that order (axes may be merged; the product is n_sets out_numel),
+ * dst_strides (in elements) where each of them goes in `out`.  Reserves, and keeps until destroy, the arenas and staging
+ * blocks beyond the path kernel's group that the members need, n_sets output buffers, and a table of a pointer and a
+ * stride per leaf (ERUNTIME when they exceed the device's free memory; the handle then stays as it was); stats[2]
+ * counts them.  stats[0] is n_sets times a run's multiply-adds, stats[1] the launches, two per group.  A run reads the
+ * stacks once: the next one needs them loaded again.  Synchronises the handle's stream before it returns.  EINVAL, each
+ * with a text of its own and the handle left as it was: a null pointer; n_sets < 1 or too large; a group outside
+ * [1, 1024]; a handle with row axes, without a path kernel, with wide accumulation or without steps; `where` not 0 or 1;
+ * with where 1 what run_loaded refuses of ndim, dims and dst_strides; a leaf whose stack holds another number of sets
+ * (the text names the leaf and both numbers); a leaf without a stack that was never loaded. */
+int tnco_hip_contract_run_sets(tnco_hip_contract h, int64_t n_sets, int64_t group, void* out, int32_t where, int64_t ndim,
+                               const int64_t* dims, const int64_t* dst_strides);
+/* counts[2]: the last run's launches of ct_sets_path_kernel and of ct_sets_reduce_kernel (one each per group; 0, 0 after
+ * any other run).  stats[1] is their sum, and every other launch counter is 0 after tnco_hip_contract_run_sets */
+int tnco_hip_contract_sets_launches(tnco_hip_contract h, int64_t* counts);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

@@ -97,6 +97,7 @@ EXPORTS = [
     "tnco_hip_contract_set_indirect",
     "tnco_hip_contract_indirect_launches", "tnco_hip_contract_set_accumulate", "tnco_hip_contract_accumulate_launches",
     "tnco_hip_contract_load_leaf", "tnco_hip_contract_run_loaded", "tnco_hip_contract_io_launches",
+    "tnco_hip_contract_load_leaf_sets", "tnco_hip_contract_run_sets", "tnco_hip_contract_sets_launches",
     "tnco_hip_contract_destroy",
     "tnco_hip_device_name", "tnco_hip_device_count", "tnco_hip_last_error", "tnco_hip_version",
 ]
@@ -221,6 +222,9 @@ def load() -> C.CDLL:
     L.tnco_hip_contract_load_leaf.argtypes = [vp, i64, vp, i32, i32, i64, vp, vp]
     L.tnco_hip_contract_run_loaded.argtypes = [vp, vp, i32, i64, vp, vp]
     L.tnco_hip_contract_io_launches.argtypes = [vp, vp]
+    L.tnco_hip_contract_load_leaf_sets.argtypes = [vp, i64, i64, vp, i32, i32, i64, vp, vp]
+    L.tnco_hip_contract_run_sets.argtypes = [vp, i64, i64, vp, i32, i64, vp, vp]
+    L.tnco_hip_contract_sets_launches.argtypes = [vp, vp]
     L.tnco_hip_contract_destroy.argtypes = [vp]
     L.tnco_hip_contract_destroy.restype = None
     L.tnco_hip_device_name.argtypes = [C.c_int, vp, C.c_int]

@@ -186,6 +186,19 @@ tensor into the handle's leaf buffer, ct_emit_kernel the output buffer into the 
 tensor's pointer is a kernel argument only -- torch's HIP runtime is not the one the library links, and memory of the one
 is unknown to the other -- and the two sides are ordered by full synchronisation.  The result is that of `contract` for
 the same arrays and keywords, byte for byte.
+
+Leaf sets: `Contractor.run_many(stacks, group=, out=)` (with `path_kernel=`, a plan with steps, no `accumulate=`) runs R
+leaf sets of the plan in one call: `stacks` is {leaf number: array}, each array the R versions of that leaf along one
+leading axis; every other leaf is bound and shared.  A member of a launch is a pair (set i, assignment a), numbered
+set-major: with slice_range = (lo, hi) and A = hi - lo, member m = i A + (a - lo); launches take `group` consecutive
+members (1 to MAX_PATH_KERNEL, None: MAX_PATH_KERNEL; effective min(group, R A)), so a group may end inside a set, at its
+end, or span several, and R sets are ceil(R A / group) pairs of launches (csrc/contract_sets.h: the path kernel with a
+leaf's base moved on by set x stride, the stride 0 for a shared leaf; the fold kernel with set i's copy of the output).
+Set i is folded in ascending assignment order with the placement and beta bits of the plan's own table, so array[i] of
+the ManyResult is byte for byte `run` of leaf set i, whatever the group; blocks that slice_range does not reach are zero
+in every set.  A stack lives in a device buffer of its own: a bound leaf given as a stack stays bound and untouched.
+`many_bytes(R, group)` is the device memory the handle holds after such a call, term by term; what a call grew stays
+until a larger call or close().
 """
 from __future__ import annotations
 
@@ -201,7 +214,7 @@ from .app import tn as tnmod
 __all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
            "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage", "SCALINGS", "scale_exponent", "scale_to_storage",
            "MAX_SLICE_BATCH", "COMPUTES", "split_bf16", "MAX_PATH_KERNEL", "MAX_PATH_STEP_MACS", "INDIRECT_KERNEL_PATHS",
-           "ACCUMULATES", "Contractor", "merge_axes", "check_extent"]
+           "ACCUMULATES", "Contractor", "merge_axes", "check_extent", "ManyResult"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -276,6 +289,21 @@ class ContractionResult:
     #                                       INDIRECT_KERNEL_PATHS order; part of `launches`, of no slot of kernel_launches
     matrix_launches: int = 0  # compute="matrix": launches of the matrix kernel (they are part of their tiled slot of
     #                           kernel_launches)
+
+
+@dataclass(frozen=True)
+class ManyResult:
+    """What `Contractor.run_many` returns: the results of R leaf sets of one plan."""
+    inds: tuple  # ("set",) + Plan.inds
+    array: object  # (R,) + Plan.shape: array[i] is byte for byte `run` of leaf set i; numpy array or torch tensor
+    sets: int  # R
+    group: int  # members (set, assignment) per launch, the effective value: min(what was asked for, R x assignments)
+    macs: int  # multiply-adds launched: R times a run's
+    launches: int  # kernel launches
+    path_launches: tuple  # launches of the path kernel over sets and of the kernel that folds a group's blocks into the
+    #                       outputs: ceil(R x assignments / group) each; `launches` is their sum
+    peak_device_bytes: int  # device memory the handle holds after the call (`Contractor.many_bytes`)
+    device_s: float = 0.0  # device time of the kernels (copies in and out excluded)
 
 
 @dataclass
@@ -1566,6 +1594,8 @@ class Contractor:
         self._lib, self._h, self._closed = None, None, False
         self._bound = set()
         self._exps = np.zeros(len(shapes), np.int32)  # scaling: the exponents of the leaves the handle holds
+        # run_many: what its calls made the handle reserve (sets per stacked leaf, members, outputs), the leaves last stacked
+        self._many = dict(stacks={}, members=0, out=0, last=())
 
     def __enter__(self):
         return self
@@ -1662,7 +1692,162 @@ class Contractor:
             array = out
         return ContractionResult(p.inds, array, **fields)
 
+    def run_many(self, stacks, *, group=None, out=None) -> ManyResult:
+        """Runs the plan over R leaf sets in one call: `stacks` is {leaf number: array}, each array the R versions of that
+        leaf along one leading axis, (R,) + the leaf's shape; every other leaf must be bound and is shared by the sets.
+        `array[i]` of the result is byte for byte `run({t: stacks[t][i]}).array` (module docstring, Leaf sets).  The
+        arrays follow the rules of `run`; a set axis of stride 0 gives R equal sets.  A bound leaf may be given as a stack:
+        the call reads the stack, and the leaf stays bound and as it was.  `group`: members (set, assignment) per launch,
+        None or 1 to MAX_PATH_KERNEL (None: MAX_PATH_KERNEL); `out`: C-contiguous, of shape (R,) + plan.shape and of the
+        plan's dtype.  It needs `path_kernel=` and a plan with steps, and is not supported with `accumulate=`."""
+        from . import _lib
+        self._check_open()
+        p = self.plan
+        group = self._check_many(group)
+        if not isinstance(stacks, dict) or not stacks:
+            raise ValueError("'stacks' must be a dict {leaf number: array} with at least one leaf.")
+        given, torch_in = self._check_arrays(stacks)
+        sets, ready = self._prepare_stacks(given, torch_in)
+        missing = [t for t in range(len(self._shapes)) if t not in self._bound and t not in ready]
+        if missing:
+            raise ValueError(f"leaf {missing[0]} is neither bound nor given.")
+        torch_out = _is_tensor(out)
+        if out is not None:
+            self._check_out(out, torch_out, (sets,) + tuple(p.shape))
+        to_device = torch_out or (out is None and torch_in)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        i64 = lambda v: ptr(np.array(v, np.int64)) if len(v) else None  # noqa: E731
+        L, h = self._handle()
+        if torch_in or to_device:
+            import torch
+            torch.cuda.synchronize(self.device)
+        for t, (a, code, dims, strides) in ready.items():
+            where = 1 if torch_in else 0
+            src = C.c_void_p(a.data_ptr()) if torch_in else ptr(a)
+            _lib.check(L.tnco_hip_contract_load_leaf_sets(h, t, sets, src, where, code, len(dims), i64(dims), i64(strides)))
+        rest = tuple(x for x in p.inds if x not in set(p.slice_inds))
+        held = p.block_inds + rest  # the axes of one output buffer; where each of them goes in a set of the result
+        at = [p.inds.index(x) for x in held]
+        if to_device:
+            if out is None:
+                kind = next(k for k, v in _torch_dtypes().items() if v == p.dtype)
+                out = torch.empty((sets,) + tuple(p.shape), dtype=kind, device=f"cuda:{self.device}")
+            steps = _c_strides((sets,) + tuple(p.shape))
+            dims, strides = merge_axes([sets] + [p.shape[q] for q in at], [steps[0]] + [steps[1 + q] for q in at])
+            _lib.check(L.tnco_hip_contract_run_sets(h, sets, group, C.c_void_p(out.data_ptr()), 1, len(dims), i64(dims), i64(strides)))
+            array = out
+        else:
+            staging = np.empty((sets, p.out_numel), p.dtype)
+            _lib.check(L.tnco_hip_contract_run_sets(h, sets, group, ptr(staging), 0, 0, None, None))
+            array = staging.reshape((sets,) + tuple(p.shape[q] for q in at))
+            array = array.transpose([0] + [1 + held.index(x) for x in p.inds]).copy(order="C")
+            if out is not None:
+                np.copyto(out, array)
+                array = out
+        self._grow(sets, group, ready)
+        stats, counts = np.zeros(4, np.int64), np.zeros(2, np.int64)
+        _lib.check(L.tnco_hip_contract_stats(h, ptr(stats)))
+        _lib.check(L.tnco_hip_contract_sets_launches(h, ptr(counts)))
+        members = sets * (p.slice_range[1] - p.slice_range[0])
+        return ManyResult(("set",) + tuple(p.inds), array, sets, min(group, members), int(stats[0]), int(stats[1]),
+                          (int(counts[0]), int(counts[1])), int(stats[2]), float(stats[3]) * 1e-9)
+
+    def many_bytes(self, n_sets, group=None, leaves=None) -> int:
+        """The device bytes the handle holds after `run_many` of `n_sets` sets with that `group` and stacks of the leaves
+        `leaves` (None: those of the last `run_many`, none before the first), `peak_device_bytes` of its result: what the
+        handle holds without the call; a stack of n_sets versions per stacked leaf; the arenas and staging blocks that
+        min(group, n_sets x assignments) members need beyond `Plan.path_kernel`; n_sets outputs; a pointer and a stride
+        per leaf.  What an earlier call grew stays until close(): each term is the largest so far."""
+        self._check_open()
+        p = self.plan
+        group = self._check_many(group)
+        if isinstance(n_sets, bool) or not isinstance(n_sets, (int, np.integer)) or n_sets < 1:
+            raise ValueError("'n_sets' must be a positive integer.")
+        n = len(self._shapes)
+        leaves = self._many["last"] if leaves is None else tuple(leaves)
+        for t in leaves:
+            if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t < n:
+                raise ValueError(f"{t!r} is not a leaf of the plan (0 to {n - 1}).")
+        item, A = p.dtype.itemsize, p.slice_range[1] - p.slice_range[0]
+        block = p.out_numel // math.prod(p.shape[p.inds.index(x)] for x in p.block_inds)
+        # what the handle of this plan holds (csrc/contract.hip: create and tnco_hip_contract_set_path_kernel): the leaves,
+        # each padded to 64 elements, path_kernel arenas and staging blocks, the output, the tables and a pointer per leaf
+        held = item * sum(-(-int(v) // ALIGN) * ALIGN for v in p.leaf_numel) + item * max(p.arena_elems, 1) + item * p.out_numel
+        held += 8 * (p.perms.size + p.leaf_sl.size + 2 * len(p.slice_dims)) + 8 * max(n, 1)
+        held += item * ((p.path_kernel - 1) * p.arena_elems + p.path_kernel * block) + 8 * (p.steps.size + 2 * (len(p.steps) + 1) + A)
+        caps = self._many
+        stacked = dict(caps["stacks"])
+        for t in leaves:
+            stacked[int(t)] = max(stacked.get(int(t), 0), int(n_sets))
+        stacks = item * sum(r * int(p.leaf_numel[t]) for t, r in stacked.items())
+        members = max(caps["members"], min(group, int(n_sets) * A))
+        grown = item * max(members - p.path_kernel, 0) * (p.arena_elems + block)
+        outputs = item * max(caps["out"], int(n_sets)) * p.out_numel
+        return held + stacks + grown + outputs + 16 * n
+
     # -- the checks; none of them touches the device through this library
+
+    def _check_many(self, group) -> int:
+        """What run_many refuses of the Contractor and of `group`; the group as a number."""
+        p = self.plan
+        if p.path_kernel is None:
+            raise NotImplementedError("'run_many' needs a Contractor with 'path_kernel'.")
+        if p.accumulate is not None:
+            raise NotImplementedError("'accumulate' is not supported with 'run_many'.")
+        if not len(p.steps):
+            raise NotImplementedError("'run_many' needs a plan with steps.")
+        if group is None:
+            return MAX_PATH_KERNEL
+        if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or not 1 <= group <= MAX_PATH_KERNEL:
+            raise ValueError(f"'group' must be None or an integer from 1 to {MAX_PATH_KERNEL}.")
+        return int(group)
+
+    def _prepare_stacks(self, given, torch_in):
+        """(R, {leaf number: (array or tensor, dtype code, dims, strides)} in leaf order): what load_leaf_sets takes."""
+        p, sets = self.plan, None
+        for t in sorted(given):
+            a = given[t] if torch_in else np.asarray(given[t])
+            given[t] = a
+            if len(a.shape) < 1:
+                raise ValueError(f"the stack of leaf {t} has no set axis.")
+            if tuple(a.shape[1:]) != self._shapes[t]:
+                raise ValueError(f"the stack of leaf {t} has the shape {tuple(a.shape[1:])} after its set axis, not the leaf's "
+                                 f"{self._shapes[t]}.")
+            if a.shape[0] < 1:
+                raise ValueError(f"the stack of leaf {t} holds no set.")
+            sets = int(a.shape[0]) if sets is None else sets
+            if a.shape[0] != sets:
+                raise ValueError(f"the stack of leaf {t} holds {a.shape[0]} sets, the first stack {sets}.")
+        ready = {}
+        for t in sorted(given):
+            a = given[t]
+            if not torch_in:
+                if not np.can_cast(a.dtype, p.dtype, "safe"):
+                    raise TypeError(f"an array of dtype {a.dtype} does not cast safely to {p.dtype}.")
+                a = np.ascontiguousarray(a, dtype=p.dtype)
+                ready[t] = (a, DTYPES[p.dtype], (a.size,), ())
+                continue
+            src = _torch_dtypes().get(a.dtype)
+            if src is None or not (src == p.dtype or p.dtype in _WIDENS[src]):
+                raise TypeError(f"a tensor of dtype {a.dtype} does not widen exactly to {p.dtype}.")
+            _check_plain(a, "a tensor")
+            if a.device.type != "cuda" or a.device.index != self.device:
+                raise ValueError(f"a tensor is on {a.device}, not on cuda:{self.device}.")
+            dims, strides = merge_axes(a.shape, a.stride())
+            check_extent(a.storage_offset(), dims, strides, a.untyped_storage().nbytes() // a.element_size())
+            if not dims:  # (one element in all: an axis for the library to count)
+                dims, strides = (1,), (1,)
+            ready[t] = (a, DTYPES[src], dims, strides)
+        return sets, ready
+
+    def _grow(self, sets, group, ready) -> None:
+        """Notes what a run_many made the handle reserve (many_bytes)."""
+        caps, p = self._many, self.plan
+        for t in ready:
+            caps["stacks"][t] = max(caps["stacks"].get(t, 0), sets)
+        caps["members"] = max(caps["members"], min(group, sets * (p.slice_range[1] - p.slice_range[0])))
+        caps["out"] = max(caps["out"], sets)
+        caps["last"] = tuple(ready)
 
     def _check_open(self) -> None:
         if self._closed:
@@ -1722,9 +1907,9 @@ class Contractor:
                     raise ValueError("an array has finite values beyond the range of the bfloat16 split (|x| >= 2^128 - 2^119).")
         return ready
 
-    def _check_out(self, out, torch_out) -> None:
+    def _check_out(self, out, torch_out, shape=None) -> None:
         p = self.plan
-        shape = tuple(p.shape)
+        shape = tuple(p.shape) if shape is None else shape
         if torch_out:
             if _torch_dtypes().get(out.dtype) != p.dtype:
                 raise TypeError(f"'out' must be of dtype {p.dtype}, not {out.dtype}.")

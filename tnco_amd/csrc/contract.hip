@@ -54,6 +54,11 @@
 // run what is loaded", and the halves are entry points of their own; a leaf or the result may lie in a caller's device
 // memory, which only
 //   ct_ingest_kernel, ct_emit_kernel  ever touch (a caller's pointer may belong to another HIP runtime in the process).
+// Leaf sets (tnco_hip_contract_load_leaf_sets, tnco_hip_contract_run_sets; contract_sets.h): on a handle with a path
+// kernel a member of a launch is a pair (leaf set, assignment); a leaf that differs between the sets lies in a stack
+// [n_sets][leaf_numel] of the handle's own, and
+//   ct_sets_path_kernel, ct_sets_reduce_kernel  the twins of the two path kernels
+// leave the output of every set in [n_sets][out_numel], each bit-equal to a run of that set alone.
 // No atomics in any sum: every sum runs in one fixed order, so a run is bit-reproducible (the one atomic, the integer max
 // behind a scaled tensor's exponent, does not depend on order).
 #include "../../include/tnco_hip.h"
@@ -410,6 +415,7 @@ __global__ __launch_bounds__(256) void ct_batch_reduce_kernel(T* out, const T* s
 }
 
 #include "contract_path.h"
+#include "contract_sets.h"
 #include "contract_accumulate.h"
 
 // A step with a row axis: row r of the result reads row a_map[r] of A and row b_map[r] of B.  A null map with a row
@@ -607,6 +613,16 @@ struct tnco_hip_contract_s {
   int64_t by_row_kernel[TNCO_HIP_CONTRACT_N_ROW_KERNELS] = {};  // the same of the row-mapped paths
   std::vector<char> loaded;        // [n_leaves]: the leaf buffer holds a leaf (tnco_hip_contract_load_leaf, tnco_hip_contract_run)
   int64_t io_launches[2] = {0, 0};  // launches of ct_ingest_kernel and of ct_emit_kernel since create
+  // leaf sets (tnco_hip_contract_load_leaf_sets, tnco_hip_contract_run_sets); every buffer grows and never shrinks
+  std::vector<void*> d_stack;      // [n_leaves]: the leaf's stack [sets][leaf_numel], apart from its single buffer
+  std::vector<int64_t> stack_cap;  // [n_leaves]: sets the stack has room for
+  std::vector<int64_t> stack_sets;  // [n_leaves]: sets the stack holds for the next tnco_hip_contract_run_sets, 0: none
+  int64_t path_cap = 0;            // members d_arena and d_path_stage have room for (tnco_hip_contract_set_path_kernel: path_group)
+  void* d_sets_out = nullptr;      // [sets_out_cap][out_numel]
+  int64_t sets_out_cap = 0;
+  char* d_sets_tables = nullptr;   // [n_leaves][2]: a leaf's pointer and its set stride
+  std::vector<int64_t> sets_image;  // the host copy of d_sets_tables of the last run
+  int64_t sets_launches[2] = {0, 0};  // launches of ct_sets_path_kernel and of ct_sets_reduce_kernel in the last run
 };
 
 namespace {
@@ -1135,13 +1151,9 @@ int run_impl(tnco_hip_contract_s* c) {
   return TNCO_HIP_OK;
 }
 
-// The fused loop of a handle with a path kernel: per group of up to c->path_group assignments one ct_path_kernel and
-// one ct_path_reduce_kernel.
-template <class T>
-int run_path(tnco_hip_contract_s* c) {
+// the arguments of the path kernel but the first assignment; *d_place: the placement table of the run's assignments
+PathArgs path_args(const tnco_hip_contract_s* c, const int64_t** d_place) {
   const int64_t S = (int64_t)c->steps.size() / STEP_W, P = (int64_t)c->perms.size() / PERM_W;
-  constexpr bool single = std::is_same<T, float>::value || std::is_same<T, cplx<float>>::value;
-  const bool wide = single && c->accumulate;  // the folds go into the accumulator (run_path: a plan with steps)
   PathArgs a;
   a.perms = c->d_tables;
   a.leaf_sl = c->d_tables + P * PERM_W;
@@ -1152,13 +1164,30 @@ int run_path(tnco_hip_contract_s* c) {
   a.leaves = (const void* const*)c->d_leaf_ptrs;
   a.arena = c->d_arena, a.stage = c->d_path_stage;
   a.arena_elems = c->arena_elems, a.block_numel = c->block_numel;
+  a.sid0 = 0;
   a.n_steps = (int)S;
-  const int64_t* d_place = a.groups + 2 * (S + 1);
+  *d_place = a.groups + 2 * (S + 1);
+  return a;
+}
+
+int64_t macs_per_assignment(const tnco_hip_contract_s* c) {
   int64_t per_slice = 0;
-  for (int64_t k = 0; k < S; ++k) {
+  for (size_t k = 0; k < c->steps.size() / STEP_W; ++k) {
     const int64_t* st = &c->steps[k * STEP_W];
     per_slice += st[10] * st[11] * st[12] * st[13];
   }
+  return per_slice;
+}
+
+// The fused loop of a handle with a path kernel: per group of up to c->path_group assignments one ct_path_kernel and
+// one ct_path_reduce_kernel.
+template <class T>
+int run_path(tnco_hip_contract_s* c) {
+  constexpr bool single = std::is_same<T, float>::value || std::is_same<T, cplx<float>>::value;
+  const bool wide = single && c->accumulate;  // the folds go into the accumulator (run_path: a plan with steps)
+  const int64_t* d_place = nullptr;
+  PathArgs a = path_args(c, &d_place);
+  const int64_t per_slice = macs_per_assignment(c);
   for (int64_t sid = c->start; sid < c->stop; sid += c->path_group) {
     const int64_t n = std::min(c->path_group, c->stop - sid);
     a.sid0 = sid;
@@ -1183,6 +1212,43 @@ int run_path(tnco_hip_contract_s* c) {
     if (wide) return narrow_accumulator<T>(c);
   }
   return TNCO_HIP_OK;
+}
+
+// The fused loop over leaf sets: the members (set, assignment) of n_sets sets, set-major, in groups of `group`
+// consecutive ones, one ct_sets_path_kernel and one ct_sets_reduce_kernel per group (contract_sets.h).  The caller has made
+// room for `group` members and n_sets outputs and has uploaded the leaf pointers and set strides.
+template <class T>
+int run_sets(tnco_hip_contract_s* c, int64_t n_sets, int64_t group) {
+  const int64_t A = c->stop - c->start;
+  const int64_t* d_place = nullptr;
+  SetsArgs s;
+  s.p = path_args(c, &d_place);
+  s.set_leaves = (const int64_t*)c->d_sets_tables;
+  s.n_assign = A, s.start = c->start;
+  const int64_t per_slice = macs_per_assignment(c), members = n_sets * A;
+  for (int64_t m0 = 0; m0 < members; m0 += group) {
+    const int64_t n = std::min(group, members - m0);
+    s.m0 = m0;
+    hipLaunchKernelGGL(ct_sets_path_kernel<T>, dim3((unsigned)n), dim3(PATH_LANES), 0, c->stream, s);
+    CT_TRY(hipGetLastError());
+    const dim3 grid((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048));
+    hipLaunchKernelGGL(ct_sets_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (T*)c->d_sets_out, (const T*)c->d_path_stage,
+                       c->block_numel, (int)n, m0, A, c->out_numel, d_place);
+    CT_TRY(hipGetLastError());
+    c->launches += 2;
+    c->sets_launches[0] += 1, c->sets_launches[1] += 1;
+    c->macs += per_slice * n;
+  }
+  return TNCO_HIP_OK;
+}
+
+// what the leaf-set entry points refuse of a handle, or nullptr
+const char* sets_refusal(const tnco_hip_contract_s* c) {
+  if (!c->row_steps.empty() || !c->row_maps.empty()) return "leaf sets are not supported with row axes.";
+  if (!c->path_group) return "leaf sets need a path kernel: call tnco_hip_contract_set_path_kernel first.";
+  if (c->accumulate) return "leaf sets are not supported with wide accumulation.";
+  if (c->steps.empty()) return "leaf sets need a plan with steps.";
+  return nullptr;
 }
 
 int64_t n_assignments(const tnco_hip_contract_s* c) {
@@ -1391,18 +1457,21 @@ int launch_ingest(tnco_hip_contract_s* c, void* dst, const void* src, int from, 
 }
 
 template <class T>
-void launch_emit_as(tnco_hip_contract_s* c, void* dst, const IoAxes& ax) {
-  hipLaunchKernelGGL(ct_emit_kernel<T>, dim3(io_blocks(c->out_numel, sizeof(T), ax.nd < 0)), dim3(256), 0, c->stream, (T*)dst,
-                     (const T*)c->d_out, c->out_numel, ax);
+void launch_emit_as(tnco_hip_contract_s* c, void* dst, const IoAxes& ax, const void* src, int64_t numel) {
+  hipLaunchKernelGGL(ct_emit_kernel<T>, dim3(io_blocks(numel, sizeof(T), ax.nd < 0)), dim3(256), 0, c->stream, (T*)dst,
+                     (const T*)src, numel, ax);
 }
 
-// the output buffer into `dst`, a caller's device memory of the output's type (a storage dtype: float32 / complex64)
-int launch_emit(tnco_hip_contract_s* c, void* dst, const IoAxes& ax) {
+// the output buffer (leaf sets: `sets` of them, back to back) into `dst`, a caller's device memory of the output's type
+// (a storage dtype: float32 / complex64)
+int launch_emit(tnco_hip_contract_s* c, void* dst, const IoAxes& ax, int64_t sets = 0) {
+  const void* src = sets ? c->d_sets_out : c->d_out;
+  const int64_t numel = c->out_numel * std::max<int64_t>(sets, 1);
   switch (c->dtype) {
-    case 1: launch_emit_as<double>(c, dst, ax); break;
-    case 3: launch_emit_as<cplx<double>>(c, dst, ax); break;
-    case 2: case 5: case 7: launch_emit_as<cplx<float>>(c, dst, ax); break;
-    default: launch_emit_as<float>(c, dst, ax);
+    case 1: launch_emit_as<double>(c, dst, ax, src, numel); break;
+    case 3: launch_emit_as<cplx<double>>(c, dst, ax, src, numel); break;
+    case 2: case 5: case 7: launch_emit_as<cplx<float>>(c, dst, ax, src, numel); break;
+    default: launch_emit_as<float>(c, dst, ax, src, numel);
   }
   CT_TRY(hipGetLastError());
   c->io_launches[1] += 1;
@@ -1427,6 +1496,7 @@ int run_loaded(tnco_hip_contract_s* c, void* out, const IoAxes* emit) {
   }
   c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->matrix_launches = c->last_member = 0;
   c->path_launches[0] = c->path_launches[1] = c->acc_launches[0] = c->acc_launches[1] = 0;
+  c->sets_launches[0] = c->sets_launches[1] = 0;
   std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
   std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
   std::fill(std::begin(c->by_ix), std::end(c->by_ix), 0);
@@ -1475,6 +1545,8 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
   static const size_t elem[8] = {4, 8, 8, 16, 2, 4, 2, 4}, out_elem[8] = {4, 8, 8, 16, 4, 8, 4, 8};
   c->dtype = d->dtype, c->elem = elem[d->dtype], c->out_elem = out_elem[d->dtype], c->device = d->device;
   c->loaded.assign(c->leaf_numel.size(), 0);
+  c->d_stack.assign(c->leaf_numel.size(), nullptr);
+  c->stack_cap.assign(c->leaf_numel.size(), 0), c->stack_sets.assign(c->leaf_numel.size(), 0);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || d->device < 0 || d->device >= ndev) {
     delete c;
@@ -1601,6 +1673,156 @@ int tnco_hip_contract_run_loaded(tnco_hip_contract c, void* out, int32_t where, 
 int tnco_hip_contract_io_launches(tnco_hip_contract c, int64_t* counts) {
   if (!c || !counts) return fail(TNCO_HIP_EINVAL, "null argument.");
   counts[0] = c->io_launches[0], counts[1] = c->io_launches[1];
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_load_leaf_sets(tnco_hip_contract c, int64_t leaf, int64_t n_sets, const void* src, int32_t where,
+                                     int32_t src_dtype, int64_t ndim, const int64_t* dims, const int64_t* strides) {
+  if (!c || !src) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (leaf < 0 || leaf >= (int64_t)c->leaf_numel.size()) return fail(TNCO_HIP_EINVAL, "'leaf' is not a leaf of the plan.");
+  if (n_sets < 1) return fail(TNCO_HIP_EINVAL, "'n_sets' must be at least 1.");
+  if (const char* e = sets_refusal(c)) return fail(TNCO_HIP_EINVAL, e);
+  if (where != 0 && where != 1) return fail(TNCO_HIP_EINVAL, "'where' must be 0 (host) or 1 (device).");
+  const int64_t leaf_numel = c->leaf_numel[leaf];
+  if (n_sets > (INT64_MAX >> 8) / leaf_numel) return fail(TNCO_HIP_EINVAL, "'n_sets' is too large.");
+  const int64_t numel = n_sets * leaf_numel;
+  IoAxes ax;
+  bool contiguous = false;
+  if (const char* e = io_axes(ndim, dims, strides, numel, "dims do not multiply to the sets' elements.", &ax, &contiguous))
+    return fail(TNCO_HIP_EINVAL, e);
+  if (where == 0) {
+    if (src_dtype != c->dtype) return fail(TNCO_HIP_EINVAL, "a host stack must have the plan's dtype.");
+    if (strides) return fail(TNCO_HIP_EINVAL, "a host stack must be C-contiguous: 'strides' must be NULL.");
+  } else if (src_dtype < 0 || src_dtype > 3 || !io_widens(src_dtype, c->dtype)) {
+    return fail(TNCO_HIP_EINVAL, "'src_dtype' does not widen to the plan's dtype.");
+  }
+  CT_TRY(hipSetDevice(c->device));
+  if (n_sets > c->stack_cap[leaf]) {  // a larger stack: the new buffer first, so that a failure leaves the old one
+    const size_t bytes = (size_t)numel * c->elem;
+    size_t free_b = 0, total_b = 0;
+    CT_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (bytes > free_b)
+      return fail(TNCO_HIP_ERUNTIME, "the stack needs " + std::to_string(bytes) + " bytes of device memory, " +
+                                         std::to_string(free_b) + " are free.");
+    void* d_new = nullptr;
+    if (hipMalloc(&d_new, bytes) != hipSuccess) return fail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+    if (c->d_stack[leaf]) (void)hipFree(c->d_stack[leaf]);
+    c->bytes += (n_sets - c->stack_cap[leaf]) * leaf_numel * (int64_t)c->elem;
+    c->d_stack[leaf] = d_new, c->stack_cap[leaf] = n_sets, c->stack_sets[leaf] = 0;
+  }
+  if (where == 0) {
+    CT_TRY(hipMemcpyAsync(c->d_stack[leaf], src, (size_t)numel * c->elem, hipMemcpyHostToDevice, c->stream));
+  } else {
+    if (contiguous) {  // one axis; of the plan's dtype: the vector path
+      ax.nd = src_dtype == c->dtype ? -1 : 1;
+      ax.dim[0] = numel, ax.stride[0] = 1;
+    }
+    if (int rc = launch_ingest(c, c->d_stack[leaf], src, src_dtype, numel, ax)) return rc;
+  }
+  CT_TRY(hipStreamSynchronize(c->stream));
+  c->stack_sets[leaf] = n_sets;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_run_sets(tnco_hip_contract c, int64_t n_sets, int64_t group, void* out, int32_t where, int64_t ndim,
+                               const int64_t* dims, const int64_t* dst_strides) {
+  if (!c || !out) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (n_sets < 1) return fail(TNCO_HIP_EINVAL, "'n_sets' must be at least 1.");
+  if (group < 1 || group > MAX_PATH_GROUP) return fail(TNCO_HIP_EINVAL, "'group' must be from 1 to 1024.");
+  if (const char* e = sets_refusal(c)) return fail(TNCO_HIP_EINVAL, e);
+  if (where != 0 && where != 1) return fail(TNCO_HIP_EINVAL, "'where' must be 0 (host) or 1 (device).");
+  const int64_t A = c->stop - c->start, L = (int64_t)c->leaf_numel.size();
+  if (n_sets > (INT64_MAX >> 8) / std::max(c->out_numel, A)) return fail(TNCO_HIP_EINVAL, "'n_sets' is too large.");
+  IoAxes ax;
+  if (where == 1) {
+    if (ndim && !dst_strides) return fail(TNCO_HIP_EINVAL, "null argument.");
+    bool contiguous = false;
+    if (const char* e = io_axes(ndim, dims, dst_strides, n_sets * c->out_numel, "dims do not multiply to the sets' outputs.", &ax,
+                                &contiguous))
+      return fail(TNCO_HIP_EINVAL, e);
+    for (int k = 0; k < ax.nd; ++k)
+      if (ax.dim[k] > 1 && ax.stride[k] == 0) return fail(TNCO_HIP_EINVAL, "a destination stride is 0.");
+    if (contiguous) ax.nd = -1;
+  }
+  for (int64_t t = 0; t < L; ++t) {
+    if (c->stack_sets[t] && c->stack_sets[t] != n_sets)
+      return fail(TNCO_HIP_EINVAL, "leaf " + std::to_string(t) + " has a stack of " + std::to_string(c->stack_sets[t]) +
+                                       " sets loaded, not of " + std::to_string(n_sets) + ".");
+    if (!c->stack_sets[t] && !c->loaded[t]) return fail(TNCO_HIP_EINVAL, "leaf " + std::to_string(t) + " was never loaded.");
+  }
+  CT_TRY(hipSetDevice(c->device));
+  // Room for min(group, members) members and n_sets outputs; the tables once.  The new buffers first: a handle that this
+  // call fails on stays as it was.  (The arenas and the staging hold nothing between runs.)
+  const int64_t G = std::min(group, n_sets * A);
+  const size_t arena = (size_t)c->arena_elems * c->elem, block = (size_t)c->block_numel * c->out_elem;
+  const size_t outb = (size_t)c->out_numel * c->out_elem, tables = (size_t)L * (sizeof(void*) + sizeof(int64_t));
+  const bool more_members = G > c->path_cap, more_out = n_sets > c->sets_out_cap, new_tables = !c->d_sets_tables;
+  const size_t need = (more_members ? (size_t)G * (arena + block) : 0) + (more_out ? (size_t)n_sets * outb : 0) + (new_tables ? tables : 0);
+  if (need) {
+    CT_TRY(hipStreamSynchronize(c->stream));
+    size_t free_b = 0, total_b = 0;
+    CT_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b)
+      return fail(TNCO_HIP_ERUNTIME, "the leaf sets need " + std::to_string(need) + " bytes of device memory, " +
+                                         std::to_string(free_b) + " are free.");
+    void *d_arena = nullptr, *d_stage = nullptr, *d_out = nullptr, *d_tab = nullptr;
+    if ((more_members && (hipMalloc(&d_arena, std::max<size_t>((size_t)G * arena, c->elem)) != hipSuccess ||
+                          hipMalloc(&d_stage, (size_t)G * block) != hipSuccess)) ||
+        (more_out && hipMalloc(&d_out, (size_t)n_sets * outb) != hipSuccess) ||
+        (new_tables && hipMalloc(&d_tab, tables) != hipSuccess)) {
+      for (void* p : {d_arena, d_stage, d_out, d_tab})
+        if (p) (void)hipFree(p);
+      return fail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+    }
+    if (more_members) {
+      (void)hipFree(c->d_arena), (void)hipFree(c->d_path_stage);
+      c->bytes += (G - c->path_cap) * (int64_t)(arena + block);
+      c->d_arena = d_arena, c->d_path_stage = d_stage, c->path_cap = G;
+    }
+    if (more_out) {
+      if (c->d_sets_out) (void)hipFree(c->d_sets_out);
+      c->bytes += (n_sets - c->sets_out_cap) * (int64_t)outb;
+      c->d_sets_out = d_out, c->sets_out_cap = n_sets;
+    }
+    if (new_tables) c->d_sets_tables = (char*)d_tab, c->bytes += (int64_t)tables;
+  }
+  static_assert(sizeof(void*) == sizeof(int64_t), "the pointers and the strides share one table");
+  c->sets_image.assign(2 * L, 0);
+  for (int64_t t = 0; t < L; ++t) {
+    c->sets_image[2 * t] = (int64_t)(uintptr_t)(c->stack_sets[t] ? c->d_stack[t] : (void*)(c->d_leaves + c->leaf_off[t] * c->elem));
+    c->sets_image[2 * t + 1] = c->stack_sets[t] ? c->leaf_numel[t] : 0;
+  }
+  CT_TRY(hipMemcpyAsync(c->d_sets_tables, c->sets_image.data(), 2 * L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  CT_TRY(hipMemsetAsync(c->d_sets_out, 0, (size_t)n_sets * outb, c->stream));
+  c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->matrix_launches = c->last_member = 0;
+  c->path_launches[0] = c->path_launches[1] = c->acc_launches[0] = c->acc_launches[1] = 0;
+  c->sets_launches[0] = c->sets_launches[1] = 0;
+  std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
+  std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
+  std::fill(std::begin(c->by_ix), std::end(c->by_ix), 0);
+  CT_TRY(hipEventRecord(c->ev[0], c->stream));
+  if (int rc = c->dtype == 0   ? run_sets<float>(c, n_sets, G)
+               : c->dtype == 1 ? run_sets<double>(c, n_sets, G)
+               : c->dtype == 2 ? run_sets<cplx<float>>(c, n_sets, G)
+                               : run_sets<cplx<double>>(c, n_sets, G))
+    return rc;
+  CT_TRY(hipEventRecord(c->ev[1], c->stream));
+  if (where == 1) {
+    if (int rc = launch_emit(c, out, ax, n_sets)) return rc;
+  } else {
+    CT_TRY(hipMemcpyAsync(out, c->d_sets_out, (size_t)n_sets * outb, hipMemcpyDeviceToHost, c->stream));
+  }
+  CT_TRY(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  CT_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+  c->device_ns = (int64_t)((double)ms * 1e6);
+  std::fill(c->stack_sets.begin(), c->stack_sets.end(), 0);  // the stacks were for this run
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_sets_launches(tnco_hip_contract c, int64_t* counts) {
+  if (!c || !counts) return fail(TNCO_HIP_EINVAL, "null argument.");
+  counts[0] = c->sets_launches[0], counts[1] = c->sets_launches[1];
   return TNCO_HIP_OK;
 }
 
@@ -1797,7 +2019,7 @@ int tnco_hip_contract_set_path_kernel(tnco_hip_contract c, int64_t group) {
   if (c->d_arena) (void)hipFree(c->d_arena);
   c->d_arena = d_arena, c->d_path_stage = d_stage, c->d_path_tables = (int64_t*)d_tab;
   drop_accumulate_stage(c);
-  c->path_group = group, c->bytes = bytes;
+  c->path_group = c->path_cap = group, c->bytes = bytes;
   return TNCO_HIP_OK;
 }
 
@@ -1988,7 +2210,9 @@ void tnco_hip_contract_destroy(tnco_hip_contract c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_leaves, c->d_arena, c->d_out, (void*)c->d_tables, (void*)c->d_leaf_ptrs, (void*)c->d_row_maps,
                   (void*)c->d_exps, c->d_batch_out, c->d_path_stage, (void*)c->d_path_tables, (void*)c->d_ind, c->d_acc,
-                  c->d_acc_stage})
+                  c->d_acc_stage, c->d_sets_out, (void*)c->d_sets_tables})
+    if (p) (void)hipFree(p);
+  for (void* p : c->d_stack)
     if (p) (void)hipFree(p);
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);

@@ -26,7 +26,9 @@ Sycamore leg with accumulate=None and "float64", unbatched, with slice_batch=64 
 and the error of each against the same plan in complex128, in one process); the resident use (`--resident`: wall time
 per call of contract() and of one Contractor run with numpy arrays, with every leaf bound from numpy, and with every leaf
 bound from torch tensors and the result written into a tensor, on the sliced Sycamore leg under path_kernel=1024 and on
-the bandwidth-bound step of the indirect leg, in one process).  Engine figures are its
+the bandwidth-bound step of the indirect leg, in one process); leaf sets (`--many`: Contractor.run_many against the loop of
+Contractor.run() over the same sets on the same Contractor, wall time per set, on the sliced Sycamore leg under
+path_kernel=1024: 1024 sets of one assignment each, and 8 sets of every assignment, in one process).  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device); the resident leg measures what that leaves out.
 """
@@ -656,6 +658,80 @@ def resident(lines, depth, max_width, max_slices, reps=5):
     lines.extend(notes)
 
 
+def many(lines, depth, max_width, max_slices, reps=5, stacked=8):
+    """Contractor.run_many against the loop of Contractor.run() over the same leaf sets on the same Contractor, which is
+    what there is without it: the sliced Sycamore amplitude of the path-kernel leg, complex64, path_kernel=1024, every
+    leaf a torch tensor on the device, the results written into one tensor on the device.  The stacked leaves are the
+    `stacked` leaves of fewest elements (ties by leaf number), the others are bound.  Wall seconds (perf_counter, the
+    device synchronised on both sides), the minimum of `reps` calls after a warm-up and their spread, both sides of a
+    row pair in this process.  Two legs: (a) one assignment per set, 1024 sets -- bound by launches and by the calls;
+    (b) every assignment, 8 sets -- bound by the device."""
+    lines.append("")
+    tn, r0, leaves = _sliced_sycamore(depth, max_width)
+    shapes = [a.shape for a in leaves]
+    p = ctr.plan(r0.path, tn.ts_inds, shapes, tn.output_inds, slices=r0.slices)
+    m = min(p.n_slices, max_slices)
+    order = sorted(range(len(leaves)), key=lambda t: (leaves[t].size, t))[:stacked]
+    lines.append(f"## run_many, sliced Sycamore-53 amplitude, depth {depth}, complex64, max_width {max_width}, cost {r0.cost}, "
+                 f"{len(leaves)} leaves, {len(r0.path)} steps, path_kernel=1024; stacked: the {len(order)} leaves of fewest elements "
+                 f"{order} ({sum(leaves[t].size for t in order)} elements per set), the others bound; torch tensors in, one "
+                 f"tensor out; wall seconds (perf_counter, device synchronised on both sides), the minimum of {reps} calls after a "
+                 "warm-up, spread = (max - min) / min; a loop row is R calls of run(); both rows of a leg in one process")
+    lines.append(f"{'leg':>34} {'setting':>24} {'wall s':>10} {'spread':>7} {'us / set':>10} {'loop / this':>11} {'launches':>9} "
+                 f"{'peak bytes':>12} {'same bytes':>10}")
+    rng = np.random.RandomState(3)
+    notes = []
+    for leg, rng_, R in (("(a) assignments [0, 1), R = 1024", (0, 1), 1024), (f"(b) assignments [0, {m}), R = 8", (0, m), 8)):
+        stacks = {t: torch.from_numpy(np.stack([leaves[t] * np.complex64(np.exp(2j * np.pi * rng.uniform())) for _ in range(R)])).cuda()
+                  for t in order}
+        with ctr.Contractor(r0.path, tn.ts_inds, shapes, tn.output_inds, dtype=np.complex64, slices=r0.slices, slice_range=rng_,
+                            path_kernel=1024) as c:
+            c.bind({t: torch.from_numpy(a).cuda() for t, a in enumerate(leaves) if t not in stacks})
+            outs = [torch.zeros((R,) + tuple(c.plan.shape), dtype=torch.complex64, device="cuda") for _ in range(2)]
+            seen = {}
+
+            def loop():
+                n = 0
+                for i in range(R):
+                    r = c.run({t: s[i] for t, s in stacks.items()}, out=outs[0][i])
+                    n += r.launches
+                seen.setdefault("loop", (n, r.peak_device_bytes))  # (the memory before run_many grows the handle)
+
+            def batched():
+                r = c.run_many(stacks, group=1024, out=outs[1])
+                seen["many"] = (r.launches, r.peak_device_bytes)
+
+            rows = []
+            for name, key, call in ((f"{R} x run()", "loop", loop), ("run_many(group=1024)", "many", batched)):
+                call()  # warm-up
+                times = []
+                for _ in range(reps):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    call()
+                    torch.cuda.synchronize()
+                    times.append(time.perf_counter() - t0)
+                rows.append((name, min(times), (max(times) - min(times)) / min(times), seen[key]))
+            same = bool(torch.equal(torch.view_as_real(outs[0]), torch.view_as_real(outs[1])))
+        (_, t_loop, s_loop, _), (_, t_many, s_many, _) = rows
+        for name, t, spread, (launches, peak) in rows:
+            lines.append(f"{leg:>34} {name:>24} {t:10.6f} {spread:7.3f} {t / R * 1e6:10.2f} {t_loop / t:11.2f} {launches:9d} "
+                         f"{peak:12d} {str(same):>10}")
+            print(lines[-1], flush=True)
+        wider = max(s_loop, s_many)
+        if t_many * (1 + wider) < t_loop:
+            notes.append(f"  {leg}: run_many is faster than the loop by more than the larger spread ({wider:.3f})")
+        elif t_many > t_loop * (1 + wider):
+            notes.append(f"  {leg}: run_many is SLOWER than the loop by more than the larger spread ({wider:.3f})")
+        else:
+            notes.append(f"  {leg}: run_many and the loop are within the larger spread ({wider:.3f}) of each other")
+        if not same:
+            notes.append(f"  {leg}: THE BYTES OF run_many DIFFER FROM THE LOOP'S")
+        del stacks, outs
+    lines.extend(notes)
+    print("\n".join(notes), flush=True)
+
+
 def compute(lines, n, depth, max_width, max_slices):
     """The compute mode against the plain engine in the same process: the large square step with compute=None (the tiled
     LDS kernel, the yardstick), compute="bf16x3" (ct_split_tiled_kernel) and storage="bfloat16" (ct_mfma_tiled_kernel), and
@@ -835,15 +911,19 @@ def main():
     ap.add_argument("--reuse", action="store_true", help="only the reuse leg, appended to --out")
     ap.add_argument("--accumulate", action="store_true", help="only the wide-accumulation leg, appended to --out")
     ap.add_argument("--resident", action="store_true", help="only the resident (Contractor) leg, appended to --out")
+    ap.add_argument("--many", action="store_true", help="only the run_many leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect + a.reuse + a.accumulate + a.resident > 1:
-        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix, --indirect, --reuse, --accumulate and --resident each "
+    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect + a.reuse + a.accumulate + a.resident + a.many > 1:
+        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix, --indirect, --reuse, --accumulate, --resident and --many each "
                  "append one leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect or a.reuse or a.accumulate or a.resident:  # (the other legs' sections stay as they are)
-        if a.resident:
+    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect or a.reuse or a.accumulate or a.resident or a.many:  # (the other legs' sections stay as they are)
+        if a.many:
+            lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
+            many(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+        elif a.resident:
             lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
             resident(lines, a.depth, a.max_width, min(a.max_slices, 2048))
         elif a.accumulate:
@@ -893,6 +973,7 @@ def main():
     reuse(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     accumulate(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     resident(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+    many(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
