@@ -755,6 +755,63 @@ int tnco_hip_contract_run_sets(tnco_hip_contract h, int64_t n_sets, int64_t grou
 /* counts[2]: the last run's launches of ct_sets_path_kernel and of ct_sets_reduce_kernel (one each per group; 0, 0 after
  * any other run).  stats[1] is their sum, and every other launch counter is 0 after tnco_hip_contract_run_sets */
 int tnco_hip_contract_sets_launches(tnco_hip_contract h, int64_t* counts);
+/* Walkers: the state of a gate-by-gate circuit sampler on the device (csrc/contract_walk.h).  A walkers object is the
+ * library's own and belongs to no contraction handle: `bits`, a uint8 table [n_qubits][n_walkers] (qubit-major), all 0
+ * at creation; a `dead` flag per walker, 0 at creation; a 64-bit seed.  Every entry point synchronises before it
+ * returns. Each refusal below has a text of its own, comes before any allocation and leaves the object as it was.
+ *
+ * create: EINVAL for a null pointer, n_walkers < 1, n_qubits < 1, more than 2^40 bits, a device that is not there;
+ * ERUNTIME when the table exceeds the device's free memory.  destroy: NULL is fine. read: the table
+ * [n_qubits][n_walkers] into bits_out and the flags [n_walkers] into dead_out, host memory; one of the two may be
+ * NULL.  write: the table from bits_in, host memory; the flags stay; EINVAL for a byte that is not 0 or 1. reset:
+ * every bit and every flag 0. */
+typedef struct tnco_hip_walkers_s* tnco_hip_walkers;
+int tnco_hip_walkers_create(int32_t device, int64_t n_walkers, int64_t n_qubits, uint64_t seed, tnco_hip_walkers* out);
+void tnco_hip_walkers_destroy(tnco_hip_walkers w);
+int tnco_hip_walkers_read(tnco_hip_walkers w, uint8_t* bits_out, uint8_t* dead_out);
+int tnco_hip_walkers_write(tnco_hip_walkers w, const uint8_t* bits_in);
+int tnco_hip_walkers_reset(tnco_hip_walkers w);
+/* A classical gate on k <= 8 qubits (ct_walk_permute_kernel, one lane per walker): with v the number that a walker's
+ * bits of qubits[0..k) spell, the first qubit the most significant, those bits become table[v].  EINVAL: a null
+ * pointer; k outside [1, 8]; a qubit outside [0, n_qubits) or named twice; a table that is no permutation of 0 .. 2^k
+ * - 1. */
+int tnco_hip_walkers_permute(tnco_hip_walkers w, int64_t k, const int64_t* qubits, const uint8_t* table);
+/* Indexed leaves.  load_leaf_versions: tnco_hip_contract_load_leaf_sets for the versions of a leaf,
+ * [n_versions][leaf_numel] under its rules of where, src_dtype, ndim, dims and strides, into a buffer of the handle's
+ * own apart from the leaf's single buffer and from its stack; n_versions must be 2.  The versions stay until they are
+ * loaded again or the handle is destroyed: a run does not use them up.  stats[2] counts the buffer.  EINVAL as
+ * load_leaf_sets, and n_versions != 2.
+ *
+ * run_walkers: tnco_hip_contract_run_sets with n_sets = n_walkers and no stacks: walker i reads leaf t with
+ * leaf_qubit[t] = q >= 0 at the version bits[q][i] of its two versions, which must be loaded, and every other leaf
+ * (leaf_qubit[t] = -1) from its single buffer, which must be loaded (ct_walk_path_kernel, then ct_sets_reduce_kernel;
+ * min(group, n_walkers A) members per launch).  Output i is bit for bit that of tnco_hip_contract_run_loaded over the
+ * leaves walker i selects.  The n_walkers outputs stay in the handle's set-output buffer, [n_walkers][out_numel],
+ * until the handle's next run of any kind; nothing is copied to the caller.  Where no leaf is indexed no output
+ * depends on the walker: one set is run (n_sets = 1 in every count), and its one output serves every walker.  Reserves
+ * what run_sets reserves, and a table of three words per leaf (ERUNTIME when they exceed the device's free memory; the
+ * handle then stays as it was).  stats and tnco_hip_contract_sets_launches count as after run_sets.  EINVAL, the
+ * handle and the walkers left as they were: a null pointer; a group outside [1, 1024]; what run_sets refuses of the
+ * handle; walkers on another device than the handle's; too many walkers for 64-bit offsets; a leaf_qubit outside [-1,
+ * n_qubits) (the text names leaf and qubit); an indexed leaf without versions; another leaf that was never loaded.
+ *
+ * walkers_output: the outputs of the last run, [n_walkers][out_numel] raw output buffers ([1][out_numel] where no leaf
+ * was indexed), into host memory: what a test or a caller that does not choose on the device reads.  EINVAL unless the
+ * handle's last run was a run_walkers over `w`. */
+int tnco_hip_contract_load_leaf_versions(tnco_hip_contract h, int64_t leaf, int64_t n_versions, const void* src,
+                                         int32_t where, int32_t src_dtype, int64_t ndim, const int64_t* dims,
+                                         const int64_t* strides);
+int tnco_hip_contract_run_walkers(tnco_hip_contract h, tnco_hip_walkers w, const int64_t* leaf_qubit, int64_t group);
+int tnco_hip_contract_walkers_output(tnco_hip_contract h, tnco_hip_walkers w, void* out);
+/* The new bit of one qubit for every walker (ct_walk_choose_kernel, one lane per walker).  The handle's last run must
+ * be a run_walkers over `w` whose output holds exactly 2 elements, the amplitudes a0, a1 of the qubit's two values.
+ * In float64, every operation rounded on its own and none fused: p = re re + im im with the parts widened exactly (a a
+ * for a real dtype), s = p0 + p1.  u comes from Philox4x32-10 with key (seed lo, seed hi) and counter (i lo, i hi,
+ * step, 0) for walker i: u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53 of its first two output words.  bits[qubit][i] = (u s
+ * < p1).  Where s is 0 or not finite the bit becomes 0 and dead[i] is set.  No state is kept between draws: the choice
+ * is a function of (seed, i, step, a0, a1).  EINVAL: a null pointer; a last run that was not a run_walkers over `w`;
+ * an output of another size than 2; a qubit outside [0, n_qubits); a step outside [0, 2^32). */
+int tnco_hip_walkers_choose(tnco_hip_walkers w, tnco_hip_contract h, int64_t qubit, int64_t step);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

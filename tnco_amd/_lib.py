@@ -98,6 +98,9 @@ EXPORTS = [
     "tnco_hip_contract_indirect_launches", "tnco_hip_contract_set_accumulate", "tnco_hip_contract_accumulate_launches",
     "tnco_hip_contract_load_leaf", "tnco_hip_contract_run_loaded", "tnco_hip_contract_io_launches",
     "tnco_hip_contract_load_leaf_sets", "tnco_hip_contract_run_sets", "tnco_hip_contract_sets_launches",
+    "tnco_hip_contract_load_leaf_versions", "tnco_hip_contract_run_walkers", "tnco_hip_contract_walkers_output",
+    "tnco_hip_walkers_create", "tnco_hip_walkers_destroy", "tnco_hip_walkers_read", "tnco_hip_walkers_write",
+    "tnco_hip_walkers_reset", "tnco_hip_walkers_permute", "tnco_hip_walkers_choose",
     "tnco_hip_contract_destroy",
     "tnco_hip_device_name", "tnco_hip_device_count", "tnco_hip_last_error", "tnco_hip_version",
 ]
@@ -225,6 +228,17 @@ def load() -> C.CDLL:
     L.tnco_hip_contract_load_leaf_sets.argtypes = [vp, i64, i64, vp, i32, i32, i64, vp, vp]
     L.tnco_hip_contract_run_sets.argtypes = [vp, i64, i64, vp, i32, i64, vp, vp]
     L.tnco_hip_contract_sets_launches.argtypes = [vp, vp]
+    L.tnco_hip_contract_load_leaf_versions.argtypes = [vp, i64, i64, vp, i32, i32, i64, vp, vp]
+    L.tnco_hip_contract_run_walkers.argtypes = [vp, vp, vp, i64]
+    L.tnco_hip_contract_walkers_output.argtypes = [vp, vp, vp]
+    L.tnco_hip_walkers_create.argtypes = [i32, i64, i64, C.c_uint64, C.POINTER(vp)]
+    L.tnco_hip_walkers_destroy.argtypes = [vp]
+    L.tnco_hip_walkers_destroy.restype = None
+    L.tnco_hip_walkers_read.argtypes = [vp, vp, vp]
+    L.tnco_hip_walkers_write.argtypes = [vp, vp]
+    L.tnco_hip_walkers_reset.argtypes = [vp]
+    L.tnco_hip_walkers_permute.argtypes = [vp, i64, vp, vp]
+    L.tnco_hip_walkers_choose.argtypes = [vp, vp, i64, i64]
     L.tnco_hip_contract_destroy.argtypes = [vp]
     L.tnco_hip_contract_destroy.restype = None
     L.tnco_hip_device_name.argtypes = [C.c_int, vp, C.c_int]

@@ -199,6 +199,19 @@ the ManyResult is byte for byte `run` of leaf set i, whatever the group; blocks 
 in every set.  A stack lives in a device buffer of its own: a bound leaf given as a stack stays bound and untouched.
 `many_bytes(R, group)` is the device memory the handle holds after such a call, term by term; what a call grew stays
 until a larger call or close().
+
+Walkers: the state of a gate-by-gate circuit sampler (tnco_amd/sampling.py) is a table of bits, R walkers x n qubits, and
+it lives on the device in a `Walkers` object (csrc/contract_walk.h).  A leaf that depends on one of a walker's bits -- a
+one-hot vector -- is bound once as its two versions, `Contractor.bind_versions({leaf: array of shape (2,) + leaf shape})`,
+and `Contractor.run_walkers(walkers, {leaf: qubit})` is `run_many` over R sets in which walker i reads version
+bits[i, qubit] of such a leaf and every other leaf where it is bound: nothing is stacked, nothing is reloaded, and the R
+outputs stay on the device (`ManyResult.array` is None; `walker_outputs` copies them out, byte for byte those of
+`run_many` over the explicit stacks).  Where the plan's output has 2 elements, the amplitudes of one qubit's two values,
+`Contractor.choose(walkers, qubit, step)` draws the qubit's new bit for every walker: p = |a|^2 in float64, u from
+Philox4x32-10 with key (seed lo, seed hi) and counter (i lo, i hi, step, 0), u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53,
+bit = (u (p0 + p1) < p1); a walker whose p0 + p1 is 0 or not finite gets the bit 0 and is flagged dead.  A choice is a
+function of (seed, walker, step, amplitudes): no generator state is kept.  `Walkers.permute(qubits, table)` is a classical
+gate: the bits of up to 8 qubits, the first the most significant, become table[their value].
 """
 from __future__ import annotations
 
@@ -214,7 +227,7 @@ from .app import tn as tnmod
 __all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
            "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage", "SCALINGS", "scale_exponent", "scale_to_storage",
            "MAX_SLICE_BATCH", "COMPUTES", "split_bf16", "MAX_PATH_KERNEL", "MAX_PATH_STEP_MACS", "INDIRECT_KERNEL_PATHS",
-           "ACCUMULATES", "Contractor", "merge_axes", "check_extent", "ManyResult"]
+           "ACCUMULATES", "Contractor", "merge_axes", "check_extent", "ManyResult", "Walkers", "MAX_PERMUTE_QUBITS"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -233,6 +246,7 @@ MAX_PATH_KERNEL = 1024  # path kernel: assignments per launch at most (csrc/cont
 # path kernel: multiply-adds (H M N K) of one step at most -- one workgroup runs it.  A guard against a step that would
 # hold one compute unit of a shared card for long, not a tuned threshold (csrc/contract_path.h MAX_PATH_STEP_MACS)
 MAX_PATH_STEP_MACS = 1 << 24
+MAX_PERMUTE_QUBITS = 8  # qubits of one Walkers.permute at the most (csrc/contract_walk.h WALK_MAX_PERMUTE)
 
 # operand / destination kinds and table widths: include/tnco_hip.h (tnco_hip_contract_desc)
 LEAF, ARENA, OUT = 0, 1, 2
@@ -296,6 +310,7 @@ class ManyResult:
     """What `Contractor.run_many` returns: the results of R leaf sets of one plan."""
     inds: tuple  # ("set",) + Plan.inds
     array: object  # (R,) + Plan.shape: array[i] is byte for byte `run` of leaf set i; numpy array or torch tensor
+    #                (run_walkers: None, the outputs stay on the device)
     sets: int  # R
     group: int  # members (set, assignment) per launch, the effective value: min(what was asked for, R x assignments)
     macs: int  # multiply-adds launched: R times a run's
@@ -1595,7 +1610,9 @@ class Contractor:
         self._bound = set()
         self._exps = np.zeros(len(shapes), np.int32)  # scaling: the exponents of the leaves the handle holds
         # run_many: what its calls made the handle reserve (sets per stacked leaf, members, outputs), the leaves last stacked
-        self._many = dict(stacks={}, members=0, out=0, last=())
+        self._many = dict(stacks={}, members=0, out=0, last=(), walked=False)
+        self._versions = set()  # bind_versions: the leaves whose two versions the handle holds
+        self._walked = None  # run_walkers: the Walkers of the handle's last run, if that was one
 
     def __enter__(self):
         return self
@@ -1645,6 +1662,7 @@ class Contractor:
         self._check_open()
         p = self.plan
         given, torch_in = self._check_arrays({} if arrays is None else arrays)
+        self._walked = None
         torch_out = _is_tensor(out)
         if torch_out and self._host_only:
             raise NotImplementedError(f"a torch tensor as 'out' is not supported with '{self._host_only}'.")
@@ -1707,6 +1725,7 @@ class Contractor:
         if not isinstance(stacks, dict) or not stacks:
             raise ValueError("'stacks' must be a dict {leaf number: array} with at least one leaf.")
         given, torch_in = self._check_arrays(stacks)
+        self._walked = None
         sets, ready = self._prepare_stacks(given, torch_in)
         missing = [t for t in range(len(self._shapes)) if t not in self._bound and t not in ready]
         if missing:
@@ -1752,12 +1771,133 @@ class Contractor:
         return ManyResult(("set",) + tuple(p.inds), array, sets, min(group, members), int(stats[0]), int(stats[1]),
                           (int(counts[0]), int(counts[1])), int(stats[2]), float(stats[3]) * 1e-9)
 
+    def bind_versions(self, versions) -> None:
+        """Loads the two versions of the leaves {leaf number: array of shape (2,) + the leaf's shape} now; they stay until
+        bound again or until close(), apart from what `bind` holds of the leaf.  `run_walkers` reads version b of such a
+        leaf for a walker whose bit of the leaf's qubit is b.  Arrays as `bind` takes them, numpy or torch.  It needs
+        `path_kernel=` and a plan with steps, and is not supported with `accumulate=`."""
+        from . import _lib
+        self._check_open()
+        self._check_many(None, "bind_versions")
+        if not isinstance(versions, dict) or not versions:
+            raise ValueError("'versions' must be a dict {leaf number: array} with at least one leaf.")
+        given, _ = self._check_arrays(versions, one_kind=False)
+        for t in sorted(given):
+            shape = tuple(given[t].shape) if _is_tensor(given[t]) else np.shape(given[t])
+            if shape != (2,) + self._shapes[t]:
+                raise ValueError(f"the versions of leaf {t} have the shape {shape}, not (2,) + the leaf's {self._shapes[t]}.")
+        kinds = [(kind, self._prepare_stacks({t: a for t, a in given.items() if _is_tensor(a) == kind}, kind)[1])
+                 for kind in (False, True)]
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        i64 = lambda v: ptr(np.array(v, np.int64)) if len(v) else None  # noqa: E731
+        for kind, ready in kinds:
+            if not ready:
+                continue
+            L, h = self._handle()
+            if kind:
+                import torch
+                torch.cuda.synchronize(self.device)
+            for t, (a, code, dims, strides) in ready.items():
+                self._versions.discard(t)
+                src = C.c_void_p(a.data_ptr()) if kind else ptr(a)
+                _lib.check(L.tnco_hip_contract_load_leaf_versions(h, t, 2, src, int(kind), code, len(dims), i64(dims), i64(strides)))
+                self._versions.add(t)
+
+    def _check_walk(self, walkers) -> None:
+        """What run_walkers and choose refuse of `walkers`."""
+        if not isinstance(walkers, Walkers):
+            raise TypeError(f"'walkers' must be a Walkers object, not {type(walkers).__name__}.")
+        walkers._check_open()
+        if walkers.device != self.device:
+            raise ValueError(f"the walkers are on device {walkers.device}, the Contractor on device {self.device}.")
+
+    def run_walkers(self, walkers, leaf_qubit, *, group=None) -> ManyResult:
+        """`run_many` over the walkers of `walkers` as sets: `leaf_qubit` is {leaf number: qubit}; walker i reads such a
+        leaf at version walkers.bits[i, qubit] of the two that `bind_versions` loaded, and every other leaf where it is
+        bound.  The outputs stay on the device for `choose` (or `walker_outputs`): `array` of the result is None.  With an
+        empty `leaf_qubit` no output depends on the walker: one set is run for all of them (`sets` of the result is 1).
+        `group` as in `run_many`.  Refuses what `run_many` refuses of the Contractor."""
+        from . import _lib
+        self._check_open()
+        p, n = self.plan, len(self._shapes)
+        group = self._check_many(group, "run_walkers")
+        self._check_walk(walkers)
+        if not isinstance(leaf_qubit, dict):
+            raise ValueError("'leaf_qubit' must be a dict {leaf number: qubit}.")
+        table = np.full(max(n, 1), -1, np.int64)
+        for t, q in leaf_qubit.items():
+            if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t < n:
+                raise ValueError(f"{t!r} is not a leaf of the plan (0 to {n - 1}).")
+            if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 0 <= q < walkers.n_qubits:
+                raise ValueError(f"{q!r} is not a qubit of the walkers (0 to {walkers.n_qubits - 1}).")
+            if int(t) not in self._versions:
+                raise ValueError(f"leaf {int(t)} has no versions: call bind_versions first.")
+            table[int(t)] = int(q)
+        missing = [t for t in range(n) if table[t] < 0 and t not in self._bound]
+        if missing:
+            raise ValueError(f"leaf {missing[0]} is neither bound nor indexed by a qubit.")
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        L, h = self._handle()
+        self._walked = None
+        _lib.check(L.tnco_hip_contract_run_walkers(h, walkers._handle(), ptr(table), group))
+        self._walked = walkers
+        sets = walkers.n_walkers if leaf_qubit else 1  # (no leaf indexed: one output serves every walker, one set is run)
+        caps = self._many  # (what the handle reserved: many_bytes; the leaves last stacked stay those of the last run_many)
+        caps["members"] = max(caps["members"], min(group, sets * (p.slice_range[1] - p.slice_range[0])))
+        caps["out"] = max(caps["out"], sets)
+        caps["walked"], self._walked_sets = True, sets
+        stats, counts = np.zeros(4, np.int64), np.zeros(2, np.int64)
+        _lib.check(L.tnco_hip_contract_stats(h, ptr(stats)))
+        _lib.check(L.tnco_hip_contract_sets_launches(h, ptr(counts)))
+        members = sets * (p.slice_range[1] - p.slice_range[0])
+        return ManyResult(("set",) + tuple(p.inds), None, sets, min(group, members), int(stats[0]), int(stats[1]),
+                          (int(counts[0]), int(counts[1])), int(stats[2]), float(stats[3]) * 1e-9)
+
+    def walker_outputs(self, walkers) -> np.ndarray:
+        """The outputs that the last `run_walkers` over `walkers` left on the device, as `run_many` lays its array out:
+        (walkers,) + plan.shape.  A copy to the host: for tests and for callers that do not `choose` on the device."""
+        from . import _lib
+        self._check_open()
+        self._check_walk(walkers)
+        if self._walked is not walkers:
+            raise ValueError("the last run of the Contractor was not a 'run_walkers' over these walkers.")
+        p, sets = self.plan, self._walked_sets
+        L, h = self._handle()
+        staging = np.empty((sets, p.out_numel), p.dtype)
+        _lib.check(L.tnco_hip_contract_walkers_output(h, walkers._handle(), staging.ctypes.data_as(C.c_void_p)))
+        rest = tuple(x for x in p.inds if x not in set(p.slice_inds))
+        held = p.block_inds + rest
+        at = [p.inds.index(x) for x in held]
+        array = staging.reshape((sets,) + tuple(p.shape[q] for q in at))
+        array = array.transpose([0] + [1 + held.index(x) for x in p.inds])
+        return np.broadcast_to(array, (walkers.n_walkers,) + array.shape[1:]).copy(order="C")
+
+    def choose(self, walkers, qubit, step) -> None:
+        """Draws the new bit of `qubit` for every walker from the two amplitudes that the last `run_walkers` over
+        `walkers` left (module docstring, Walkers): the plan's output must hold exactly 2 elements.  `step` (0 to
+        2^32 - 1) numbers the draw: with the walkers' seed and the walker's number it fixes the uniform."""
+        from . import _lib
+        self._check_open()
+        self._check_many(None, "choose")
+        self._check_walk(walkers)
+        if self.plan.out_numel != 2:
+            raise ValueError(f"the output of the plan holds {self.plan.out_numel} elements, not the 2 amplitudes of a choice.")
+        if isinstance(qubit, bool) or not isinstance(qubit, (int, np.integer)) or not 0 <= qubit < walkers.n_qubits:
+            raise ValueError(f"{qubit!r} is not a qubit of the walkers (0 to {walkers.n_qubits - 1}).")
+        if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 0 <= step < 2 ** 32:
+            raise ValueError("'step' must be an integer from 0 to 2^32 - 1.")
+        if self._walked is not walkers:
+            raise ValueError("the last run of the Contractor was not a 'run_walkers' over these walkers.")
+        L, h = self._handle()
+        _lib.check(L.tnco_hip_walkers_choose(walkers._handle(), h, int(qubit), int(step)))
+
     def many_bytes(self, n_sets, group=None, leaves=None) -> int:
         """The device bytes the handle holds after `run_many` of `n_sets` sets with that `group` and stacks of the leaves
         `leaves` (None: those of the last `run_many`, none before the first), `peak_device_bytes` of its result: what the
         handle holds without the call; a stack of n_sets versions per stacked leaf; the arenas and staging blocks that
         min(group, n_sets x assignments) members need beyond `Plan.path_kernel`; n_sets outputs; a pointer and a stride
-        per leaf.  What an earlier call grew stays until close(): each term is the largest so far."""
+        per leaf.  What an earlier call grew stays until close(): each term is the largest so far.  The walkers' terms
+        are part of it: two versions per leaf of `bind_versions`, and three words per leaf once `run_walkers` has run."""
         self._check_open()
         p = self.plan
         group = self._check_many(group)
@@ -1783,19 +1923,21 @@ class Contractor:
         members = max(caps["members"], min(group, int(n_sets) * A))
         grown = item * max(members - p.path_kernel, 0) * (p.arena_elems + block)
         outputs = item * max(caps["out"], int(n_sets)) * p.out_numel
-        return held + stacks + grown + outputs + 16 * n
+        # (walkers: two versions per leaf of bind_versions; three words per leaf once run_walkers has run)
+        walked = item * 2 * sum(int(p.leaf_numel[t]) for t in self._versions) + (24 * n if caps["walked"] else 0)
+        return held + stacks + grown + outputs + 16 * n + walked
 
     # -- the checks; none of them touches the device through this library
 
-    def _check_many(self, group) -> int:
-        """What run_many refuses of the Contractor and of `group`; the group as a number."""
+    def _check_many(self, group, name="run_many") -> int:
+        """What run_many (or its kin `name`) refuses of the Contractor and of `group`; the group as a number."""
         p = self.plan
         if p.path_kernel is None:
-            raise NotImplementedError("'run_many' needs a Contractor with 'path_kernel'.")
+            raise NotImplementedError(f"'{name}' needs a Contractor with 'path_kernel'.")
         if p.accumulate is not None:
-            raise NotImplementedError("'accumulate' is not supported with 'run_many'.")
+            raise NotImplementedError(f"'accumulate' is not supported with '{name}'.")
         if not len(p.steps):
-            raise NotImplementedError("'run_many' needs a plan with steps.")
+            raise NotImplementedError(f"'{name}' needs a plan with steps.")
         if group is None:
             return MAX_PATH_KERNEL
         if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or not 1 <= group <= MAX_PATH_KERNEL:
@@ -1971,3 +2113,120 @@ class Contractor:
             _lib.check(L.tnco_hip_contract_load_leaf(h, t, C.c_void_p(a.data_ptr()), 1, code, len(dims),
                                                      d.ctypes.data_as(C.c_void_p) if len(dims) else None,
                                                      s.ctypes.data_as(C.c_void_p) if len(dims) else None))
+
+
+def _is_index(v, lo, hi) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer)) and lo <= v < hi
+
+
+class Walkers:
+    """The walkers of a circuit sampler on the device (module docstring, Walkers): `bits`, n_walkers x n_qubits and all 0
+    at first, a `dead` flag per walker, and the seed of the draws of `Contractor.choose`.
+
+        with Walkers(4096, n_qubits, seed=7) as w:
+            w.permute((0, 1), (0, 1, 3, 2))       # a CNOT of qubit 0 on qubit 1
+            c.run_walkers(w, {5: 0, 6: 2}); c.choose(w, 1, step=0)
+            w.bits, w.dead                         # numpy: uint8 [n_walkers, n_qubits], bool [n_walkers]
+
+    The constructor does not touch the device: the object there is created at the first use."""
+
+    def __init__(self, n_walkers, n_qubits, seed=0, device=None):
+        from . import parallel
+        if not _is_index(n_walkers, 1, 1 << 62):
+            raise ValueError("'n_walkers' must be a positive integer.")
+        if not _is_index(n_qubits, 1, 1 << 62):
+            raise ValueError("'n_qubits' must be a positive integer.")
+        if int(n_walkers) * int(n_qubits) > 1 << 40:
+            raise ValueError("'n_walkers' x 'n_qubits' must be 2^40 at the most.")
+        if not _is_index(seed, 0, 1 << 64):
+            raise ValueError("'seed' must be an integer from 0 to 2^64 - 1.")
+        self.n_walkers, self.n_qubits, self.seed = int(n_walkers), int(n_qubits), int(seed)
+        self.device = parallel.local_device() if device is None else int(device)
+        self._lib, self._w, self._closed = None, None, False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def close(self) -> None:
+        """Destroys the object on the device; every use afterwards is refused.  Closing twice is fine."""
+        if self._w is not None:
+            self._lib.tnco_hip_walkers_destroy(self._w)
+        self._w, self._closed = None, True
+
+    def _check_open(self) -> None:
+        if self._closed:
+            raise ValueError("the Walkers are closed.")
+
+    def _handle(self):
+        from . import _lib
+        self._check_open()
+        if self._w is None:
+            L, w = _lib.load(), C.c_void_p()
+            _lib.check(L.tnco_hip_walkers_create(self.device, self.n_walkers, self.n_qubits, self.seed, C.byref(w)))
+            self._lib, self._w = L, w
+        return self._w
+
+    def _read(self):
+        from . import _lib
+        w = self._handle()
+        bits, dead = np.empty((self.n_qubits, self.n_walkers), np.uint8), np.empty(self.n_walkers, np.uint8)
+        _lib.check(self._lib.tnco_hip_walkers_read(w, bits.ctypes.data_as(C.c_void_p), dead.ctypes.data_as(C.c_void_p)))
+        return np.ascontiguousarray(bits.T), dead.astype(bool)
+
+    @property
+    def bits(self) -> np.ndarray:
+        """uint8 [n_walkers, n_qubits], a copy."""
+        return self._read()[0]
+
+    @property
+    def dead(self) -> np.ndarray:
+        """bool [n_walkers]: the walkers that a `choose` found without a finite, positive probability."""
+        return self._read()[1]
+
+    def write(self, bits) -> None:
+        """Sets the table from an integer array [n_walkers, n_qubits] of zeros and ones; the dead flags stay."""
+        from . import _lib
+        self._check_open()
+        bits = np.asarray(bits)
+        if bits.shape != (self.n_walkers, self.n_qubits) or bits.dtype.kind not in "biu":
+            raise ValueError(f"'bits' must be an integer array of shape {(self.n_walkers, self.n_qubits)}.")
+        if bits.size and not ((bits == 0) | (bits == 1)).all():
+            raise ValueError("'bits' must hold zeros and ones only.")
+        table = np.ascontiguousarray(bits.T, dtype=np.uint8)
+        w = self._handle()
+        _lib.check(self._lib.tnco_hip_walkers_write(w, table.ctypes.data_as(C.c_void_p)))
+
+    def reset(self) -> None:
+        """Every bit and every dead flag 0."""
+        from . import _lib
+        w = self._handle()
+        _lib.check(self._lib.tnco_hip_walkers_reset(w))
+
+    def permute(self, qubits, table) -> None:
+        """A classical gate on every walker: with v the number that its bits of `qubits` spell, the first qubit the most
+        significant, those bits become table[v]; `table` is a permutation of 0 .. 2^k - 1, k = len(qubits) <= 8."""
+        from . import _lib
+        self._check_open()
+        qubits, table = tuple(qubits), tuple(table)
+        if not 1 <= len(qubits) <= MAX_PERMUTE_QUBITS:
+            raise ValueError(f"'qubits' must name 1 to {MAX_PERMUTE_QUBITS} qubits.")
+        for q in qubits:
+            if not _is_index(q, 0, self.n_qubits):
+                raise ValueError(f"{q!r} is not a qubit of the walkers (0 to {self.n_qubits - 1}).")
+        if len(set(qubits)) != len(qubits):
+            raise ValueError("'qubits' names a qubit twice.")
+        n = 1 << len(qubits)
+        if len(table) != n or any(not _is_index(v, 0, n) for v in table) or len(set(table)) != n:
+            raise ValueError(f"'table' must be a permutation of 0 to {n - 1}.")
+        qs, tb = np.array(qubits, np.int64), np.array(table, np.uint8)
+        w = self._handle()
+        _lib.check(self._lib.tnco_hip_walkers_permute(w, len(qubits), qs.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p)))

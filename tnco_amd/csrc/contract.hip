@@ -59,6 +59,12 @@
 // [n_sets][leaf_numel] of the handle's own, and
 //   ct_sets_path_kernel, ct_sets_reduce_kernel  the twins of the two path kernels
 // leave the output of every set in [n_sets][out_numel], each bit-equal to a run of that set alone.
+// Walkers (tnco_hip_walkers_*, tnco_hip_contract_load_leaf_versions, tnco_hip_contract_run_walkers; contract_walk.h): the
+// sets are the walkers of a circuit sampler, whose bits lie in a table on the device; a leaf with two versions is read
+// at the version the walker's bit of one qubit picks, and the versions stay loaded from run to run:
+//   ct_walk_path_kernel    ct_sets_path_kernel with the indexed leaves; ct_sets_reduce_kernel folds its blocks;
+//   ct_walk_choose_kernel, ct_walk_permute_kernel  the new bit of a qubit from the two amplitudes and a Philox draw; a
+//                          classical gate on up to 8 qubits.
 // No atomics in any sum: every sum runs in one fixed order, so a run is bit-reproducible (the one atomic, the integer max
 // behind a scaled tensor's exponent, does not depend on order).
 #include "../../include/tnco_hip.h"
@@ -66,6 +72,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -416,6 +423,7 @@ __global__ __launch_bounds__(256) void ct_batch_reduce_kernel(T* out, const T* s
 
 #include "contract_path.h"
 #include "contract_sets.h"
+#include "contract_walk.h"
 #include "contract_accumulate.h"
 
 // A step with a row axis: row r of the result reads row a_map[r] of A and row b_map[r] of B.  A null map with a row
@@ -623,6 +631,24 @@ struct tnco_hip_contract_s {
   char* d_sets_tables = nullptr;   // [n_leaves][2]: a leaf's pointer and its set stride
   std::vector<int64_t> sets_image;  // the host copy of d_sets_tables of the last run
   int64_t sets_launches[2] = {0, 0};  // launches of ct_sets_path_kernel and of ct_sets_reduce_kernel in the last run
+  // walkers (tnco_hip_contract_load_leaf_versions, tnco_hip_contract_run_walkers)
+  std::vector<void*> d_versions;   // [n_leaves]: the leaf's two versions [2][leaf_numel], nullptr: never loaded
+  std::vector<int64_t> versions_cap, versions;  // [n_leaves]: versions d_versions[t] has room for / holds (0 or 2)
+  char* d_walk_tables = nullptr;   // [n_leaves][WALK_W]: a leaf's pointer, its qubit and its version stride
+  std::vector<int64_t> walk_image;  // the host copy of d_walk_tables of the last run
+  uint64_t last_walk = 0;          // the id of the walkers of the last run if that was a tnco_hip_contract_run_walkers, else 0
+  int64_t walk_sets = 0;           // the outputs that run left: one per walker, or 1 for all of them (no leaf was indexed)
+};
+
+// The state of a sampler's walkers: a table of bits and a dead flag per walker, on one device, and the seed of the draws.
+struct tnco_hip_walkers_s {
+  int device = 0;
+  int64_t n_walkers = 0, n_qubits = 0;
+  uint64_t seed = 0, id = 0;       // id: unique in the process, never 0
+  uint8_t* d_bits = nullptr;       // [n_qubits][n_walkers]
+  uint8_t* d_dead = nullptr;       // [n_walkers]
+  int64_t* d_perm = nullptr;       // ct_walk_permute_kernel's qubits and table
+  hipStream_t stream = nullptr;
 };
 
 namespace {
@@ -1251,6 +1277,81 @@ const char* sets_refusal(const tnco_hip_contract_s* c) {
   return nullptr;
 }
 
+// The fused loop over walkers: run_sets with the walkers' bits in the place of the set strides (contract_walk.h).
+template <class T>
+int run_walkers(tnco_hip_contract_s* c, const tnco_hip_walkers_s* w, int64_t group, int64_t n_sets) {
+  const int64_t A = c->stop - c->start;
+  const int64_t* d_place = nullptr;
+  WalkArgs s;
+  s.p = path_args(c, &d_place);
+  s.walk_leaves = (const int64_t*)c->d_walk_tables;
+  s.bits = w->d_bits, s.n_walkers = w->n_walkers;
+  s.n_assign = A, s.start = c->start;
+  const int64_t per_slice = macs_per_assignment(c), members = n_sets * A;
+  for (int64_t m0 = 0; m0 < members; m0 += group) {
+    const int64_t n = std::min(group, members - m0);
+    s.m0 = m0;
+    hipLaunchKernelGGL(ct_walk_path_kernel<T>, dim3((unsigned)n), dim3(PATH_LANES), 0, c->stream, s);
+    CT_TRY(hipGetLastError());
+    const dim3 grid((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048));
+    hipLaunchKernelGGL(ct_sets_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (T*)c->d_sets_out, (const T*)c->d_path_stage,
+                       c->block_numel, (int)n, m0, A, c->out_numel, d_place);
+    CT_TRY(hipGetLastError());
+    c->launches += 2;
+    c->sets_launches[0] += 1, c->sets_launches[1] += 1;
+    c->macs += per_slice * n;
+  }
+  return TNCO_HIP_OK;
+}
+
+// every counter of a run, and whose walkers it ran over, before the run starts
+void zero_run_counters(tnco_hip_contract_s* c) {
+  c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->matrix_launches = c->last_member = 0;
+  c->path_launches[0] = c->path_launches[1] = c->acc_launches[0] = c->acc_launches[1] = 0;
+  c->sets_launches[0] = c->sets_launches[1] = 0;
+  c->last_walk = 0;
+  std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
+  std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
+  std::fill(std::begin(c->by_ix), std::end(c->by_ix), 0);
+}
+
+// Room for G members and n_sets outputs, and for the `tables` bytes of *d_tables once.  The new buffers first: a handle
+// that this fails on stays as it was.  (The arenas and the staging hold nothing between runs.)  `what` needs the bytes.
+int sets_room(tnco_hip_contract_s* c, int64_t n_sets, int64_t G, char** d_tables, size_t tables, const char* what) {
+  const size_t arena = (size_t)c->arena_elems * c->elem, block = (size_t)c->block_numel * c->out_elem;
+  const size_t outb = (size_t)c->out_numel * c->out_elem;
+  const bool more_members = G > c->path_cap, more_out = n_sets > c->sets_out_cap, new_tables = !*d_tables;
+  const size_t need = (more_members ? (size_t)G * (arena + block) : 0) + (more_out ? (size_t)n_sets * outb : 0) + (new_tables ? tables : 0);
+  if (!need) return TNCO_HIP_OK;
+  CT_TRY(hipStreamSynchronize(c->stream));
+  size_t free_b = 0, total_b = 0;
+  CT_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (need > free_b)
+    return fail(TNCO_HIP_ERUNTIME, std::string(what) + " need " + std::to_string(need) + " bytes of device memory, " +
+                                       std::to_string(free_b) + " are free.");
+  void *d_arena = nullptr, *d_stage = nullptr, *d_out = nullptr, *d_tab = nullptr;
+  if ((more_members && (hipMalloc(&d_arena, std::max<size_t>((size_t)G * arena, c->elem)) != hipSuccess ||
+                        hipMalloc(&d_stage, (size_t)G * block) != hipSuccess)) ||
+      (more_out && hipMalloc(&d_out, (size_t)n_sets * outb) != hipSuccess) ||
+      (new_tables && hipMalloc(&d_tab, tables) != hipSuccess)) {
+    for (void* p : {d_arena, d_stage, d_out, d_tab})
+      if (p) (void)hipFree(p);
+    return fail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+  }
+  if (more_members) {
+    (void)hipFree(c->d_arena), (void)hipFree(c->d_path_stage);
+    c->bytes += (G - c->path_cap) * (int64_t)(arena + block);
+    c->d_arena = d_arena, c->d_path_stage = d_stage, c->path_cap = G;
+  }
+  if (more_out) {
+    if (c->d_sets_out) (void)hipFree(c->d_sets_out);
+    c->bytes += (n_sets - c->sets_out_cap) * (int64_t)outb;
+    c->d_sets_out = d_out, c->sets_out_cap = n_sets;
+  }
+  if (new_tables) *d_tables = (char*)d_tab, c->bytes += (int64_t)tables;
+  return TNCO_HIP_OK;
+}
+
 int64_t n_assignments(const tnco_hip_contract_s* c) {
   int64_t n = 1;
   for (int64_t d : c->slice_dims) n *= d;
@@ -1478,6 +1579,49 @@ int launch_emit(tnco_hip_contract_s* c, void* dst, const IoAxes& ax, int64_t set
   return TNCO_HIP_OK;
 }
 
+// A stack [n][leaf_numel] of leaf `leaf` from `src` into *buf, which has room for *cap of them and grows to n (the new
+// buffer first, so that a failure leaves the old one); *held: how many the buffer holds, 0 while it holds none whole.
+int load_stack(tnco_hip_contract_s* c, int64_t leaf, int64_t n, const void* src, int32_t where, int32_t src_dtype, int64_t ndim,
+               const int64_t* dims, const int64_t* strides, void** buf, int64_t* cap, int64_t* held, const char* dims_text) {
+  const int64_t leaf_numel = c->leaf_numel[leaf];
+  const int64_t numel = n * leaf_numel;
+  IoAxes ax;
+  bool contiguous = false;
+  if (const char* e = io_axes(ndim, dims, strides, numel, dims_text, &ax, &contiguous)) return fail(TNCO_HIP_EINVAL, e);
+  if (where == 0) {
+    if (src_dtype != c->dtype) return fail(TNCO_HIP_EINVAL, "a host stack must have the plan's dtype.");
+    if (strides) return fail(TNCO_HIP_EINVAL, "a host stack must be C-contiguous: 'strides' must be NULL.");
+  } else if (src_dtype < 0 || src_dtype > 3 || !io_widens(src_dtype, c->dtype)) {
+    return fail(TNCO_HIP_EINVAL, "'src_dtype' does not widen to the plan's dtype.");
+  }
+  CT_TRY(hipSetDevice(c->device));
+  if (n > *cap) {
+    const size_t bytes = (size_t)numel * c->elem;
+    size_t free_b = 0, total_b = 0;
+    CT_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (bytes > free_b)
+      return fail(TNCO_HIP_ERUNTIME, "the stack needs " + std::to_string(bytes) + " bytes of device memory, " +
+                                         std::to_string(free_b) + " are free.");
+    void* d_new = nullptr;
+    if (hipMalloc(&d_new, bytes) != hipSuccess) return fail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+    if (*buf) (void)hipFree(*buf);
+    c->bytes += (n - *cap) * leaf_numel * (int64_t)c->elem;
+    *buf = d_new, *cap = n, *held = 0;
+  }
+  if (where == 0) {
+    CT_TRY(hipMemcpyAsync(*buf, src, (size_t)numel * c->elem, hipMemcpyHostToDevice, c->stream));
+  } else {
+    if (contiguous) {  // one axis; of the plan's dtype: the vector path
+      ax.nd = src_dtype == c->dtype ? -1 : 1;
+      ax.dim[0] = numel, ax.stride[0] = 1;
+    }
+    if (int rc = launch_ingest(c, *buf, src, src_dtype, numel, ax)) return rc;
+  }
+  CT_TRY(hipStreamSynchronize(c->stream));
+  *held = n;
+  return TNCO_HIP_OK;
+}
+
 // The run over the leaves that the leaf buffers hold, from the zeroing of the output on.  emit == nullptr: `out` is host
 // memory and gets the raw output buffer; otherwise `out` is a caller's device memory and ct_emit_kernel writes it
 int run_loaded(tnco_hip_contract_s* c, void* out, const IoAxes* emit) {
@@ -1494,12 +1638,7 @@ int run_loaded(tnco_hip_contract_s* c, void* out, const IoAxes* emit) {
       CT_TRY(hipMemcpyAsync(c->d_exps, c->leaf_exps.data(), c->leaf_exps.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
   }
-  c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->matrix_launches = c->last_member = 0;
-  c->path_launches[0] = c->path_launches[1] = c->acc_launches[0] = c->acc_launches[1] = 0;
-  c->sets_launches[0] = c->sets_launches[1] = 0;
-  std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
-  std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
-  std::fill(std::begin(c->by_ix), std::end(c->by_ix), 0);
+  zero_run_counters(c);
   CT_TRY(hipEventRecord(c->ev[0], c->stream));
   const bool fused = c->path_group > 0 && n_steps > 0;  // (a plan without steps runs as it does without the call)
   int rc = fused ? (c->dtype == 0 ? run_path<float>(c)
@@ -1547,6 +1686,8 @@ int tnco_hip_contract_create(const tnco_hip_contract_desc* d, tnco_hip_contract*
   c->loaded.assign(c->leaf_numel.size(), 0);
   c->d_stack.assign(c->leaf_numel.size(), nullptr);
   c->stack_cap.assign(c->leaf_numel.size(), 0), c->stack_sets.assign(c->leaf_numel.size(), 0);
+  c->d_versions.assign(c->leaf_numel.size(), nullptr);
+  c->versions_cap.assign(c->leaf_numel.size(), 0), c->versions.assign(c->leaf_numel.size(), 0);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || d->device < 0 || d->device >= ndev) {
     delete c;
@@ -1683,45 +1824,9 @@ int tnco_hip_contract_load_leaf_sets(tnco_hip_contract c, int64_t leaf, int64_t 
   if (n_sets < 1) return fail(TNCO_HIP_EINVAL, "'n_sets' must be at least 1.");
   if (const char* e = sets_refusal(c)) return fail(TNCO_HIP_EINVAL, e);
   if (where != 0 && where != 1) return fail(TNCO_HIP_EINVAL, "'where' must be 0 (host) or 1 (device).");
-  const int64_t leaf_numel = c->leaf_numel[leaf];
-  if (n_sets > (INT64_MAX >> 8) / leaf_numel) return fail(TNCO_HIP_EINVAL, "'n_sets' is too large.");
-  const int64_t numel = n_sets * leaf_numel;
-  IoAxes ax;
-  bool contiguous = false;
-  if (const char* e = io_axes(ndim, dims, strides, numel, "dims do not multiply to the sets' elements.", &ax, &contiguous))
-    return fail(TNCO_HIP_EINVAL, e);
-  if (where == 0) {
-    if (src_dtype != c->dtype) return fail(TNCO_HIP_EINVAL, "a host stack must have the plan's dtype.");
-    if (strides) return fail(TNCO_HIP_EINVAL, "a host stack must be C-contiguous: 'strides' must be NULL.");
-  } else if (src_dtype < 0 || src_dtype > 3 || !io_widens(src_dtype, c->dtype)) {
-    return fail(TNCO_HIP_EINVAL, "'src_dtype' does not widen to the plan's dtype.");
-  }
-  CT_TRY(hipSetDevice(c->device));
-  if (n_sets > c->stack_cap[leaf]) {  // a larger stack: the new buffer first, so that a failure leaves the old one
-    const size_t bytes = (size_t)numel * c->elem;
-    size_t free_b = 0, total_b = 0;
-    CT_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (bytes > free_b)
-      return fail(TNCO_HIP_ERUNTIME, "the stack needs " + std::to_string(bytes) + " bytes of device memory, " +
-                                         std::to_string(free_b) + " are free.");
-    void* d_new = nullptr;
-    if (hipMalloc(&d_new, bytes) != hipSuccess) return fail(TNCO_HIP_ERUNTIME, "device allocation failed.");
-    if (c->d_stack[leaf]) (void)hipFree(c->d_stack[leaf]);
-    c->bytes += (n_sets - c->stack_cap[leaf]) * leaf_numel * (int64_t)c->elem;
-    c->d_stack[leaf] = d_new, c->stack_cap[leaf] = n_sets, c->stack_sets[leaf] = 0;
-  }
-  if (where == 0) {
-    CT_TRY(hipMemcpyAsync(c->d_stack[leaf], src, (size_t)numel * c->elem, hipMemcpyHostToDevice, c->stream));
-  } else {
-    if (contiguous) {  // one axis; of the plan's dtype: the vector path
-      ax.nd = src_dtype == c->dtype ? -1 : 1;
-      ax.dim[0] = numel, ax.stride[0] = 1;
-    }
-    if (int rc = launch_ingest(c, c->d_stack[leaf], src, src_dtype, numel, ax)) return rc;
-  }
-  CT_TRY(hipStreamSynchronize(c->stream));
-  c->stack_sets[leaf] = n_sets;
-  return TNCO_HIP_OK;
+  if (n_sets > (INT64_MAX >> 8) / c->leaf_numel[leaf]) return fail(TNCO_HIP_EINVAL, "'n_sets' is too large.");
+  return load_stack(c, leaf, n_sets, src, where, src_dtype, ndim, dims, strides, &c->d_stack[leaf], &c->stack_cap[leaf],
+                    &c->stack_sets[leaf], "dims do not multiply to the sets' elements.");
 }
 
 int tnco_hip_contract_run_sets(tnco_hip_contract c, int64_t n_sets, int64_t group, void* out, int32_t where, int64_t ndim,
@@ -1751,41 +1856,10 @@ int tnco_hip_contract_run_sets(tnco_hip_contract c, int64_t n_sets, int64_t grou
     if (!c->stack_sets[t] && !c->loaded[t]) return fail(TNCO_HIP_EINVAL, "leaf " + std::to_string(t) + " was never loaded.");
   }
   CT_TRY(hipSetDevice(c->device));
-  // Room for min(group, members) members and n_sets outputs; the tables once.  The new buffers first: a handle that this
-  // call fails on stays as it was.  (The arenas and the staging hold nothing between runs.)
+  // room for min(group, members) members and n_sets outputs; the tables once
   const int64_t G = std::min(group, n_sets * A);
-  const size_t arena = (size_t)c->arena_elems * c->elem, block = (size_t)c->block_numel * c->out_elem;
-  const size_t outb = (size_t)c->out_numel * c->out_elem, tables = (size_t)L * (sizeof(void*) + sizeof(int64_t));
-  const bool more_members = G > c->path_cap, more_out = n_sets > c->sets_out_cap, new_tables = !c->d_sets_tables;
-  const size_t need = (more_members ? (size_t)G * (arena + block) : 0) + (more_out ? (size_t)n_sets * outb : 0) + (new_tables ? tables : 0);
-  if (need) {
-    CT_TRY(hipStreamSynchronize(c->stream));
-    size_t free_b = 0, total_b = 0;
-    CT_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b)
-      return fail(TNCO_HIP_ERUNTIME, "the leaf sets need " + std::to_string(need) + " bytes of device memory, " +
-                                         std::to_string(free_b) + " are free.");
-    void *d_arena = nullptr, *d_stage = nullptr, *d_out = nullptr, *d_tab = nullptr;
-    if ((more_members && (hipMalloc(&d_arena, std::max<size_t>((size_t)G * arena, c->elem)) != hipSuccess ||
-                          hipMalloc(&d_stage, (size_t)G * block) != hipSuccess)) ||
-        (more_out && hipMalloc(&d_out, (size_t)n_sets * outb) != hipSuccess) ||
-        (new_tables && hipMalloc(&d_tab, tables) != hipSuccess)) {
-      for (void* p : {d_arena, d_stage, d_out, d_tab})
-        if (p) (void)hipFree(p);
-      return fail(TNCO_HIP_ERUNTIME, "device allocation failed.");
-    }
-    if (more_members) {
-      (void)hipFree(c->d_arena), (void)hipFree(c->d_path_stage);
-      c->bytes += (G - c->path_cap) * (int64_t)(arena + block);
-      c->d_arena = d_arena, c->d_path_stage = d_stage, c->path_cap = G;
-    }
-    if (more_out) {
-      if (c->d_sets_out) (void)hipFree(c->d_sets_out);
-      c->bytes += (n_sets - c->sets_out_cap) * (int64_t)outb;
-      c->d_sets_out = d_out, c->sets_out_cap = n_sets;
-    }
-    if (new_tables) c->d_sets_tables = (char*)d_tab, c->bytes += (int64_t)tables;
-  }
+  const size_t outb = (size_t)c->out_numel * c->out_elem;
+  if (int rc = sets_room(c, n_sets, G, &c->d_sets_tables, (size_t)L * (sizeof(void*) + sizeof(int64_t)), "the leaf sets")) return rc;
   static_assert(sizeof(void*) == sizeof(int64_t), "the pointers and the strides share one table");
   c->sets_image.assign(2 * L, 0);
   for (int64_t t = 0; t < L; ++t) {
@@ -1794,12 +1868,7 @@ int tnco_hip_contract_run_sets(tnco_hip_contract c, int64_t n_sets, int64_t grou
   }
   CT_TRY(hipMemcpyAsync(c->d_sets_tables, c->sets_image.data(), 2 * L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   CT_TRY(hipMemsetAsync(c->d_sets_out, 0, (size_t)n_sets * outb, c->stream));
-  c->macs = c->launches = c->narrow_launches = c->batch_launches = c->split_launches = c->matrix_launches = c->last_member = 0;
-  c->path_launches[0] = c->path_launches[1] = c->acc_launches[0] = c->acc_launches[1] = 0;
-  c->sets_launches[0] = c->sets_launches[1] = 0;
-  std::fill(std::begin(c->by_kernel), std::end(c->by_kernel), 0);
-  std::fill(std::begin(c->by_row_kernel), std::end(c->by_row_kernel), 0);
-  std::fill(std::begin(c->by_ix), std::end(c->by_ix), 0);
+  zero_run_counters(c);
   CT_TRY(hipEventRecord(c->ev[0], c->stream));
   if (int rc = c->dtype == 0   ? run_sets<float>(c, n_sets, G)
                : c->dtype == 1 ? run_sets<double>(c, n_sets, G)
@@ -1823,6 +1892,194 @@ int tnco_hip_contract_run_sets(tnco_hip_contract c, int64_t n_sets, int64_t grou
 int tnco_hip_contract_sets_launches(tnco_hip_contract c, int64_t* counts) {
   if (!c || !counts) return fail(TNCO_HIP_EINVAL, "null argument.");
   counts[0] = c->sets_launches[0], counts[1] = c->sets_launches[1];
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_load_leaf_versions(tnco_hip_contract c, int64_t leaf, int64_t n_versions, const void* src, int32_t where,
+                                         int32_t src_dtype, int64_t ndim, const int64_t* dims, const int64_t* strides) {
+  if (!c || !src) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (leaf < 0 || leaf >= (int64_t)c->leaf_numel.size()) return fail(TNCO_HIP_EINVAL, "'leaf' is not a leaf of the plan.");
+  if (n_versions != 2) return fail(TNCO_HIP_EINVAL, "'n_versions' must be 2.");
+  if (const char* e = sets_refusal(c)) return fail(TNCO_HIP_EINVAL, e);
+  if (where != 0 && where != 1) return fail(TNCO_HIP_EINVAL, "'where' must be 0 (host) or 1 (device).");
+  return load_stack(c, leaf, n_versions, src, where, src_dtype, ndim, dims, strides, &c->d_versions[leaf], &c->versions_cap[leaf],
+                    &c->versions[leaf], "dims do not multiply to the versions' elements.");
+}
+
+int tnco_hip_contract_run_walkers(tnco_hip_contract c, tnco_hip_walkers w, const int64_t* leaf_qubit, int64_t group) {
+  if (!c || !w || (!leaf_qubit && !c->leaf_numel.empty())) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (group < 1 || group > MAX_PATH_GROUP) return fail(TNCO_HIP_EINVAL, "'group' must be from 1 to 1024.");
+  if (const char* e = sets_refusal(c)) return fail(TNCO_HIP_EINVAL, e);
+  if (w->device != c->device)
+    return fail(TNCO_HIP_EINVAL, "the walkers are on device " + std::to_string(w->device) + ", the handle on device " +
+                                     std::to_string(c->device) + ".");
+  const int64_t A = c->stop - c->start, L = (int64_t)c->leaf_numel.size();
+  if (w->n_walkers > (INT64_MAX >> 8) / std::max(c->out_numel, A)) return fail(TNCO_HIP_EINVAL, "there are too many walkers.");
+  bool any_indexed = false;
+  for (int64_t t = 0; t < L; ++t) {
+    any_indexed |= leaf_qubit[t] >= 0;
+    if (leaf_qubit[t] < -1 || leaf_qubit[t] >= w->n_qubits)
+      return fail(TNCO_HIP_EINVAL, "the qubit " + std::to_string(leaf_qubit[t]) + " of leaf " + std::to_string(t) +
+                                       " is not -1 or a qubit of the walkers (0 to " + std::to_string(w->n_qubits - 1) + ").");
+    if (leaf_qubit[t] >= 0 && !c->versions[t]) return fail(TNCO_HIP_EINVAL, "leaf " + std::to_string(t) + " has no versions loaded.");
+    if (leaf_qubit[t] < 0 && !c->loaded[t]) return fail(TNCO_HIP_EINVAL, "leaf " + std::to_string(t) + " was never loaded.");
+  }
+  CT_TRY(hipSetDevice(c->device));
+  // without an indexed leaf no output depends on the walker: one set is run, and every walker reads its output
+  const int64_t R = any_indexed ? w->n_walkers : 1;
+  const int64_t G = std::min(group, R * A);
+  const size_t outb = (size_t)c->out_numel * c->out_elem;
+  if (int rc = sets_room(c, R, G, &c->d_walk_tables, (size_t)L * WALK_W * sizeof(int64_t), "the walkers")) return rc;
+  c->walk_image.assign(WALK_W * L, 0);
+  for (int64_t t = 0; t < L; ++t) {
+    const bool indexed = leaf_qubit[t] >= 0;
+    c->walk_image[WALK_W * t] = (int64_t)(uintptr_t)(indexed ? c->d_versions[t] : (void*)(c->d_leaves + c->leaf_off[t] * c->elem));
+    c->walk_image[WALK_W * t + 1] = leaf_qubit[t];
+    c->walk_image[WALK_W * t + 2] = indexed ? c->leaf_numel[t] : 0;
+  }
+  CT_TRY(hipMemcpyAsync(c->d_walk_tables, c->walk_image.data(), WALK_W * L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  CT_TRY(hipMemsetAsync(c->d_sets_out, 0, (size_t)R * outb, c->stream));
+  zero_run_counters(c);
+  CT_TRY(hipEventRecord(c->ev[0], c->stream));
+  if (int rc = c->dtype == 0   ? run_walkers<float>(c, w, G, R)
+               : c->dtype == 1 ? run_walkers<double>(c, w, G, R)
+               : c->dtype == 2 ? run_walkers<cplx<float>>(c, w, G, R)
+                               : run_walkers<cplx<double>>(c, w, G, R))
+    return rc;
+  CT_TRY(hipEventRecord(c->ev[1], c->stream));
+  CT_TRY(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  CT_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+  c->device_ns = (int64_t)((double)ms * 1e6);
+  c->last_walk = w->id, c->walk_sets = R;
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_contract_walkers_output(tnco_hip_contract c, tnco_hip_walkers w, void* out) {
+  if (!c || !w || !out) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (c->last_walk != w->id)
+    return fail(TNCO_HIP_EINVAL, "the handle's last run was not a tnco_hip_contract_run_walkers over these walkers.");
+  CT_TRY(hipSetDevice(c->device));
+  CT_TRY(hipMemcpyAsync(out, c->d_sets_out, (size_t)c->walk_sets * c->out_numel * c->out_elem, hipMemcpyDeviceToHost, c->stream));
+  CT_TRY(hipStreamSynchronize(c->stream));
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_walkers_create(int32_t device, int64_t n_walkers, int64_t n_qubits, uint64_t seed, tnco_hip_walkers* out) {
+  if (!out) return fail(TNCO_HIP_EINVAL, "null argument.");
+  *out = nullptr;
+  if (n_walkers < 1) return fail(TNCO_HIP_EINVAL, "'n_walkers' must be at least 1.");
+  if (n_qubits < 1) return fail(TNCO_HIP_EINVAL, "'n_qubits' must be at least 1.");
+  if (n_walkers > ((int64_t)1 << 40) / n_qubits) return fail(TNCO_HIP_EINVAL, "the table of bits is too large (2^40 at the most).");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(TNCO_HIP_EINVAL, "'device' is not valid.");
+  CT_TRY(hipSetDevice(device));
+  const size_t table = (size_t)n_walkers * n_qubits, perm = WALK_MAX_PERMUTE * sizeof(int64_t) + ((size_t)1 << WALK_MAX_PERMUTE);
+  size_t free_b = 0, total_b = 0;
+  CT_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (table + (size_t)n_walkers + perm > free_b)
+    return fail(TNCO_HIP_ERUNTIME, "the walkers need " + std::to_string(table + (size_t)n_walkers + perm) +
+                                       " bytes of device memory, " + std::to_string(free_b) + " are free.");
+  static std::atomic<uint64_t> next_id{0};  // (walkers may be created from several threads at once)
+  auto* w = new tnco_hip_walkers_s();
+  w->device = device, w->n_walkers = n_walkers, w->n_qubits = n_qubits, w->seed = seed, w->id = ++next_id;
+  if (hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess ||
+      hipMalloc((void**)&w->d_bits, table) != hipSuccess || hipMalloc((void**)&w->d_dead, (size_t)n_walkers) != hipSuccess ||
+      hipMalloc((void**)&w->d_perm, perm) != hipSuccess || hipMemsetAsync(w->d_bits, 0, table, w->stream) != hipSuccess ||
+      hipMemsetAsync(w->d_dead, 0, (size_t)n_walkers, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) {
+    tnco_hip_walkers_destroy(w);
+    return fail(TNCO_HIP_ERUNTIME, "device allocation failed.");
+  }
+  *out = w;
+  return TNCO_HIP_OK;
+}
+
+void tnco_hip_walkers_destroy(tnco_hip_walkers w) {
+  if (!w) return;
+  if (w->stream) (void)hipStreamSynchronize(w->stream);
+  for (void* p : {(void*)w->d_bits, (void*)w->d_dead, (void*)w->d_perm})
+    if (p) (void)hipFree(p);
+  if (w->stream) (void)hipStreamDestroy(w->stream);
+  delete w;
+}
+
+int tnco_hip_walkers_read(tnco_hip_walkers w, uint8_t* bits_out, uint8_t* dead_out) {
+  if (!w || (!bits_out && !dead_out)) return fail(TNCO_HIP_EINVAL, "null argument.");
+  CT_TRY(hipSetDevice(w->device));
+  if (bits_out) CT_TRY(hipMemcpyAsync(bits_out, w->d_bits, (size_t)w->n_walkers * w->n_qubits, hipMemcpyDeviceToHost, w->stream));
+  if (dead_out) CT_TRY(hipMemcpyAsync(dead_out, w->d_dead, (size_t)w->n_walkers, hipMemcpyDeviceToHost, w->stream));
+  CT_TRY(hipStreamSynchronize(w->stream));
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_walkers_write(tnco_hip_walkers w, const uint8_t* bits_in) {
+  if (!w || !bits_in) return fail(TNCO_HIP_EINVAL, "null argument.");
+  const size_t table = (size_t)w->n_walkers * w->n_qubits;
+  for (size_t e = 0; e < table; ++e)
+    if (bits_in[e] > 1) return fail(TNCO_HIP_EINVAL, "a bit is neither 0 nor 1.");
+  CT_TRY(hipSetDevice(w->device));
+  CT_TRY(hipMemcpyAsync(w->d_bits, bits_in, table, hipMemcpyHostToDevice, w->stream));
+  CT_TRY(hipStreamSynchronize(w->stream));
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_walkers_reset(tnco_hip_walkers w) {
+  if (!w) return fail(TNCO_HIP_EINVAL, "null argument.");
+  CT_TRY(hipSetDevice(w->device));
+  CT_TRY(hipMemsetAsync(w->d_bits, 0, (size_t)w->n_walkers * w->n_qubits, w->stream));
+  CT_TRY(hipMemsetAsync(w->d_dead, 0, (size_t)w->n_walkers, w->stream));
+  CT_TRY(hipStreamSynchronize(w->stream));
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_walkers_choose(tnco_hip_walkers w, tnco_hip_contract c, int64_t qubit, int64_t step) {
+  if (!w || !c) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (c->last_walk != w->id)
+    return fail(TNCO_HIP_EINVAL, "the handle's last run was not a tnco_hip_contract_run_walkers over these walkers.");
+  if (c->out_numel != 2)
+    return fail(TNCO_HIP_EINVAL, "the output of the handle holds " + std::to_string(c->out_numel) + " elements, not the 2 amplitudes of a choice.");
+  if (qubit < 0 || qubit >= w->n_qubits)
+    return fail(TNCO_HIP_EINVAL, "'qubit' is not a qubit of the walkers (0 to " + std::to_string(w->n_qubits - 1) + ").");
+  if (step < 0 || step > (int64_t)UINT32_MAX) return fail(TNCO_HIP_EINVAL, "'step' must be from 0 to 2^32 - 1.");
+  CT_TRY(hipSetDevice(w->device));
+  // (the run has synchronised the handle's stream: its outputs are there)
+  const dim3 grid((unsigned)std::min<int64_t>((w->n_walkers + 255) / 256, 65536));
+  uint8_t* row = w->d_bits + qubit * w->n_walkers;
+  const int64_t each = c->walk_sets == 1 ? 0 : 2;  // elements between two walkers' amplitudes (one output for all: 0)
+  switch (c->dtype) {
+    case 0: hipLaunchKernelGGL(ct_walk_choose_kernel<float>, grid, dim3(256), 0, w->stream, row, w->d_dead, (const float*)c->d_sets_out, each, w->n_walkers, w->seed, (uint32_t)step); break;
+    case 1: hipLaunchKernelGGL(ct_walk_choose_kernel<double>, grid, dim3(256), 0, w->stream, row, w->d_dead, (const double*)c->d_sets_out, each, w->n_walkers, w->seed, (uint32_t)step); break;
+    case 2: hipLaunchKernelGGL(ct_walk_choose_kernel<cplx<float>>, grid, dim3(256), 0, w->stream, row, w->d_dead, (const cplx<float>*)c->d_sets_out, each, w->n_walkers, w->seed, (uint32_t)step); break;
+    default: hipLaunchKernelGGL(ct_walk_choose_kernel<cplx<double>>, grid, dim3(256), 0, w->stream, row, w->d_dead, (const cplx<double>*)c->d_sets_out, each, w->n_walkers, w->seed, (uint32_t)step);
+  }
+  CT_TRY(hipGetLastError());
+  CT_TRY(hipStreamSynchronize(w->stream));
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_walkers_permute(tnco_hip_walkers w, int64_t k, const int64_t* qubits, const uint8_t* table) {
+  if (!w || !qubits || !table) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (k < 1 || k > WALK_MAX_PERMUTE) return fail(TNCO_HIP_EINVAL, "'k' must be from 1 to 8.");
+  for (int64_t j = 0; j < k; ++j) {
+    if (qubits[j] < 0 || qubits[j] >= w->n_qubits)
+      return fail(TNCO_HIP_EINVAL, "a qubit is not a qubit of the walkers (0 to " + std::to_string(w->n_qubits - 1) + ").");
+    if (std::count(qubits, qubits + j, qubits[j])) return fail(TNCO_HIP_EINVAL, "a qubit is named twice.");
+  }
+  const int64_t n = (int64_t)1 << k;
+  std::vector<char> seen(n, 0);
+  for (int64_t v = 0; v < n; ++v) {
+    if (table[v] >= n || seen[table[v]]) return fail(TNCO_HIP_EINVAL, "'table' is not a permutation of 0 to 2^k - 1.");
+    seen[table[v]] = 1;
+  }
+  int64_t image[WALK_MAX_PERMUTE + (1 << WALK_MAX_PERMUTE) / sizeof(int64_t)] = {};
+  std::copy(qubits, qubits + k, image);
+  std::memcpy(image + WALK_MAX_PERMUTE, table, (size_t)n);
+  CT_TRY(hipSetDevice(w->device));
+  CT_TRY(hipMemcpyAsync(w->d_perm, image, sizeof(image), hipMemcpyHostToDevice, w->stream));
+  const dim3 grid((unsigned)std::min<int64_t>((w->n_walkers + 255) / 256, 65536));
+  hipLaunchKernelGGL(ct_walk_permute_kernel, grid, dim3(256), 0, w->stream, w->d_bits, w->n_walkers, (int)k, (const int64_t*)w->d_perm);
+  CT_TRY(hipGetLastError());
+  CT_TRY(hipStreamSynchronize(w->stream));  // (the image lies on this call's stack)
   return TNCO_HIP_OK;
 }
 
@@ -2210,10 +2467,11 @@ void tnco_hip_contract_destroy(tnco_hip_contract c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_leaves, c->d_arena, c->d_out, (void*)c->d_tables, (void*)c->d_leaf_ptrs, (void*)c->d_row_maps,
                   (void*)c->d_exps, c->d_batch_out, c->d_path_stage, (void*)c->d_path_tables, (void*)c->d_ind, c->d_acc,
-                  c->d_acc_stage, c->d_sets_out, (void*)c->d_sets_tables})
+                  c->d_acc_stage, c->d_sets_out, (void*)c->d_sets_tables, (void*)c->d_walk_tables})
     if (p) (void)hipFree(p);
-  for (void* p : c->d_stack)
-    if (p) (void)hipFree(p);
+  for (const auto* bufs : {&c->d_stack, &c->d_versions})
+    for (void* p : *bufs)
+      if (p) (void)hipFree(p);
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);
   if (c->stream) (void)hipStreamDestroy(c->stream);

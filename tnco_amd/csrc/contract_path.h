@@ -35,18 +35,27 @@ struct PathArgs {
   int n_steps;
 };
 
-// Leaf t as assignment sid reads it: at the slice offset of the assignment.  SETS (leaf sets, contract_sets.h): the leaf
+// Leaf t as assignment sid reads it: at the slice offset of the assignment.  MODE 1 (leaf sets, contract_sets.h): the leaf
 // comes from set_leaves, [n_leaves][2]: its pointer and the elements between two sets of it (0 or the leaf's elements),
 // and the base moves on by set times that, a 64-bit product; pointer and stride lie side by side, one read, and it is
 // asked for before the slice offset is worked out, as ct_path_kernel asks for its pointer (every block of a launch reads
 // the same entry at about the same time: read after the offset loop, its latency lay open once per leaf and cost the
-// kernel a quarter of its time).  Without SETS (ct_path_kernel) nothing is added and nothing more is read.
-template <class T, bool SETS = false>
+// kernel a quarter of its time).  MODE 2 (walkers, contract_walk.h): the table is [n_leaves][WALK_W], the leaf's pointer,
+// the qubit whose bit picks one of its two versions (-1: none) and the elements between them; `set` is then the number of
+// walkers and column[qubit * set] the member's bit, a uniform address, asked for right after the entry and before the
+// offset too.  MODE 0 (ct_path_kernel): nothing is added and nothing more is read.  (MODE was a bool before the walkers:
+// contract_sets.h still passes `true`, which is MODE 1.)
+constexpr int WALK_W = 3;
+template <class T, int MODE = 0>
 __device__ inline const T* ct_path_leaf(const PathArgs& p, int64_t t, int64_t sid, const int64_t* set_leaves = nullptr,
-                                        int64_t set = 0) {
-  if constexpr (SETS) {
+                                        int64_t set = 0, const uint8_t* column = nullptr) {
+  if constexpr (MODE == 1) {
     const int64_t base = set_leaves[2 * t], step = set_leaves[2 * t + 1];  // (asked for before the offset is worked out)
     return (const T*)base + (ct_slice_offset(p.leaf_sl + t * LEAF_SL_W, p.slice_place, p.slice_dims, sid) + set * step);
+  } else if constexpr (MODE == 2) {
+    const int64_t base = set_leaves[WALK_W * t], qubit = set_leaves[WALK_W * t + 1], step = set_leaves[WALK_W * t + 2];
+    const int64_t version = qubit < 0 ? 0 : column[qubit * set] & 1;  // (both before the offset is worked out)
+    return (const T*)base + (ct_slice_offset(p.leaf_sl + t * LEAF_SL_W, p.slice_place, p.slice_dims, sid) + version * step);
   } else {
     return (const T*)p.leaves[t] + ct_slice_offset(p.leaf_sl + t * LEAF_SL_W, p.slice_place, p.slice_dims, sid);
   }
@@ -54,9 +63,9 @@ __device__ inline const T* ct_path_leaf(const PathArgs& p, int64_t t, int64_t si
 
 // the rows of one permute group, one after the other (they are independent of each other: one launch in the unfused
 // loop): ct_gather_body's element loop, strided over the block.  A permute feeds a step, so numel < 2^24.
-template <class T, bool SETS = false>
+template <class T, int MODE = 0>
 __device__ inline void ct_path_permutes(const PathArgs& p, int64_t group, T* arena, int64_t sid,
-                                        const int64_t* set_leaves = nullptr, int64_t set = 0) {
+                                        const int64_t* set_leaves = nullptr, int64_t set = 0, const uint8_t* column = nullptr) {
   const int64_t first = p.groups[2 * (group + 1)], count = p.groups[2 * (group + 1) + 1];
   for (int64_t r = first; r < first + count; ++r) {
     const int64_t* row = p.perms + r * PERM_W;
@@ -64,7 +73,7 @@ __device__ inline void ct_path_permutes(const PathArgs& p, int64_t group, T* are
     const int nd = (int)row[4];
     const T* src;
     if (row[0] == K_LEAF)
-      src = ct_path_leaf<T, SETS>(p, row[1], sid, set_leaves, set);
+      src = ct_path_leaf<T, MODE>(p, row[1], sid, set_leaves, set, column);
     else
       src = arena + row[1];
     T* dst = arena + row[3];

@@ -28,7 +28,10 @@ per call of contract() and of one Contractor run with numpy arrays, with every l
 bound from torch tensors and the result written into a tensor, on the sliced Sycamore leg under path_kernel=1024 and on
 the bandwidth-bound step of the indirect leg, in one process); leaf sets (`--many`: Contractor.run_many against the loop of
 Contractor.run() over the same sets on the same Contractor, wall time per set, on the sliced Sycamore leg under
-path_kernel=1024: 1024 sets of one assignment each, and 8 sets of every assignment, in one process).  Engine figures are its
+path_kernel=1024: 1024 sets of one assignment each, and 8 sets of every assignment, in one process); sampling (`--sample`:
+one gate-by-gate walk of a random circuit of 1-qubit gates and CZs for all samples at once, through sampling.Sampler --
+walkers on the device, indexed leaves, the choice in a kernel -- and through the loop that run_many allows without them,
+on the same Contractors, in one process).  Engine figures are its
 own device time (events around the slice loop: the copies in and out are excluded, as they are for torch, whose
 operands stay on the device); the resident leg measures what that leaves out.
 """
@@ -732,6 +735,83 @@ def many(lines, depth, max_width, max_slices, reps=5, stacked=8):
     print("\n".join(notes), flush=True)
 
 
+def sample(lines, n_qubits=8, n_gates=40, n_samples=4096, reps=5):
+    """One walk of a fixed random circuit (1-qubit unitaries and CZs, seeded) for `n_samples` samples, two ways, on the
+    same Contractors (one per 1-qubit gate, the Sampler's) in one process.  (a) sampling.Sampler: Walkers on the device,
+    run_walkers + choose per 1-qubit gate, permute per CZ, one read of the bits.  (b) the best a caller can write with
+    run_many alone: the bits a torch tensor on the device, per 1-qubit gate the one-hot stacks of the closing leaves
+    built by torch indexing, one run_many with the measured qubit's index open (two amplitudes per walker), the choice
+    in torch (torch's own generator); per CZ nothing (it moves no bit), one copy of the bits to the host at the end.
+    Wall seconds (perf_counter, device synchronised), the minimum of `reps` walks after a warm-up and the spread."""
+    from tnco_amd import sampling
+    lines.append("")
+    rng = np.random.RandomState(17)
+    cz = np.diag([1, 1, 1, -1]).astype(np.complex64)
+
+    def unitary():
+        q, r = np.linalg.qr(rng.normal(size=(2, 2)) + 1j * rng.normal(size=(2, 2)))
+        return (q * (np.diag(r) / np.abs(np.diag(r)))).astype(np.complex64)
+
+    circuit = [(unitary(), (q,)) for q in range(n_qubits)]
+    while len(circuit) < n_gates:
+        if rng.randint(0, 2):
+            circuit.append((unitary(), (int(rng.randint(0, n_qubits)),)))
+        else:
+            a, b = rng.choice(n_qubits, 2, replace=False)
+            circuit.append((cz, (int(a), int(b))))
+    with sampling.Sampler(circuit, seed=0) as s:
+        drawing = sorted(s.contractors)
+        lines.append(f"## sampling: {n_qubits} qubits, {n_gates} gates ({len(drawing)} 1-qubit gates, {n_gates - len(drawing)} CZ), "
+                     f"{n_samples} samples, complex64, path_kernel=group=1024, one Contractor per 1-qubit gate (infinite-memory SA, "
+                     f"8 runs x 100 sweeps); wall seconds of one walk (perf_counter, device synchronised), the minimum of {reps} "
+                     "after a warm-up, spread = (max - min) / min; both rows in one process on the same Contractors")
+        eye = torch.eye(2, dtype=torch.complex64, device="cuda")
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(0)
+
+        def with_walkers():
+            return s.sample(n_samples)[0]
+
+        def with_run_many():
+            bits = torch.zeros((n_samples, n_qubits), dtype=torch.long, device="cuda")
+            for g in drawing:
+                c, closing = s.contractors[g]
+                q = s.gates[g][1][0]
+                if closing:
+                    amp = c.run_many({t: eye[bits[:, x]] for t, x in closing.items()}, group=1024).array
+                else:  # (nothing depends on the walker: one run for all)
+                    amp = c.run(out=torch.empty(2, dtype=torch.complex64, device="cuda")).array.expand(n_samples, 2)
+                p = amp.real.double() ** 2 + amp.imag.double() ** 2
+                u = torch.rand(n_samples, dtype=torch.float64, device="cuda", generator=gen)
+                bits[:, q] = (u * (p[:, 0] + p[:, 1]) < p[:, 1]).long()
+            return sampling.tally(bits.cpu().numpy())
+
+        rows = []
+        for name, call in (("Sampler.sample (walkers)", with_walkers), ("run_many + torch (no walkers)", with_run_many)):
+            hits = call()  # warm-up
+            times = []
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                call()
+                torch.cuda.synchronize()
+                times.append(time.perf_counter() - t0)
+            rows.append((name, min(times), (max(times) - min(times)) / min(times), len(hits)))
+    lines.append(f"{'way':>32} {'wall s':>10} {'spread':>7} {'us / sample':>12} {'ms / 1-qubit gate':>18} {'bitstrings seen':>16}")
+    for name, t, spread, seen in rows:
+        lines.append(f"{name:>32} {t:10.6f} {spread:7.3f} {t / n_samples * 1e6:12.3f} {t / len(drawing) * 1e3:18.4f} {seen:16d}")
+    (_, t_new, s_new, _), (_, t_old, s_old, _) = rows
+    both = s_new + s_old
+    lines.append(f"  run_many loop / walkers = {t_old / t_new:.2f}x (the two spreads together: {both:.3f})")
+    if t_new > t_old * (1 + both):
+        lines.append("  THE WALKERS ARE SLOWER than the run_many loop by more than the two spreads")
+    elif t_new * (1 + both) < t_old:
+        lines.append("  the walkers are faster than the run_many loop by more than the two spreads")
+    else:
+        lines.append("  the walkers and the run_many loop are within the two spreads of each other")
+    print("\n".join(lines[-5:]), flush=True)
+
+
 def compute(lines, n, depth, max_width, max_slices):
     """The compute mode against the plain engine in the same process: the large square step with compute=None (the tiled
     LDS kernel, the yardstick), compute="bf16x3" (ct_split_tiled_kernel) and storage="bfloat16" (ct_mfma_tiled_kernel), and
@@ -912,15 +992,19 @@ def main():
     ap.add_argument("--accumulate", action="store_true", help="only the wide-accumulation leg, appended to --out")
     ap.add_argument("--resident", action="store_true", help="only the resident (Contractor) leg, appended to --out")
     ap.add_argument("--many", action="store_true", help="only the run_many leg, appended to --out")
+    ap.add_argument("--sample", action="store_true", help="only the sampling leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect + a.reuse + a.accumulate + a.resident + a.many > 1:
-        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix, --indirect, --reuse, --accumulate, --resident and --many each "
+    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect + a.reuse + a.accumulate + a.resident + a.many + a.sample > 1:
+        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix, --indirect, --reuse, --accumulate, --resident, --many and --sample each "
                  "append one leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect or a.reuse or a.accumulate or a.resident or a.many:  # (the other legs' sections stay as they are)
-        if a.many:
+    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect or a.reuse or a.accumulate or a.resident or a.many or a.sample:  # (the other legs' sections stay as they are)
+        if a.sample:
+            lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
+            sample(lines)
+        elif a.many:
             lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
             many(lines, a.depth, a.max_width, min(a.max_slices, 2048))
         elif a.resident:
@@ -974,6 +1058,7 @@ def main():
     accumulate(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     resident(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     many(lines, a.depth, a.max_width, min(a.max_slices, 2048))
+    sample(lines)
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
