@@ -14,7 +14,7 @@ stored step and as the output step, at its smallest edge:
     tiled   M = N = 64 with K = 33 (the least K of the class, a k tail of 1 in the tiled kernel's 16-wide stage) and
             M = N = 65 with K = 48 (a second tile of one row and one column, no k tail);
     dot     K = 512 (the least) with 1 output (three quarters of the block idle), 5 (a second trip with one quarter at
-            work) and 8192 outputs (the most);
+            work) and 8192 outputs (the most); K = 515 with 5 outputs: a third trip over k that 3 lanes of a quarter take;
     stream  fewer outputs than the 1024 lanes of a block, and 1200: a second trip of the element loop.
 Two more index patterns:
     "batch"     an index h (3) held by A, B, C and the output: both steps have H = 3;
@@ -86,8 +86,10 @@ CASES = [
     bc.Chain("stream-1200-1200", (40, 7, 30, 30), ("stream", "stream")),
     Batch("batch-h3", (5, 7, 6, 4), ("stream", "stream")),
     Permuted("permuted-intermediate", (5, 7, 6, 4), ("stream", "stream")),
+    bc.Chain("dot-5-k515-stored", (5, 515, 1, 3), ("dot", "stream")),
 ]
 SMALL = CASES[10]
+DOT_TAIL, STREAM_TRIPS = CASES[14], CASES[11]  # a k tail in the dot class; a second trip of the element loop
 SUMMED, PLACED = bc.SUMMED, bc.PLACED
 
 for _c in CASES:

@@ -159,6 +159,23 @@ def test_groups_that_end_inside_a_set_at_its_end_and_beyond_it(ctr, dtype, stack
             assert_einsum(chain, leaf_set(sets, stacked, i), r.array[i], c.plan.inds, dtype, f"stacked {stacked} set {i}")
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.complex128], ids=["float32", "complex128"])
+def test_three_sets_of_three_assignments_in_groups_of_two_and_four(ctr, dtype):
+    """Every launch but the first starts inside a set, and both groups end inside one; the range (3, 6) holds the last
+    assignment of block p = 0 and the first two of p = 1."""
+    chain, R, stacked = pc.SMALL, 3, (0, 1, 2)
+    sets = mc.fill_sets(chain, dtype, R, seed=90)
+    with contractor(ctr, chain, dtype, slice_range=(3, 6)) as c:
+        want = oracles(c, sets, stacked)
+        stacks = {t: mc.stack(sets, t) for t in stacked}
+        for group in (2, 4):
+            what = f"{np.dtype(dtype).name} A = 3 R = 3 group = {group}"
+            r = c.run_many(stacks, group=group)
+            assert_many(c, r, want, R, group, what)
+            assert_counters(ctr, c, r, R, group, what)
+            assert r.path_launches == ((5, 5) if group == 2 else (3, 3)), what
+
+
 # ---- block placement and ranges --------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("slice_range", [None, (1, 11)], ids=["whole", "range-1-11"])

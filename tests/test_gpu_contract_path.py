@@ -118,6 +118,19 @@ def test_a_range_that_starts_off_a_multiple_of_the_group(ctr, dtype):
     assert not np.array_equal(bits(whole.array), bits(base.array))  # (assignments 0 and 11 are missing from the range)
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.complex128], ids=["float32", "complex128"])
+def test_three_assignments_in_groups_of_two_and_four(ctr, dtype):
+    """A last group of one member, and a group larger than the range; the range (3, 6) holds the last assignment of block
+    p = 0 and the first two of p = 1."""
+    chain = pc.SMALL
+    arrays = pc.fill(chain, dtype, 78)
+    call = lambda **more: ctr.contract(pc.PATH, chain.ts, arrays, chain.output, slices=pc.SLICES, slice_range=(3, 6),  # noqa: E731
+                                       **more)
+    base = call()
+    for G in (2, 4):
+        assert_fused_equals(ctr, base, call(path_kernel=G), G, 3, f"slice_range (3, 6) G = {G}")
+
+
 @pytest.mark.parametrize("chain", [pc.SUMMED, pc.PLACED], ids=["one_block", "a_block_per_assignment"])
 @pytest.mark.parametrize("dtype", [np.float32, np.complex128], ids=["float32", "complex128"])
 def test_members_that_all_share_a_block_and_members_that_never_do(ctr, chain, dtype):

@@ -144,6 +144,54 @@ def test_three_blocks_one_block_and_twelve_blocks(ctr, dtype, variant, slice_ran
             assert not a[:, 0].any() and not a[:, 11].any() and (a[:, 1:11] != 0).all()
 
 
+def assert_walkers_equal_runs(c, got, versions, leaf_qubit, bits, what):
+    """Output i of a run_walkers with every leaf indexed against run() over the versions that walker i's bits select (the
+    leaves are bound no longer afterwards)."""
+    assert sorted(leaf_qubit) == [0, 1, 2]
+    for i in range(len(bits)):
+        one = c.run([versions[t][bits[i, leaf_qubit[t]]] for t in range(3)])
+        assert np.array_equal(bits_of(got[i]), bits_of(one.array)), f"{what}: walker {i} differs from run()"
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.complex128], ids=["float32", "complex128"])
+@pytest.mark.parametrize("chain", [pc.DOT_TAIL, pc.STREAM_TRIPS], ids=[pc.DOT_TAIL.name, pc.STREAM_TRIPS.name])
+def test_a_dot_step_with_a_k_tail_and_a_second_trip_of_the_element_loop(ctr, chain, dtype):
+    """The paths of ct_path_step that the small chain does not reach: the dot class with 5 outputs (a second trip with one
+    quarter of the block at work) and K = 515 (a k tail), and 1200 outputs of one lane each (the 1024 lanes go round twice)."""
+    R, group = 3, 5
+    sets = mc.fill_sets(chain, dtype, 2, seed=94)
+    versions = {t: mc.stack(sets, t) for t in range(3)}
+    bits = random_bits(R, seed=12)
+    assert len({tuple(row[[1, 3, 0]]) for row in bits}) == R  # (the walkers read different leaves)
+    what = f"{chain.name} {np.dtype(dtype).name}"
+    with contractor(ctr, chain, dtype) as c, ctr.Walkers(R, N_QUBITS) as w:
+        c.bind({t: sets[0][t] for t in range(3)})
+        c.bind_versions(versions)
+        w.write(bits)
+        got = check_walk(c, w, versions, INDEXED[2], bits, group, what)
+        assert_walkers_equal_runs(c, got, versions, INDEXED[2], bits, what)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.complex128], ids=["float32", "complex128"])
+def test_three_walkers_of_three_assignments_in_groups_of_two_and_four(ctr, dtype):
+    """Every launch but the first starts inside a walker, and both groups end inside one."""
+    chain, R = pc.SMALL, 3
+    sets = mc.fill_sets(chain, dtype, 2, seed=95)
+    versions = {t: mc.stack(sets, t) for t in range(3)}
+    bits = random_bits(R, seed=12)
+    with contractor(ctr, chain, dtype, slice_range=(3, 6)) as c, ctr.Walkers(R, N_QUBITS) as w:
+        c.bind({t: sets[0][t] for t in range(3)})
+        c.bind_versions(versions)
+        w.write(bits)
+        got = {}
+        for group in (2, 4):
+            what = f"{np.dtype(dtype).name} A = 3 R = 3 group = {group}"
+            got[group] = check_walk(c, w, versions, INDEXED[2], bits, group, what)
+            assert c.run_walkers(w, INDEXED[2], group=group).path_launches == ((5, 5) if group == 2 else (3, 3)), what
+        for group in (2, 4):
+            assert_walkers_equal_runs(c, got[group], versions, INDEXED[2], bits, f"group = {group}")
+
+
 # ---- the choice ------------------------------------------------------------------------------------------------------------
 
 N_PAIRS, N_INDEX = 1024, 10

@@ -487,6 +487,20 @@ def _is_count(most):
     return lambda v: not isinstance(v, bool) and isinstance(v, int) and 1 <= v <= most
 
 
+def _is_index(v, lo, hi) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer)) and lo <= v < hi
+
+
+def _ptr(a):
+    """A numpy array's memory as an argument of the library (the pointer keeps the array alive)."""
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _i64(v):
+    """A sequence of integers as an int64 table for the library; None for an empty one."""
+    return _ptr(np.array(v, np.int64)) if len(v) else None
+
+
 def _is_order(v) -> bool:
     """What can be said without the network: that a sequence names every sliced index once is checked where they are known."""
     if isinstance(v, str):
@@ -1282,7 +1296,6 @@ def _create(L, p: Plan, device: int):
 def _describe(p: Plan, device: int):
     """(the tnco_hip_contract_desc of the plan, the arrays its pointers refer to: to be kept until create returns)."""
     from . import _lib
-    i64p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     keep = dict(leaf_numel=np.ascontiguousarray(p.leaf_numel), leaf_sl=np.ascontiguousarray(p.leaf_sl),
                 perms=np.ascontiguousarray(p.perms), steps=np.ascontiguousarray(p.steps),
                 slice_dims=np.array(p.slice_dims, np.int64).reshape(-1),
@@ -1290,19 +1303,19 @@ def _describe(p: Plan, device: int):
     d = _lib.ContractDesc()
     code = DTYPES[p.dtype] if p.storage is None else STORAGES[p.storage] + (p.dtype.kind == "c")
     d.dtype, d.device, d.max_axes = code, device, MAX_AXES
-    d.n_leaves, d.leaf_numel, d.leaf_sl = len(p.leaf_numel), i64p(keep["leaf_numel"]), i64p(keep["leaf_sl"])
-    d.n_perms, d.perms = len(p.perms), i64p(keep["perms"])
-    d.n_steps, d.steps = len(p.steps), i64p(keep["steps"])
+    d.n_leaves, d.leaf_numel, d.leaf_sl = len(p.leaf_numel), _ptr(keep["leaf_numel"]), _ptr(keep["leaf_sl"])
+    d.n_perms, d.perms = len(p.perms), _ptr(keep["perms"])
+    d.n_steps, d.steps = len(p.steps), _ptr(keep["steps"])
     d.arena_elems, d.out_numel = p.arena_elems, p.out_numel
-    d.n_slice_dims, d.slice_dims = len(p.slice_dims), i64p(keep["slice_dims"])
-    d.n_block, d.block_slices = len(p.block_inds), i64p(keep["block"])
+    d.n_slice_dims, d.slice_dims = len(p.slice_dims), _ptr(keep["slice_dims"])
+    d.n_block, d.block_slices = len(p.block_inds), _ptr(keep["block"])
     d.slice_start, d.slice_stop = p.slice_range
     if p.row_steps is not None:
         keep.update(row_steps=np.ascontiguousarray(p.row_steps), row_maps=np.ascontiguousarray(p.row_maps))
-        d.row_steps, d.n_row_maps, d.row_maps = i64p(keep["row_steps"]), p.row_maps.size, i64p(keep["row_maps"])
+        d.row_steps, d.n_row_maps, d.row_maps = _ptr(keep["row_steps"]), p.row_maps.size, _ptr(keep["row_maps"])
     if p.scaling is not None:
         keep.update(stage_refs=np.ascontiguousarray(p.stage_refs, np.int64))
-        d.scaling, d.stage_refs = 1, i64p(keep["stage_refs"])
+        d.scaling, d.stage_refs = 1, _ptr(keep["stage_refs"])
     return d, keep
 
 
@@ -1311,10 +1324,10 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
     try:
         _set_modes(L, h, p)
         if p.scaling is not None:
-            _lib.check(L.tnco_hip_contract_set_exponents(h, leaf_exps.ctypes.data_as(C.c_void_p)))
+            _lib.check(L.tnco_hip_contract_set_exponents(h, _ptr(leaf_exps)))
         staging = np.empty(p.out_numel, p.dtype)
         ptrs = (C.c_void_p * max(1, len(leaves)))(*[a.ctypes.data for a in leaves])
-        _lib.check(L.tnco_hip_contract_run(h, ptrs, staging.ctypes.data_as(C.c_void_p)))
+        _lib.check(L.tnco_hip_contract_run(h, ptrs, _ptr(staging)))
         fields = _read_counters(L, h, p)
     finally:
         L.tnco_hip_contract_destroy(h)
@@ -1324,8 +1337,7 @@ def _run_handle(L, h, p: Plan, leaves, leaf_exps) -> ContractionResult:
 def _set_modes(L, h, p: Plan) -> None:
     """The set calls of the plan's keywords on a new handle (the leaves' exponents of scaling apart: they belong to the arrays)."""
     from . import _lib
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    i64 = lambda a: None if a is None else np.ascontiguousarray(a, np.int64)  # noqa: E731
+    i64 = lambda a: None if a is None else np.ascontiguousarray(a, np.int64)  # noqa: E731 -- (an array: passed below)
     matrix, split = p.compute == "matrix", p.compute not in (None, "matrix")
     # (is it on, entry point, arguments), in an order the library takes.  Nothing hoisted, every period 1 or nothing
     # folded: the run of the plan without the keyword
@@ -1340,13 +1352,12 @@ def _set_modes(L, h, p: Plan) -> None:
         (p.accumulate is not None, L.tnco_hip_contract_set_accumulate, (1,)))
     for on, entry, args in setters:
         if on:
-            _lib.check(entry(h, *(ptr(a) if isinstance(a, np.ndarray) else a for a in args)))
+            _lib.check(entry(h, *(_ptr(a) if isinstance(a, np.ndarray) else a for a in args)))
 
 
 def _read_counters(L, h, p: Plan) -> dict:
     """The fields of a ContractionResult that the handle knows after a run: every one but `inds` and `array`."""
     from . import _lib
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     matrix, split = p.compute == "matrix", p.compute not in (None, "matrix")
     wide = p.accumulate is not None
     # (is it on, entry point, length, field of the result)
@@ -1361,15 +1372,15 @@ def _read_counters(L, h, p: Plan) -> dict:
         (p.indirect, L.tnco_hip_contract_indirect_launches, len(INDIRECT_KERNEL_PATHS), "indirect_launches"))
     exponents, counted = None, {}
     stats = np.zeros(4, np.int64)
-    _lib.check(L.tnco_hip_contract_stats(h, ptr(stats)))
+    _lib.check(L.tnco_hip_contract_stats(h, _ptr(stats)))
     if p.scaling is not None:
         slots = np.zeros(len(p.leaf_numel) + len(p.steps), np.int32)
-        _lib.check(L.tnco_hip_contract_exponents(h, ptr(slots)))
+        _lib.check(L.tnco_hip_contract_exponents(h, _ptr(slots)))
         exponents = tuple(int(v) for v in slots)
     for on, entry, length, name in counters:
         if on:
             counts = np.zeros(length, np.int64)
-            _lib.check(entry(h, ptr(counts)))
+            _lib.check(entry(h, _ptr(counts)))
             counted[name] = int(counts[0]) if length == 1 else tuple(int(v) for v in counts)
     return dict(macs=int(stats[0]), n_slices=p.slice_range[1] - p.slice_range[0], peak_device_bytes=int(stats[2]),
                 launches=int(stats[1]), device_s=float(stats[3]) * 1e-9, scaling=p.scaling, exponents=exponents,
@@ -1377,14 +1388,33 @@ def _read_counters(L, h, p: Plan) -> dict:
                 reused=p.reused, indirect=p.indirect, **counted)
 
 
+def _held_axes(p: Plan) -> tuple:
+    """The axes of one output buffer of a plan without projections, [block axes][the others], by name."""
+    return p.block_inds + tuple(x for x in p.inds if x not in set(p.slice_inds))
+
+
+def _result_view(p: Plan, staging, sets=None) -> np.ndarray:
+    """`staging`, one output buffer ([block axes][the others]) or `sets` of them back to back, in the result's own axis
+    order, the set axis first: a view."""
+    held, lead = _held_axes(p), () if sets is None else (sets,)
+    array = staging.reshape(lead + tuple(p.shape[p.inds.index(x)] for x in held))
+    return array.transpose(list(range(len(lead))) + [len(lead) + held.index(x) for x in p.inds])
+
+
+def _result_axes(p: Plan, sets=None) -> tuple:
+    """(dims, strides): where the elements of the output buffers, in the order `_result_view` reads them, lie in a
+    C-contiguous result of shape (sets,) + p.shape."""
+    lead = () if sets is None else (sets,)
+    at = [p.inds.index(x) for x in _held_axes(p)]
+    steps = _c_strides(lead + tuple(p.shape))
+    return merge_axes(list(lead) + [p.shape[q] for q in at], list(steps[:len(lead)]) + [steps[len(lead) + q] for q in at])
+
+
 def _host_layout(p: Plan, staging) -> np.ndarray:
     """The output buffer, [block axes][the others] (with projections: [block axes][rows of the final tensor][the
     others]), in the result's own axis order; the distinct rows expanded to the P projections with one take."""
     if p.out_rows is None:
-        rest = tuple(x for x in p.inds if x not in set(p.slice_inds))
-        held = p.block_inds + rest
-        array = staging.reshape(tuple(p.shape[p.inds.index(x)] for x in held))
-        return array.transpose([held.index(x) for x in p.inds]).copy(order="C")  # (0-d stays 0-d)
+        return _result_view(p, staging).copy(order="C")  # (0-d stays 0-d)
     n_rows, row_of_proj = p.out_rows
     named = p.inds[1:]  # (position 0 is the projection axis)
     rest = tuple(x for x in named if x not in set(p.slice_inds))
@@ -1640,7 +1670,7 @@ class Contractor:
             return (0, 0)
         from . import _lib
         counts = np.zeros(2, np.int64)
-        _lib.check(self._lib.tnco_hip_contract_io_launches(self._h, counts.ctypes.data_as(C.c_void_p)))
+        _lib.check(self._lib.tnco_hip_contract_io_launches(self._h, _ptr(counts)))
         return (int(counts[0]), int(counts[1]))
 
     def bind(self, leaves) -> None:
@@ -1673,7 +1703,6 @@ class Contractor:
         if missing:
             raise ValueError(f"leaf {missing[0]} is neither bound nor given.")
         to_device = torch_out or (out is None and torch_in)
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
         L, h = self._handle()
         # before anything is loaded: a bound leaf that a run is given another array for is no longer the one the handle
         # holds, also when the run fails half way
@@ -1682,7 +1711,7 @@ class Contractor:
             self._note_exponents(ready)
             staging = np.empty(p.out_numel, p.dtype)
             ptrs = (C.c_void_p * max(1, len(ready)))(*[ready[t][0].ctypes.data for t in range(len(ready))])
-            _lib.check(L.tnco_hip_contract_run(h, ptrs, ptr(staging)))
+            _lib.check(L.tnco_hip_contract_run(h, ptrs, _ptr(staging)))
         else:
             self._load(ready, torch_in)
             if to_device:
@@ -1690,17 +1719,12 @@ class Contractor:
                 if out is None:
                     kind = next(k for k, v in _torch_dtypes().items() if v == p.dtype)
                     out = torch.empty(p.shape, dtype=kind, device=f"cuda:{self.device}")
-                rest = tuple(x for x in p.inds if x not in set(p.slice_inds))
-                held = p.block_inds + rest  # the output buffer's axes; where each of them goes in the result
-                at = [p.inds.index(x) for x in held]
-                steps = _c_strides(p.shape)
-                dims, strides = merge_axes([p.shape[q] for q in at], [steps[q] for q in at])
+                dims, strides = _result_axes(p)
                 torch.cuda.synchronize(self.device)
-                i64 = lambda v: ptr(np.array(v, np.int64)) if v else None  # noqa: E731
-                _lib.check(L.tnco_hip_contract_run_loaded(h, C.c_void_p(out.data_ptr()), 1, len(dims), i64(dims), i64(strides)))
+                _lib.check(L.tnco_hip_contract_run_loaded(h, C.c_void_p(out.data_ptr()), 1, len(dims), _i64(dims), _i64(strides)))
             else:
                 staging = np.empty(p.out_numel, p.dtype)
-                _lib.check(L.tnco_hip_contract_run_loaded(h, ptr(staging), 0, 0, None, None))
+                _lib.check(L.tnco_hip_contract_run_loaded(h, _ptr(staging), 0, 0, None, None))
         fields = _read_counters(L, h, p)
         if to_device:
             return ContractionResult(p.inds, out, **fields)
@@ -1734,42 +1758,30 @@ class Contractor:
         if out is not None:
             self._check_out(out, torch_out, (sets,) + tuple(p.shape))
         to_device = torch_out or (out is None and torch_in)
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        i64 = lambda v: ptr(np.array(v, np.int64)) if len(v) else None  # noqa: E731
         L, h = self._handle()
         if torch_in or to_device:
             import torch
             torch.cuda.synchronize(self.device)
         for t, (a, code, dims, strides) in ready.items():
             where = 1 if torch_in else 0
-            src = C.c_void_p(a.data_ptr()) if torch_in else ptr(a)
-            _lib.check(L.tnco_hip_contract_load_leaf_sets(h, t, sets, src, where, code, len(dims), i64(dims), i64(strides)))
-        rest = tuple(x for x in p.inds if x not in set(p.slice_inds))
-        held = p.block_inds + rest  # the axes of one output buffer; where each of them goes in a set of the result
-        at = [p.inds.index(x) for x in held]
+            src = C.c_void_p(a.data_ptr()) if torch_in else _ptr(a)
+            _lib.check(L.tnco_hip_contract_load_leaf_sets(h, t, sets, src, where, code, len(dims), _i64(dims), _i64(strides)))
         if to_device:
             if out is None:
                 kind = next(k for k, v in _torch_dtypes().items() if v == p.dtype)
                 out = torch.empty((sets,) + tuple(p.shape), dtype=kind, device=f"cuda:{self.device}")
-            steps = _c_strides((sets,) + tuple(p.shape))
-            dims, strides = merge_axes([sets] + [p.shape[q] for q in at], [steps[0]] + [steps[1 + q] for q in at])
-            _lib.check(L.tnco_hip_contract_run_sets(h, sets, group, C.c_void_p(out.data_ptr()), 1, len(dims), i64(dims), i64(strides)))
+            dims, strides = _result_axes(p, sets)
+            _lib.check(L.tnco_hip_contract_run_sets(h, sets, group, C.c_void_p(out.data_ptr()), 1, len(dims), _i64(dims), _i64(strides)))
             array = out
         else:
             staging = np.empty((sets, p.out_numel), p.dtype)
-            _lib.check(L.tnco_hip_contract_run_sets(h, sets, group, ptr(staging), 0, 0, None, None))
-            array = staging.reshape((sets,) + tuple(p.shape[q] for q in at))
-            array = array.transpose([0] + [1 + held.index(x) for x in p.inds]).copy(order="C")
+            _lib.check(L.tnco_hip_contract_run_sets(h, sets, group, _ptr(staging), 0, 0, None, None))
+            array = _result_view(p, staging, sets).copy(order="C")
             if out is not None:
                 np.copyto(out, array)
                 array = out
         self._grow(sets, group, ready)
-        stats, counts = np.zeros(4, np.int64), np.zeros(2, np.int64)
-        _lib.check(L.tnco_hip_contract_stats(h, ptr(stats)))
-        _lib.check(L.tnco_hip_contract_sets_launches(h, ptr(counts)))
-        members = sets * (p.slice_range[1] - p.slice_range[0])
-        return ManyResult(("set",) + tuple(p.inds), array, sets, min(group, members), int(stats[0]), int(stats[1]),
-                          (int(counts[0]), int(counts[1])), int(stats[2]), float(stats[3]) * 1e-9)
+        return self._many_result(sets, group, array)
 
     def bind_versions(self, versions) -> None:
         """Loads the two versions of the leaves {leaf number: array of shape (2,) + the leaf's shape} now; they stay until
@@ -1788,8 +1800,6 @@ class Contractor:
                 raise ValueError(f"the versions of leaf {t} have the shape {shape}, not (2,) + the leaf's {self._shapes[t]}.")
         kinds = [(kind, self._prepare_stacks({t: a for t, a in given.items() if _is_tensor(a) == kind}, kind)[1])
                  for kind in (False, True)]
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        i64 = lambda v: ptr(np.array(v, np.int64)) if len(v) else None  # noqa: E731
         for kind, ready in kinds:
             if not ready:
                 continue
@@ -1799,8 +1809,8 @@ class Contractor:
                 torch.cuda.synchronize(self.device)
             for t, (a, code, dims, strides) in ready.items():
                 self._versions.discard(t)
-                src = C.c_void_p(a.data_ptr()) if kind else ptr(a)
-                _lib.check(L.tnco_hip_contract_load_leaf_versions(h, t, 2, src, int(kind), code, len(dims), i64(dims), i64(strides)))
+                src = C.c_void_p(a.data_ptr()) if kind else _ptr(a)
+                _lib.check(L.tnco_hip_contract_load_leaf_versions(h, t, 2, src, int(kind), code, len(dims), _i64(dims), _i64(strides)))
                 self._versions.add(t)
 
     def _check_walk(self, walkers) -> None:
@@ -1819,16 +1829,16 @@ class Contractor:
         `group` as in `run_many`.  Refuses what `run_many` refuses of the Contractor."""
         from . import _lib
         self._check_open()
-        p, n = self.plan, len(self._shapes)
+        n = len(self._shapes)
         group = self._check_many(group, "run_walkers")
         self._check_walk(walkers)
         if not isinstance(leaf_qubit, dict):
             raise ValueError("'leaf_qubit' must be a dict {leaf number: qubit}.")
         table = np.full(max(n, 1), -1, np.int64)
         for t, q in leaf_qubit.items():
-            if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t < n:
+            if not _is_index(t, 0, n):
                 raise ValueError(f"{t!r} is not a leaf of the plan (0 to {n - 1}).")
-            if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 0 <= q < walkers.n_qubits:
+            if not _is_index(q, 0, walkers.n_qubits):
                 raise ValueError(f"{q!r} is not a qubit of the walkers (0 to {walkers.n_qubits - 1}).")
             if int(t) not in self._versions:
                 raise ValueError(f"leaf {int(t)} has no versions: call bind_versions first.")
@@ -1836,22 +1846,14 @@ class Contractor:
         missing = [t for t in range(n) if table[t] < 0 and t not in self._bound]
         if missing:
             raise ValueError(f"leaf {missing[0]} is neither bound nor indexed by a qubit.")
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
         L, h = self._handle()
         self._walked = None
-        _lib.check(L.tnco_hip_contract_run_walkers(h, walkers._handle(), ptr(table), group))
+        _lib.check(L.tnco_hip_contract_run_walkers(h, walkers._handle(), _ptr(table), group))
         self._walked = walkers
         sets = walkers.n_walkers if leaf_qubit else 1  # (no leaf indexed: one output serves every walker, one set is run)
-        caps = self._many  # (what the handle reserved: many_bytes; the leaves last stacked stay those of the last run_many)
-        caps["members"] = max(caps["members"], min(group, sets * (p.slice_range[1] - p.slice_range[0])))
-        caps["out"] = max(caps["out"], sets)
-        caps["walked"], self._walked_sets = True, sets
-        stats, counts = np.zeros(4, np.int64), np.zeros(2, np.int64)
-        _lib.check(L.tnco_hip_contract_stats(h, ptr(stats)))
-        _lib.check(L.tnco_hip_contract_sets_launches(h, ptr(counts)))
-        members = sets * (p.slice_range[1] - p.slice_range[0])
-        return ManyResult(("set",) + tuple(p.inds), None, sets, min(group, members), int(stats[0]), int(stats[1]),
-                          (int(counts[0]), int(counts[1])), int(stats[2]), float(stats[3]) * 1e-9)
+        self._grow(sets, group)
+        self._many["walked"], self._walked_sets = True, sets
+        return self._many_result(sets, group, None)
 
     def walker_outputs(self, walkers) -> np.ndarray:
         """The outputs that the last `run_walkers` over `walkers` left on the device, as `run_many` lays its array out:
@@ -1864,12 +1866,8 @@ class Contractor:
         p, sets = self.plan, self._walked_sets
         L, h = self._handle()
         staging = np.empty((sets, p.out_numel), p.dtype)
-        _lib.check(L.tnco_hip_contract_walkers_output(h, walkers._handle(), staging.ctypes.data_as(C.c_void_p)))
-        rest = tuple(x for x in p.inds if x not in set(p.slice_inds))
-        held = p.block_inds + rest
-        at = [p.inds.index(x) for x in held]
-        array = staging.reshape((sets,) + tuple(p.shape[q] for q in at))
-        array = array.transpose([0] + [1 + held.index(x) for x in p.inds])
+        _lib.check(L.tnco_hip_contract_walkers_output(h, walkers._handle(), _ptr(staging)))
+        array = _result_view(p, staging, sets)
         return np.broadcast_to(array, (walkers.n_walkers,) + array.shape[1:]).copy(order="C")
 
     def choose(self, walkers, qubit, step) -> None:
@@ -1882,9 +1880,9 @@ class Contractor:
         self._check_walk(walkers)
         if self.plan.out_numel != 2:
             raise ValueError(f"the output of the plan holds {self.plan.out_numel} elements, not the 2 amplitudes of a choice.")
-        if isinstance(qubit, bool) or not isinstance(qubit, (int, np.integer)) or not 0 <= qubit < walkers.n_qubits:
+        if not _is_index(qubit, 0, walkers.n_qubits):
             raise ValueError(f"{qubit!r} is not a qubit of the walkers (0 to {walkers.n_qubits - 1}).")
-        if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 0 <= step < 2 ** 32:
+        if not _is_index(step, 0, 2 ** 32):
             raise ValueError("'step' must be an integer from 0 to 2^32 - 1.")
         if self._walked is not walkers:
             raise ValueError("the last run of the Contractor was not a 'run_walkers' over these walkers.")
@@ -1901,12 +1899,12 @@ class Contractor:
         self._check_open()
         p = self.plan
         group = self._check_many(group)
-        if isinstance(n_sets, bool) or not isinstance(n_sets, (int, np.integer)) or n_sets < 1:
+        if not _is_index(n_sets, 1, math.inf):
             raise ValueError("'n_sets' must be a positive integer.")
         n = len(self._shapes)
         leaves = self._many["last"] if leaves is None else tuple(leaves)
         for t in leaves:
-            if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t < n:
+            if not _is_index(t, 0, n):
                 raise ValueError(f"{t!r} is not a leaf of the plan (0 to {n - 1}).")
         item, A = p.dtype.itemsize, p.slice_range[1] - p.slice_range[0]
         block = p.out_numel // math.prod(p.shape[p.inds.index(x)] for x in p.block_inds)
@@ -1940,7 +1938,7 @@ class Contractor:
             raise NotImplementedError(f"'{name}' needs a plan with steps.")
         if group is None:
             return MAX_PATH_KERNEL
-        if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or not 1 <= group <= MAX_PATH_KERNEL:
+        if not _is_index(group, 1, MAX_PATH_KERNEL + 1):
             raise ValueError(f"'group' must be None or an integer from 1 to {MAX_PATH_KERNEL}.")
         return int(group)
 
@@ -1982,14 +1980,27 @@ class Contractor:
             ready[t] = (a, DTYPES[src], dims, strides)
         return sets, ready
 
-    def _grow(self, sets, group, ready) -> None:
-        """Notes what a run_many made the handle reserve (many_bytes)."""
+    def _grow(self, sets, group, ready=None) -> None:
+        """Notes what a run_many (`ready`: its stacks) or a run_walkers (None: the leaves last stacked stay those of the
+        last run_many) made the handle reserve (many_bytes)."""
         caps, p = self._many, self.plan
-        for t in ready:
-            caps["stacks"][t] = max(caps["stacks"].get(t, 0), sets)
         caps["members"] = max(caps["members"], min(group, sets * (p.slice_range[1] - p.slice_range[0])))
         caps["out"] = max(caps["out"], sets)
-        caps["last"] = tuple(ready)
+        if ready is not None:
+            for t in ready:
+                caps["stacks"][t] = max(caps["stacks"].get(t, 0), sets)
+            caps["last"] = tuple(ready)
+
+    def _many_result(self, sets, group, array) -> ManyResult:
+        """The ManyResult of the run over `sets` sets that the handle has just made."""
+        from . import _lib
+        p, (L, h) = self.plan, self._handle()
+        stats, counts = np.zeros(4, np.int64), np.zeros(2, np.int64)
+        _lib.check(L.tnco_hip_contract_stats(h, _ptr(stats)))
+        _lib.check(L.tnco_hip_contract_sets_launches(h, _ptr(counts)))
+        members = sets * (p.slice_range[1] - p.slice_range[0])
+        return ManyResult(("set",) + tuple(p.inds), array, sets, min(group, members), int(stats[0]), int(stats[1]),
+                          (int(counts[0]), int(counts[1])), int(stats[2]), float(stats[3]) * 1e-9)
 
     def _check_open(self) -> None:
         if self._closed:
@@ -2001,7 +2012,7 @@ class Contractor:
         if isinstance(arrays, dict):
             given = dict(arrays)
             for t in given:
-                if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t < n:
+                if not _is_index(t, 0, n):
                     raise ValueError(f"{t!r} is not a leaf of the plan (0 to {n - 1}).")
             given = {int(t): a for t, a in given.items()}
         else:
@@ -2090,7 +2101,7 @@ class Contractor:
             return
         for t, (_a, e) in ready.items():
             self._exps[t] = e
-        _lib.check(self._lib.tnco_hip_contract_set_exponents(self._h, self._exps.ctypes.data_as(C.c_void_p)))
+        _lib.check(self._lib.tnco_hip_contract_set_exponents(self._h, _ptr(self._exps)))
 
     def _load(self, ready, torch_in) -> None:
         from . import _lib
@@ -2102,21 +2113,12 @@ class Contractor:
             code = DTYPES[p.dtype] if p.storage is None else STORAGES[p.storage] + (p.dtype.kind == "c")
             self._note_exponents(ready)
             for t, (a, _e) in ready.items():
-                n = np.array([p.leaf_numel[t]], np.int64)
-                _lib.check(L.tnco_hip_contract_load_leaf(h, t, a.ctypes.data_as(C.c_void_p), 0, code, 1,
-                                                         n.ctypes.data_as(C.c_void_p), None))
+                _lib.check(L.tnco_hip_contract_load_leaf(h, t, _ptr(a), 0, code, 1, _i64([p.leaf_numel[t]]), None))
             return
         import torch
         torch.cuda.synchronize(self.device)
         for t, (a, code, dims, strides) in ready.items():
-            d, s = np.array(dims, np.int64), np.array(strides, np.int64)
-            _lib.check(L.tnco_hip_contract_load_leaf(h, t, C.c_void_p(a.data_ptr()), 1, code, len(dims),
-                                                     d.ctypes.data_as(C.c_void_p) if len(dims) else None,
-                                                     s.ctypes.data_as(C.c_void_p) if len(dims) else None))
-
-
-def _is_index(v, lo, hi) -> bool:
-    return not isinstance(v, bool) and isinstance(v, (int, np.integer)) and lo <= v < hi
+            _lib.check(L.tnco_hip_contract_load_leaf(h, t, C.c_void_p(a.data_ptr()), 1, code, len(dims), _i64(dims), _i64(strides)))
 
 
 class Walkers:
@@ -2179,7 +2181,7 @@ class Walkers:
         from . import _lib
         w = self._handle()
         bits, dead = np.empty((self.n_qubits, self.n_walkers), np.uint8), np.empty(self.n_walkers, np.uint8)
-        _lib.check(self._lib.tnco_hip_walkers_read(w, bits.ctypes.data_as(C.c_void_p), dead.ctypes.data_as(C.c_void_p)))
+        _lib.check(self._lib.tnco_hip_walkers_read(w, _ptr(bits), _ptr(dead)))
         return np.ascontiguousarray(bits.T), dead.astype(bool)
 
     @property
@@ -2203,7 +2205,7 @@ class Walkers:
             raise ValueError("'bits' must hold zeros and ones only.")
         table = np.ascontiguousarray(bits.T, dtype=np.uint8)
         w = self._handle()
-        _lib.check(self._lib.tnco_hip_walkers_write(w, table.ctypes.data_as(C.c_void_p)))
+        _lib.check(self._lib.tnco_hip_walkers_write(w, _ptr(table)))
 
     def reset(self) -> None:
         """Every bit and every dead flag 0."""
@@ -2229,4 +2231,4 @@ class Walkers:
             raise ValueError(f"'table' must be a permutation of 0 to {n - 1}.")
         qs, tb = np.array(qubits, np.int64), np.array(table, np.uint8)
         w = self._handle()
-        _lib.check(self._lib.tnco_hip_walkers_permute(w, len(qubits), qs.ctypes.data_as(C.c_void_p), tb.ctypes.data_as(C.c_void_p)))
+        _lib.check(self._lib.tnco_hip_walkers_permute(w, len(qubits), _ptr(qs), _ptr(tb)))

@@ -1205,67 +1205,81 @@ int64_t macs_per_assignment(const tnco_hip_contract_s* c) {
   return per_slice;
 }
 
-// The fused loop of a handle with a path kernel: per group of up to c->path_group assignments one ct_path_kernel and
-// one ct_path_reduce_kernel.
+// The fused loop of every kind of member (contract_path.h): `members` members in groups of `group` consecutive ones, per
+// group member(m0, n), the launch of the path kernel of the kind over the members [m0, m0 + n), and fold(m0, n), the
+// launch of the kernel that folds their blocks; counters: the two launch counts of the kind.
+template <class Member, class Fold>
+int run_groups(tnco_hip_contract_s* c, int64_t members, int64_t group, int64_t* counters, Member member, Fold fold) {
+  const int64_t per_slice = macs_per_assignment(c);
+  for (int64_t m0 = 0; m0 < members; m0 += group) {
+    const int64_t n = std::min(group, members - m0);
+    member(m0, n);
+    CT_TRY(hipGetLastError());
+    fold(m0, n);
+    CT_TRY(hipGetLastError());
+    c->launches += 2;
+    counters[0] += 1, counters[1] += 1;
+    c->macs += per_slice * n;
+  }
+  return TNCO_HIP_OK;
+}
+
+dim3 fold_grid(const tnco_hip_contract_s* c) { return dim3((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048)); }
+
+// A handle with a path kernel: the members are the assignments of the plan's range, c->path_group per ct_path_kernel, and
+// ct_path_reduce_kernel folds them.
 template <class T>
 int run_path(tnco_hip_contract_s* c) {
   constexpr bool single = std::is_same<T, float>::value || std::is_same<T, cplx<float>>::value;
   const bool wide = single && c->accumulate;  // the folds go into the accumulator (run_path: a plan with steps)
   const int64_t* d_place = nullptr;
   PathArgs a = path_args(c, &d_place);
-  const int64_t per_slice = macs_per_assignment(c);
-  for (int64_t sid = c->start; sid < c->stop; sid += c->path_group) {
-    const int64_t n = std::min(c->path_group, c->stop - sid);
-    a.sid0 = sid;
-    hipLaunchKernelGGL(ct_path_kernel<T>, dim3((unsigned)n), dim3(PATH_LANES), 0, c->stream, a);
-    CT_TRY(hipGetLastError());
-    const dim3 grid((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048));
-    if constexpr (single) {
-      if (wide)
-        hipLaunchKernelGGL(ct_acc_path_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (ct_wide_t<T>*)c->d_acc,
-                           (const T*)c->d_path_stage, c->block_numel, (int)n, d_place + (sid - c->start));
-    }
-    if (!wide)
-      hipLaunchKernelGGL(ct_path_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (T*)c->d_out, (const T*)c->d_path_stage,
-                         c->block_numel, (int)n, d_place + (sid - c->start));
-    CT_TRY(hipGetLastError());
-    c->launches += 2;
-    c->path_launches[0] += 1, c->path_launches[1] += 1;
-    c->acc_launches[0] += wide;
-    c->macs += per_slice * n;
-  }
+  const dim3 grid = fold_grid(c);
+  const int rc = run_groups(
+      c, c->stop - c->start, c->path_group, c->path_launches,
+      [&](int64_t m0, int64_t n) {
+        a.sid0 = c->start + m0;
+        hipLaunchKernelGGL(ct_path_kernel<T>, dim3((unsigned)n), dim3(PATH_LANES), 0, c->stream, a);
+      },
+      [&](int64_t m0, int64_t n) {
+        if constexpr (single) {
+          if (wide)
+            hipLaunchKernelGGL(ct_acc_path_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (ct_wide_t<T>*)c->d_acc,
+                               (const T*)c->d_path_stage, c->block_numel, (int)n, d_place + m0);
+        }
+        if (!wide)
+          hipLaunchKernelGGL(ct_path_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (T*)c->d_out, (const T*)c->d_path_stage,
+                             c->block_numel, (int)n, d_place + m0);
+        c->acc_launches[0] += wide;
+      });
+  if (rc) return rc;
   if constexpr (single) {
     if (wide) return narrow_accumulator<T>(c);
   }
   return TNCO_HIP_OK;
 }
 
-// The fused loop over leaf sets: the members (set, assignment) of n_sets sets, set-major, in groups of `group`
-// consecutive ones, one ct_sets_path_kernel and one ct_sets_reduce_kernel per group (contract_sets.h).  The caller has made
-// room for `group` members and n_sets outputs and has uploaded the leaf pointers and set strides.
-template <class T>
-int run_sets(tnco_hip_contract_s* c, int64_t n_sets, int64_t group) {
+// Leaf sets and walkers: the members (set, assignment) of n_sets sets, set-major, `group` per launch of `kernel`
+// (ct_sets_path_kernel over SetsArgs, ct_walk_path_kernel over WalkArgs: contract_sets.h, contract_walk.h; the caller
+// has filled in what says where the leaves are), and ct_sets_reduce_kernel folds them.  The caller has made room for
+// `group` members and n_sets outputs and has uploaded the table of the leaves.
+template <class T, class Args>
+int run_set_members(tnco_hip_contract_s* c, int64_t n_sets, int64_t group, Args s, void (*kernel)(Args)) {
   const int64_t A = c->stop - c->start;
   const int64_t* d_place = nullptr;
-  SetsArgs s;
   s.p = path_args(c, &d_place);
-  s.set_leaves = (const int64_t*)c->d_sets_tables;
   s.n_assign = A, s.start = c->start;
-  const int64_t per_slice = macs_per_assignment(c), members = n_sets * A;
-  for (int64_t m0 = 0; m0 < members; m0 += group) {
-    const int64_t n = std::min(group, members - m0);
-    s.m0 = m0;
-    hipLaunchKernelGGL(ct_sets_path_kernel<T>, dim3((unsigned)n), dim3(PATH_LANES), 0, c->stream, s);
-    CT_TRY(hipGetLastError());
-    const dim3 grid((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048));
-    hipLaunchKernelGGL(ct_sets_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (T*)c->d_sets_out, (const T*)c->d_path_stage,
-                       c->block_numel, (int)n, m0, A, c->out_numel, d_place);
-    CT_TRY(hipGetLastError());
-    c->launches += 2;
-    c->sets_launches[0] += 1, c->sets_launches[1] += 1;
-    c->macs += per_slice * n;
-  }
-  return TNCO_HIP_OK;
+  const dim3 grid = fold_grid(c);
+  return run_groups(
+      c, n_sets * A, group, c->sets_launches,
+      [&](int64_t m0, int64_t n) {
+        s.m0 = m0;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(PATH_LANES), 0, c->stream, s);
+      },
+      [&](int64_t m0, int64_t n) {
+        hipLaunchKernelGGL(ct_sets_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (T*)c->d_sets_out, (const T*)c->d_path_stage,
+                           c->block_numel, (int)n, m0, A, c->out_numel, d_place);
+      });
 }
 
 // what the leaf-set entry points refuse of a handle, or nullptr
@@ -1277,31 +1291,19 @@ const char* sets_refusal(const tnco_hip_contract_s* c) {
   return nullptr;
 }
 
-// The fused loop over walkers: run_sets with the walkers' bits in the place of the set strides (contract_walk.h).
+// f(ct_type<T>()) for the element type T of a handle of a plain dtype (codes 0 to 3)
 template <class T>
-int run_walkers(tnco_hip_contract_s* c, const tnco_hip_walkers_s* w, int64_t group, int64_t n_sets) {
-  const int64_t A = c->stop - c->start;
-  const int64_t* d_place = nullptr;
-  WalkArgs s;
-  s.p = path_args(c, &d_place);
-  s.walk_leaves = (const int64_t*)c->d_walk_tables;
-  s.bits = w->d_bits, s.n_walkers = w->n_walkers;
-  s.n_assign = A, s.start = c->start;
-  const int64_t per_slice = macs_per_assignment(c), members = n_sets * A;
-  for (int64_t m0 = 0; m0 < members; m0 += group) {
-    const int64_t n = std::min(group, members - m0);
-    s.m0 = m0;
-    hipLaunchKernelGGL(ct_walk_path_kernel<T>, dim3((unsigned)n), dim3(PATH_LANES), 0, c->stream, s);
-    CT_TRY(hipGetLastError());
-    const dim3 grid((unsigned)std::min<int64_t>((c->block_numel + 255) / 256, 2048));
-    hipLaunchKernelGGL(ct_sets_reduce_kernel<T>, grid, dim3(256), 0, c->stream, (T*)c->d_sets_out, (const T*)c->d_path_stage,
-                       c->block_numel, (int)n, m0, A, c->out_numel, d_place);
-    CT_TRY(hipGetLastError());
-    c->launches += 2;
-    c->sets_launches[0] += 1, c->sets_launches[1] += 1;
-    c->macs += per_slice * n;
+struct ct_type {
+  using type = T;
+};
+template <class F>
+int with_plain_type(const tnco_hip_contract_s* c, F f) {
+  switch (c->dtype) {
+    case 0: return f(ct_type<float>());
+    case 1: return f(ct_type<double>());
+    case 2: return f(ct_type<cplx<float>>());
+    default: return f(ct_type<cplx<double>>());
   }
-  return TNCO_HIP_OK;
 }
 
 // every counter of a run, and whose walkers it ran over, before the run starts
@@ -1349,6 +1351,24 @@ int sets_room(tnco_hip_contract_s* c, int64_t n_sets, int64_t G, char** d_tables
     c->d_sets_out = d_out, c->sets_out_cap = n_sets;
   }
   if (new_tables) *d_tables = (char*)d_tab, c->bytes += (int64_t)tables;
+  return TNCO_HIP_OK;
+}
+
+// What a run over leaf sets or walkers does before its first launch: room for G members and n_sets outputs (sets_room);
+// the table of the leaves, `width` words per leaf that row(t, words) fills in, built in *image and uploaded to
+// *d_tables; the outputs and the counters zeroed; the first event.
+template <class Row>
+int begin_sets_run(tnco_hip_contract_s* c, int64_t n_sets, int64_t G, char** d_tables, std::vector<int64_t>* image, int width,
+                   const char* what, Row row) {
+  const int64_t L = (int64_t)c->leaf_numel.size();
+  static_assert(sizeof(void*) == sizeof(int64_t), "the pointers and the other words share one table");
+  if (int rc = sets_room(c, n_sets, G, d_tables, (size_t)L * width * sizeof(int64_t), what)) return rc;
+  image->assign(width * L, 0);
+  for (int64_t t = 0; t < L; ++t) row(t, image->data() + width * t);
+  CT_TRY(hipMemcpyAsync(*d_tables, image->data(), width * L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  CT_TRY(hipMemsetAsync(c->d_sets_out, 0, (size_t)n_sets * c->out_numel * c->out_elem, c->stream));
+  zero_run_counters(c);
+  CT_TRY(hipEventRecord(c->ev[0], c->stream));
   return TNCO_HIP_OK;
 }
 
@@ -1557,6 +1577,16 @@ int launch_ingest(tnco_hip_contract_s* c, void* dst, const void* src, int from, 
   return TNCO_HIP_OK;
 }
 
+// launch_ingest of a source whose axes io_axes gave as `ax` and `contiguous`: a contiguous one is one axis, and of the
+// plan's dtype it takes the vector path
+int ingest_source(tnco_hip_contract_s* c, void* dst, const void* src, int from, int64_t numel, IoAxes ax, bool contiguous) {
+  if (contiguous) {
+    ax.nd = from == c->dtype ? -1 : 1;
+    ax.dim[0] = numel, ax.stride[0] = 1;
+  }
+  return launch_ingest(c, dst, src, from, numel, ax);
+}
+
 template <class T>
 void launch_emit_as(tnco_hip_contract_s* c, void* dst, const IoAxes& ax, const void* src, int64_t numel) {
   hipLaunchKernelGGL(ct_emit_kernel<T>, dim3(io_blocks(numel, sizeof(T), ax.nd < 0)), dim3(256), 0, c->stream, (T*)dst,
@@ -1610,15 +1640,41 @@ int load_stack(tnco_hip_contract_s* c, int64_t leaf, int64_t n, const void* src,
   }
   if (where == 0) {
     CT_TRY(hipMemcpyAsync(*buf, src, (size_t)numel * c->elem, hipMemcpyHostToDevice, c->stream));
-  } else {
-    if (contiguous) {  // one axis; of the plan's dtype: the vector path
-      ax.nd = src_dtype == c->dtype ? -1 : 1;
-      ax.dim[0] = numel, ax.stride[0] = 1;
-    }
-    if (int rc = launch_ingest(c, *buf, src, src_dtype, numel, ax)) return rc;
+  } else if (int rc = ingest_source(c, *buf, src, src_dtype, numel, ax, contiguous)) {
+    return rc;
   }
   CT_TRY(hipStreamSynchronize(c->stream));
   *held = n;
+  return TNCO_HIP_OK;
+}
+
+// The axes of a result of `numel` elements in a caller's device memory: no stride 0, and a contiguous one takes the
+// vector path.  dims_text: what is said of dims that do not multiply to numel.
+int dest_axes(int64_t ndim, const int64_t* dims, const int64_t* dst_strides, int64_t numel, const char* dims_text, IoAxes* ax) {
+  if (ndim && !dst_strides) return fail(TNCO_HIP_EINVAL, "null argument.");
+  bool contiguous = false;
+  if (const char* e = io_axes(ndim, dims, dst_strides, numel, dims_text, ax, &contiguous)) return fail(TNCO_HIP_EINVAL, e);
+  for (int k = 0; k < ax->nd; ++k)
+    if (ax->dim[k] > 1 && ax->stride[k] == 0) return fail(TNCO_HIP_EINVAL, "a destination stride is 0.");
+  if (contiguous) ax->nd = -1;
+  return TNCO_HIP_OK;
+}
+
+// What a run does after its last kernel: the second event; the result (sets == 0: the output buffer, else `sets` outputs
+// of d_sets_out) to `out` -- through ct_emit_kernel into a caller's device memory with the axes *emit, as it lies into
+// host memory when emit == nullptr, nowhere when out == nullptr --; the wait; the time between the events.
+int finish_run(tnco_hip_contract_s* c, void* out, const IoAxes* emit, int64_t sets = 0) {
+  CT_TRY(hipEventRecord(c->ev[1], c->stream));
+  if (emit) {
+    if (int rc = launch_emit(c, out, *emit, sets)) return rc;
+  } else if (out) {
+    CT_TRY(hipMemcpyAsync(out, sets ? c->d_sets_out : c->d_out, (size_t)std::max<int64_t>(sets, 1) * c->out_numel * c->out_elem,
+                          hipMemcpyDeviceToHost, c->stream));
+  }
+  CT_TRY(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  CT_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+  c->device_ns = (int64_t)((double)ms * 1e6);
   return TNCO_HIP_OK;
 }
 
@@ -1641,30 +1697,17 @@ int run_loaded(tnco_hip_contract_s* c, void* out, const IoAxes* emit) {
   zero_run_counters(c);
   CT_TRY(hipEventRecord(c->ev[0], c->stream));
   const bool fused = c->path_group > 0 && n_steps > 0;  // (a plan without steps runs as it does without the call)
-  int rc = fused ? (c->dtype == 0 ? run_path<float>(c)
-                    : c->dtype == 1 ? run_path<double>(c)
-                    : c->dtype == 2 ? run_path<cplx<float>>(c)
-                                    : run_path<cplx<double>>(c))
-           : c->dtype == 0 ? run_impl<float>(c)
-           : c->dtype == 1 ? run_impl<double>(c)
-           : c->dtype == 2 ? run_impl<cplx<float>>(c)
-           : c->dtype == 3 ? run_impl<cplx<double>>(c)
+  auto plain = [&](auto t) {  // (a path kernel is set on a plain dtype only)
+    using T = typename decltype(t)::type;
+    return fused ? run_path<T>(c) : run_impl<T>(c);
+  };
+  int rc = c->dtype < 4    ? with_plain_type(c, plain)
            : c->dtype == 4 ? run_impl<float, st_f16>(c)
            : c->dtype == 5 ? run_impl<cplx<float>, cplx<st_f16>>(c)
            : c->dtype == 6 ? run_impl<float, st_bf16>(c)
                            : run_impl<cplx<float>, cplx<st_bf16>>(c);
   if (rc) return rc;
-  CT_TRY(hipEventRecord(c->ev[1], c->stream));
-  if (emit) {
-    if (int rc2 = launch_emit(c, out, *emit)) return rc2;
-  } else {
-    CT_TRY(hipMemcpyAsync(out, c->d_out, (size_t)c->out_numel * c->out_elem, hipMemcpyDeviceToHost, c->stream));
-  }
-  CT_TRY(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  CT_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-  c->device_ns = (int64_t)((double)ms * 1e6);
-  return TNCO_HIP_OK;
+  return finish_run(c, out, emit);
 }
 
 }  // namespace
@@ -1777,11 +1820,8 @@ int tnco_hip_contract_load_leaf(tnco_hip_contract c, int64_t leaf, const void* s
   if (src_dtype < 0 || src_dtype > 3 || !io_widens(src_dtype, c->dtype))
     return fail(TNCO_HIP_EINVAL, "'src_dtype' does not widen to the plan's dtype.");
   CT_TRY(hipSetDevice(c->device));
-  if (contiguous) {  // one axis; of the plan's dtype: the vector path
-    ax.nd = src_dtype == c->dtype ? -1 : 1;
-    ax.dim[0] = c->leaf_numel[leaf], ax.stride[0] = 1;
-  }
-  if (int rc = launch_ingest(c, c->d_leaves + c->leaf_off[leaf] * c->elem, src, src_dtype, c->leaf_numel[leaf], ax)) return rc;
+  if (int rc = ingest_source(c, c->d_leaves + c->leaf_off[leaf] * c->elem, src, src_dtype, c->leaf_numel[leaf], ax, contiguous))
+    return rc;
   CT_TRY(hipStreamSynchronize(c->stream));
   c->loaded[leaf] = 1;
   return TNCO_HIP_OK;
@@ -1797,13 +1837,7 @@ int tnco_hip_contract_run_loaded(tnco_hip_contract c, void* out, int32_t where, 
   if (where == 1) {
     if (!c->row_steps.empty() || !c->row_maps.empty())
       return fail(TNCO_HIP_EINVAL, "a device result is not supported with row axes.");
-    if (ndim && !dst_strides) return fail(TNCO_HIP_EINVAL, "null argument.");
-    bool contiguous = false;
-    if (const char* e = io_axes(ndim, dims, dst_strides, c->out_numel, "dims do not multiply to the output's elements.", &ax, &contiguous))
-      return fail(TNCO_HIP_EINVAL, e);
-    for (int k = 0; k < ax.nd; ++k)
-      if (ax.dim[k] > 1 && ax.stride[k] == 0) return fail(TNCO_HIP_EINVAL, "a destination stride is 0.");
-    if (contiguous) ax.nd = -1;
+    if (int rc = dest_axes(ndim, dims, dst_strides, c->out_numel, "dims do not multiply to the output's elements.", &ax)) return rc;
   }
   for (size_t t = 0; t < c->loaded.size(); ++t)
     if (!c->loaded[t]) return fail(TNCO_HIP_EINVAL, "leaf " + std::to_string(t) + " was never loaded.");
@@ -1839,16 +1873,8 @@ int tnco_hip_contract_run_sets(tnco_hip_contract c, int64_t n_sets, int64_t grou
   const int64_t A = c->stop - c->start, L = (int64_t)c->leaf_numel.size();
   if (n_sets > (INT64_MAX >> 8) / std::max(c->out_numel, A)) return fail(TNCO_HIP_EINVAL, "'n_sets' is too large.");
   IoAxes ax;
-  if (where == 1) {
-    if (ndim && !dst_strides) return fail(TNCO_HIP_EINVAL, "null argument.");
-    bool contiguous = false;
-    if (const char* e = io_axes(ndim, dims, dst_strides, n_sets * c->out_numel, "dims do not multiply to the sets' outputs.", &ax,
-                                &contiguous))
-      return fail(TNCO_HIP_EINVAL, e);
-    for (int k = 0; k < ax.nd; ++k)
-      if (ax.dim[k] > 1 && ax.stride[k] == 0) return fail(TNCO_HIP_EINVAL, "a destination stride is 0.");
-    if (contiguous) ax.nd = -1;
-  }
+  if (where == 1)
+    if (int rc = dest_axes(ndim, dims, dst_strides, n_sets * c->out_numel, "dims do not multiply to the sets' outputs.", &ax)) return rc;
   for (int64_t t = 0; t < L; ++t) {
     if (c->stack_sets[t] && c->stack_sets[t] != n_sets)
       return fail(TNCO_HIP_EINVAL, "leaf " + std::to_string(t) + " has a stack of " + std::to_string(c->stack_sets[t]) +
@@ -1858,33 +1884,19 @@ int tnco_hip_contract_run_sets(tnco_hip_contract c, int64_t n_sets, int64_t grou
   CT_TRY(hipSetDevice(c->device));
   // room for min(group, members) members and n_sets outputs; the tables once
   const int64_t G = std::min(group, n_sets * A);
-  const size_t outb = (size_t)c->out_numel * c->out_elem;
-  if (int rc = sets_room(c, n_sets, G, &c->d_sets_tables, (size_t)L * (sizeof(void*) + sizeof(int64_t)), "the leaf sets")) return rc;
-  static_assert(sizeof(void*) == sizeof(int64_t), "the pointers and the strides share one table");
-  c->sets_image.assign(2 * L, 0);
-  for (int64_t t = 0; t < L; ++t) {
-    c->sets_image[2 * t] = (int64_t)(uintptr_t)(c->stack_sets[t] ? c->d_stack[t] : (void*)(c->d_leaves + c->leaf_off[t] * c->elem));
-    c->sets_image[2 * t + 1] = c->stack_sets[t] ? c->leaf_numel[t] : 0;
-  }
-  CT_TRY(hipMemcpyAsync(c->d_sets_tables, c->sets_image.data(), 2 * L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-  CT_TRY(hipMemsetAsync(c->d_sets_out, 0, (size_t)n_sets * outb, c->stream));
-  zero_run_counters(c);
-  CT_TRY(hipEventRecord(c->ev[0], c->stream));
-  if (int rc = c->dtype == 0   ? run_sets<float>(c, n_sets, G)
-               : c->dtype == 1 ? run_sets<double>(c, n_sets, G)
-               : c->dtype == 2 ? run_sets<cplx<float>>(c, n_sets, G)
-                               : run_sets<cplx<double>>(c, n_sets, G))
+  auto row = [&](int64_t t, int64_t* words) {  // the leaf's pointer (its stack, or its single buffer), its set stride
+    words[0] = (int64_t)(uintptr_t)(c->stack_sets[t] ? c->d_stack[t] : (void*)(c->d_leaves + c->leaf_off[t] * c->elem));
+    words[1] = c->stack_sets[t] ? c->leaf_numel[t] : 0;
+  };
+  if (int rc = begin_sets_run(c, n_sets, G, &c->d_sets_tables, &c->sets_image, 2, "the leaf sets", row)) return rc;
+  SetsArgs s{};
+  s.set_leaves = (const int64_t*)c->d_sets_tables;
+  if (int rc = with_plain_type(c, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return run_set_members<T>(c, n_sets, G, s, ct_sets_path_kernel<T>);
+      }))
     return rc;
-  CT_TRY(hipEventRecord(c->ev[1], c->stream));
-  if (where == 1) {
-    if (int rc = launch_emit(c, out, ax, n_sets)) return rc;
-  } else {
-    CT_TRY(hipMemcpyAsync(out, c->d_sets_out, (size_t)n_sets * outb, hipMemcpyDeviceToHost, c->stream));
-  }
-  CT_TRY(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  CT_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-  c->device_ns = (int64_t)((double)ms * 1e6);
+  if (int rc = finish_run(c, out, where == 1 ? &ax : nullptr, n_sets)) return rc;
   std::fill(c->stack_sets.begin(), c->stack_sets.end(), 0);  // the stacks were for this run
   return TNCO_HIP_OK;
 }
@@ -1928,29 +1940,22 @@ int tnco_hip_contract_run_walkers(tnco_hip_contract c, tnco_hip_walkers w, const
   // without an indexed leaf no output depends on the walker: one set is run, and every walker reads its output
   const int64_t R = any_indexed ? w->n_walkers : 1;
   const int64_t G = std::min(group, R * A);
-  const size_t outb = (size_t)c->out_numel * c->out_elem;
-  if (int rc = sets_room(c, R, G, &c->d_walk_tables, (size_t)L * WALK_W * sizeof(int64_t), "the walkers")) return rc;
-  c->walk_image.assign(WALK_W * L, 0);
-  for (int64_t t = 0; t < L; ++t) {
+  auto row = [&](int64_t t, int64_t* words) {  // the leaf's pointer (its versions, or its single buffer), qubit, version stride
     const bool indexed = leaf_qubit[t] >= 0;
-    c->walk_image[WALK_W * t] = (int64_t)(uintptr_t)(indexed ? c->d_versions[t] : (void*)(c->d_leaves + c->leaf_off[t] * c->elem));
-    c->walk_image[WALK_W * t + 1] = leaf_qubit[t];
-    c->walk_image[WALK_W * t + 2] = indexed ? c->leaf_numel[t] : 0;
-  }
-  CT_TRY(hipMemcpyAsync(c->d_walk_tables, c->walk_image.data(), WALK_W * L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-  CT_TRY(hipMemsetAsync(c->d_sets_out, 0, (size_t)R * outb, c->stream));
-  zero_run_counters(c);
-  CT_TRY(hipEventRecord(c->ev[0], c->stream));
-  if (int rc = c->dtype == 0   ? run_walkers<float>(c, w, G, R)
-               : c->dtype == 1 ? run_walkers<double>(c, w, G, R)
-               : c->dtype == 2 ? run_walkers<cplx<float>>(c, w, G, R)
-                               : run_walkers<cplx<double>>(c, w, G, R))
+    words[0] = (int64_t)(uintptr_t)(indexed ? c->d_versions[t] : (void*)(c->d_leaves + c->leaf_off[t] * c->elem));
+    words[1] = leaf_qubit[t];
+    words[2] = indexed ? c->leaf_numel[t] : 0;
+  };
+  if (int rc = begin_sets_run(c, R, G, &c->d_walk_tables, &c->walk_image, WALK_W, "the walkers", row)) return rc;
+  WalkArgs s{};
+  s.walk_leaves = (const int64_t*)c->d_walk_tables;
+  s.bits = w->d_bits, s.n_walkers = w->n_walkers;
+  if (int rc = with_plain_type(c, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return run_set_members<T>(c, R, G, s, ct_walk_path_kernel<T>);
+      }))
     return rc;
-  CT_TRY(hipEventRecord(c->ev[1], c->stream));
-  CT_TRY(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  CT_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-  c->device_ns = (int64_t)((double)ms * 1e6);
+  if (int rc = finish_run(c, nullptr, nullptr)) return rc;
   c->last_walk = w->id, c->walk_sets = R;
   return TNCO_HIP_OK;
 }

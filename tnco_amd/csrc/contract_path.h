@@ -11,6 +11,10 @@
 // The four plain dtypes only.  Every sum keeps the order of the kernel launch_gemm would have chosen for the step, so a
 // run is bit for bit that of the unfused loop (see ct_path_step).  The tables are read through uniform addresses only,
 // and every loop bound and branch around a barrier is a table value: all lanes of a block pass the same barriers.
+// What a member does is written once, here (ct_path_member, over ct_path_permutes, ct_path_leaf and ct_path_step), for
+// the three kinds of member (PathMember): an assignment of the plan (ct_path_kernel), a pair (leaf set, assignment)
+// (ct_sets_path_kernel, contract_sets.h) and a pair (walker, assignment) (ct_walk_path_kernel, contract_walk.h).  The
+// kinds differ in where a leaf is read (ct_path_leaf), and the kernels in how a block finds its member.
 #pragma once
 
 constexpr int MAX_PATH_GROUP = 1024;  // assignments per launch at most (tnco_amd/contraction.py MAX_PATH_KERNEL)
@@ -35,26 +39,31 @@ struct PathArgs {
   int n_steps;
 };
 
-// Leaf t as assignment sid reads it: at the slice offset of the assignment.  MODE 1 (leaf sets, contract_sets.h): the leaf
-// comes from set_leaves, [n_leaves][2]: its pointer and the elements between two sets of it (0 or the leaf's elements),
-// and the base moves on by set times that, a 64-bit product; pointer and stride lie side by side, one read, and it is
-// asked for before the slice offset is worked out, as ct_path_kernel asks for its pointer (every block of a launch reads
-// the same entry at about the same time: read after the offset loop, its latency lay open once per leaf and cost the
-// kernel a quarter of its time).  MODE 2 (walkers, contract_walk.h): the table is [n_leaves][WALK_W], the leaf's pointer,
-// the qubit whose bit picks one of its two versions (-1: none) and the elements between them; `set` is then the number of
-// walkers and column[qubit * set] the member's bit, a uniform address, asked for right after the entry and before the
-// offset too.  MODE 0 (ct_path_kernel): nothing is added and nothing more is read.  (MODE was a bool before the walkers:
-// contract_sets.h still passes `true`, which is MODE 1.)
+// The kinds of member, and where a member's leaves come from beyond the plan's tables: nothing for MEMBER_PLAN.
+enum PathMember { MEMBER_PLAN, MEMBER_SETS, MEMBER_WALK };
+struct LeafFrom {
+  const int64_t* table = nullptr;   // MEMBER_SETS: [n_leaves][2]; MEMBER_WALK: [n_leaves][WALK_W]
+  int64_t set = 0;                  // MEMBER_SETS: the member's set; MEMBER_WALK: the number of walkers
+  const uint8_t* column = nullptr;  // MEMBER_WALK: the walker's column of the table of bits
+};
+
+// Leaf t as assignment sid reads it: at the slice offset of the assignment.  MEMBER_SETS: the leaf comes from the table,
+// [n_leaves][2]: its pointer and the elements between two sets of it (0 or the leaf's elements), and the base moves on by
+// set times that, a 64-bit product; pointer and stride lie side by side, one read, and it is asked for before the slice
+// offset is worked out, as a MEMBER_PLAN asks for its pointer (every block of a launch reads the same entry at about the
+// same time: read after the offset loop, its latency lay open once per leaf and cost the kernel a quarter of its time).
+// MEMBER_WALK: the table is [n_leaves][WALK_W], the leaf's pointer, the qubit whose bit picks one of its two versions
+// (-1: none) and the elements between them; column[qubit * number of walkers] is the member's bit, a uniform address,
+// asked for right after the entry and before the offset too.  MEMBER_PLAN: nothing is added and nothing more is read.
 constexpr int WALK_W = 3;
-template <class T, int MODE = 0>
-__device__ inline const T* ct_path_leaf(const PathArgs& p, int64_t t, int64_t sid, const int64_t* set_leaves = nullptr,
-                                        int64_t set = 0, const uint8_t* column = nullptr) {
-  if constexpr (MODE == 1) {
-    const int64_t base = set_leaves[2 * t], step = set_leaves[2 * t + 1];  // (asked for before the offset is worked out)
-    return (const T*)base + (ct_slice_offset(p.leaf_sl + t * LEAF_SL_W, p.slice_place, p.slice_dims, sid) + set * step);
-  } else if constexpr (MODE == 2) {
-    const int64_t base = set_leaves[WALK_W * t], qubit = set_leaves[WALK_W * t + 1], step = set_leaves[WALK_W * t + 2];
-    const int64_t version = qubit < 0 ? 0 : column[qubit * set] & 1;  // (both before the offset is worked out)
+template <class T, PathMember MODE>
+__device__ inline const T* ct_path_leaf(const PathArgs& p, int64_t t, int64_t sid, const LeafFrom& from) {
+  if constexpr (MODE == MEMBER_SETS) {
+    const int64_t base = from.table[2 * t], step = from.table[2 * t + 1];  // (asked for before the offset is worked out)
+    return (const T*)base + (ct_slice_offset(p.leaf_sl + t * LEAF_SL_W, p.slice_place, p.slice_dims, sid) + from.set * step);
+  } else if constexpr (MODE == MEMBER_WALK) {
+    const int64_t base = from.table[WALK_W * t], qubit = from.table[WALK_W * t + 1], step = from.table[WALK_W * t + 2];
+    const int64_t version = qubit < 0 ? 0 : from.column[qubit * from.set] & 1;  // (both before the offset is worked out)
     return (const T*)base + (ct_slice_offset(p.leaf_sl + t * LEAF_SL_W, p.slice_place, p.slice_dims, sid) + version * step);
   } else {
     return (const T*)p.leaves[t] + ct_slice_offset(p.leaf_sl + t * LEAF_SL_W, p.slice_place, p.slice_dims, sid);
@@ -63,9 +72,8 @@ __device__ inline const T* ct_path_leaf(const PathArgs& p, int64_t t, int64_t si
 
 // the rows of one permute group, one after the other (they are independent of each other: one launch in the unfused
 // loop): ct_gather_body's element loop, strided over the block.  A permute feeds a step, so numel < 2^24.
-template <class T, int MODE = 0>
-__device__ inline void ct_path_permutes(const PathArgs& p, int64_t group, T* arena, int64_t sid,
-                                        const int64_t* set_leaves = nullptr, int64_t set = 0, const uint8_t* column = nullptr) {
+template <class T, PathMember MODE>
+__device__ inline void ct_path_permutes(const PathArgs& p, int64_t group, T* arena, int64_t sid, const LeafFrom& from) {
   const int64_t first = p.groups[2 * (group + 1)], count = p.groups[2 * (group + 1) + 1];
   for (int64_t r = first; r < first + count; ++r) {
     const int64_t* row = p.perms + r * PERM_W;
@@ -73,7 +81,7 @@ __device__ inline void ct_path_permutes(const PathArgs& p, int64_t group, T* are
     const int nd = (int)row[4];
     const T* src;
     if (row[0] == K_LEAF)
-      src = ct_path_leaf<T, MODE>(p, row[1], sid, set_leaves, set, column);
+      src = ct_path_leaf<T, MODE>(p, row[1], sid, from);
     else
       src = arena + row[1];
     T* dst = arena + row[3];
@@ -138,33 +146,39 @@ __device__ inline void ct_path_step(const int64_t* st, const T* A, const T* B, T
   }
 }
 
-// One block per member of the group, PATH_LANES lanes (the four quarters of the dot class; 16 wavefronts leave a lane
-// 128 registers).  Registers (gfx950, ROCm 7.0 hipcc): 34 VGPRs for float, 38 for double, 38 for cplx<float>, 44 for
-// cplx<double>; no scratch; LDS: the 1024 partials of the dot class, 4 to 16 KiB.  __syncthreads() orders the block's
-// global writes for the block, and an arena copy and a block of the staging belong to one block only.
-template <class T>
-__global__ __launch_bounds__(PATH_LANES) void ct_path_kernel(PathArgs p) {
-  __shared__ T part[PATH_LANES];
-  const int64_t b = blockIdx.x, sid = p.sid0 + b;
+// What the block of a member does: block b of the launch runs assignment sid in arena copy b and leaves the member's
+// block in stage[b]; `part`: the block's PATH_LANES partials of the dot class.  b, sid and `from` are uniform over the
+// block.  __syncthreads() orders the block's global writes for the block, and an arena copy and a block of the staging
+// belong to one block only.
+template <class T, PathMember MODE>
+__device__ inline void ct_path_member(const PathArgs& p, int64_t b, int64_t sid, const LeafFrom& from, T* part) {
   T* arena = (T*)p.arena + b * p.arena_elems;
-  ct_path_permutes<T>(p, -1, arena, sid);
+  ct_path_permutes<T, MODE>(p, -1, arena, sid, from);
   __syncthreads();
   for (int k = 0; k < p.n_steps; ++k) {
-    ct_path_permutes<T>(p, k, arena, sid);
+    ct_path_permutes<T, MODE>(p, k, arena, sid, from);
     __syncthreads();
     const int64_t* st = p.steps + (int64_t)k * STEP_W;
     const T* opnd[2];
     for (int side = 0; side < 2; ++side) {
       const int64_t kind = st[4 * side], ref = st[4 * side + 1];
-      // a leaf read in place: at the slice offset of this member's assignment, as ct_member has it
-      opnd[side] = kind == K_LEAF
-                       ? (const T*)p.leaves[ref] + ct_slice_offset(p.leaf_sl + ref * LEAF_SL_W, p.slice_place, p.slice_dims, sid)
-                       : arena + ref;
+      // (a leaf read in place: at the slice offset of this member's assignment, as ct_member has it)
+      opnd[side] = kind == K_LEAF ? ct_path_leaf<T, MODE>(p, ref, sid, from) : arena + ref;
     }
     T* C = st[8] == K_OUT ? (T*)p.stage + b * p.block_numel : arena + st[9];
     ct_path_step<T>(st, opnd[0], opnd[1], C, part);
     __syncthreads();
   }
+}
+
+// One block per member of the group, PATH_LANES lanes (the four quarters of the dot class; 16 wavefronts leave a lane
+// 128 registers).  Registers (gfx950, ROCm 7.0 hipcc): 34 VGPRs for float, 38 for double, 38 for cplx<float>, 44 for
+// cplx<double>; no scratch; LDS: the 1024 partials of the dot class, 4 to 16 KiB.
+template <class T>
+__global__ __launch_bounds__(PATH_LANES) void ct_path_kernel(PathArgs p) {
+  __shared__ T part[PATH_LANES];
+  const int64_t b = blockIdx.x;
+  ct_path_member<T, MEMBER_PLAN>(p, b, p.sid0 + b, LeafFrom{}, part);
 }
 
 // What ct_batch_reduce_kernel does, for up to MAX_PATH_GROUP members: place[b] = (element offset of member b's block of

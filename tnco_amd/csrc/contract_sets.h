@@ -3,10 +3,10 @@
 // A caller that runs one plan thousands of times changes a few small leaves between runs.  Here a member of a launch is
 // a pair (leaf set i, slice assignment a), numbered set-major: with A = stop - start assignments per set, member
 // m = i A + (a - start).  R sets are ceil(R A / group) pairs of launches:
-//   ct_sets_path_kernel    block b = member m0 + b, in arena copy b: what ct_path_kernel does for assignment a, every leaf
-//                          read at its pointer + i times its set stride (+ the slice offset of a); the stride is the
-//                          leaf's elements for a leaf that has a stack [n_sets][leaf_numel], 0 for a leaf that every set
-//                          shares, and the pointer is the stack's or the single buffer's;
+//   ct_sets_path_kernel    block b = member m0 + b, in arena copy b: ct_path_member (contract_path.h) for assignment a as a
+//                          MEMBER_SETS, every leaf read at its pointer + i times its set stride (+ the slice offset of a);
+//                          the stride is the leaf's elements for a leaf that has a stack [n_sets][leaf_numel], 0 for a
+//                          leaf that every set shares, and the pointer is the stack's or the single buffer's;
 //   ct_sets_reduce_kernel  stage [n][block] -> out [n_sets][out_numel], one lane per element of a block, the members in
 //                          order, member m to set i's copy of the output at the block offset and with the beta bit of
 //                          entry a - start of the plan's placement table (ct_path_reduce_kernel's, A entries: nothing here
@@ -25,32 +25,15 @@ struct SetsArgs {
   int64_t n_assign, start;    // A and the first assignment of the plan's slice range
 };
 
-// One block per member, PATH_LANES lanes, the body of ct_path_kernel through the same device functions.  Registers
-// (gfx950, ROCm 7.0 hipcc): 34 VGPRs for float, 38 for double, 38 for cplx<float>, 44 for cplx<double>, those of
-// ct_path_kernel (the set lives in scalar registers: 82 SGPRs against 78); no scratch, no spill; LDS: the
-// 1024 partials of the dot class, 4 to 16 KiB, as ct_path_kernel.
+// One block per member, PATH_LANES lanes.  Registers (gfx950, ROCm 7.0 hipcc): 34 VGPRs for float, 38 for double, 38 for
+// cplx<float>, 44 for cplx<double>, those of ct_path_kernel (the set lives in scalar registers: 80 SGPRs against 78); no
+// scratch, no spill; LDS: the 1024 partials of the dot class, 4 to 16 KiB, as ct_path_kernel.
 template <class T>
 __global__ __launch_bounds__(PATH_LANES) void ct_sets_path_kernel(SetsArgs s) {
   __shared__ T part[PATH_LANES];
-  const PathArgs& p = s.p;
   const int64_t b = blockIdx.x, m = s.m0 + b;
   const int64_t set = m / s.n_assign, sid = s.start + m % s.n_assign;
-  T* arena = (T*)p.arena + b * p.arena_elems;
-  ct_path_permutes<T, true>(p, -1, arena, sid, s.set_leaves, set);
-  __syncthreads();
-  for (int k = 0; k < p.n_steps; ++k) {
-    ct_path_permutes<T, true>(p, k, arena, sid, s.set_leaves, set);
-    __syncthreads();
-    const int64_t* st = p.steps + (int64_t)k * STEP_W;
-    const T* opnd[2];
-    for (int side = 0; side < 2; ++side) {
-      const int64_t kind = st[4 * side], ref = st[4 * side + 1];
-      opnd[side] = kind == K_LEAF ? ct_path_leaf<T, true>(p, ref, sid, s.set_leaves, set) : arena + ref;
-    }
-    T* C = st[8] == K_OUT ? (T*)p.stage + b * p.block_numel : arena + st[9];
-    ct_path_step<T>(st, opnd[0], opnd[1], C, part);
-    __syncthreads();
-  }
+  ct_path_member<T, MEMBER_SETS>(s.p, b, sid, LeafFrom{s.set_leaves, set, nullptr}, part);
 }
 
 // ct_path_reduce_kernel with the set axis: lane e of a block's elements takes the n members one after the other, so the

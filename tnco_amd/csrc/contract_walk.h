@@ -5,9 +5,9 @@
 // vectors: two constant versions and a bit that says which.  So the table stays on the device, a leaf's two versions lie
 // in a buffer [2][leaf_numel] of the handle's that is loaded once, and a member (walker i, assignment a) of a launch
 // reads an indexed leaf at versions + bits[qubit of the leaf][i] leaf_numel:
-//   ct_walk_path_kernel    ct_sets_path_kernel with that one more form of ct_path_leaf (contract_path.h, MODE 2); the
-//                          blocks are folded by ct_sets_reduce_kernel as they are there: out[i] is bit for bit the output
-//                          of a run over the leaves that walker i's bits select;
+//   ct_walk_path_kernel    ct_path_member (contract_path.h) for a MEMBER_WALK, numbered as ct_sets_path_kernel numbers its
+//                          members; the blocks are folded by ct_sets_reduce_kernel as they are there: out[i] is bit for
+//                          bit the output of a run over the leaves that walker i's bits select;
 //   ct_walk_choose_kernel  one lane per walker: the two amplitudes of the walker's output, a Philox4x32-10 draw and the
 //                          new bit of one qubit;
 //   ct_walk_permute_kernel one lane per walker: k <= 8 of its bits through a table of 2^k entries (a classical gate).
@@ -24,34 +24,17 @@ struct WalkArgs {
   int64_t n_assign, start;     // A and the first assignment of the plan's slice range
 };
 
-// One block per member, PATH_LANES lanes: the body of ct_sets_path_kernel, the set being the walker.  bits + walker is
-// the walker's column of the table; the bit of qubit q lies q n_walkers bytes further, an address that is uniform over
-// the block, as every table address is.  (Reading the bits of the first 64 qubits once per block instead, lane by lane
-// and through a ballot, took the same 39 ms on the timing leg: not kept.)  Registers as ct_sets_path_kernel's; no
-// scratch, no spill; LDS: the 1024 partials of the dot class.
+// One block per member, PATH_LANES lanes, the set being the walker.  bits + walker is the walker's column of the table;
+// the bit of qubit q lies q n_walkers bytes further, an address that is uniform over the block, as every table address
+// is.  (Reading the bits of the first 64 qubits once per block instead, lane by lane and through a ballot, took the same
+// 39 ms on the timing leg: not kept.)  Registers as ct_sets_path_kernel's (82 SGPRs); no scratch, no spill; LDS: the
+// 1024 partials of the dot class.
 template <class T>
 __global__ __launch_bounds__(PATH_LANES) void ct_walk_path_kernel(WalkArgs s) {
   __shared__ T part[PATH_LANES];
-  const PathArgs& p = s.p;
   const int64_t b = blockIdx.x, m = s.m0 + b;
   const int64_t walker = m / s.n_assign, sid = s.start + m % s.n_assign;
-  const uint8_t* column = s.bits + walker;
-  T* arena = (T*)p.arena + b * p.arena_elems;
-  ct_path_permutes<T, 2>(p, -1, arena, sid, s.walk_leaves, s.n_walkers, column);
-  __syncthreads();
-  for (int k = 0; k < p.n_steps; ++k) {
-    ct_path_permutes<T, 2>(p, k, arena, sid, s.walk_leaves, s.n_walkers, column);
-    __syncthreads();
-    const int64_t* st = p.steps + (int64_t)k * STEP_W;
-    const T* opnd[2];
-    for (int side = 0; side < 2; ++side) {
-      const int64_t kind = st[4 * side], ref = st[4 * side + 1];
-      opnd[side] = kind == K_LEAF ? ct_path_leaf<T, 2>(p, ref, sid, s.walk_leaves, s.n_walkers, column) : arena + ref;
-    }
-    T* C = st[8] == K_OUT ? (T*)p.stage + b * p.block_numel : arena + st[9];
-    ct_path_step<T>(st, opnd[0], opnd[1], C, part);
-    __syncthreads();
-  }
+  ct_path_member<T, MEMBER_WALK>(s.p, b, sid, LeafFrom{s.walk_leaves, s.n_walkers, s.bits + walker}, part);
 }
 
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11): ten rounds of
