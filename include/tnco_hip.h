@@ -371,6 +371,16 @@ uint64_t tnco_hip_diag_greedy_cost_key(int32_t a, int32_t b, int32_t c);
 void tnco_hip_greedy_device_release(void);
 /* diagnostics: trees of the last device call that the host version did (-1: the whole batch) */
 int64_t tnco_hip_diag_greedy_device_redone(void);
+/* diagnostics: what the last tnco_hip_greedy_trees_device call launched (values the host computed for the launch, nothing
+ * read back from a kernel but the statuses it reads anyway).  out8[0] form: 0 = the whole batch went to the host version,
+ * 1 = set form (greedy_kernel), 2 = graph form (greedy_graph_kernel); [1] ROWS of the instantiation launched (set form:
+ * 0 = the queue in LDS); [2] shuffle kernel: 0 = state in memory (py_shuffle_kernel), else the trees per workgroup of
+ * py_shuffle_lds_kernel (8 or 16); [3] G, the wavefronts launched (each works through the trees g, g + G, ...);
+ * [4] LDS bytes per wavefront of the greedy kernel; [5] R, the trees asked for; [6] trees the host version redid (-1:
+ * the whole batch); [7] bit s set: some tree ended with status s (0 = done by the kernel; 3 = outer products left,
+ * 7 = a neighbour list past its capacity, 9 = a merged tensor or a pair's shared legs past 255; 4, 5, 6: internal limits
+ * of the set form).  Form 0: [1]..[4] and [7] are 0. */
+int tnco_hip_diag_greedy_device_last(int64_t* out8);
 
 /*
  * The exchange between the GPUs of one node -- replaces what little tnco/parallel.py:330-341 moves between its worker

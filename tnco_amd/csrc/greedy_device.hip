@@ -31,6 +31,22 @@
 // Limits of this path (the host version takes the rest): n_inds <= 2040, n_leaves <= 2000, every
 // index held by at most GREEDY_MAXH tensors, LDS need <= 64 KB.  A tree that ends with more than one
 // tensor (outer products left) is flagged and redone on the host.
+//
+// Which test reaches which instantiation (tests/greedy_cases.py restates the dispatch below and names a network per
+// variant; tests/test_greedy_cases_plan.py asserts the rule without a GPU, tests/test_gpu_greedy_variants.py asserts from
+// tnco_hip_diag_greedy_device_last that the variant was launched and that the trees are the host's):
+//   greedy_graph_kernel<4, 8, 12, 16>  the 3-regular graphs of 8, 200, 512 tensors and the Sycamore-53 depth-20 network
+//                                      (test_the_small_variants_are_reached_as_recorded; tests/test_gpu_greedy.py)
+//   greedy_graph_kernel<24>            3-regular, 1 000 tensors (E = 1 500) and 700 (E = 1 050, the first of its rows)
+//   greedy_kernel<4>                   the 3-regular graph of 8 tensors with TNCO_HIP_GREEDY_GRAPH=0
+//   greedy_kernel<8, 12, 16>           random hyper networks of 40 tensors: 2 words x 3, 3 x 4, 3 x 5 candidates per index
+//                                      (indices on 4, 5, 6 tensors); 24 tensors, one word, six holders
+//   greedy_kernel<24>                  the 3-regular graphs of 1 000 and 700 tensors with TNCO_HIP_GREEDY_GRAPH=0
+//   greedy_kernel<0>                   by the rule: hyper networks of need 20 (little LDS), 25, and 36 at 900 tensors /
+//                                      32 KB; the chain of 2 000 tensors; 2 040 indices; forced: TNCO_HIP_GREEDY_LDS_QUEUE=1
+//   py_shuffle_kernel                  TNCO_HIP_SHUFFLE_LDS=0, up to 1 000 tensors
+//   py_shuffle_lds_kernel<16>, <8>     up to 800 tensors; 900, 1 000, 1 360, 2 000 tensors
+// and there: a wavefront's second and third tree (R > 2 G) in both forms, trees handed back one by one (status 9).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -132,6 +148,16 @@ static int64_t g_last_redone = -1;
 // trees of the last tnco_hip_greedy_trees_device call that the host version did (-1: the whole batch)
 extern "C" int64_t tnco_hip_diag_greedy_device_redone(void) { return g_last_redone; }
 
+// what the last tnco_hip_greedy_trees_device call launched (include/tnco_hip.h): form, ROWS, shuffle kernel, G, LDS bytes,
+// R, trees redone, statuses seen -- values the host has anyway, for the tests that mean to reach one instantiation
+// (tests/greedy_cases.py) to see that they did
+static int64_t g_last_diag[8] = {0, 0, 0, 0, 0, 0, -1, 0};
+extern "C" int tnco_hip_diag_greedy_device_last(int64_t* out8) {
+  if (!out8) return TNCO_HIP_EINVAL;
+  for (int i = 0; i < 8; ++i) out8[i] = g_last_diag[i];
+  return TNCO_HIP_OK;
+}
+
 // 1 when tnco_hip_greedy_trees_device takes this network itself (else it hands the batch to the host version)
 extern "C" int tnco_hip_diag_greedy_device_supported(int32_t n_leaves, int32_t n_inds, const int32_t* holders_off) {
   if (n_leaves < 3 || n_leaves > 2000 || n_inds < 1 || n_inds > GREEDY_KEY_MAX_EXP || !holders_off) return 0;
@@ -157,6 +183,9 @@ extern "C" int tnco_hip_greedy_trees_device(int32_t device, int32_t n_leaves, in
   if (links_device) *links_device = nullptr;
   if (n_replicas == 0) return TNCO_HIP_OK;
   g_last_redone = -1;
+  for (int64_t& v : g_last_diag) v = 0;
+  g_last_diag[5] = n_replicas;
+  g_last_diag[6] = -1;
   if (!tnco_hip_diag_greedy_device_supported(n_leaves, n_inds, holders_off)) {
     // the host version; the trees go to the device afterwards if the caller wants them there
     const size_t cnt = (size_t)n_replicas * 3 * (2 * (size_t)n_leaves - 1);
@@ -313,6 +342,7 @@ extern "C" int tnco_hip_greedy_trees_device(int32_t device, int32_t n_leaves, in
     const size_t per_tree = (size_t)624 * 4 + (size_t)n * 2;
     const char* e = std::getenv("TNCO_HIP_SHUFFLE_LDS");
     const bool in_lds = !(e && std::atoi(e) == 0) && 4 * per_tree <= 64 * 1024;
+    // (the <4> branch has no network: 8 trees per workgroup fit up to n = 2848, and this path ends at n = 2000)
     if (!in_lds) {
       hipLaunchKernelGGL(py_shuffle_kernel, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, 0, sp);
     } else if (16 * per_tree <= 64 * 1024) {
@@ -322,6 +352,7 @@ extern "C" int tnco_hip_greedy_trees_device(int32_t device, int32_t n_leaves, in
     } else {
       hipLaunchKernelGGL(py_shuffle_lds_kernel<4>, dim3((unsigned)((R + 3) / 4)), dim3(64), 4 * per_tree, 0, sp);
     }
+    g_last_diag[2] = !in_lds ? 0 : 16 * per_tree <= 64 * 1024 ? 16 : 8 * per_tree <= 64 * 1024 ? 8 : 4;
   }
   G_TRY(hipGetLastError());
   if (dbg) G_TRY(hipEventRecord(ev[1], 0));
@@ -336,7 +367,11 @@ extern "C" int tnco_hip_greedy_trees_device(int32_t device, int32_t n_leaves, in
     qp.t_off = d_toff; qp.t_nbr = d_tnbr; qp.t_mult = d_tmult; qp.t_fp = d_tfp; qp.t_kp = d_tkp;
     qp.e_ends = d_eends; qp.e_key = d_ekey; qp.links = gp.links; qp.status = gp.status; qp.prof = gp.prof;
     const int rows = (gh.E + 63) / 64;
-#define TNCO_GRAPH_LAUNCH(RW) hipLaunchKernelGGL(greedy_graph_kernel<RW>, dim3((unsigned)G), dim3(64), lds, 0, qp)
+#define TNCO_GRAPH_LAUNCH(RW)                                                                     \
+  do {                                                                                            \
+    g_last_diag[1] = RW;                                                                          \
+    hipLaunchKernelGGL(greedy_graph_kernel<RW>, dim3((unsigned)G), dim3(64), lds, 0, qp);         \
+  } while (0)
     if (rows <= 4) TNCO_GRAPH_LAUNCH(4);
     else if (rows <= 8) TNCO_GRAPH_LAUNCH(8);
     else if (rows <= 12) TNCO_GRAPH_LAUNCH(12);
@@ -344,7 +379,11 @@ extern "C" int tnco_hip_greedy_trees_device(int32_t device, int32_t n_leaves, in
     else TNCO_GRAPH_LAUNCH(24);
 #undef TNCO_GRAPH_LAUNCH
   } else {
-#define TNCO_SET_LAUNCH(RW) hipLaunchKernelGGL(greedy_kernel<RW>, dim3((unsigned)G), dim3(64), lds, 0, gp)
+#define TNCO_SET_LAUNCH(RW)                                                                 \
+  do {                                                                                      \
+    g_last_diag[1] = RW;                                                                    \
+    hipLaunchKernelGGL(greedy_kernel<RW>, dim3((unsigned)G), dim3(64), lds, 0, gp);         \
+  } while (0)
     switch (set_rows) {
       case 4: TNCO_SET_LAUNCH(4); break;
       case 8: TNCO_SET_LAUNCH(8); break;
@@ -355,6 +394,9 @@ extern "C" int tnco_hip_greedy_trees_device(int32_t device, int32_t n_leaves, in
     }
 #undef TNCO_SET_LAUNCH
   }
+  g_last_diag[0] = graph ? 2 : 1;
+  g_last_diag[3] = G;
+  g_last_diag[4] = (int64_t)lds;
   G_TRY(hipGetLastError());
   if (dbg) G_TRY(hipEventRecord(ev[2], 0));
   G_TRY(hipDeviceSynchronize());
@@ -393,9 +435,12 @@ extern "C" int tnco_hip_greedy_trees_device(int32_t device, int32_t n_leaves, in
   }
   // the trees the kernel left to the host (outer products at the end, limits)
   std::vector<int64_t> redo;
-  for (int64_t r = 0; r < R; ++r)
+  for (int64_t r = 0; r < R; ++r) {
     if (status[r] != 0) redo.push_back(r);
+    if (status[r] >= 0 && status[r] < 63) g_last_diag[7] |= (int64_t)1 << status[r];
+  }
   g_last_redone = (int64_t)redo.size();
+  g_last_diag[6] = g_last_redone;
   if (!redo.empty()) {
     if (std::getenv("TNCO_HIP_DEBUG"))
       for (size_t k = 0; k < std::min<size_t>(redo.size(), 8); ++k)
