@@ -822,6 +822,19 @@ int tnco_hip_contract_walkers_output(tnco_hip_contract h, tnco_hip_walkers w, vo
  * is a function of (seed, i, step, a0, a1).  EINVAL: a null pointer; a last run that was not a run_walkers over `w`;
  * an output of another size than 2; a qubit outside [0, n_qubits); a step outside [0, 2^32). */
 int tnco_hip_walkers_choose(tnco_hip_walkers w, tnco_hip_contract h, int64_t qubit, int64_t step);
+/* The new bits of k <= 6 qubits for every walker, drawn jointly (ct_walk_choose_joint_kernel, one lane per walker). The
+ * handle's last run must be a run_walkers over `w` whose output holds exactly N = 2^k elements.  Outcome v, 0 <= v < N,
+ * has qubits[0] as its most significant bit: bit_j(v) = (v >> (k - 1 - j)) & 1, and its amplitude a_v is the element
+ * sum_j bit_j(v) strides[j] of the walker's output.  In float64, every operation rounded on its own: p_v as choose has
+ * p; tail(N - 1) = p_{N-1}, tail(v) = tail(v + 1) + p_v, s = tail(0); u is choose's u for (seed, i, step), one draw
+ * whatever k is; t = u s.  The outcome is the largest v >= 1 with t < tail(v), or 0 if there is none;
+ * bits[qubits[j]][i] = bit_j of it.  Where s is 0 or not finite the k bits become 0 and dead[i] is set.  So an outcome
+ * v >= 1 with p_v = 0 is never drawn, and outcome 0 with p_0 = 0 only where u s rounds up to s.  At k = 1 the bytes are
+ * those of tnco_hip_walkers_choose.  EINVAL, checked in this order and before any launch: a null pointer; a last run
+ * that was not a run_walkers over `w`; k outside [1, 6]; an output of another size than 2^k; a qubit outside [0,
+ * n_qubits) or named twice; strides that are no permutation of 1, 2, ..., 2^(k-1); a step outside [0, 2^32). */
+int tnco_hip_walkers_choose_joint(tnco_hip_walkers w, tnco_hip_contract h, int64_t k, const int64_t* qubits,
+                                  const int64_t* strides, int64_t step);
 void tnco_hip_contract_destroy(tnco_hip_contract h);
 
 /* "name|pci ...|uuid ...|N CUs" of a device: what a multi-GPU bench line lists per rank */

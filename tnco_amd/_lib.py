@@ -101,6 +101,7 @@ EXPORTS = [
     "tnco_hip_contract_load_leaf_versions", "tnco_hip_contract_run_walkers", "tnco_hip_contract_walkers_output",
     "tnco_hip_walkers_create", "tnco_hip_walkers_destroy", "tnco_hip_walkers_read", "tnco_hip_walkers_write",
     "tnco_hip_walkers_reset", "tnco_hip_walkers_permute", "tnco_hip_walkers_choose",
+    "tnco_hip_walkers_choose_joint",
     "tnco_hip_contract_destroy",
     "tnco_hip_device_name", "tnco_hip_device_count", "tnco_hip_last_error", "tnco_hip_version",
 ]
@@ -240,6 +241,7 @@ def load() -> C.CDLL:
     L.tnco_hip_walkers_reset.argtypes = [vp]
     L.tnco_hip_walkers_permute.argtypes = [vp, i64, vp, vp]
     L.tnco_hip_walkers_choose.argtypes = [vp, vp, i64, i64]
+    L.tnco_hip_walkers_choose_joint.argtypes = [vp, vp, i64, vp, vp, i64]
     L.tnco_hip_contract_destroy.argtypes = [vp]
     L.tnco_hip_contract_destroy.restype = None
     L.tnco_hip_device_name.argtypes = [C.c_int, vp, C.c_int]

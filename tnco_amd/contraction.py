@@ -227,7 +227,8 @@ from .app import tn as tnmod
 __all__ = ["contract", "contract_results", "plan", "Plan", "ContractionResult", "MAX_AXES", "DTYPES", "KERNEL_PATHS",
            "ROW_KERNEL_PATHS", "STORAGES", "round_to_storage", "SCALINGS", "scale_exponent", "scale_to_storage",
            "MAX_SLICE_BATCH", "COMPUTES", "split_bf16", "MAX_PATH_KERNEL", "MAX_PATH_STEP_MACS", "INDIRECT_KERNEL_PATHS",
-           "ACCUMULATES", "Contractor", "merge_axes", "check_extent", "ManyResult", "Walkers", "MAX_PERMUTE_QUBITS"]
+           "ACCUMULATES", "Contractor", "merge_axes", "check_extent", "ManyResult", "Walkers", "MAX_PERMUTE_QUBITS",
+           "MAX_CHOOSE_QUBITS"]
 
 MAX_AXES = 32  # axes per tensor the kernels take (after slicing); csrc/contract.hip CT_MAX_AXES
 DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.complex64): 2, np.dtype(np.complex128): 3}
@@ -247,6 +248,7 @@ MAX_PATH_KERNEL = 1024  # path kernel: assignments per launch at most (csrc/cont
 # hold one compute unit of a shared card for long, not a tuned threshold (csrc/contract_path.h MAX_PATH_STEP_MACS)
 MAX_PATH_STEP_MACS = 1 << 24
 MAX_PERMUTE_QUBITS = 8  # qubits of one Walkers.permute at the most (csrc/contract_walk.h WALK_MAX_PERMUTE)
+MAX_CHOOSE_QUBITS = 6  # qubits of one Contractor.choose_joint at the most (csrc/contract_walk.h WALK_MAX_CHOOSE)
 
 # operand / destination kinds and table widths: include/tnco_hip.h (tnco_hip_contract_desc)
 LEAF, ARENA, OUT = 0, 1, 2
@@ -1888,6 +1890,49 @@ class Contractor:
             raise ValueError("the last run of the Contractor was not a 'run_walkers' over these walkers.")
         L, h = self._handle()
         _lib.check(L.tnco_hip_walkers_choose(walkers._handle(), h, int(qubit), int(step)))
+
+    def choose_joint(self, walkers, qubits, step, inds=None) -> None:
+        """Draws the new bits of the 1 to 6 distinct `qubits` jointly for every walker, from the 2^k amplitudes that the
+        last `run_walkers` over `walkers` left (csrc/contract_walk.h, ct_walk_choose_joint_kernel).  `inds` is the open
+        index of each qubit, in the qubits' order (None: `plan.inds` in order); it names every index of the plan's
+        output once, and each has dimension 2.  Outcome v, the first qubit its most significant bit, has the amplitude
+        out[inds = the bits of v]: the strides come from the layout of the output on the device, so a draw does not
+        depend on the path.  With p_v = |a_v|^2 and tail(v) = p_v + ... + p_{N-1} summed from the top in float64, the
+        outcome is the largest v >= 1 with u tail(0) < tail(v), or 0; u is `choose`'s, one draw per call.  A walker
+        whose tail(0) is 0 or not finite gets 0 in all k bits and its dead flag.  At k = 1 the bytes are `choose`'s."""
+        from . import _lib
+        self._check_open()
+        self._check_many(None, "choose_joint")
+        self._check_walk(walkers)
+        p = self.plan
+        qubits = tuple(qubits)
+        if not 1 <= len(qubits) <= MAX_CHOOSE_QUBITS:
+            raise ValueError(f"'qubits' must name 1 to {MAX_CHOOSE_QUBITS} qubits.")
+        for q in qubits:
+            if not _is_index(q, 0, walkers.n_qubits):
+                raise ValueError(f"{q!r} is not a qubit of the walkers (0 to {walkers.n_qubits - 1}).")
+        if len(set(qubits)) != len(qubits):
+            raise ValueError("'qubits' names a qubit twice.")
+        if p.block_inds:  # (projections, the other output that is not one block, are refused with path_kernel)
+            raise NotImplementedError("'choose_joint' needs an output whose axes are all held at once: this plan's is a block "
+                                      "that a sliced index selects.")
+        if any(d != 2 for d in p.shape):
+            raise ValueError(f"every axis of the output must have dimension 2, not {tuple(p.shape)}.")
+        if p.out_numel != 1 << len(qubits):
+            raise ValueError(f"the output of the plan holds {p.out_numel} elements, not the {1 << len(qubits)} amplitudes of a "
+                             f"choice of {len(qubits)} qubits.")
+        inds = tuple(p.inds) if inds is None else tuple(inds)
+        if len(inds) != len(p.inds) or set(inds) != set(p.inds):
+            raise ValueError(f"'inds' must name every index of the output {tuple(p.inds)} once, one per qubit.")
+        if not _is_index(step, 0, 2 ** 32):
+            raise ValueError("'step' must be an integer from 0 to 2^32 - 1.")
+        if self._walked is not walkers:
+            raise ValueError("the last run of the Contractor was not a 'run_walkers' over these walkers.")
+        held = _held_axes(p)  # the device layout, every dimension 2: the last axis has stride 1
+        strides = np.array([1 << (len(held) - 1 - held.index(x)) for x in inds], np.int64)
+        qs = np.array(qubits, np.int64)
+        L, h = self._handle()
+        _lib.check(L.tnco_hip_walkers_choose_joint(walkers._handle(), h, len(qubits), _ptr(qs), _ptr(strides), int(step)))
 
     def many_bytes(self, n_sets, group=None, leaves=None) -> int:
         """The device bytes the handle holds after `run_many` of `n_sets` sets with that `group` and stacks of the leaves

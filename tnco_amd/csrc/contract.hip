@@ -64,7 +64,8 @@
 // at the version the walker's bit of one qubit picks, and the versions stay loaded from run to run:
 //   ct_walk_path_kernel    ct_sets_path_kernel with the indexed leaves; ct_sets_reduce_kernel folds its blocks;
 //   ct_walk_choose_kernel, ct_walk_permute_kernel  the new bit of a qubit from the two amplitudes and a Philox draw; a
-//                          classical gate on up to 8 qubits.
+//                          classical gate on up to 8 qubits;
+//   ct_walk_choose_joint_kernel  the new bits of up to 6 qubits, drawn jointly from the 2^k amplitudes.
 // No atomics in any sum: every sum runs in one fixed order, so a run is bit-reproducible (the one atomic, the integer max
 // behind a scaled tensor's exponent, does not depend on order).
 #include "../../include/tnco_hip.h"
@@ -2057,6 +2058,48 @@ int tnco_hip_walkers_choose(tnco_hip_walkers w, tnco_hip_contract c, int64_t qub
     case 2: hipLaunchKernelGGL(ct_walk_choose_kernel<cplx<float>>, grid, dim3(256), 0, w->stream, row, w->d_dead, (const cplx<float>*)c->d_sets_out, each, w->n_walkers, w->seed, (uint32_t)step); break;
     default: hipLaunchKernelGGL(ct_walk_choose_kernel<cplx<double>>, grid, dim3(256), 0, w->stream, row, w->d_dead, (const cplx<double>*)c->d_sets_out, each, w->n_walkers, w->seed, (uint32_t)step);
   }
+  CT_TRY(hipGetLastError());
+  CT_TRY(hipStreamSynchronize(w->stream));
+  return TNCO_HIP_OK;
+}
+
+int tnco_hip_walkers_choose_joint(tnco_hip_walkers w, tnco_hip_contract c, int64_t k, const int64_t* qubits, const int64_t* strides,
+                                  int64_t step) {
+  if (!w || !c || !qubits || !strides) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (c->last_walk != w->id)
+    return fail(TNCO_HIP_EINVAL, "the handle's last run was not a tnco_hip_contract_run_walkers over these walkers.");
+  if (k < 1 || k > WALK_MAX_CHOOSE) return fail(TNCO_HIP_EINVAL, "'k' must be from 1 to 6.");
+  const int64_t n = (int64_t)1 << k;
+  if (c->out_numel != n)
+    return fail(TNCO_HIP_EINVAL, "the output of the handle holds " + std::to_string(c->out_numel) + " elements, not the " +
+                                     std::to_string(n) + " amplitudes of a joint choice of " + std::to_string(k) + " qubits.");
+  for (int64_t j = 0; j < k; ++j) {
+    if (qubits[j] < 0 || qubits[j] >= w->n_qubits)
+      return fail(TNCO_HIP_EINVAL, "a qubit is not a qubit of the walkers (0 to " + std::to_string(w->n_qubits - 1) + ").");
+    if (std::count(qubits, qubits + j, qubits[j])) return fail(TNCO_HIP_EINVAL, "a qubit is named twice.");
+  }
+  WalkChoose a{};
+  bool natural = true;
+  int64_t seen = 0;  // the strides met, a bit each
+  for (int64_t j = 0; j < k; ++j) {
+    const int64_t s = strides[j];
+    if (s < 1 || s >= n || (s & (s - 1)) || (seen & s)) return fail(TNCO_HIP_EINVAL, "'strides' is not a permutation of 1, 2, ..., 2^(k - 1).");
+    seen |= s;
+    natural &= s == (int64_t)1 << (k - 1 - j);
+    a.qubit[j] = qubits[j], a.stride[j] = s;
+  }
+  if (step < 0 || step > (int64_t)UINT32_MAX) return fail(TNCO_HIP_EINVAL, "'step' must be from 0 to 2^32 - 1.");
+  CT_TRY(hipSetDevice(w->device));
+  // (the run has synchronised the handle's stream: its outputs are there)
+  const dim3 grid((unsigned)std::min<int64_t>((w->n_walkers + 255) / 256, 65536));
+  const int64_t each = c->walk_sets == 1 ? 0 : n;  // elements between two walkers' amplitudes (one output for all: 0)
+  if (int rc = with_plain_type(c, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(ct_walk_choose_joint_kernel<T>, grid, dim3(256), 0, w->stream, w->d_bits, w->d_dead, (const T*)c->d_sets_out,
+                           each, w->n_walkers, w->seed, (uint32_t)step, (int)k, (int)natural, a);
+        return (int)TNCO_HIP_OK;
+      }))
+    return rc;
   CT_TRY(hipGetLastError());
   CT_TRY(hipStreamSynchronize(w->stream));
   return TNCO_HIP_OK;

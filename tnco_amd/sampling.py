@@ -19,7 +19,12 @@ single read of the bits at its end.
 A part of that network that is not connected to q's index is a scalar factor of both amplitudes and cancels in the
 choice: the Sampler contracts the component that holds q's index only.
 
-Limits: one handle per 1-qubit gate, all of them held at once; two versions per leaf, so qubits only; nothing is reused
+With `max_gate_qubits=k` (2 to `contraction.MAX_CHOOSE_QUBITS`) a gate on at most k qubits that is not classical -- fSim, a
+CPHASE with a generic angle, a fused pair of gates -- is a drawing gate too: after it the walker redraws the gate's bits
+jointly, from the 2^k amplitudes of its bitstring with those bits open (`Contractor.choose_joint`).  Its partial network
+keeps the last index of each of its qubits open; all of them are axes of the gate's tensor, so one component holds them.
+
+Limits: one handle per gate that draws, all of them held at once; two versions per leaf, so qubits only; nothing is reused
 between the networks of consecutive gates, each is contracted from the |0> vectors on; no slicing (`max_width`, `slices`).
 """
 from __future__ import annotations
@@ -58,35 +63,38 @@ def classical_table(matrix):
 
 
 def partial_network(gates, g, n_qubits):
-    """The network whose contraction gives a walker's two amplitudes after gate g, a 1-qubit gate on qubit q.
+    """The network whose contraction gives a walker's 2^k amplitudes after gate g, a gate that draws on its k qubits qs
+    (k = 1: the two amplitudes of a 1-qubit gate).
 
     gates: [(array of shape (2,) * 2k, positions of its k qubits)], axes (out_1 .. out_k, in_1 .. in_k).  Returns
     (ts_inds, arrays, output_inds, closing): the tensors are a |0> vector per qubit, the gates 0 .. g, and a closing leaf
-    on the last index of every qubit but q, in that order; `arrays` holds None for a closing leaf, which is (1, 0) or
-    (0, 1) as the walker's bit says; `closing` is {leaf number: qubit}; output_inds is q's last index alone."""
-    (q,) = gates[g][1]
+    on the last index of every qubit but those of qs, in that order; `arrays` holds None for a closing leaf, which is
+    (1, 0) or (0, 1) as the walker's bit says; `closing` is {leaf number: qubit}; output_inds are the last indices of qs,
+    in the order of qs: all of them axes of gate g's tensor."""
+    qs = tuple(gates[g][1])
     last = [f"q{x}_0" for x in range(n_qubits)]
     ts_inds = [(x,) for x in last]
     arrays = [np.array([1, 0]) for _ in range(n_qubits)]
     for pos in range(g + 1):
-        array, qs = gates[pos]
-        new = [f"q{x}_{pos + 1}" for x in qs]
-        ts_inds.append(tuple(new) + tuple(last[x] for x in qs))
+        array, at = gates[pos]
+        new = [f"q{x}_{pos + 1}" for x in at]
+        ts_inds.append(tuple(new) + tuple(last[x] for x in at))
         arrays.append(array)
-        for x, name in zip(qs, new):
+        for x, name in zip(at, new):
             last[x] = name
     closing = {}
     for x in range(n_qubits):
-        if x != q:
+        if x not in qs:
             closing[len(ts_inds)] = x
             ts_inds.append((last[x],))
             arrays.append(None)
-    return ts_inds, arrays, (last[q],), closing
+    return ts_inds, arrays, tuple(last[x] for x in qs), closing
 
 
 def connected_to(ts_inds, index) -> list:
-    """The tensors of the connected component that holds `index`, in their order."""
-    reached, found = {index}, set()
+    """The tensors of the connected component that holds `index`, in their order; for a tuple or list of indices, of the
+    union of their components."""
+    reached, found = set(index) if isinstance(index, (tuple, list)) else {index}, set()
     grown = True
     while grown:
         grown = False
@@ -102,14 +110,25 @@ class Sampler:
     """Samples bitstrings from `circuit`, an iterable of (matrix, qubits): 1-qubit gates and classical gates (module
     docstring); anything else is a ValueError.  qubit_order: the qubits of the circuit in the order of the bitstrings
     (None: sorted by str).  dtype: of the contractions.  seed: of the optimisations and of the draws (None: from the
-    system).  group: members per launch of the walkers' path kernel.  optimize_params go to `Optimizer.optimize` for
+    system).  group: members per launch of the walkers' path kernel.  max_gate_qubits: with 2 to 6, a gate that is not
+    classical on at most that many qubits is taken too and its bits are drawn jointly (its matrix must be 2^k x 2^k); the
+    default, 1, refuses it as before.  optimize_params go to `Optimizer.optimize` for
     every partial network (betas, n_steps, n_runs default to (0, 100), 100, 8); a finite `max_width` or `slices` is
     not implemented.  The handles live until close(); the object is a context manager."""
 
-    def __init__(self, circuit, *, qubit_order=None, dtype=np.complex64, seed=None, device=None, group=1024, **optimize_params):
+    def __init__(self, circuit, *, qubit_order=None, dtype=np.complex64, seed=None, device=None, group=1024, max_gate_qubits=1,
+                 **optimize_params):
+        most = contraction.MAX_CHOOSE_QUBITS
+        if isinstance(max_gate_qubits, bool) or not isinstance(max_gate_qubits, (int, np.integer)) or not 1 <= max_gate_qubits <= most:
+            raise ValueError(f"'max_gate_qubits' must be an integer from 1 to {most}.")
         circuit = [(np.asarray(m), tuple(qs)) for m, qs in circuit]
         tables = [None if len(qs) == 1 else classical_table(m) for m, qs in circuit]
         for (m, qs), table in zip(circuit, tables):
+            if len(qs) > 1 and table is None and len(qs) <= max_gate_qubits:  # a drawing gate of several qubits
+                if m.shape != (1 << len(qs),) * 2:
+                    raise ValueError(f"the matrix of a gate on {len(qs)} qubits must be {1 << len(qs)} x {1 << len(qs)}, not of shape "
+                                     f"{m.shape}.")
+                continue
             ok = m.shape == (2, 2) if len(qs) == 1 else (table is not None and len(table) == 1 << len(qs))
             if not ok:
                 raise ValueError(GATES_ERROR)
@@ -143,7 +162,8 @@ class Sampler:
         at = {x: k for k, x in enumerate(self.qubits)}
         self.gates = [(m.reshape((2,) * (2 * len(qs))), tuple(at[x] for x in qs)) for m, qs in circuit]
         self.tables = tables
-        self.contractors = {}  # {gate position: (Contractor, {leaf: qubit})} for the 1-qubit gates
+        self.contractors = {}  # {gate position: (Contractor, {leaf: qubit})} for the gates that draw
+        self.open_inds = {}  # {gate position: the open index of each of the gate's qubits}
         self.last_walk_seed = None  # the seed of the walkers of the last sample()
         self._closed = False
         params = dict(dict(betas=(0, 100), n_steps=100, n_runs=8), **optimize_params)
@@ -158,9 +178,10 @@ class Sampler:
     def _contractor(self, g, params):
         from .app import Optimizer
         ts_inds, arrays, output, closing = partial_network(self.gates, g, len(self.qubits))
-        # the components that do not hold the open index are scalars, factors of both amplitudes alike: they cancel in
-        # p1 / (p0 + p1) and are left out
-        kept = connected_to(ts_inds, output[0])
+        # the components that do not hold an open index are scalars, factors of all amplitudes alike: they cancel in
+        # p_v / s and are left out (the open indices are all axes of the gate's tensor: one component holds them)
+        kept = connected_to(ts_inds, output[0] if len(output) == 1 else output)
+        self.open_inds[g] = output
         closing = {k: closing[t] for k, t in enumerate(kept) if t in closing}
         ts_inds, arrays = [ts_inds[t] for t in kept], [arrays[t] for t in kept]
         seed = self._rng.randrange(2 ** 32)
@@ -203,7 +224,10 @@ class Sampler:
                 continue
             c, closing = self.contractors[g]
             c.run_walkers(walkers, closing, group=self.group)
-            c.choose(walkers, qs[0], g)
+            if len(qs) == 1:
+                c.choose(walkers, qs[0], g)
+            else:
+                c.choose_joint(walkers, qs, g, inds=self.open_inds[g])
             if stop_at_dead and walkers.dead.any():
                 return g
         return None
@@ -223,8 +247,10 @@ class Sampler:
             if dead.any():
                 w.reset()
                 g = self._walk(w, stop_at_dead=True)  # (the same seed, the same walk: which gate it was)
+                names = tuple(self.qubits[x] for x in self.gates[g][1])
+                gate = f"a 1-qubit gate on qubit {names[0]!r}" if len(names) == 1 else f"a {len(names)}-qubit gate on qubits {names!r}"
                 raise FloatingPointError(f"{int(dead.sum())} of {n_samples} walkers met probabilities that sum to 0 or are not "
-                                         f"finite, the first at gate {g} (a 1-qubit gate on qubit {self.qubits[self.gates[g][1][0]]!r}).")
+                                         f"finite, the first at gate {g} ({gate}).")
         self.last_bits = bits
         return tally(bits, normalize), self.qubits
 

@@ -735,6 +735,93 @@ def many(lines, depth, max_width, max_slices, reps=5, stacked=8):
     print("\n".join(notes), flush=True)
 
 
+def sample_joint(lines, n_qubits=8, n_gates=40, n_samples=4096, reps=5):
+    """The walk of `sample`'s circuit with every CZ replaced by fSim(pi / 2, pi / 6), a 2-qubit gate that draws (as numpy
+    computes it: cos(pi / 2) is 6e-17 and the phase's modulus is not 1 to the last bit, so it is no permutation with phases
+    for `classical_table`), through sampling.Sampler(max_gate_qubits=2), two ways on the same Contractors in one process.
+    (a) Sampler.sample: run_walkers + choose_joint per fSim, on the device.  (b) the best a caller can write without the
+    joint-draw kernel: the same Walkers, run_walkers, `choose` for the 1-qubit gates, and for an fSim the four amplitudes
+    per walker from `walker_outputs`, the tails and the draw in torch on the device (torch's own generator), the two new
+    bits written back through Walkers.bits / Walkers.write.  Wall seconds as in `sample`."""
+    from tnco_amd import contraction, sampling
+    lines.append("")
+    rng = np.random.RandomState(17)
+    theta, phi = np.pi / 2, np.pi / 6
+    fsim = np.array([[1, 0, 0, 0], [0, np.cos(theta), -1j * np.sin(theta), 0], [0, -1j * np.sin(theta), np.cos(theta), 0],
+                     [0, 0, 0, np.exp(-1j * phi)]]).astype(np.complex64)
+
+    def unitary():
+        q, r = np.linalg.qr(rng.normal(size=(2, 2)) + 1j * rng.normal(size=(2, 2)))
+        return (q * (np.diag(r) / np.abs(np.diag(r)))).astype(np.complex64)
+
+    circuit = [(unitary(), (q,)) for q in range(n_qubits)]
+    while len(circuit) < n_gates:
+        if rng.randint(0, 2):
+            circuit.append((unitary(), (int(rng.randint(0, n_qubits)),)))
+        else:
+            a, b = rng.choice(n_qubits, 2, replace=False)
+            circuit.append((fsim, (int(a), int(b))))
+    with sampling.Sampler(circuit, seed=0, max_gate_qubits=2) as s:
+        joint = [g for g in sorted(s.contractors) if len(s.gates[g][1]) == 2]
+        if len(s.contractors) != n_gates:
+            raise RuntimeError("a gate of the circuit does not draw.")
+        lines.append(f"## sampling with joint draws: {n_qubits} qubits, {n_gates} gates ({n_gates - len(joint)} 1-qubit gates, {len(joint)} "
+                     f"fSim(pi/2, pi/6), each a drawing gate of 2 qubits), {n_samples} samples, complex64, path_kernel=group=1024, "
+                     f"one Contractor per gate (infinite-memory SA, 8 runs x 100 sweeps); wall seconds of one walk (perf_counter, "
+                     f"device synchronised), the minimum of {reps} after a warm-up, spread = (max - min) / min; both rows in one "
+                     "process on the same Contractors")
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(0)
+
+        def with_kernel():
+            return s.sample(n_samples)[0]
+
+        def with_torch():
+            with contraction.Walkers(n_samples, n_qubits, seed=0, device=s.device) as w:
+                for g, (_, qs) in enumerate(s.gates):
+                    c, closing = s.contractors[g]
+                    c.run_walkers(w, closing, group=s.group)
+                    if len(qs) == 1:
+                        c.choose(w, qs[0], g)
+                        continue
+                    axes = [1 + c.plan.inds.index(x) for x in s.open_inds[g]]
+                    amp = torch.from_numpy(c.walker_outputs(w)).to("cuda").permute(0, *axes).reshape(n_samples, -1)
+                    p = amp.real.double() ** 2 + amp.imag.double() ** 2
+                    tail = p.flip(1).cumsum(1).flip(1)
+                    u = torch.rand(n_samples, dtype=torch.float64, device="cuda", generator=gen)
+                    v = ((u * tail[:, 0])[:, None] < tail[:, 1:]).sum(1).cpu().numpy()  # (the tails do not rise with v)
+                    bits = w.bits
+                    for j, q in enumerate(qs):
+                        bits[:, q] = (v >> (len(qs) - 1 - j)) & 1
+                    w.write(bits)
+                return sampling.tally(w.bits)
+
+        rows = []
+        for name, call in (("Sampler.sample (choose_joint)", with_kernel), ("walker_outputs + torch draw", with_torch)):
+            hits = call()  # warm-up
+            times = []
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                call()
+                torch.cuda.synchronize()
+                times.append(time.perf_counter() - t0)
+            rows.append((name, min(times), (max(times) - min(times)) / min(times), len(hits)))
+    lines.append(f"{'way':>32} {'wall s':>10} {'spread':>7} {'us / sample':>12} {'ms / gate':>10} {'bitstrings seen':>16}")
+    for name, t, spread, seen in rows:
+        lines.append(f"{name:>32} {t:10.6f} {spread:7.3f} {t / n_samples * 1e6:12.3f} {t / n_gates * 1e3:10.4f} {seen:16d}")
+    (_, t_new, s_new, _), (_, t_old, s_old, _) = rows
+    both = s_new + s_old
+    lines.append(f"  torch draw / choose_joint = {t_old / t_new:.2f}x (the two spreads together: {both:.3f})")
+    if t_new > t_old * (1 + both):
+        lines.append("  THE KERNEL'S WALK IS SLOWER than the torch draw's by more than the two spreads")
+    elif t_new * (1 + both) < t_old:
+        lines.append("  the kernel's walk is faster than the torch draw's by more than the two spreads")
+    else:
+        lines.append("  the two walks are within their spreads of each other")
+    print("\n".join(lines[-6:]), flush=True)
+
+
 def sample(lines, n_qubits=8, n_gates=40, n_samples=4096, reps=5):
     """One walk of a fixed random circuit (1-qubit unitaries and CZs, seeded) for `n_samples` samples, two ways, on the
     same Contractors (one per 1-qubit gate, the Sampler's) in one process.  (a) sampling.Sampler: Walkers on the device,
@@ -993,15 +1080,19 @@ def main():
     ap.add_argument("--resident", action="store_true", help="only the resident (Contractor) leg, appended to --out")
     ap.add_argument("--many", action="store_true", help="only the run_many leg, appended to --out")
     ap.add_argument("--sample", action="store_true", help="only the sampling leg, appended to --out")
+    ap.add_argument("--sample-joint", action="store_true", help="only the joint-draw sampling leg, appended to --out")
     ap.add_argument("--counts", type=int, nargs="+", default=[64, 1024, 16384])
     ap.add_argument("--loop-max", type=int, default=256)
     a = ap.parse_args()
-    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect + a.reuse + a.accumulate + a.resident + a.many + a.sample > 1:
-        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix, --indirect, --reuse, --accumulate, --resident, --many and --sample each "
+    if a.projs + a.storage + a.scaling + a.slice_batch + a.compute + a.path_kernel + a.hoist + a.matrix + a.indirect + a.reuse + a.accumulate + a.resident + a.many + a.sample + a.sample_joint > 1:
+        ap.error("--projs, --storage, --scaling, --slice-batch, --compute, --path-kernel, --hoist, --matrix, --indirect, --reuse, --accumulate, --resident, --many, --sample and --sample-joint each "
                  "append one leg: run them one after the other")
     lines = [f"# tools/time_contract.py on {torch.cuda.get_device_name(0)}; torch {torch.__version__}", ""]
-    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect or a.reuse or a.accumulate or a.resident or a.many or a.sample:  # (the other legs' sections stay as they are)
-        if a.sample:
+    if a.projs or a.storage or a.scaling or a.slice_batch or a.compute or a.path_kernel or a.hoist or a.matrix or a.indirect or a.reuse or a.accumulate or a.resident or a.many or a.sample or a.sample_joint:  # (the other legs' sections stay as they are)
+        if a.sample_joint:
+            lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
+            sample_joint(lines)
+        elif a.sample:
             lines.append(f"(the leg below: {torch.cuda.get_device_name(0)}; torch {torch.__version__})")
             sample(lines)
         elif a.many:
@@ -1059,6 +1150,7 @@ def main():
     resident(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     many(lines, a.depth, a.max_width, min(a.max_slices, 2048))
     sample(lines)
+    sample_joint(lines)
     Path(a.out).write_text("\n".join(lines) + "\n")
 
 
