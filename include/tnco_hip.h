@@ -121,6 +121,16 @@ typedef struct tnco_hip_desc {
  * not valid." / "Precision is too low." as the reference throws. */
 int tnco_hip_create(const tnco_hip_desc* desc, tnco_hip_handle* out);
 
+/* Diagnostics: the tree check of tnco_hip_create on EVERY one of `ntrees` trees ([3][N] each, `stride` >= 3N int32
+ * apart, HOST memory), one code per tree into status_out (host): 0 valid, 1..6 the first failing check of
+ * Tree::is_valid read strictly ("Nodes are not valid", "Last node should be root.", "There should be only one root.",
+ * "All leaves should be first.", "Number of nodes is not constenst with the number of leaves.", "Tree is not valid."),
+ * 7 = not every node is reached from the root ("Tree is not valid." too; the reference has no such check).
+ * where = 0: the host check (what `links` / `min_links` in host memory get), no device use.  where = 1: the trees are
+ * uploaded to `device` and checked by the kernel that device links get; it has no check 7 and answers 0 there. */
+int tnco_hip_diag_tree_check(int32_t device, int32_t N, const int32_t* links, int64_t stride, int64_t ntrees, int where,
+                             int32_t* status_out);
+
 /* Replaces the Python step loop `for beta in betas: prob.beta = beta;
  * opt.update(prob)` (tnco/app/infinite_memory/sa.py:199-209 over
  * Optimizer::update, infinite_memory/optimizer.hpp:90-221): n_steps sweeps on
@@ -363,6 +373,9 @@ int tnco_hip_greedy_trees_device(int32_t device, int32_t n_leaves, int32_t n_ind
                                  int32_t** links_device, int32_t n_threads);
 /* device -> host copy of such a buffer */
 int tnco_hip_copy_to_host(void* dst, const void* device_src, uint64_t bytes);
+/* host -> device copy into such a buffer (diagnostics: the tests plant damaged trees in it; the pointer must be one
+ * this library handed out -- memory of another HIP runtime in the process, a torch tensor's, is not known to this one) */
+int tnco_hip_copy_to_device(void* device_dst, const void* src, uint64_t bytes);
 int tnco_hip_diag_greedy_device_supported(int32_t n_leaves, int32_t n_inds, const int32_t* holders_off);
 /* diagnostics: the 36-bit key of the cost 2^a - 2^b - 2^c by which the device generator orders its
  * candidates (larger cost <=> larger key; a, b, c <= 2040) */

@@ -251,8 +251,8 @@ def test_invalid_inputs(core):
     seeds = H.replica_seeds(4)
     links = prob.links(seeds)
     bad = links.copy()
-    bad[2, 2, 0] = 5  # wrong parent
-    with pytest.raises(ValueError):
+    bad[2, 2, 0] = 5  # wrong parent: a leaf (check 6 of the tree check; every refusal: tests/test_tree_check_model.py)
+    with pytest.raises(ValueError, match=r"^Tree is not valid\.$"):
         core.BatchedOptimizer(prob.leaf_masks, bad, seeds, n_inds=prob.n_inds)
     with pytest.raises(NotImplementedError):
         core.BatchedOptimizer(prob.leaf_masks, links, seeds, n_inds=prob.n_inds, cost_type="float128")

@@ -159,7 +159,7 @@ def test_restore_arguments_are_checked(core):
     kw = dict(n_inds=prob.n_inds, dims=2)
     bad = links.copy()
     bad[1, 2, 0] = 5  # wrong parent in a best tree
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match=r"^Tree is not valid\.$"):
         core.BatchedOptimizer(prob.leaf_masks, links, seeds, min_links=bad, **kw)
     st = np.zeros((4, 625), np.uint32)
     st[2, 624] = 700

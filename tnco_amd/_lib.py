@@ -85,7 +85,7 @@ EXPORTS = [
     "tnco_hip_best", "tnco_hip_min_cost_device", "tnco_hip_get_trees", "tnco_hip_linear_paths", "tnco_hip_linear_paths_ssa", "tnco_hip_diag_counters", "tnco_hip_diag_moves", "tnco_hip_diag_full_copies",
     "tnco_hip_diag_kernel_time", "tnco_hip_diag_kernel_times", "tnco_hip_diag_stage_cycles",
     "tnco_hip_diag_launch_groups", "tnco_hip_diag_device_bytes", "tnco_hip_set_stream", "tnco_hip_destroy", "tnco_hip_release_cached", "tnco_hip_diag_cached_bytes", "tnco_hip_random_trees", "tnco_hip_greedy_trees",
-    "tnco_hip_greedy_trees_device", "tnco_hip_diag_greedy_device_supported", "tnco_hip_diag_greedy_device_redone", "tnco_hip_diag_greedy_device_last", "tnco_hip_greedy_device_release", "tnco_hip_copy_to_host", "tnco_hip_diag_greedy_cost_key",
+    "tnco_hip_greedy_trees_device", "tnco_hip_diag_greedy_device_supported", "tnco_hip_diag_greedy_device_redone", "tnco_hip_diag_greedy_device_last", "tnco_hip_greedy_device_release", "tnco_hip_copy_to_host", "tnco_hip_copy_to_device", "tnco_hip_diag_tree_check", "tnco_hip_diag_greedy_cost_key",
     "tnco_hip_comm_unique_id", "tnco_hip_comm_init", "tnco_hip_comm_destroy", "tnco_hip_comm_allreduce_min", "tnco_hip_comm_allgather",
     "tnco_hip_comm_barrier", "tnco_hip_comm_last_error",
     "tnco_hip_contract_create", "tnco_hip_contract_run", "tnco_hip_contract_stats", "tnco_hip_contract_kernel_launches",
@@ -186,6 +186,8 @@ def load() -> C.CDLL:
     L.tnco_hip_greedy_trees.argtypes = [i32, i32, vp, vp, vp, i64, vp, vp, vp, i32]
     L.tnco_hip_greedy_trees_device.argtypes = [i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, i32]
     L.tnco_hip_copy_to_host.argtypes = [vp, vp, C.c_uint64]
+    L.tnco_hip_copy_to_device.argtypes = [vp, vp, C.c_uint64]
+    L.tnco_hip_diag_tree_check.argtypes = [i32, i32, vp, i64, i64, C.c_int, vp]
     L.tnco_hip_diag_greedy_cost_key.argtypes = [i32, i32, i32]
     L.tnco_hip_diag_greedy_cost_key.restype = C.c_uint64
     L.tnco_hip_diag_greedy_device_supported.argtypes = [i32, i32, vp]

@@ -481,3 +481,9 @@ extern "C" int tnco_hip_copy_to_host(void* dst, const void* device_src, uint64_t
   G_TRY(hipMemcpy(dst, device_src, (size_t)bytes, hipMemcpyDeviceToHost));
   return TNCO_HIP_OK;
 }
+// ... and host -> device, into such a buffer (tests damage the trees before tnco_hip_create checks them)
+extern "C" int tnco_hip_copy_to_device(void* device_dst, const void* src, uint64_t bytes) {
+  if (!device_dst || !src) return TNCO_HIP_EINVAL;
+  G_TRY(hipMemcpy(device_dst, src, (size_t)bytes, hipMemcpyHostToDevice));
+  return TNCO_HIP_OK;
+}

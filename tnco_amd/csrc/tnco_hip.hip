@@ -287,45 +287,63 @@ __global__ void restore_min_kernel(ReplicaState* rs, int64_t r0, int64_t count, 
 
 // ---- host-side tree checks: Node::is_valid (include/tnco/node.hpp:72-107) +
 // Tree::is_valid (include/tnco/tree.hpp:58-139) -----------------------------
-const char* tree_check(int32_t N, const int32_t* left, const int32_t* right, const int32_t* parent,
-                       std::vector<int32_t>& cp, std::vector<int32_t>& cc) {
+// 0, or the number of the first check that fails (the text: tree_check_message).  Checks 1-6 are the reference's, read
+// strictly (an entry is -1 or in range; its two counters compared as their comments say; every child link answered by the
+// child's parent pointer).  Check 7 is this library's own: the traverse from the root reaches all N nodes.  Without it a
+// root over two leaves plus a ring of internal nodes that hold one another (A -> B -> C -> A, a leaf each) passes: every
+// count is right and every link is answered, yet the traverse visits 3 nodes and build_kernel's later passes would walk
+// order[] entries that nobody wrote.
+int tree_check(int32_t N, const int32_t* left, const int32_t* right, const int32_t* parent,
+               std::vector<int32_t>& cp, std::vector<int32_t>& cc) {
   const int32_t n = (N + 1) / 2;
   int roots = 0, leaves = 0;
   for (int32_t i = 0; i < N; ++i) {
     const int32_t xs[3] = {parent[i], left[i], right[i]};
     for (int k = 0; k < 3; ++k)
-      if (!(xs[k] == -1 || (xs[k] >= 0 && xs[k] < N))) return "Nodes are not valid";
-    if ((left[i] < 0) != (right[i] < 0)) return "Nodes are not valid";
-    if (left[i] >= 0 && left[i] == right[i]) return "Nodes are not valid";
-    if (left[i] >= 0 && parent[i] >= 0 && (parent[i] == left[i] || parent[i] == right[i]))
-      return "Nodes are not valid";
+      if (!(xs[k] == -1 || (xs[k] >= 0 && xs[k] < N))) return 1;
+    if ((left[i] < 0) != (right[i] < 0)) return 1;
+    if (left[i] >= 0 && left[i] == right[i]) return 1;
+    if (left[i] >= 0 && parent[i] >= 0 && (parent[i] == left[i] || parent[i] == right[i])) return 1;
     roots += parent[i] < 0;
     leaves += left[i] < 0;
   }
-  if (parent[N - 1] != -1) return "Last node should be root.";
-  if (roots != 1) return "There should be only one root.";
+  if (parent[N - 1] != -1) return 2;
+  if (roots != 1) return 3;
   for (int32_t i = 0; i < n; ++i)
-    if (left[i] >= 0) return "All leaves should be first.";
-  if (leaves != n) return "Number of nodes is not constenst with the number of leaves.";
-  std::fill(cp.begin(), cp.end(), 0);
-  std::fill(cc.begin(), cc.end(), 0);
+    if (left[i] >= 0) return 4;
+  if (leaves != n) return 5;
+  cp.assign((size_t)N, 0);
+  cc.assign((size_t)N, 0);
   for (int32_t i = 0; i < N; ++i) {
     if (left[i] >= 0) { cc[left[i]]++; cc[right[i]]++; }
     if (parent[i] >= 0) cp[parent[i]]++;
   }
   for (int32_t i = 0; i < N; ++i) {
-    if (cp[i] != (left[i] < 0 ? 0 : 2)) return "Tree is not valid.";
-    if (cc[i] != (parent[i] < 0 ? 0 : 1)) return "Tree is not valid.";
-    if (left[i] >= 0 && (parent[left[i]] != i || parent[right[i]] != i)) return "Tree is not valid.";
+    if (cp[i] != (left[i] < 0 ? 0 : 2)) return 6;
+    if (cc[i] != (parent[i] < 0 ? 0 : 1)) return 6;
+    if (left[i] >= 0 && (parent[left[i]] != i || parent[right[i]] != i)) return 6;
   }
-  return nullptr;
+  // the nodes host_traverse would visit, counted (cp as the stack: every node is named by one child link at most now, so
+  // it is pushed once at most, the stack never holds more than N entries and the walk ends)
+  int32_t top = 0, reached = 0;
+  cp[top++] = N - 1;
+  while (top > 0) {
+    const int32_t i = cp[--top];
+    ++reached;
+    if (left[i] >= 0) { cp[top++] = left[i]; cp[top++] = right[i]; }
+  }
+  return reached == N ? 0 : 7;
 }
 
-// The same checks for trees that are already in device memory (tnco_hip_greedy_trees_device leaves
+// Checks 1-6 for trees that are already in device memory (tnco_hip_greedy_trees_device leaves
 // them there), one wavefront per tree.  The host version's two counters (how often a node is named as
 // a parent / as a child) follow from the rest: with one root, n leaves, every child link answered by the
 // child's parent pointer and left != right, the 2(n - 1) child links name 2(n - 1) different nodes
-// other than the root -- each exactly once -- and the N - 1 parent pointers are those links.
+// other than the root -- each exactly once -- and the N - 1 parent pointers are those links
+// (tests/test_tree_check_model.py holds that argument against the host check, tests/test_gpu_tree_check.py this kernel).
+// The ONE difference from the host check: no check 7.  The kernel follows no link chain, so the ring described above
+// gets 0 here.  Device links come only from the library's own greedy, which builds trees by merging; host links and
+// min_links pass the host check.
 // Status: 0 ok, else the number of the first check of tree_check that fails.
 __global__ __launch_bounds__(64) void tree_check_kernel(int32_t N, const int32_t* links, int64_t stride, int64_t ntrees,
                                                         int32_t* out_status) {
@@ -371,8 +389,16 @@ const char* tree_check_message(int st) {
     case 3: return "There should be only one root.";
     case 4: return "All leaves should be first.";
     case 5: return "Number of nodes is not constenst with the number of leaves.";
-    default: return "Tree is not valid.";
+    default: return "Tree is not valid.";  // (6 and 7)
   }
+}
+// tree_check_kernel over `ntrees` trees, 3N int32 apart in device memory: statuses into the host array `status`
+// (tnco_hip_create for device links, tnco_hip_diag_tree_check)
+hipError_t check_trees_device(hipStream_t stream, int32_t N, const int32_t* dlinks, int64_t ntrees, int32_t* dcheck, int32_t* status) {
+  hipLaunchKernelGGL(tree_check_kernel, dim3((unsigned)ntrees), dim3(64), 0, stream, N, dlinks, 3 * (int64_t)N, ntrees, dcheck);
+  if (hipError_t e = hipGetLastError()) return e;
+  if (hipError_t e = hipMemcpyAsync(status, dcheck, (size_t)ntrees * 4, hipMemcpyDeviceToHost, stream)) return e;
+  return hipStreamSynchronize(stream);
 }
 
 // Post-order of include/tnco/utils.hpp:34-51.
@@ -427,7 +453,7 @@ const char* status_message(int st) {
     case 10:
     case 11: return "Contraction is not valid.";
     case 12: return "'node_masks' leaves differ from 'leaf_masks'.";
-    default: return "Tree is not valid.";
+    default: return tree_check_message(6);  // (build_kernel leaves 0, 10, 11 or 12)
   }
 }
 
@@ -471,23 +497,25 @@ hipError_t copy_rows(T* dst, int64_t dst_stride, const T* src, int64_t src_strid
   return hipMemcpy2D(dst, (size_t)dst_stride * sizeof(T), src, (size_t)src_stride * sizeof(T), (size_t)row * sizeof(T), (size_t)rows, kind);
 }
 
-// host-side structural validation of `ntrees` trees, `stride` int32 apart: the message of a failing one, or nullptr
+// host-side structural validation of `ntrees` trees, `stride` int32 apart: the message of the LOWEST-numbered failing
+// one (whatever the thread count: thread t takes the trees t, t + nth, ... and stops at its first failure), or nullptr
 const char* check_trees_host(int32_t N, const int32_t* links, int64_t stride, int64_t ntrees) {
   const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ntrees / 64 + 1, 16), std::thread::hardware_concurrency()));
-  std::vector<const char*> errs((size_t)nth, nullptr);
+  std::vector<int64_t> first((size_t)nth, ntrees);  // per thread: its first failing tree and that tree's code
+  std::vector<int> code((size_t)nth, 0);
   std::vector<std::thread> th;
   for (int t = 0; t < nth; ++t)
     th.emplace_back([&, t]() {
-      std::vector<int32_t> cp((size_t)N), cc((size_t)N);
-      for (int64_t r = t; r < ntrees && !errs[t]; r += nth) {
+      std::vector<int32_t> cp, cc;
+      for (int64_t r = t; r < ntrees && !code[t]; r += nth) {
         const int32_t* lk = links + r * stride;
-        errs[t] = tree_check(N, lk, lk + N, lk + 2 * (int64_t)N, cp, cc);
+        code[t] = tree_check(N, lk, lk + N, lk + 2 * (int64_t)N, cp, cc);
+        if (code[t]) first[t] = r;
       }
     });
   for (auto& x : th) x.join();
-  for (auto e : errs)
-    if (e) return e;
-  return nullptr;
+  const size_t t = (size_t)(std::min_element(first.begin(), first.end()) - first.begin());
+  return code[t] ? tree_check_message(code[t]) : nullptr;
 }
 
 // the leaves that hold each index, in leaf order: cnt[i] of them, the first `cap` in who[i * cap ...]
@@ -912,11 +940,8 @@ struct Create {
     if (links_on_device) {
       int32_t* dcheck = nullptr;
       HIP_TRY(tmp->alloc(&dcheck, ntrees));
-      hipLaunchKernelGGL(tree_check_kernel, dim3((unsigned)ntrees), dim3(64), 0, h->stream, (int32_t)N, dlinks, 3 * (int64_t)N, ntrees, dcheck);
-      HIP_TRY(hipGetLastError());
       std::vector<int32_t> chk((size_t)ntrees);
-      HIP_TRY(hipMemcpyAsync(chk.data(), dcheck, (size_t)ntrees * 4, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h->sync_all());
+      HIP_TRY(check_trees_device(h->stream, (int32_t)N, dlinks, ntrees, dcheck, chk.data()));
       for (int64_t r = 0; r < ntrees; ++r)
         if (chk[r]) return fail(TNCO_HIP_EINVAL, tree_check_message(chk[r]));
     }
@@ -1462,6 +1487,33 @@ int tnco_hip_create(const tnco_hip_desc* d, tnco_hip_handle* out) {
   if (int rc = c.configure_launch()) return rc;
   c.cmark("the rest (finite width, min trees)");
   *out = c.owner.release();
+  return TNCO_HIP_OK;
+}
+
+// diagnostics: the verdict of the tree check on EVERY tree of a host array (tnco_hip_create stops at the first refusal)
+int tnco_hip_diag_tree_check(int32_t device, int32_t N, const int32_t* links, int64_t stride, int64_t ntrees, int where,
+                             int32_t* status_out) {
+  if (!links || !status_out) return fail(TNCO_HIP_EINVAL, "null argument.");
+  if (N < 1 || N % 2 == 0 || ntrees < 1 || ntrees > 0x7fffffff || stride < 3 * (int64_t)N || (where != 0 && where != 1))
+    return fail(TNCO_HIP_EINVAL, "'N' / 'ntrees' / 'stride' / 'where' are not valid.");
+  if (where == 0) {  // the host check, no device use
+    std::vector<int32_t> cp, cc;
+    for (int64_t r = 0; r < ntrees; ++r) {
+      const int32_t* lk = links + r * stride;
+      status_out[r] = tree_check(N, lk, lk + N, lk + 2 * (int64_t)N, cp, cc);
+    }
+    return TNCO_HIP_OK;
+  }
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(TNCO_HIP_EINVAL, "'device' is not valid.");
+  HIP_TRY(hipSetDevice(device));
+  TempBufs tmp;
+  int32_t *dlinks = nullptr, *dcheck = nullptr;
+  HIP_TRY(tmp.alloc(&dlinks, ntrees * 3 * N));
+  HIP_TRY(tmp.alloc(&dcheck, ntrees));
+  HIP_TRY(copy_rows(dlinks, 3 * (int64_t)N, links, stride, 3 * (int64_t)N, ntrees, hipMemcpyHostToDevice));
+  HIP_TRY(check_trees_device(nullptr, N, dlinks, ntrees, dcheck, status_out));
   return TNCO_HIP_OK;
 }
 
