@@ -250,11 +250,21 @@ MAX_PATH_STEP_MACS = 1 << 24
 MAX_PERMUTE_QUBITS = 8  # qubits of one Walkers.permute at the most (csrc/contract_walk.h WALK_MAX_PERMUTE)
 MAX_CHOOSE_QUBITS = 6  # qubits of one Contractor.choose_joint at the most (csrc/contract_walk.h WALK_MAX_CHOOSE)
 
-# operand / destination kinds and table widths: include/tnco_hip.h (tnco_hip_contract_desc)
+# operand / destination kinds, table widths and columns: the layout is specified by include/tnco_hip.h
+# (tnco_hip_contract_desc); the names and values are those of csrc/contract_tables.h
 LEAF, ARENA, OUT = 0, 1, 2
 PERM_W = 8 + 2 * MAX_AXES
 STEP_W = 16
 LEAF_SL_W = 1 + 2 * MAX_AXES
+# steps: an operand's kind, ref and two strides, those of B ST_SIDE after those of A; the exponent slots under scaling
+ST_A_KIND, ST_A_REF, ST_A_M, ST_A_K, ST_B_KIND, ST_B_REF, ST_B_K, ST_B_N = range(8)
+ST_C_KIND, ST_C_REF, ST_H, ST_M, ST_N, ST_K, ST_A_SLOT, ST_B_SLOT = range(8, 16)
+ST_SIDE = 4
+# perms: column 7 is 0; PM_DIMS and PM_STRIDES start blocks of MAX_AXES columns
+PM_SRC_KIND, PM_SRC_REF, PM_DST_KIND, PM_DST_REF, PM_NDIM, PM_NUMEL, PM_GROUP = range(7)
+PM_DIMS, PM_STRIDES = 8, 8 + MAX_AXES
+# leaf_sl: the number of sliced axes, then their slice positions and their element strides
+LS_COUNT, LS_SLOTS, LS_STRIDES = 0, 1, 1 + MAX_AXES
 # the kernel paths of csrc/contract.hip in the order tnco_hip_contract_kernel_launches counts them; a tiled name gives
 # the memory order of A, then of B (mk_kn: A [m][k], B [k][n])
 KERNEL_PATHS = ("gather", "tiled_km_nk", "tiled_km_kn", "tiled_mk_nk", "tiled_mk_kn", "dot", "stream")
@@ -263,7 +273,14 @@ ROW_KERNEL_PATHS = ("rows_tiled", "rows_dot", "rows_stream")
 # the kernels that read a folded operand in place (indirect=True) in the order tnco_hip_contract_indirect_launches counts them
 INDIRECT_KERNEL_PATHS = ("ix_tiled", "ix_dot", "ix_stream")
 IND_W = 6  # ind_steps: offsets into ind_maps of the tables of A by h, m, k and of B by h, k, n; -1: the operand is not folded
+IX_A_H, IX_A_M, IX_A_K, IX_B_H, IX_B_K, IX_B_N = range(IND_W)
+IX_SIDE = 3
 ROW_W = 5  # row_steps: R, rows of A, map of A, rows of B, map of B (a map: offset into row_maps, -1 none)
+RW_R, RW_A_ROWS, RW_A_MAP, RW_B_ROWS, RW_B_MAP = range(ROW_W)
+RW_SIDE = 2
+# words per row of the tables that exist on the device only: the permute groups of the path kernel (first row, count), the
+# leaves of a run over leaf sets (pointer, set stride) and over walkers (pointer, qubit, version stride)
+GR_W, SET_W, WALK_W = 2, 2, 3
 PROJ = "proj"  # the first axis of a projected result
 ALIGN = 64  # arena offsets in elements: 64 x (4..16 B) keeps every buffer 256-byte aligned
 
@@ -400,7 +417,7 @@ class Plan:
         # a path kernel: also the tables that are new on the device: the steps, the first row and the count of every
         # permute group, the placement of every assignment
         if self.path_kernel is not None and len(self.steps):
-            tables += 8 * (self.steps.size + 2 * (len(self.steps) + 1) + self.slice_range[1] - self.slice_range[0])
+            tables += 8 * (self.steps.size + GR_W * (len(self.steps) + 1) + self.slice_range[1] - self.slice_range[0])
         if self.ind_steps is not None:
             tables += 8 * (self.ind_steps.size + self.ind_maps.size)
         # accumulate: the wide accumulator, and unbatched a staging block of its own; a plan without steps sums nothing
@@ -592,7 +609,7 @@ def _named_order(slice_order, slice_inds) -> tuple:
 
 def _step_macs(row) -> int:
     """H M N K of a row of `Plan.steps`."""
-    return int(row[10]) * int(row[11]) * int(row[12]) * int(row[13])
+    return int(row[ST_H]) * int(row[ST_M]) * int(row[ST_N]) * int(row[ST_K])
 
 
 def _runs(period: int, lo: int, hi: int) -> int:
@@ -644,7 +661,7 @@ def _offset_table(group, st, dims) -> np.ndarray:
 def _check_path_steps(p) -> None:
     """ValueError when a step of the plan is beyond what one workgroup of the path kernel is given."""
     for k, row in enumerate(p.steps):
-        H, M, N, K = (int(v) for v in row[10:14])
+        H, M, N, K = (int(row[q]) for q in (ST_H, ST_M, ST_N, ST_K))
         if H * M * N * K > MAX_PATH_STEP_MACS:
             raise ValueError(f"step {k} (H M N K = {H} x {M} x {N} x {K}) has more than 2^24 multiply-adds: too large for "
                              "'path_kernel', which runs a step in one workgroup.")
@@ -820,68 +837,94 @@ def _unique_rows(table):
     return rows, inverse.reshape(-1)
 
 
-def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
-         sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
-         hoist=None, indirect=None, reuse=None, slice_order=None, accumulate=None) -> Plan:
-    """The device plan of one contraction along a path that leaves one tensor (no GPU).
-    `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`, `slice_batch`,
-    `compute`, `path_kernel`, `hoist`, `indirect`, `reuse`, `slice_order`, `accumulate`: see the module docstring."""
-    options = _Options(storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute, path_kernel=path_kernel,
-                       hoist=hoist, indirect=indirect, reuse=reuse, slice_order=slice_order, accumulate=accumulate)
-    options.check(dtype, projs)
-    if isinstance(slice_order, str):  # "reuse": the default order unless the greedy one has strictly fewer multiply-adds
-        mode = dict(slices=slices, slice_range=slice_range, dtype=dtype)
-        p = plan(path, ts_inds, shapes, output_inds, **mode, **options.keywords(slice_order=None))
-        dims = dict(zip(p.slice_inds, p.slice_dims))
-        deps = _step_deps(_check_path(path, len(p.leaf_numel)), [tuple(xs) for xs in ts_inds],
-                          frozenset(x for x in slices if dims[x] > 1))
-        each = [_step_macs(r) for r in p.steps]
-        greedy = _reuse_order(p.slice_inds, deps, each)
-        if greedy != p.slice_inds and _reuse_macs(greedy, deps, each, dims, *p.slice_range) < p.macs:
-            p = plan(path, ts_inds, shapes, output_inds, **mode, **options.keywords(slice_order=greedy))
-        return p
-    ts_inds = [tuple(xs) for xs in ts_inds]
-    shapes = [tuple(int(d) for d in s) for s in shapes]
-    dims = _dims_of(ts_inds, shapes)
-    steps = _check_path(path, len(ts_inds))
-    final, out_inds = tnmod.contract(steps, ts_inds, output_inds, dims)
-    if len(final) != 1:
-        raise ValueError("plan() needs a path that leaves one tensor.")
-    final = tuple(final[0])
-    sl = frozenset(slices)
-    if projs is None and tuple(sparse_inds):
-        raise ValueError("'sparse_inds' need 'projs'.")
-    rows_of, leaf_rows, row_steps, row_maps = {}, (), None, None  # _RowAxis -> its table of values [rows, len(cols)]
-    if projs is not None:
-        sparse, projs = _check_projs(sparse_inds, projs, dims, ts_inds, out_inds, sl)
-        col = {x: j for j, x in enumerate(sparse)}
+def _size(xs, dims) -> int:
+    return math.prod(dims[x] for x in xs)
 
-        def row_axis(xs):  # of a tensor that holds the indices xs, None when none of them is sparse
-            cols = tuple(sorted(col[x] for x in xs if x in col))
-            if not cols:
-                return None
-            ax = _RowAxis(cols)
-            if ax not in rows_of:
-                rows_of[ax] = _unique_rows(projs[:, cols])[0]
-                dims[ax] = len(rows_of[ax])
-            return ax
 
-        # a leaf is restricted to its rows on the host: [rows][its other axes], sliced ones included
-        leaf_rows = []
-        for t, (xs, shape) in enumerate(zip(ts_inds, shapes)):
-            ax = row_axis(xs)
-            if ax is None:
-                leaf_rows.append(None)
-                continue
-            leaf_rows.append((tuple(xs.index(sparse[j]) for j in ax.cols), rows_of[ax]))
-            kept = [k for k, x in enumerate(xs) if x not in col]
-            ts_inds[t] = (ax,) + tuple(xs[k] for k in kept)
-            shapes[t] = (dims[ax],) + tuple(shape[k] for k in kept)
-        leaf_rows = tuple(leaf_rows)
-        full_final = final
-        ax = row_axis(final)
-        final = (() if ax is None else (ax,)) + tuple(x for x in final if x not in col)
-        row_steps, row_maps = [], []
+def _dense_strides(inds, dims) -> dict:
+    """index -> element stride of a dense tensor with the axes `inds`."""
+    return {x: _size(inds[k + 1:], dims) for k, x in enumerate(inds)}
+
+
+@dataclass(frozen=True)
+class _Slices:
+    """The slice set-up of a plan."""
+    held: frozenset  # `slices` as given
+    inds: tuple  # in order: the first one the most significant digit of an assignment
+    dims: tuple
+    lo: int  # the assignments of slice_range
+    hi: int
+    place: dict  # sliced index -> the product of the dimensions after it
+
+    @property
+    def n(self) -> int:
+        return math.prod(self.dims)
+
+
+def _plan_in_reuse_order(path, ts_inds, shapes, output_inds, slices, slice_range, dtype, options) -> Plan:
+    """slice_order="reuse": the plan of the default order unless the greedy one has strictly fewer multiply-adds."""
+    mode = dict(slices=slices, slice_range=slice_range, dtype=dtype)
+    p = plan(path, ts_inds, shapes, output_inds, **mode, **options.keywords(slice_order=None))
+    dims = dict(zip(p.slice_inds, p.slice_dims))
+    deps = _step_deps(_check_path(path, len(p.leaf_numel)), [tuple(xs) for xs in ts_inds],
+                      frozenset(x for x in slices if dims[x] > 1))
+    each = [_step_macs(r) for r in p.steps]
+    greedy = _reuse_order(p.slice_inds, deps, each)
+    if greedy != p.slice_inds and _reuse_macs(greedy, deps, each, dims, *p.slice_range) < p.macs:
+        p = plan(path, ts_inds, shapes, output_inds, **mode, **options.keywords(slice_order=greedy))
+    return p
+
+
+def _row_axis(xs, sparse, projs, rows_of, dims):
+    """The row axis of a tensor that holds the indices xs, None when none of them is sparse; a new one enters `rows_of`
+    (its table of values [rows, len(cols)]) and `dims`."""
+    cols = tuple(sorted(sparse.index(x) for x in xs if x in sparse))
+    if not cols:
+        return None
+    ax = _RowAxis(cols)
+    if ax not in rows_of:
+        rows_of[ax] = _unique_rows(projs[:, cols])[0]
+        dims[ax] = len(rows_of[ax])
+    return ax
+
+
+def _project_leaves(sparse, projs, ts_inds, shapes, final, dims, rows_of):
+    """The leaves and the final tensor with their sparse indices replaced by a row axis, outermost: `ts_inds` and `shapes`
+    are changed in place (a leaf is restricted to its rows on the host: [rows][its other axes], sliced ones included).
+    Returns (leaf_rows, the final tensor's axes)."""
+    leaf_rows = []
+    for t, (xs, shape) in enumerate(zip(ts_inds, shapes)):
+        ax = _row_axis(xs, sparse, projs, rows_of, dims)
+        if ax is None:
+            leaf_rows.append(None)
+            continue
+        leaf_rows.append((tuple(xs.index(sparse[j]) for j in ax.cols), rows_of[ax]))
+        kept = [k for k, x in enumerate(xs) if x not in sparse]
+        ts_inds[t] = (ax,) + tuple(xs[k] for k in kept)
+        shapes[t] = (dims[ax],) + tuple(shape[k] for k in kept)
+    ax = _row_axis(final, sparse, projs, rows_of, dims)
+    return tuple(leaf_rows), (() if ax is None else (ax,)) + tuple(x for x in final if x not in sparse)
+
+
+def _projected_result(p, sparse, projs, leaf_rows, row_steps, row_maps, full_final, dims) -> Plan:
+    """The fields of a plan with projections: the device holds the distinct rows of the final tensor; the result has one
+    per projection, duplicates included."""
+    p.sparse_inds, p.leaf_rows = sparse, leaf_rows
+    p.row_steps = np.array(row_steps, np.int64).reshape(-1, ROW_W)
+    p.row_maps = np.concatenate(row_maps + [np.zeros(0, np.int32)]).astype(np.int32)
+    p.macs_per_slice = int(sum(int(w[RW_R]) * _step_macs(r) for w, r in zip(row_steps, p.steps)))
+    rest = tuple(x for x in full_final if x not in sparse)
+    if sparse:
+        p.out_rows = (dims[p.inds[0]], _unique_rows(projs)[1])
+    else:
+        p.out_rows = (1, np.zeros(len(projs), np.int64))
+    p.inds, p.shape = (PROJ,) + rest, (len(projs),) + tuple(dims[x] for x in rest)
+    return p
+
+
+def _slice_setup(sl, slice_order, slice_range, ts_inds, final, dims) -> _Slices:
+    """The sliced indices in order, their dimensions and places and the range of assignments; refuses what is wrong
+    with `slices`, `slice_order` and `slice_range`, and a tensor with too many axes after slicing."""
     every = list(dict.fromkeys(x for xs in ts_inds for x in xs))
     if not sl <= set(every):
         raise ValueError("'slices' has indices not in 'ts_inds'.")
@@ -895,39 +938,180 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         raise ValueError("'slice_range' is not valid.")
     if any(sum(x not in sl for x in xs) > MAX_AXES for xs in ts_inds + [final]):
         raise NotImplementedError(f"tensors with more than {MAX_AXES} axes (after slicing) are not supported.")
-    size = lambda xs: math.prod(dims[x] for x in xs)  # noqa: E731
-    slot = {x: k for k, x in enumerate(slice_inds)}
     place = {x: math.prod(slice_dims[k + 1:]) for k, x in enumerate(slice_inds)}
+    return _Slices(sl, slice_inds, slice_dims, lo, hi, place)
 
-    # The period of a tensor whose leaves hold the sliced indices `dep`: it has one value for all assignments a with
-    # equal a // period.  reuse: the smallest place of `dep`, the number of assignments when `dep` is empty.  hoist is the
-    # two-level case and needs ranks only: 2 for a slice-free tensor, 1 for every other.  Without either: 1
-    def period(dep):
-        if reuse is True:
-            return min((place[x] for x in dep), default=n_slices)
-        return 2 if hoist is True and bool(sl) and not dep else 1
 
+def _period(dep, S: _Slices, hoist, reuse) -> int:
+    """The period of a tensor whose leaves hold the sliced indices `dep`: it has one value for all assignments a with
+    equal a // period.  reuse: the smallest place of `dep`, the number of assignments when `dep` is empty.  hoist is the
+    two-level case and needs ranks only: 2 for a slice-free tensor, 1 for every other.  Without either: 1."""
+    if reuse is True:
+        return min((S.place[x] for x in dep), default=S.n)
+    return 2 if hoist is True and bool(S.held) and not dep else 1
+
+
+def _leaf_tables(ts_inds, shapes, dims, S: _Slices, hoist, reuse):
+    """(leaf_numel, leaf_sl, per leaf index -> element stride of the full (unsliced) array, the leaves as the tensors
+    the step loop starts from, each with its exponent slot, dep, per and free)."""
+    slot = {x: k for k, x in enumerate(S.inds)}
     leaf_numel = np.array([math.prod(s) for s in shapes], np.int64)
     leaf_sl = np.zeros((len(ts_inds), LEAF_SL_W), np.int64)
-    strides = []  # per leaf: index -> element stride of the full (unsliced) array
-    live = []
-    for t, (xs, shape) in enumerate(zip(ts_inds, shapes)):
-        st = dict(zip(xs, (math.prod(shape[k + 1:]) for k in range(len(xs)))))
+    strides, live = [], []
+    for t, xs in enumerate(ts_inds):
+        st = _dense_strides(xs, dims)
         strides.append(st)
-        cut = [x for x in xs if x in sl]
-        leaf_sl[t, 0] = len(cut)
-        leaf_sl[t, 1:1 + len(cut)] = [slot[x] for x in cut]
-        leaf_sl[t, 1 + MAX_AXES:1 + MAX_AXES + len(cut)] = [st[x] for x in cut]
-        kept = tuple(x for x in xs if x not in sl)
+        cut = [x for x in xs if x in S.held]
+        leaf_sl[t, LS_COUNT] = len(cut)
+        leaf_sl[t, LS_SLOTS:LS_SLOTS + len(cut)] = [slot[x] for x in cut]
+        leaf_sl[t, LS_STRIDES:LS_STRIDES + len(cut)] = [st[x] for x in cut]
+        kept = tuple(x for x in xs if x not in S.held)
         # a leaf is read in place when its kept axes are one contiguous block (sliced axes outermost, or none)
-        dense = all(st[x] == size(kept[k + 1:]) for k, x in enumerate(kept))
-        live.append(_Live(kept, LEAF if dense else None, t, t))
-        live[-1].slot = t  # (scaling: the exponent slot; a permute keeps it)
+        dense = all(st[x] == _size(kept[k + 1:], dims) for k, x in enumerate(kept))
+        T = _Live(kept, LEAF if dense else None, t, t)
+        T.slot = t  # (scaling: the exponent slot; a permute keeps it)
         # slice-free: no leaf below it holds a sliced index (it runs once per call; `indirect` leaves its permutes alone).
         # reuse: a sliced index of dimension 1 has one value in every assignment and counts as not held
-        moving = frozenset(x for x in cut if dims[x] > 1) if reuse is True else frozenset(cut)
-        live[-1].dep, live[-1].per = moving, period(moving)
-        live[-1].free = bool(sl) and not moving and (hoist is True or (reuse is True and n_slices > 1))
+        T.dep = frozenset(x for x in cut if dims[x] > 1) if reuse is True else frozenset(cut)
+        T.per = _period(T.dep, S, hoist, reuse)
+        T.free = bool(S.held) and not T.dep and (hoist is True or (reuse is True and S.n > 1))
+        live.append(T)
+    return leaf_numel, leaf_sl, strides, live
+
+
+def _step_row_axes(A, B, projs, rows_of, dims):
+    """(ra, rb, rz): the row axis of each operand and of the result of a step, each () or a 1-tuple.  Row axes stay
+    outermost and out of the roles: h, m, n, k are computed over the other indices."""
+    ra = tuple(x for x in A.inds[:1] if isinstance(x, _RowAxis))
+    rb = tuple(x for x in B.inds[:1] if isinstance(x, _RowAxis))
+    rz = (_RowAxis(sorted(set(ra[0].cols if ra else ()) | set(rb[0].cols if rb else ()))),) if ra or rb else ()
+    if rz and rz[0] not in rows_of:
+        rows_of[rz[0]] = _unique_rows(projs[:, rz[0].cols])[0]
+        dims[rz[0]] = len(rows_of[rz[0]])
+    return ra, rb, rz
+
+
+def _operand_forms(A, B, head_a, head_b, xs, ys, s, dims):
+    """(s_order, form_a, form_b): the order of the summed indices `s`, A's or B's, that moves the fewest elements, and
+    the form in which each operand can be read as it lies -- A as head_a + xs + s_order (0) or head_a + s_order + xs (1), B
+    as head_b + s_order + ys (0) or head_b + ys + s_order (1) -- None: it has to be permuted."""
+    best = None
+    for s_order in dict.fromkeys((tuple(q for q in A.inds if q in s), tuple(q for q in B.inds if q in s))):
+        fa = [f for f in (0, 1) if A.kind is not None and _fits(A.inds, head_a, xs, s_order, f == 1)]
+        fb = [f for f in (0, 1) if B.kind is not None and _fits(B.inds, head_b, ys, s_order, f == 0)]
+        moved = (0 if fa else _size(A.inds, dims)) + (0 if fb else _size(B.inds, dims))
+        if best is None or moved < best[0]:
+            best = (moved, s_order, fa[0] if fa else None, fb[0] if fb else None)
+    return best[1:]
+
+
+def _row_step(ra, rb, rz, rows_of, dims, H, M, form_a, pool_len):
+    """The row record of a projected step: (M of the step, its row of row_steps, the maps it adds to the pool of
+    `pool_len` entries, its fields of `ops`)."""
+    R = _size(rz, dims)
+    if ra == rz and not rb and H == 1 and form_a == 0:
+        # only the first operand has rows, stored [r][m][k]: a plain GEMM with R M rows
+        return R * M, [1, 1, -1, 1, -1], [], dict(M=R * M, R=1, folded=True, a_map=None, b_map=None)
+    maps = []
+    for r in (ra, rb):
+        if not r or r == rz:  # one row for every r / the rows of the result, in place
+            maps.append(None)
+            continue
+        sub = rows_of[rz[0]][:, [rz[0].cols.index(c) for c in r[0].cols]]
+        both, where = _unique_rows(np.concatenate([rows_of[r[0]], sub]))
+        assert len(both) == len(rows_of[r[0]])  # (every row of the result restricts to a row it has)
+        maps.append(where[len(both):].astype(np.int32))
+    row = [0] * ROW_W
+    row[RW_R], row[RW_A_ROWS], row[RW_B_ROWS] = R, _size(ra, dims), _size(rb, dims)
+    for at, m in zip((RW_A_MAP, RW_B_MAP), maps):
+        row[at] = -1 if m is None else pool_len
+        pool_len += 0 if m is None else len(m)
+    return M, row, [m for m in maps if m is not None], dict(R=R, folded=False, a_map=maps[0], b_map=maps[1])
+
+
+def _replay_arena(front, events, buf_size):
+    """(buffer -> arena offset, the peak).  One allocator, the phases in order of descending period (hoist: the hoisted
+    phase first), the events of a phase in path order; a phase's temporaries are released, the kept buffers never.  Why
+    that is sound when the phases run slowest first at every assignment at which they are due: a slower phase's
+    temporaries may lie where a faster phase's kept buffers lie, because whenever the slower phase is due every faster
+    one is due after it (the periods divide one another) and rewrites them.  They never lie on a slower phase's kept
+    buffers, which are still allocated when the faster phase is planned."""
+    arena, offset = _Arena(), {}
+    for what, buf in (ev for P in sorted(set(front) | set(events), reverse=True) for ev in front[P] + events[P]):
+        if what == "alloc":
+            offset[buf] = arena.alloc(buf_size[buf])
+        else:
+            arena.release(offset[buf], buf_size[buf])
+    return offset, arena.peak
+
+
+def _patch_offsets(perms, rows, offset) -> None:
+    """The buffer numbers of the arena refs of the permute and step rows replaced by their offsets."""
+    for row in perms:
+        for kind, ref in ((PM_SRC_KIND, PM_SRC_REF), (PM_DST_KIND, PM_DST_REF)):
+            if row[kind] == ARENA:
+                row[ref] = offset[row[ref]]
+    for row in rows:
+        for kind, ref in ((ST_A_KIND, ST_A_REF), (ST_B_KIND, ST_B_REF), (ST_C_KIND, ST_C_REF)):
+            if row[kind] == ARENA:
+                row[ref] = offset[row[ref]]
+
+
+def _keyword_fields(p, o: _Options, offset, buf_size, stage, kept_bufs, kept_per, step_per, perm_per, ind_rows, ind_pool) -> None:
+    """The fields of the plan that the option keywords `o` add to its tables."""
+    lo, hi = p.slice_range
+    if o.scaling is not None:
+        p.scaling = o.scaling
+        p.stage_refs = np.array([offset[b] if b >= 0 else -1 for b in stage], np.int64)
+    if o.slice_batch is not None:  # (the tables are those of the unbatched plan)
+        p.slice_batch = min(int(o.slice_batch), hi - lo) if len(p.steps) else 1
+    if o.path_kernel is not None:  # (the tables are those of the unfused plan; projections were refused above)
+        _check_path_steps(p)
+        p.path_kernel = min(int(o.path_kernel), hi - lo) if len(p.steps) else 1
+    p.kept = tuple((offset[b], buf_size[b]) for b in kept_bufs)  # (without hoist and reuse every period is 1: none)
+    if o.hoist is not None:  # (without a hoisted step or permute the tables are those of the plan without the keyword)
+        p.step_hoist, p.perm_hoist = (step_per == 2).astype(np.int64), (perm_per == 2).astype(np.int64)
+        p.hoisted = (int(p.step_hoist.sum()), int(p.perm_hoist.sum()))
+        p.hoisted_macs = int(sum(_step_macs(r) for r, h in zip(p.steps, p.step_hoist) if h))
+    if o.reuse is not None:  # (when every period is 1 the tables are those of the plan without the keyword)
+        p.step_period, p.perm_period = step_per, perm_per
+        p.reused = (int((step_per > 1).sum()), int((perm_per > 1).sum()))
+        p.kept_period = tuple(kept_per)
+    if o.indirect is not None:  # (with nothing folded the tables are those of the plan without the keyword)
+        p.indirect = sum((row[IX_A_H] >= 0) + (row[IX_B_H] >= 0) for row in ind_rows)
+        if p.indirect:
+            p.ind_steps = np.array(ind_rows, np.int64).reshape(-1, IND_W)
+            p.ind_maps = np.concatenate(ind_pool).astype(np.int64)
+
+
+def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None, dtype=np.float64,
+         sparse_inds=(), projs=None, storage=None, scaling=None, slice_batch=None, compute=None, path_kernel=None,
+         hoist=None, indirect=None, reuse=None, slice_order=None, accumulate=None) -> Plan:
+    """The device plan of one contraction along a path that leaves one tensor (no GPU).
+    `shapes`: the leaves' shapes, in ts_inds order.  `sparse_inds`, `projs`, `storage`, `scaling`, `slice_batch`,
+    `compute`, `path_kernel`, `hoist`, `indirect`, `reuse`, `slice_order`, `accumulate`: see the module docstring."""
+    options = _Options(storage=storage, scaling=scaling, slice_batch=slice_batch, compute=compute, path_kernel=path_kernel,
+                       hoist=hoist, indirect=indirect, reuse=reuse, slice_order=slice_order, accumulate=accumulate)
+    options.check(dtype, projs)
+    if isinstance(slice_order, str):
+        return _plan_in_reuse_order(path, ts_inds, shapes, output_inds, slices, slice_range, dtype, options)
+    ts_inds = [tuple(xs) for xs in ts_inds]
+    shapes = [tuple(int(d) for d in s) for s in shapes]
+    dims = _dims_of(ts_inds, shapes)
+    steps = _check_path(path, len(ts_inds))
+    final, out_inds = tnmod.contract(steps, ts_inds, output_inds, dims)
+    if len(final) != 1:
+        raise ValueError("plan() needs a path that leaves one tensor.")
+    final = full_final = tuple(final[0])
+    sl = frozenset(slices)
+    if projs is None and tuple(sparse_inds):
+        raise ValueError("'sparse_inds' need 'projs'.")
+    rows_of, row_steps, row_maps = {}, [], []  # _RowAxis -> its table of values [rows, len(cols)]
+    if projs is not None:
+        sparse, projs = _check_projs(sparse_inds, projs, dims, ts_inds, out_inds, sl)
+        leaf_rows, final = _project_leaves(sparse, projs, ts_inds, shapes, final, dims, rows_of)
+    S = _slice_setup(sl, slice_order, slice_range, ts_inds, final, dims)
+    leaf_numel, leaf_sl, strides, live = _leaf_tables(ts_inds, shapes, dims, S, hoist, reuse)
 
     # buffers are symbolic (numbers) until the event list is replayed on the arena.  One phase per period, keyed by it:
     # under `hoist` [2] the hoisted work of a call and [1] the work of an assignment, without a keyword everything in [1]
@@ -942,36 +1126,28 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         return len(buf_size) - 1
 
     def permute(src, layout, group, dst_kind=ARENA):
-        numel = size(layout)
-        if src.leaf is not None:
-            skind, sref, st = LEAF, src.leaf, strides[src.leaf]
-        else:
-            skind, sref = ARENA, src.ref
-            st = {x: size(src.inds[k + 1:]) for k, x in enumerate(src.inds)}
+        numel = _size(layout, dims)
+        st = strides[src.leaf] if src.leaf is not None else _dense_strides(src.inds, dims)
         h = src.per if dst_kind == ARENA else 1  # (a permute has the period of its source)
         assert h == src.per or src.per == 1  # (what is copied to the output depends on every sliced index)
         perm_per.append(h)
-        dst = new_buf(numel, at_start=group < 0, h=h) if dst_kind == ARENA else 0
-        row = [skind, sref, dst_kind, dst, len(layout), numel, group, 0] + [0] * (2 * MAX_AXES)
-        row[8:8 + len(layout)] = [dims[x] for x in layout]
-        row[8 + MAX_AXES:8 + MAX_AXES + len(layout)] = [st[x] for x in layout]
+        row = [0] * PERM_W
+        row[PM_SRC_KIND], row[PM_SRC_REF] = (LEAF, src.leaf) if src.leaf is not None else (ARENA, src.ref)
+        row[PM_DST_KIND], row[PM_DST_REF] = dst_kind, new_buf(numel, at_start=group < 0, h=h) if dst_kind == ARENA else 0
+        row[PM_NDIM], row[PM_NUMEL], row[PM_GROUP] = len(layout), numel, group
+        row[PM_DIMS:PM_DIMS + len(layout)] = [dims[x] for x in layout]
+        row[PM_STRIDES:PM_STRIDES + len(layout)] = [st[x] for x in layout]
         perms.append(row)
-        return dst
+        return row[PM_DST_REF]
 
     left = tnmod.get_hyper_count(ts_inds)
     keep = frozenset(out_inds) | frozenset(final)
     if not steps:  # a single leaf: copied (gathered, when sliced) into the output
-        permute(live[0], tuple(x for x in final if x not in sl), -1, OUT)
+        permute(live[0], tuple(x for x in final if x not in S.held), -1, OUT)
         ops.append(dict(copy=live[0].inds))
     for k, (a, b) in enumerate(steps):
         B, A = live.pop(b), live.pop(a)
-        # row axes stay outermost and out of the roles: h, m, n, k are computed over the other indices
-        ra = tuple(x for x in A.inds[:1] if isinstance(x, _RowAxis))
-        rb = tuple(x for x in B.inds[:1] if isinstance(x, _RowAxis))
-        rz = (_RowAxis(sorted(set(ra[0].cols if ra else ()) | set(rb[0].cols if rb else ()))),) if ra or rb else ()
-        if rz and rz[0] not in rows_of:
-            rows_of[rz[0]] = _unique_rows(projs[:, rz[0].cols])[0]
-            dims[rz[0]] = len(rows_of[rz[0]])
+        ra, rb, rz = _step_row_axes(A, B, projs, rows_of, dims)
         shared = frozenset(A.inds[len(ra):]) & frozenset(B.inds[len(rb):])
         stay = frozenset(x for x in shared if left[x] > 1) | (keep & shared)
         for x in shared:
@@ -979,15 +1155,7 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
         h = tuple(x for x in A.inds if x in stay)
         xs = tuple(x for x in A.inds[len(ra):] if x not in shared)
         ys = tuple(y for y in B.inds[len(rb):] if y not in shared)
-        s = shared - stay
-        best = None
-        for s_order in dict.fromkeys((tuple(q for q in A.inds if q in s), tuple(q for q in B.inds if q in s))):
-            fa = [f for f in (0, 1) if A.kind is not None and _fits(A.inds, ra + h, xs, s_order, f == 1)]
-            fb = [f for f in (0, 1) if B.kind is not None and _fits(B.inds, rb + h, ys, s_order, f == 0)]
-            moved = (0 if fa else size(A.inds)) + (0 if fb else size(B.inds))
-            if best is None or moved < best[0]:
-                best = (moved, s_order, fa[0] if fa else None, fb[0] if fb else None)
-        _, s_order, form_a, form_b = best
+        s_order, form_a, form_b = _operand_forms(A, B, ra + h, rb + h, xs, ys, shared - stay, dims)
         hst = min(A.per, B.per)  # the period of the step (hoist: 2, it is hoisted, when both operands are slice-free)
         step_per.append(hst)
         moved_from = []  # (the permutes of one step run in one launch: their sources are released after both)
@@ -997,10 +1165,10 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
             # are no larger than the copy they replace; roles, s_order and the result's layout stay as decided above
             groups = (h, s_order, ys) if side else (h, xs, s_order)
             if form is None and indirect is True and not T.free and T.per == hst and \
-                    8 * sum(size(g) for g in groups) <= np.dtype(dtype).itemsize * size(target):
-                st = strides[T.leaf] if T.leaf is not None else {x: size(T.inds[q + 1:]) for q, x in enumerate(T.inds)}
+                    8 * sum(_size(g, dims) for g in groups) <= np.dtype(dtype).itemsize * _size(target, dims):
+                st = strides[T.leaf] if T.leaf is not None else _dense_strides(T.inds, dims)
                 for q, g in enumerate(groups):
-                    ind[3 * side + q] = ind_top
+                    ind[IX_SIDE * side + q] = ind_top
                     ind_pool.append(_offset_table(g, st, dims))
                     ind_top += len(ind_pool[-1])
                 if T.leaf is not None:  # (also a leaf that is not dense after slicing: read at its slice offset)
@@ -1012,50 +1180,35 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
                 T.inds, T.kind, T.ref, T.leaf = target, ARENA, ref, None
         for q, per in moved_from:  # (a permute releases its source in its own phase)
             events[per].append(("free", q))
-        form_a = 0 if form_a is None else form_a
-        form_b = 0 if form_b is None else form_b
+        form_a, form_b = form_a or 0, form_b or 0
         ind_rows.append(ind)
-        H, M, N, K = size(h), size(xs), size(ys), size(s_order)
+        H, M, N, K = _size(h, dims), _size(xs, dims), _size(ys, dims), _size(s_order, dims)
         z = rz + h + xs + ys
         assert not (hst > 1 and k == len(steps) - 1)  # (the last step is above every leaf that holds a sliced index)
-        c_kind, c_ref = (OUT, 0) if k == len(steps) - 1 else (ARENA, new_buf(size(z), h=hst))
+        c_kind, c_ref = (OUT, 0) if k == len(steps) - 1 else (ARENA, new_buf(_size(z, dims), h=hst))
         if scaling is not None:
             # a stored result is summed into a float32 staging buffer (2 storage elements per element) and narrowed
             # from there: live beside the operands and the result for this step alone.  Allocated after everything
             # else of the step and released at once, it leaves every other offset as the plan without scaling has it.
-            stage.append(new_buf(2 * size(z), h=hst) if c_kind == ARENA else -1)
+            stage.append(new_buf(2 * _size(z, dims), h=hst) if c_kind == ARENA else -1)
             if c_kind == ARENA:
                 events[hst].append(("free", stage[-1]))
         op = dict(h=h, x=xs, y=ys, s=s_order, form_a=form_a, form_b=form_b, H=H, M=M, N=N, K=K)
         if projs is not None:
-            R = size(rz)
-            if ra == rz and not rb and H == 1 and form_a == 0:
-                # only the first operand has rows, stored [r][m][k]: a plain GEMM with R M rows
-                M, R = R * M, 1
-                row_steps.append([1, 1, -1, 1, -1])
-                op.update(M=M, R=1, folded=True, a_map=None, b_map=None)
-            else:
-                maps = []
-                for r in (ra, rb):
-                    if not r or r == rz:  # one row for every r / the rows of the result, in place
-                        maps.append(None)
-                        continue
-                    sub = rows_of[rz[0]][:, [rz[0].cols.index(c) for c in r[0].cols]]
-                    both, where = _unique_rows(np.concatenate([rows_of[r[0]], sub]))
-                    assert len(both) == len(rows_of[r[0]])  # (every row of the result restricts to a row it has)
-                    maps.append(where[len(both):].astype(np.int32))
-                at = []
-                for m in maps:
-                    at.append(-1 if m is None else sum(len(q) for q in row_maps))
-                    if m is not None:
-                        row_maps.append(m)
-                row_steps.append([R, size(ra), at[0], size(rb), at[1]])
-                op.update(R=R, folded=False, a_map=maps[0], b_map=maps[1])
+            M, row, maps, fields = _row_step(ra, rb, rz, rows_of, dims, H, M, form_a, sum(len(q) for q in row_maps))
+            row_steps.append(row)
+            row_maps += maps
+            op.update(fields)
         if indirect is not None:
-            op.update(ind_a=ind[0] >= 0, ind_b=ind[3] >= 0)
-        rows.append([A.kind, A.ref, *((0, 0) if ind[0] >= 0 else (K, 1) if form_a == 0 else (1, M)),
-                     B.kind, B.ref, *((0, 0) if ind[3] >= 0 else (N, 1) if form_b == 0 else (1, K)), c_kind, c_ref, H, M, N, K,
-                     *((A.slot, B.slot) if scaling is not None else (0, 0))])
+            op.update(ind_a=ind[IX_A_H] >= 0, ind_b=ind[IX_B_H] >= 0)
+        row = [0] * STEP_W
+        row[ST_A_KIND], row[ST_A_REF], row[ST_B_KIND], row[ST_B_REF] = A.kind, A.ref, B.kind, B.ref
+        row[ST_C_KIND], row[ST_C_REF] = c_kind, c_ref
+        row[ST_A_M], row[ST_A_K] = (0, 0) if ind[IX_A_H] >= 0 else (K, 1) if form_a == 0 else (1, M)
+        row[ST_B_K], row[ST_B_N] = (0, 0) if ind[IX_B_H] >= 0 else (N, 1) if form_b == 0 else (1, K)
+        row[ST_H], row[ST_M], row[ST_N], row[ST_K] = H, M, N, K
+        row[ST_A_SLOT], row[ST_B_SLOT] = (A.slot, B.slot) if scaling is not None else (0, 0)
+        rows.append(row)
         ops.append(op)
         for T in (A, B):
             if T.kind == ARENA and T.per > hst:  # kept: its reader runs more often than its writer; never released
@@ -1063,79 +1216,26 @@ def plan(path, ts_inds, shapes, output_inds=None, *, slices=(), slice_range=None
                 kept_per.append(T.per)
             elif T.kind == ARENA:
                 events[hst].append(("free", T.ref))
-        live.append(_Live(z, ARENA, c_ref))
-        live[-1].slot = len(ts_inds) + k
-        live[-1].dep, live[-1].per, live[-1].free = A.dep | B.dep, hst, A.free and B.free
+        Z = _Live(z, ARENA, c_ref)
+        Z.slot, Z.dep, Z.per, Z.free = len(ts_inds) + k, A.dep | B.dep, hst, A.free and B.free
+        live.append(Z)
 
-    # One allocator, the phases in order of descending period (hoist: the hoisted phase first), the events of a phase
-    # in path order; a phase's temporaries are released, the kept buffers never.  Why that is sound when the phases run
-    # slowest first at every assignment at which they are due: a slower phase's temporaries may lie where a faster
-    # phase's kept buffers lie, because whenever the slower phase is due every faster one is due after it (the periods
-    # divide one another) and rewrites them.  They never lie on a slower phase's kept buffers, which are still allocated
-    # when the faster phase is planned
-    arena, offset = _Arena(), {}
-    for what, buf in (ev for P in sorted(set(front) | set(events), reverse=True) for ev in front[P] + events[P]):
-        if what == "alloc":
-            offset[buf] = arena.alloc(buf_size[buf])
-        else:
-            arena.release(offset[buf], buf_size[buf])
-    for row in perms:
-        if row[0] == ARENA:
-            row[1] = offset[row[1]]
-        if row[2] == ARENA:
-            row[3] = offset[row[3]]
-    for row in rows:
-        for at in (0, 4, 8):
-            if row[at] == ARENA:
-                row[at + 1] = offset[row[at + 1]]
+    offset, peak = _replay_arena(front, events, buf_size)
+    _patch_offsets(perms, rows, offset)
     perm_tab = np.array(perms, np.int64).reshape(-1, PERM_W)
     perm_per = np.array(perm_per, np.int64).reshape(-1)
     # slice-start gathers (group -1) first; within a group the rows of one period together, the slowest (hoisted) first
-    order = np.lexsort((-perm_per, perm_tab[:, 6]))
-    perm_tab, perm_per = perm_tab[order], perm_per[order]
-    step_per = np.array(step_per, np.int64).reshape(-1)
-    step_tab = np.array(rows, np.int64).reshape(-1, STEP_W)
-    macs = int(sum(_step_macs(r) for r in rows))
-    p = Plan(dtype=np.dtype(dtype), inds=final, shape=tuple(dims[x] for x in final), slice_inds=slice_inds,
-             slice_dims=slice_dims, block_inds=tuple(x for x in slice_inds if x in final), leaf_numel=leaf_numel,
-             leaf_sl=leaf_sl, perms=perm_tab, steps=step_tab, arena_elems=arena.peak, out_numel=size(final),
-             macs_per_slice=macs, slice_range=(lo, hi), ops=ops, storage=storage, compute=compute, accumulate=accumulate)
-    if scaling is not None:
-        p.scaling = scaling
-        p.stage_refs = np.array([offset[b] if b >= 0 else -1 for b in stage], np.int64)
-    if slice_batch is not None:  # (the tables are those of the unbatched plan)
-        p.slice_batch = min(int(slice_batch), hi - lo) if steps else 1
-    if path_kernel is not None:  # (the tables are those of the unfused plan; projections were refused above)
-        _check_path_steps(p)
-        p.path_kernel = min(int(path_kernel), hi - lo) if steps else 1
-    p.kept = tuple((offset[b], buf_size[b]) for b in kept_bufs)  # (without hoist and reuse every period is 1: none)
-    if hoist is not None:  # (without a hoisted step or permute the tables are those of the plan without the keyword)
-        p.step_hoist, p.perm_hoist = (step_per == 2).astype(np.int64), (perm_per == 2).astype(np.int64)
-        p.hoisted = (int(p.step_hoist.sum()), int(p.perm_hoist.sum()))
-        p.hoisted_macs = int(sum(_step_macs(r) for r, h in zip(rows, p.step_hoist) if h))
-    if reuse is not None:  # (when every period is 1 the tables are those of the plan without the keyword)
-        p.step_period, p.perm_period = step_per, perm_per
-        p.reused = (int((step_per > 1).sum()), int((perm_per > 1).sum()))
-        p.kept_period = tuple(kept_per)
-    if indirect is not None:  # (with nothing folded the tables are those of the plan without the keyword)
-        p.indirect = sum((row[0] >= 0) + (row[3] >= 0) for row in ind_rows)
-        if p.indirect:
-            p.ind_steps = np.array(ind_rows, np.int64).reshape(-1, IND_W)
-            p.ind_maps = np.concatenate(ind_pool).astype(np.int64)
+    order = np.lexsort((-perm_per, perm_tab[:, PM_GROUP]))
+    p = Plan(dtype=np.dtype(dtype), inds=final, shape=tuple(dims[x] for x in final), slice_inds=S.inds,
+             slice_dims=S.dims, block_inds=tuple(x for x in S.inds if x in final), leaf_numel=leaf_numel,
+             leaf_sl=leaf_sl, perms=perm_tab[order], steps=np.array(rows, np.int64).reshape(-1, STEP_W), arena_elems=peak,
+             out_numel=_size(final, dims), macs_per_slice=int(sum(_step_macs(r) for r in rows)), slice_range=(S.lo, S.hi),
+             ops=ops, storage=storage, compute=compute, accumulate=accumulate)
+    _keyword_fields(p, options, offset, buf_size, stage, kept_bufs, kept_per, np.array(step_per, np.int64).reshape(-1),
+                    perm_per[order], ind_rows, ind_pool)
     if projs is None:
         return p
-    # the device holds the distinct rows of the final tensor; the result has one per projection, duplicates included
-    p.sparse_inds, p.leaf_rows = sparse, leaf_rows
-    p.row_steps = np.array(row_steps, np.int64).reshape(-1, ROW_W)
-    p.row_maps = np.concatenate(row_maps + [np.zeros(0, np.int32)]).astype(np.int32)
-    p.macs_per_slice = int(sum(int(w[0]) * _step_macs(r) for w, r in zip(row_steps, rows)))
-    rest = tuple(x for x in full_final if x not in col)
-    if sparse:
-        p.out_rows = (dims[final[0]], _unique_rows(projs)[1])
-    else:
-        p.out_rows = (1, np.zeros(len(projs), np.int64))
-    p.inds, p.shape = (PROJ,) + rest, (len(projs),) + tuple(dims[x] for x in rest)
-    return p
+    return _projected_result(p, sparse, projs, leaf_rows, row_steps, row_maps, full_final, dims)
 
 
 def check_memory(p: Plan, free_bytes: int) -> None:
@@ -1957,7 +2057,7 @@ class Contractor:
         # each padded to 64 elements, path_kernel arenas and staging blocks, the output, the tables and a pointer per leaf
         held = item * sum(-(-int(v) // ALIGN) * ALIGN for v in p.leaf_numel) + item * max(p.arena_elems, 1) + item * p.out_numel
         held += 8 * (p.perms.size + p.leaf_sl.size + 2 * len(p.slice_dims)) + 8 * max(n, 1)
-        held += item * ((p.path_kernel - 1) * p.arena_elems + p.path_kernel * block) + 8 * (p.steps.size + 2 * (len(p.steps) + 1) + A)
+        held += item * ((p.path_kernel - 1) * p.arena_elems + p.path_kernel * block) + 8 * (p.steps.size + GR_W * (len(p.steps) + 1) + A)
         caps = self._many
         stacked = dict(caps["stacks"])
         for t in leaves:
@@ -1967,8 +2067,8 @@ class Contractor:
         grown = item * max(members - p.path_kernel, 0) * (p.arena_elems + block)
         outputs = item * max(caps["out"], int(n_sets)) * p.out_numel
         # (walkers: two versions per leaf of bind_versions; three words per leaf once run_walkers has run)
-        walked = item * 2 * sum(int(p.leaf_numel[t]) for t in self._versions) + (24 * n if caps["walked"] else 0)
-        return held + stacks + grown + outputs + 16 * n + walked
+        walked = item * 2 * sum(int(p.leaf_numel[t]) for t in self._versions) + (8 * WALK_W * n if caps["walked"] else 0)
+        return held + stacks + grown + outputs + 8 * SET_W * n + walked
 
     # -- the checks; none of them touches the device through this library
 

@@ -88,13 +88,7 @@ int set_error(int code, const std::string& msg);
 
 namespace {
 
-constexpr int CT_MAX_AXES = 32;
-constexpr int PERM_W = 8 + 2 * CT_MAX_AXES;
-constexpr int STEP_W = 16;
-constexpr int LEAF_SL_W = 1 + 2 * CT_MAX_AXES;
-constexpr int ROW_W = 5;  // row_steps: R, rows of A, map of A, rows of B, map of B
-constexpr int IND_W = 6;  // ind_steps: offsets into the pool of the tables of A by h, m, k and of B by h, k, n; -1: direct
-constexpr int64_t K_LEAF = 0, K_ARENA = 1, K_OUT = 2;
+#include "contract_tables.h"
 
 int fail(int code, const std::string& msg) { return tnco::set_error(code, msg); }
 
@@ -143,9 +137,9 @@ using ct_acc_t = typename ct_acc<E>::type;
 // the offset that assignment sid gives a leaf through its sliced axes (ls: the leaf's row of leaf_sl)
 __host__ __device__ inline int64_t ct_slice_offset(const int64_t* ls, const int64_t* place, const int64_t* dims, int64_t sid) {
   int64_t off = 0;
-  for (int j = 0; j < (int)ls[0]; ++j) {
-    const int64_t s = ls[1 + j];
-    off += ((sid / place[s]) % dims[s]) * ls[1 + CT_MAX_AXES + j];
+  for (int j = 0; j < (int)ls[LS_COUNT]; ++j) {
+    const int64_t s = ls[LS_SLOTS + j];
+    off += ((sid / place[s]) % dims[s]) * ls[LS_STRIDES + j];
   }
   return off;
 }
@@ -195,25 +189,25 @@ struct GatherArgs {
 template <class D, class SI, bool SC = false>
 __device__ inline void ct_gather_body(const GatherArgs& g, const int32_t* exps = nullptr) {
   const int64_t* row = g.rows + (int64_t)blockIdx.y * PERM_W;
-  const int64_t numel = row[5];
-  const int nd = (int)row[4];
+  const int64_t numel = row[PM_NUMEL];
+  const int nd = (int)row[PM_NDIM];
   const SI* src;
   int64_t base = 0;
   const int64_t member = (int64_t)blockIdx.z * g.arena_step;
-  if (row[0] == K_LEAF) {
-    base = ct_slice_offset(g.leaf_sl + row[1] * LEAF_SL_W, g.slice_place, g.slice_dims, g.sid + blockIdx.z);
-    src = (const SI*)g.leaves[row[1]];
+  if (row[PM_SRC_KIND] == K_LEAF) {
+    base = ct_slice_offset(g.leaf_sl + row[PM_SRC_REF] * LEAF_SL_W, g.slice_place, g.slice_dims, g.sid + blockIdx.z);
+    src = (const SI*)g.leaves[row[PM_SRC_REF]];
   } else {
-    src = (const SI*)g.arena + member + row[1];
+    src = (const SI*)g.arena + member + row[PM_SRC_REF];
   }
-  D* dst = row[2] == K_ARENA ? (D*)g.arena + member + row[3] : (D*)g.out + g.out_off;
+  D* dst = row[PM_DST_KIND] == K_ARENA ? (D*)g.arena + member + row[PM_DST_REF] : (D*)g.out + g.out_off;
   [[maybe_unused]] int sh = 0;
-  if constexpr (SC) sh = row[0] == K_LEAF ? exps[row[1]] : 0;
+  if constexpr (SC) sh = row[PM_SRC_KIND] == K_LEAF ? exps[row[PM_SRC_REF]] : 0;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (int64_t)gridDim.x * blockDim.x) {
     int64_t rem = e, off = base;
     for (int k = nd - 1; k >= 0; --k) {
-      const int64_t d = row[8 + k], q = rem / d;
-      off += (rem - q * d) * row[8 + CT_MAX_AXES + k];
+      const int64_t d = row[PM_DIMS + k], q = rem / d;
+      off += (rem - q * d) * row[PM_STRIDES + k];
       rem = q;
     }
     if constexpr (SC) dst[e] = ct_ldexp(ct_load(src + off), sh);
@@ -629,7 +623,7 @@ struct tnco_hip_contract_s {
   int64_t path_cap = 0;            // members d_arena and d_path_stage have room for (tnco_hip_contract_set_path_kernel: path_group)
   void* d_sets_out = nullptr;      // [sets_out_cap][out_numel]
   int64_t sets_out_cap = 0;
-  char* d_sets_tables = nullptr;   // [n_leaves][2]: a leaf's pointer and its set stride
+  char* d_sets_tables = nullptr;   // [n_leaves][SET_W]: a leaf's pointer and its set stride
   std::vector<int64_t> sets_image;  // the host copy of d_sets_tables of the last run
   int64_t sets_launches[2] = {0, 0};  // launches of ct_sets_path_kernel and of ct_sets_reduce_kernel in the last run
   // walkers (tnco_hip_contract_load_leaf_versions, tnco_hip_contract_run_walkers)
@@ -658,10 +652,16 @@ int64_t leaf_slice_offset(const tnco_hip_contract_s* c, int64_t leaf, int64_t si
   return ct_slice_offset(&c->leaf_sl[leaf * LEAF_SL_W], c->place.data(), c->slice_dims.data(), sid);
 }
 
+// H, M, N, K of a row of `steps`
+struct StepShape {
+  int64_t H, M, N, K;
+};
+StepShape step_shape(const int64_t* st) { return StepShape{st[ST_H], st[ST_M], st[ST_N], st[ST_K]}; }
+
 int64_t leaf_slice_reach(const tnco_hip_contract_s* c, int64_t leaf) {  // the largest offset an assignment gives
   const int64_t* ls = &c->leaf_sl[leaf * LEAF_SL_W];
   int64_t off = 0;
-  for (int j = 0; j < (int)ls[0]; ++j) off += (c->slice_dims[ls[1 + j]] - 1) * ls[1 + CT_MAX_AXES + j];
+  for (int j = 0; j < (int)ls[LS_COUNT]; ++j) off += (c->slice_dims[ls[LS_SLOTS + j]] - 1) * ls[LS_STRIDES + j];
   return off;
 }
 
@@ -711,9 +711,9 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
   c->leaf_off.assign(L + 1, 0);
   for (int64_t t = 0; t < L; ++t) {
     const int64_t* ls = &c->leaf_sl[t * LEAF_SL_W];
-    if (c->leaf_numel[t] < 1 || ls[0] < 0 || ls[0] > CT_MAX_AXES) return "leaf table is not valid.";
-    for (int j = 0; j < (int)ls[0]; ++j)
-      if (ls[1 + j] < 0 || ls[1 + j] >= NS || ls[1 + CT_MAX_AXES + j] < 0) return "leaf table is not valid.";
+    if (c->leaf_numel[t] < 1 || ls[LS_COUNT] < 0 || ls[LS_COUNT] > CT_MAX_AXES) return "leaf table is not valid.";
+    for (int j = 0; j < (int)ls[LS_COUNT]; ++j)
+      if (ls[LS_SLOTS + j] < 0 || ls[LS_SLOTS + j] >= NS || ls[LS_STRIDES + j] < 0) return "leaf table is not valid.";
     if (leaf_slice_reach(c, t) >= c->leaf_numel[t]) return "leaf slices reach beyond the leaf.";
     c->leaf_off[t + 1] = c->leaf_off[t] + ((c->leaf_numel[t] + 63) / 64) * 64;
   }
@@ -722,44 +722,45 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
   int64_t prev_group = -1;
   for (int64_t r = 0; r < P; ++r) {
     const int64_t* row = &c->perms[r * PERM_W];
-    const int64_t nd = row[4], numel = row[5], g = row[6];
+    const int64_t nd = row[PM_NDIM], numel = row[PM_NUMEL], g = row[PM_GROUP];
     if (nd < 0 || nd > CT_MAX_AXES || g < -1 || g >= S || g < prev_group) return "permute table is not valid.";
     if (g != prev_group || r == 0) c->group_first[g + 1] = r;
     prev_group = g;
     c->group_count[g + 1] += 1;
     int64_t prod = 1, reach = 0;
     for (int k = 0; k < nd; ++k) {
-      if (row[8 + k] < 1 || row[8 + CT_MAX_AXES + k] < 0) return "permute table is not valid.";
-      prod *= row[8 + k];
-      reach += (row[8 + k] - 1) * row[8 + CT_MAX_AXES + k];
+      if (row[PM_DIMS + k] < 1 || row[PM_STRIDES + k] < 0) return "permute table is not valid.";
+      prod *= row[PM_DIMS + k];
+      reach += (row[PM_DIMS + k] - 1) * row[PM_STRIDES + k];
     }
     if (prod != numel) return "permute table is not valid.";
-    if (row[0] == K_LEAF) {
-      if (row[1] < 0 || row[1] >= L || reach + leaf_slice_reach(c, row[1]) >= c->leaf_numel[row[1]]) return "permute source out of range.";
-    } else if (row[0] == K_ARENA) {
-      if (row[1] < 0 || row[1] + reach >= c->arena_elems) return "permute source out of range.";
+    const int64_t src = row[PM_SRC_REF], dst = row[PM_DST_REF];
+    if (row[PM_SRC_KIND] == K_LEAF) {
+      if (src < 0 || src >= L || reach + leaf_slice_reach(c, src) >= c->leaf_numel[src]) return "permute source out of range.";
+    } else if (row[PM_SRC_KIND] == K_ARENA) {
+      if (src < 0 || src + reach >= c->arena_elems) return "permute source out of range.";
     } else {
       return "permute table is not valid.";
     }
-    if (row[2] == K_ARENA) {
-      if (row[3] < 0 || row[3] + numel > c->arena_elems) return "permute destination out of range.";
-      if (row[0] == K_ARENA && row[1] < row[3] + numel && row[3] < row[1] + reach + 1) return "permute in place.";
-    } else if (row[2] != K_OUT || numel != c->block_numel || S != 0) {
+    if (row[PM_DST_KIND] == K_ARENA) {
+      if (dst < 0 || dst + numel > c->arena_elems) return "permute destination out of range.";
+      if (row[PM_SRC_KIND] == K_ARENA && src < dst + numel && dst < src + reach + 1) return "permute in place.";
+    } else if (row[PM_DST_KIND] != K_OUT || numel != c->block_numel || S != 0) {
       return "permute table is not valid.";
     }
   }
-  if (S == 0 && !(P == 1 && c->perms[2] == K_OUT)) return "a path without steps needs one copy to the output.";
+  if (S == 0 && !(P == 1 && c->perms[PM_DST_KIND] == K_OUT)) return "a path without steps needs one copy to the output.";
   for (int64_t k = 0; k < S; ++k) {
     const int64_t* st = &c->steps[k * STEP_W];
-    const int64_t H = st[10], M = st[11], N = st[12], K = st[13];
+    const auto [H, M, N, K] = step_shape(st);
     if (H < 1 || M < 1 || N < 1 || K < 1) return "step sizes must be positive.";
     // the row axis: an operand has one row, or the result's rows (no map), or rows of its own reached through a map
     static const int64_t no_rows[ROW_W] = {1, 1, -1, 1, -1};
     const int64_t* rw = c->row_steps.empty() ? no_rows : &c->row_steps[k * ROW_W];
-    const int64_t R = rw[0];
+    const int64_t R = rw[RW_R];
     if (R < 1) return "step row counts must be positive.";
     for (int side = 0; side < 2; ++side) {
-      const int64_t rows = rw[1 + 2 * side], map = rw[2 + 2 * side];
+      const int64_t rows = rw[RW_SIDE * side + RW_A_ROWS], map = rw[RW_SIDE * side + RW_A_MAP];
       if (rows < 1) return "step row counts must be positive.";
       if (map == -1) {
         if (rows != 1 && rows != R) return "an operand without a row map has one row or the result's rows.";
@@ -770,14 +771,15 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
         if (c->row_maps[map + r] < 0 || c->row_maps[map + r] >= rows) return "row map entry beyond the operand's rows.";
     }
     // (0, 0): a folded operand, read through the tables of tnco_hip_contract_set_indirect, which a run then needs
-    const bool ind_a = st[2] == 0 && st[3] == 0, ind_b = st[6] == 0 && st[7] == 0;
-    if (!ind_a && !((st[2] == K && st[3] == 1) || (st[2] == 1 && st[3] == M))) return "A strides are not valid.";
-    if (!ind_b && !((st[6] == N && st[7] == 1) || (st[6] == 1 && st[7] == K))) return "B strides are not valid.";
+    const bool ind_a = st[ST_A_M] == 0 && st[ST_A_K] == 0, ind_b = st[ST_B_K] == 0 && st[ST_B_N] == 0;
+    if (!ind_a && !((st[ST_A_M] == K && st[ST_A_K] == 1) || (st[ST_A_M] == 1 && st[ST_A_K] == M))) return "A strides are not valid.";
+    if (!ind_b && !((st[ST_B_K] == N && st[ST_B_N] == 1) || (st[ST_B_K] == 1 && st[ST_B_N] == K))) return "B strides are not valid.";
     if ((ind_a || ind_b) && (d->dtype > 3 || d->row_steps)) return "folded operands need a plain dtype and no row axes.";
     c->folded |= ind_a || ind_b;
     int64_t lo[2], hi[2];
     for (int side = 0; side < 2; ++side) {
-      const int64_t kind = st[4 * side], ref = st[4 * side + 1], n = rw[1 + 2 * side] * H * K * (side ? N : M);
+      const int64_t kind = st[ST_SIDE * side + ST_A_KIND], ref = st[ST_SIDE * side + ST_A_REF];
+      const int64_t n = rw[RW_SIDE * side + RW_A_ROWS] * H * K * (side ? N : M);
       if (kind == K_LEAF) {
         if (ref < 0 || ref >= L || n + leaf_slice_reach(c, ref) > c->leaf_numel[ref]) return "step operand out of range.";
         lo[side] = hi[side] = -1;
@@ -790,22 +792,23 @@ const char* validate(tnco_hip_contract_s* c, const tnco_hip_contract_desc* d) {
     }
     if (c->scaling) {  // the operands' exponent slots: a leaf's own, or that of an earlier step's result
       for (int side = 0; side < 2; ++side) {
-        const int64_t slot = st[14 + side];
+        const int64_t slot = st[ST_A_SLOT + side];
         // (an operand in the arena: an earlier step's result, or a leaf that a gather moved there)
-        if (st[4 * side] == K_LEAF ? slot != st[4 * side + 1] : (slot < 0 || slot >= L + k)) return "step exponent slot is not valid.";
+        const int64_t kind = st[ST_SIDE * side + ST_A_KIND], ref = st[ST_SIDE * side + ST_A_REF];
+        if (kind == K_LEAF ? slot != ref : (slot < 0 || slot >= L + k)) return "step exponent slot is not valid.";
       }
     }
     const int64_t nc = R * H * M * N;
-    if (st[8] == K_OUT) {
+    if (st[ST_C_KIND] == K_OUT) {
       if (k != S - 1 || nc != c->block_numel) return "only the last step writes the output, one block.";
-    } else if (st[8] == K_ARENA && k != S - 1) {
-      if (st[9] < 0 || st[9] + nc > c->arena_elems) return "step result out of range.";
+    } else if (st[ST_C_KIND] == K_ARENA && k != S - 1) {
+      if (st[ST_C_REF] < 0 || st[ST_C_REF] + nc > c->arena_elems) return "step result out of range.";
       for (int side = 0; side < 2; ++side)
-        if (lo[side] >= 0 && st[9] < hi[side] && lo[side] < st[9] + nc) return "step result overlaps an operand.";
+        if (lo[side] >= 0 && st[ST_C_REF] < hi[side] && lo[side] < st[ST_C_REF] + nc) return "step result overlaps an operand.";
       if (c->scaling) {  // the float32 staging buffer: 2 nc storage elements, apart from the operands and the result
         const int64_t sg = c->stage_refs[k];
-        if (sg < 0 || sg % 8 || st[9] % 8 || sg + 2 * nc > c->arena_elems) return "step staging out of range.";
-        if (sg < st[9] + nc && st[9] < sg + 2 * nc) return "step staging overlaps the result.";
+        if (sg < 0 || sg % 8 || st[ST_C_REF] % 8 || sg + 2 * nc > c->arena_elems) return "step staging out of range.";
+        if (sg < st[ST_C_REF] + nc && st[ST_C_REF] < sg + 2 * nc) return "step staging overlaps the result.";
         for (int side = 0; side < 2; ++side)
           if (lo[side] >= 0 && sg < hi[side] && lo[side] < sg + 2 * nc) return "step staging overlaps an operand.";
       }
@@ -845,55 +848,75 @@ int launch_gathers(tnco_hip_contract_s* c, int64_t group, int64_t phase, int64_t
   return TNCO_HIP_OK;
 }
 
+// The shape class of a step: every launcher picks the kernel of its family by it.  outs: the outputs as the launcher
+// counts them, H M N (with rows: R H M N); the members of a batch (grid z) do not enter the choice.  (The path kernel
+// restates the rule on the device: contract_path.h ct_path_step.)
+enum ShapeClass { TILED, DOT, STREAM };
+ShapeClass shape_class(int64_t M, int64_t N, int64_t K, int64_t outs) {
+  if (M >= 64 && N >= 64 && K > 32) return TILED;  // every operand element reused 64 times from LDS
+  return K >= 512 && outs <= 8192 ? DOT : STREAM;  // few outputs, long sums: K split over a block
+}
+
+// the slot of tnco_hip_contract_kernel_launches of a plain or storage-mode step: the tiled class by the order of A and B
+int kernel_slot(ShapeClass cls, bool ak, bool bn) { return cls == TILED ? 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0) : cls == DOT ? 5 : 6; }
+
+// the grid of a tiled kernel: a block per bm x bn tile of each of the `batches` products, the members of a batch along z
+dim3 tiled_grid(int64_t batches, int64_t M, int64_t N, int bm, int bn, unsigned members) {
+  return dim3((unsigned)std::min<int64_t>(batches * ((M + bm - 1) / bm) * ((N + bn - 1) / bn), 1 << 20), 1, members);
+}
+dim3 stream_grid(int64_t outs, unsigned members) { return dim3((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16), 1, members); }
+
+// launch(AK, BN) with the memory order of the operands of a tiled kernel, a_k == 1 and b_n == 1, as two
+// std::integral_constant<bool, ...>: the kernel takes them as template arguments
+template <class Launch>
+void with_orders(bool ak, bool bn, Launch launch) {
+  if (ak && bn) launch(std::true_type{}, std::true_type{});
+  else if (ak) launch(std::true_type{}, std::false_type{});
+  else if (bn) launch(std::false_type{}, std::true_type{});
+  else launch(std::false_type{}, std::false_type{});
+}
+
+// after the launch of a step: its error, then the counts; slot: the launch's entry of its family's table
+int count_step(tnco_hip_contract_s* c, int64_t* slot, int64_t macs) {
+  CT_TRY(hipGetLastError());
+  c->launches += 1;
+  *slot += 1;
+  c->macs += macs;
+  return TNCO_HIP_OK;
+}
+
 template <class T>
 int launch_gemm(tnco_hip_contract_s* c, const GemmArgs<T>& p, unsigned members = 1) {
   const bool ak = p.a_k == 1, bn = p.b_n == 1;
   const int64_t outs = p.H * p.M * p.N;
-  int path;  // slot of tnco_hip_contract_kernel_launches; the members of a batch (grid z) do not enter the choice
+  const ShapeClass cls = shape_class(p.M, p.N, p.K, outs);
   constexpr bool single = std::is_same<T, float>::value || std::is_same<T, cplx<float>>::value;
-  if (p.M >= 64 && p.N >= 64 && p.K > 32 && c->matrix) {  // tiled, on the matrix cores in T's precision (contract_matrix.h)
-    constexpr int BM = 32 * ct_mx<T>::TI, BNN = 32 * ct_mx<T>::TJ;
-    const int64_t tiles = p.H * ((p.M + BM - 1) / BM) * ((p.N + BNN - 1) / BNN);
-    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20), 1, members);
-    if (ak && bn) hipLaunchKernelGGL((ct_matrix_tiled_kernel<T, true, true>), grid, dim3(256), 0, c->stream, p);
-    else if (ak) hipLaunchKernelGGL((ct_matrix_tiled_kernel<T, true, false>), grid, dim3(256), 0, c->stream, p);
-    else if (bn) hipLaunchKernelGGL((ct_matrix_tiled_kernel<T, false, true>), grid, dim3(256), 0, c->stream, p);
-    else hipLaunchKernelGGL((ct_matrix_tiled_kernel<T, false, false>), grid, dim3(256), 0, c->stream, p);
-    path = 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0);
+  if (cls == TILED && c->matrix) {  // on the matrix cores in T's precision (contract_matrix.h)
+    const dim3 grid = tiled_grid(p.H, p.M, p.N, 32 * ct_mx<T>::TI, 32 * ct_mx<T>::TJ, members);
+    with_orders(ak, bn, [&](auto AK, auto BN) {
+      hipLaunchKernelGGL((ct_matrix_tiled_kernel<T, decltype(AK)::value, decltype(BN)::value>), grid, dim3(256), 0, c->stream, p);
+    });
     c->matrix_launches += 1;
-  } else if (p.M >= 64 && p.N >= 64 && p.K > 32 && single && c->compute == 1) {  // tiled, on the matrix cores (contract_split.h)
+  } else if (cls == TILED && single && c->compute == 1) {  // on the matrix cores, split (contract_split.h)
     if constexpr (single) {
       constexpr bool CP = std::is_same<T, cplx<float>>::value;
-      const int64_t tiles = p.H * ((p.M + HB - 1) / HB) * ((p.N + HB - 1) / HB);
-      const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20), 1, members);
-      if (ak && bn) hipLaunchKernelGGL((ct_split_tiled_kernel<CP, true, true>), grid, dim3(256), 0, c->stream, p);
-      else if (ak) hipLaunchKernelGGL((ct_split_tiled_kernel<CP, true, false>), grid, dim3(256), 0, c->stream, p);
-      else if (bn) hipLaunchKernelGGL((ct_split_tiled_kernel<CP, false, true>), grid, dim3(256), 0, c->stream, p);
-      else hipLaunchKernelGGL((ct_split_tiled_kernel<CP, false, false>), grid, dim3(256), 0, c->stream, p);
+      const dim3 grid = tiled_grid(p.H, p.M, p.N, HB, HB, members);
+      with_orders(ak, bn, [&](auto AK, auto BN) {
+        hipLaunchKernelGGL((ct_split_tiled_kernel<CP, decltype(AK)::value, decltype(BN)::value>), grid, dim3(256), 0, c->stream, p);
+      });
     }
-    path = 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0);
     c->split_launches += 1;
-  } else if (p.M >= 64 && p.N >= 64 && p.K > 32) {  // tiled: every operand element reused 64 times from LDS
-    const int64_t tiles = p.H * ((p.M + TB - 1) / TB) * ((p.N + TB - 1) / TB);
-    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20), 1, members);
-    if (ak && bn) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, true, true>), grid, dim3(256), 0, c->stream, p);
-    else if (ak) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, true, false>), grid, dim3(256), 0, c->stream, p);
-    else if (bn) hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, false, true>), grid, dim3(256), 0, c->stream, p);
-    else hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, false, false>), grid, dim3(256), 0, c->stream, p);
-    path = 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0);
-  } else if (p.K >= 512 && outs <= 8192) {  // few outputs, long sums: K split over a block
+  } else if (cls == TILED) {
+    const dim3 grid = tiled_grid(p.H, p.M, p.N, TB, TB, members);
+    with_orders(ak, bn, [&](auto AK, auto BN) {
+      hipLaunchKernelGGL((ct_gemm_tiled_kernel<T, decltype(AK)::value, decltype(BN)::value>), grid, dim3(256), 0, c->stream, p);
+    });
+  } else if (cls == DOT) {
     hipLaunchKernelGGL(ct_gemm_dot_kernel<T>, dim3((unsigned)outs, 1, members), dim3(256), 0, c->stream, p);
-    path = 5;
   } else {
-    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16), 1, members);
-    hipLaunchKernelGGL(ct_gemm_stream_kernel<T>, grid, dim3(256), 0, c->stream, p);
-    path = 6;
+    hipLaunchKernelGGL(ct_gemm_stream_kernel<T>, stream_grid(outs, members), dim3(256), 0, c->stream, p);
   }
-  CT_TRY(hipGetLastError());
-  c->launches += 1;
-  c->by_kernel[path] += 1;
-  c->macs += p.H * p.M * p.N * p.K * members;
-  return TNCO_HIP_OK;
+  return count_step(c, &c->by_kernel[kernel_slot(cls, ak, bn)], outs * p.K * members);
 }
 
 // launch_gemm in storage mode: the same shape classes and slots, the tiled class on the matrix cores
@@ -902,86 +925,69 @@ int launch_half_gemm(tnco_hip_contract_s* c, HalfGemmArgs<typename std::conditio
   using E = typename std::conditional<CPLX, cplx<S>, S>::type;
   const bool ak = p.a_k == 1, bn = p.b_n == 1;
   const int64_t outs = p.H * p.M * p.N;
+  const ShapeClass cls = shape_class(p.M, p.N, p.K, outs);
   // 16-byte loads of 8 elements along the contiguous axis: the base and every row (column) of it aligned (the base of a
   // member of a batch: ct_member)
   p.a_vec = (uintptr_t)p.A % 16 == 0 && (ak ? p.a_m : p.a_k) % 8 == 0;
   p.b_vec = (uintptr_t)p.B % 16 == 0 && (bn ? p.b_k : p.b_n) % 8 == 0;
-  int path;
-  if (p.M >= 64 && p.N >= 64 && p.K > 32) {
-    const int64_t tiles = p.H * ((p.M + HB - 1) / HB) * ((p.N + HB - 1) / HB);
-    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20), 1, members);
-    if (ak && bn) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, true, true, SC>), grid, dim3(256), 0, c->stream, p);
-    else if (ak) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, true, false, SC>), grid, dim3(256), 0, c->stream, p);
-    else if (bn) hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, false, true, SC>), grid, dim3(256), 0, c->stream, p);
-    else hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, false, false, SC>), grid, dim3(256), 0, c->stream, p);
-    path = 1 + 2 * (ak ? 1 : 0) + (bn ? 1 : 0);
-  } else if (p.K >= 512 && outs <= 8192) {
+  if (cls == TILED) {
+    const dim3 grid = tiled_grid(p.H, p.M, p.N, HB, HB, members);
+    with_orders(ak, bn, [&](auto AK, auto BN) {
+      hipLaunchKernelGGL((ct_mfma_tiled_kernel<S, CPLX, decltype(AK)::value, decltype(BN)::value, SC>), grid, dim3(256), 0, c->stream, p);
+    });
+  } else if (cls == DOT) {
     hipLaunchKernelGGL((ct_half_dot_kernel<E, SC>), dim3((unsigned)outs, 1, members), dim3(256), 0, c->stream, p);
-    path = 5;
   } else {
-    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16), 1, members);
-    hipLaunchKernelGGL((ct_half_stream_kernel<E, SC>), grid, dim3(256), 0, c->stream, p);
-    path = 6;
+    hipLaunchKernelGGL((ct_half_stream_kernel<E, SC>), stream_grid(outs, members), dim3(256), 0, c->stream, p);
   }
-  CT_TRY(hipGetLastError());
-  c->launches += 1;
-  c->by_kernel[path] += 1;
-  c->macs += outs * p.K * members;
-  return TNCO_HIP_OK;
+  return count_step(c, &c->by_kernel[kernel_slot(cls, ak, bn)], outs * p.K * members);
 }
 
 // launch_gemm for a step with a row axis: the same shape classes, outputs counted with the rows
 template <class T>
 int launch_rows_gemm(tnco_hip_contract_s* c, const RowGemmArgs<T>& p) {
-  const bool ak = p.a_k == 1, bn = p.b_n == 1;
   const int64_t outs = p.R * p.H * p.M * p.N;
-  int path;  // slot of tnco_hip_contract_row_launches
-  if (p.M >= 64 && p.N >= 64 && p.K > 32) {
-    const int64_t tiles = p.R * p.H * ((p.M + TB - 1) / TB) * ((p.N + TB - 1) / TB);
-    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20));
-    if (ak && bn) hipLaunchKernelGGL((ct_rows_tiled_kernel<T, true, true>), grid, dim3(256), 0, c->stream, p);
-    else if (ak) hipLaunchKernelGGL((ct_rows_tiled_kernel<T, true, false>), grid, dim3(256), 0, c->stream, p);
-    else if (bn) hipLaunchKernelGGL((ct_rows_tiled_kernel<T, false, true>), grid, dim3(256), 0, c->stream, p);
-    else hipLaunchKernelGGL((ct_rows_tiled_kernel<T, false, false>), grid, dim3(256), 0, c->stream, p);
-    path = 0;
-  } else if (p.K >= 512 && outs <= 8192) {
+  const ShapeClass cls = shape_class(p.M, p.N, p.K, outs);
+  if (cls == TILED) {
+    const dim3 grid = tiled_grid(p.R * p.H, p.M, p.N, TB, TB, 1);
+    with_orders(p.a_k == 1, p.b_n == 1, [&](auto AK, auto BN) {
+      hipLaunchKernelGGL((ct_rows_tiled_kernel<T, decltype(AK)::value, decltype(BN)::value>), grid, dim3(256), 0, c->stream, p);
+    });
+  } else if (cls == DOT) {
     hipLaunchKernelGGL(ct_rows_dot_kernel<T>, dim3((unsigned)outs), dim3(256), 0, c->stream, p);
-    path = 1;
   } else {
-    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16));
-    hipLaunchKernelGGL(ct_rows_stream_kernel<T>, grid, dim3(256), 0, c->stream, p);
-    path = 2;
+    hipLaunchKernelGGL(ct_rows_stream_kernel<T>, stream_grid(outs, 1), dim3(256), 0, c->stream, p);
   }
-  CT_TRY(hipGetLastError());
-  c->launches += 1;
-  c->by_row_kernel[path] += 1;
-  c->macs += outs * p.K;
-  return TNCO_HIP_OK;
+  return count_step(c, &c->by_row_kernel[cls], outs * p.K);  // (slot of tnco_hip_contract_row_launches: the class)
 }
 
-// launch_gemm for a step with a folded operand: the same thresholds, the kernels of contract_indirect.h
+// launch_gemm for a step with a folded operand: the same shape classes, the kernels of contract_indirect.h
 template <class T>
 int launch_ix_gemm(tnco_hip_contract_s* c, const IxGemmArgs<T>& p, unsigned members = 1) {
   const int64_t outs = p.H * p.M * p.N;
-  int path;  // slot of tnco_hip_contract_indirect_launches
-  if (p.M >= 64 && p.N >= 64 && p.K > 32) {
-    const int64_t tiles = p.H * ((p.M + TB - 1) / TB) * ((p.N + TB - 1) / TB);
-    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1 << 20), 1, members);
-    hipLaunchKernelGGL(ct_ix_tiled_kernel<T>, grid, dim3(256), 0, c->stream, p);
-    path = 0;
-  } else if (p.K >= 512 && outs <= 8192) {
+  const ShapeClass cls = shape_class(p.M, p.N, p.K, outs);
+  if (cls == TILED)
+    hipLaunchKernelGGL(ct_ix_tiled_kernel<T>, tiled_grid(p.H, p.M, p.N, TB, TB, members), dim3(256), 0, c->stream, p);
+  else if (cls == DOT)
     hipLaunchKernelGGL(ct_ix_dot_kernel<T>, dim3((unsigned)outs, 1, members), dim3(256), 0, c->stream, p);
-    path = 1;
-  } else {
-    const dim3 grid((unsigned)std::min<int64_t>((outs + 255) / 256, 1 << 16), 1, members);
-    hipLaunchKernelGGL(ct_ix_stream_kernel<T>, grid, dim3(256), 0, c->stream, p);
-    path = 2;
-  }
-  CT_TRY(hipGetLastError());
-  c->launches += 1;
-  c->by_ix[path] += 1;
-  c->macs += outs * p.K * members;
-  return TNCO_HIP_OK;
+  else
+    hipLaunchKernelGGL(ct_ix_stream_kernel<T>, stream_grid(outs, members), dim3(256), 0, c->stream, p);
+  return count_step(c, &c->by_ix[cls], outs * p.K * members);  // (slot of tnco_hip_contract_indirect_launches: the class)
+}
+
+// What the argument structs of the four families have in common, from a row of `steps`: the operands, the strides and
+// sizes, beta and, where the family's launches have members, the member record
+template <class Args, class = void>
+struct has_members : std::false_type {};
+template <class Args>
+struct has_members<Args, std::void_t<decltype(Args::mb)>> : std::true_type {};
+template <class Args, class E>
+void fill_step(Args& p, const int64_t* st, const E* const* opnd, int beta, const MemberArgs& mb) {
+  p.A = opnd[0], p.B = opnd[1];
+  p.a_m = st[ST_A_M], p.a_k = st[ST_A_K], p.b_k = st[ST_B_K], p.b_n = st[ST_B_N];
+  p.H = st[ST_H], p.M = st[ST_M], p.N = st[ST_N], p.K = st[ST_K];
+  p.beta = beta;
+  if constexpr (has_members<Args>::value) p.mb = mb;
 }
 
 // wide accumulation, after the last assignment of a run: the accumulator rounded once into the output
@@ -1032,7 +1038,7 @@ int run_impl(tnco_hip_contract_s* c) {
     MemberArgs mb = bat ? mb0 : MemberArgs{};
     mb.sid0 = sid;
     for (int side = 0; side < 2; ++side) {
-      const int64_t kind = st[4 * side], ref = st[4 * side + 1];
+      const int64_t kind = st[ST_SIDE * side + ST_A_KIND], ref = st[ST_SIDE * side + ST_A_REF];
       if (kind != K_LEAF) {  // (of a batch: each member's own arena; a kept tensor: copy 0 for every member)
         opnd[side] = arena + ref;
         (side ? mb.b_step : mb.a_step) = sc.kept_opnd[2 * k + side] ? 0 : member_bytes;
@@ -1043,34 +1049,30 @@ int run_impl(tnco_hip_contract_s* c) {
       if (bat) (side ? mb.b_ls : mb.a_ls) = d_leaf_sl + ref * LEAF_SL_W;
     }
     // batched: the last step writes every member's block, with beta 0, to the batch staging buffer
-    const bool last = st[8] == K_OUT;
+    const bool last = st[ST_C_KIND] == K_OUT;
     // (wide accumulation, unbatched: the same, one block, to the staging block of the accumulator)
     T* out_dest = bat ? (T*)c->d_batch_out : wide ? (T*)c->d_acc_stage : out + out_off;
     const int out_beta = bat || wide ? 0 : beta;
     if (bat) mb.c_step = last ? c->block_numel * (int64_t)sizeof(T) : arena_bytes;
     if constexpr (half) {
       HalfGemmArgs<E> p;
-      p.A = opnd[0], p.B = opnd[1];
-      p.Cs = last ? nullptr : arena + st[9];
+      fill_step(p, st, opnd, last ? out_beta : 0, mb);
+      p.Cs = last ? nullptr : arena + st[ST_C_REF];
       p.C = last ? out_dest : nullptr;
-      p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
-      p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
-      p.beta = last ? out_beta : 0;
       p.a_vec = p.b_vec = 0;
       p.exps = nullptr, p.sa = p.sb = 0, p.amax = nullptr;
-      p.mb = mb;
       using St = typename ct_storage_of<E>::type;
       if (!c->scaling) return launch_half_gemm<St, sizeof(E) == 4, false>(c, p, members);
-      p.exps = c->d_exps, p.sa = (int)st[14], p.sb = (int)st[15];
-      if (st[8] != K_OUT) {  // unrounded to the staging buffer, then narrowed at the exponent of the whole result
+      p.exps = c->d_exps, p.sa = (int)st[ST_A_SLOT], p.sb = (int)st[ST_B_SLOT];
+      if (!last) {  // unrounded to the staging buffer, then narrowed at the exponent of the whole result
         p.Cs = nullptr, p.C = (T*)(arena + c->stage_refs[k]), p.amax = c->d_amax + k;
       }
       if ((rc = launch_half_gemm<St, sizeof(E) == 4, true>(c, p, members))) return rc;
-      if (st[8] != K_OUT) {
+      if (!last) {
         const int64_t nc = p.H * p.M * p.N, quads = nc * (sizeof(E) == 4 ? 2 : 1) / 4;
         const dim3 grid((unsigned)std::min<int64_t>(std::max<int64_t>((quads + 255) / 256, 1), 2048), 1, members);
         hipLaunchKernelGGL((ct_scale_narrow_kernel<St, sizeof(E) == 4>), grid, dim3(256), 0, c->stream, (const float*)p.C,
-                           (St*)(arena + st[9]), nc, (const uint32_t*)p.amax, c->d_exps, p.sa, p.sb, (int)(L + k),
+                           (St*)(arena + st[ST_C_REF]), nc, (const uint32_t*)p.amax, c->d_exps, p.sa, p.sb, (int)(L + k),
                            member_bytes, mb.exp_step, mb.amax_step);
         CT_TRY(hipGetLastError());
         c->launches += 1;
@@ -1078,43 +1080,34 @@ int run_impl(tnco_hip_contract_s* c) {
       }
       return TNCO_HIP_OK;
     } else {
-      T* dest = last ? out_dest : arena + st[9];
+      T* dest = last ? out_dest : arena + st[ST_C_REF];
       const int64_t* rw = c->row_steps.empty() ? nullptr : &c->row_steps[k * ROW_W];
-      if (rw && (rw[0] > 1 || rw[2] >= 0 || rw[4] >= 0)) {
+      if (rw && (rw[RW_R] > 1 || rw[RW_A_MAP] >= 0 || rw[RW_B_MAP] >= 0)) {
         RowGemmArgs<T> p;
-        p.A = opnd[0], p.B = opnd[1], p.C = dest;
-        p.a_map = rw[2] >= 0 ? c->d_row_maps + rw[2] : nullptr;
-        p.b_map = rw[4] >= 0 ? c->d_row_maps + rw[4] : nullptr;
-        p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
-        p.R = rw[0], p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
-        p.a_row = rw[2] < 0 && rw[1] == 1 ? 0 : p.H * p.M * p.K;
-        p.b_row = rw[4] < 0 && rw[3] == 1 ? 0 : p.H * p.K * p.N;
-        p.beta = st[8] == K_OUT ? beta : 0;
+        fill_step(p, st, opnd, last ? beta : 0, mb);
+        p.C = dest;
+        p.a_map = rw[RW_A_MAP] >= 0 ? c->d_row_maps + rw[RW_A_MAP] : nullptr;
+        p.b_map = rw[RW_B_MAP] >= 0 ? c->d_row_maps + rw[RW_B_MAP] : nullptr;
+        p.R = rw[RW_R];
+        p.a_row = rw[RW_A_MAP] < 0 && rw[RW_A_ROWS] == 1 ? 0 : p.H * p.M * p.K;
+        p.b_row = rw[RW_B_MAP] < 0 && rw[RW_B_ROWS] == 1 ? 0 : p.H * p.K * p.N;
         return launch_rows_gemm<T>(c, p);
       }
       const int64_t* ix = c->ind_steps.empty() ? nullptr : &c->ind_steps[k * IND_W];
-      if (ix && (ix[0] >= 0 || ix[3] >= 0)) {  // a folded operand: read in place through its tables
+      if (ix && (ix[IX_A_H] >= 0 || ix[IX_B_H] >= 0)) {  // a folded operand: read in place through its tables
         const int64_t* pool = c->d_ind + c->ind_steps.size();
         IxGemmArgs<T> p;
-        p.A = opnd[0], p.B = opnd[1];
+        fill_step(p, st, opnd, last ? out_beta : 0, mb);
         p.C = dest;
-        p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
-        p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
-        p.beta = last ? out_beta : 0;
-        p.mb = mb;
-        const bool fa = ix[0] >= 0, fb = ix[3] >= 0;
-        p.a_h = fa ? pool + ix[0] : nullptr, p.a_mo = fa ? pool + ix[1] : nullptr, p.a_ko = fa ? pool + ix[2] : nullptr;
-        p.b_h = fb ? pool + ix[3] : nullptr, p.b_ko = fb ? pool + ix[4] : nullptr, p.b_no = fb ? pool + ix[5] : nullptr;
+        const bool fa = ix[IX_A_H] >= 0, fb = ix[IX_B_H] >= 0;
+        p.a_h = fa ? pool + ix[IX_A_H] : nullptr, p.a_mo = fa ? pool + ix[IX_A_M] : nullptr, p.a_ko = fa ? pool + ix[IX_A_K] : nullptr;
+        p.b_h = fb ? pool + ix[IX_B_H] : nullptr, p.b_ko = fb ? pool + ix[IX_B_K] : nullptr, p.b_no = fb ? pool + ix[IX_B_N] : nullptr;
         p.a_kfast = c->ind_fast[2 * k], p.b_nfast = c->ind_fast[2 * k + 1];
         return launch_ix_gemm<T>(c, p, members);
       }
       GemmArgs<T> p;
-      p.A = opnd[0], p.B = opnd[1];
+      fill_step(p, st, opnd, last ? out_beta : 0, mb);
       p.C = dest;
-      p.a_m = st[2], p.a_k = st[3], p.b_k = st[6], p.b_n = st[7];
-      p.H = st[10], p.M = st[11], p.N = st[12], p.K = st[13];
-      p.beta = last ? out_beta : 0;
-      p.mb = mb;
       return launch_gemm<T>(c, p, members);
     }
   };
@@ -1193,15 +1186,15 @@ PathArgs path_args(const tnco_hip_contract_s* c, const int64_t** d_place) {
   a.arena_elems = c->arena_elems, a.block_numel = c->block_numel;
   a.sid0 = 0;
   a.n_steps = (int)S;
-  *d_place = a.groups + 2 * (S + 1);
+  *d_place = a.groups + GR_W * (S + 1);
   return a;
 }
 
 int64_t macs_per_assignment(const tnco_hip_contract_s* c) {
   int64_t per_slice = 0;
   for (size_t k = 0; k < c->steps.size() / STEP_W; ++k) {
-    const int64_t* st = &c->steps[k * STEP_W];
-    per_slice += st[10] * st[11] * st[12] * st[13];
+    const auto [H, M, N, K] = step_shape(&c->steps[k * STEP_W]);
+    per_slice += H * M * N * K;
   }
   return per_slice;
 }
@@ -1409,30 +1402,30 @@ const char* make_schedule(const tnco_hip_contract_s* c, const int64_t* step_peri
                           Schedule* s) {
   const int64_t S = (int64_t)c->steps.size() / STEP_W, P = (int64_t)c->perms.size() / PERM_W, G = S + 1;
   for (int64_t k = 0; k < S; ++k)
-    if (c->steps[k * STEP_W + 8] == K_OUT && step_period[k] != 1) return t.out_step;
+    if (c->steps[k * STEP_W + ST_C_KIND] == K_OUT && step_period[k] != 1) return t.out_step;
   for (int64_t r = 0; r < P; ++r) {
     const int64_t* row = &c->perms[r * PERM_W];
-    if (row[2] == K_OUT && perm_period[r] != 1) return t.out_perm;
-    if (r && row[6] == row[6 - PERM_W] && perm_period[r] > perm_period[r - 1]) return t.order;
+    if (row[PM_DST_KIND] == K_OUT && perm_period[r] != 1) return t.out_perm;
+    if (r && row[PM_GROUP] == row[PM_GROUP - PERM_W] && perm_period[r] > perm_period[r - 1]) return t.order;
   }
   // what a leaf allows an item that reads it: the smallest place of its sliced axes, everything without one (an axis of
   // dimension 1 has one value in every assignment and allows everything; not so for hoist flags, which take a leaf with
   // any sliced axis to change with the assignment)
   auto leaf_period = [&](int64_t leaf) {
     const int64_t* ls = &c->leaf_sl[leaf * LEAF_SL_W];
-    int64_t per = t.hoist && ls[0] ? 1 : INT64_MAX;
-    for (int j = 0; j < (int)ls[0]; ++j)
-      if (c->slice_dims[ls[1 + j]] > 1) per = std::min(per, c->place[ls[1 + j]]);
+    int64_t per = t.hoist && ls[LS_COUNT] ? 1 : INT64_MAX;
+    for (int j = 0; j < (int)ls[LS_COUNT]; ++j)
+      if (c->slice_dims[ls[LS_SLOTS + j]] > 1) per = std::min(per, c->place[ls[LS_SLOTS + j]]);
     return per;
   };
   for (int64_t r = 0; r < P; ++r) {
     const int64_t* row = &c->perms[r * PERM_W];
-    if (row[0] == K_LEAF && perm_period[r] > leaf_period(row[1])) return t.leaf_perm;
+    if (row[PM_SRC_KIND] == K_LEAF && perm_period[r] > leaf_period(row[PM_SRC_REF])) return t.leaf_perm;
   }
   for (int64_t k = 0; k < S; ++k)
     for (int side = 0; side < 2; ++side) {
       const int64_t* st = &c->steps[k * STEP_W];
-      if (st[4 * side] == K_LEAF && step_period[k] > leaf_period(st[4 * side + 1])) return t.leaf_step;
+      if (st[ST_SIDE * side + ST_A_KIND] == K_LEAF && step_period[k] > leaf_period(st[ST_SIDE * side + ST_A_REF])) return t.leaf_step;
     }
   // Replay the path: who wrote what an item reads.  A write: [lo, hi) of the arena and the period of its item, in path
   // order; read: an item has consumed it (every tensor has one reader) or nothing reads it (a staging buffer)
@@ -1489,22 +1482,24 @@ const char* make_schedule(const tnco_hip_contract_s* c, const int64_t* step_peri
     for (int64_t r = c->group_first[g + 1], n = 0; n < c->group_count[g + 1] && !e; ++r, ++n) {
       const int64_t* row = &c->perms[r * PERM_W];
       const int64_t per = perm_period[r];
-      if (row[0] == K_ARENA) source(row[1], per, row[5], true);
-      if (row[2] == K_ARENA) writes.push_back(Write{row[3], row[3] + row[5], per, 0});
+      if (row[PM_SRC_KIND] == K_ARENA) source(row[PM_SRC_REF], per, row[PM_NUMEL], true);
+      if (row[PM_DST_KIND] == K_ARENA) writes.push_back(Write{row[PM_DST_REF], row[PM_DST_REF] + row[PM_NUMEL], per, 0});
       const int64_t at = (std::find(phase.begin(), phase.end(), per) - phase.begin()) * G + g + 1;
       if (!s->count[at]++) s->first[at] = r;
-      s->largest[at] = std::max(s->largest[at], row[5]);
+      s->largest[at] = std::max(s->largest[at], row[PM_NUMEL]);
     }
   };
   perm_rows(-1);
   for (int64_t k = 0; k < S && !e; ++k) {
     perm_rows(k);
     const int64_t* st = &c->steps[k * STEP_W];
-    const int64_t H = st[10], M = st[11], N = st[12], K = st[13], nc = H * M * N;
+    const auto [H, M, N, K] = step_shape(st);
+    const int64_t nc = H * M * N;
     for (int side = 0; side < 2 && !e; ++side)
-      if (st[4 * side] == K_ARENA) s->kept_opnd[2 * k + side] = source(st[4 * side + 1], step_period[k], H * K * (side ? N : M), false);
-    if (st[8] == K_ARENA) {
-      writes.push_back(Write{st[9], st[9] + nc, step_period[k], 0});
+      if (st[ST_SIDE * side + ST_A_KIND] == K_ARENA)
+        s->kept_opnd[2 * k + side] = source(st[ST_SIDE * side + ST_A_REF], step_period[k], H * K * (side ? N : M), false);
+    if (st[ST_C_KIND] == K_ARENA) {
+      writes.push_back(Write{st[ST_C_REF], st[ST_C_REF] + nc, step_period[k], 0});
       if (c->scaling) writes.push_back(Write{c->stage_refs[k], c->stage_refs[k] + 2 * nc, step_period[k], 1});
     }
   }
@@ -1886,10 +1881,10 @@ int tnco_hip_contract_run_sets(tnco_hip_contract c, int64_t n_sets, int64_t grou
   // room for min(group, members) members and n_sets outputs; the tables once
   const int64_t G = std::min(group, n_sets * A);
   auto row = [&](int64_t t, int64_t* words) {  // the leaf's pointer (its stack, or its single buffer), its set stride
-    words[0] = (int64_t)(uintptr_t)(c->stack_sets[t] ? c->d_stack[t] : (void*)(c->d_leaves + c->leaf_off[t] * c->elem));
-    words[1] = c->stack_sets[t] ? c->leaf_numel[t] : 0;
+    words[SET_PTR] = (int64_t)(uintptr_t)(c->stack_sets[t] ? c->d_stack[t] : (void*)(c->d_leaves + c->leaf_off[t] * c->elem));
+    words[SET_STRIDE] = c->stack_sets[t] ? c->leaf_numel[t] : 0;
   };
-  if (int rc = begin_sets_run(c, n_sets, G, &c->d_sets_tables, &c->sets_image, 2, "the leaf sets", row)) return rc;
+  if (int rc = begin_sets_run(c, n_sets, G, &c->d_sets_tables, &c->sets_image, SET_W, "the leaf sets", row)) return rc;
   SetsArgs s{};
   s.set_leaves = (const int64_t*)c->d_sets_tables;
   if (int rc = with_plain_type(c, [&](auto t) {
@@ -1943,9 +1938,9 @@ int tnco_hip_contract_run_walkers(tnco_hip_contract c, tnco_hip_walkers w, const
   const int64_t G = std::min(group, R * A);
   auto row = [&](int64_t t, int64_t* words) {  // the leaf's pointer (its versions, or its single buffer), qubit, version stride
     const bool indexed = leaf_qubit[t] >= 0;
-    words[0] = (int64_t)(uintptr_t)(indexed ? c->d_versions[t] : (void*)(c->d_leaves + c->leaf_off[t] * c->elem));
-    words[1] = leaf_qubit[t];
-    words[2] = indexed ? c->leaf_numel[t] : 0;
+    words[WK_PTR] = (int64_t)(uintptr_t)(indexed ? c->d_versions[t] : (void*)(c->d_leaves + c->leaf_off[t] * c->elem));
+    words[WK_QUBIT] = leaf_qubit[t];
+    words[WK_STRIDE] = indexed ? c->leaf_numel[t] : 0;
   };
   if (int rc = begin_sets_run(c, R, G, &c->d_walk_tables, &c->walk_image, WALK_W, "the walkers", row)) return rc;
   WalkArgs s{};
@@ -2272,7 +2267,7 @@ int tnco_hip_contract_set_path_kernel(tnco_hip_contract c, int64_t group) {
     const int64_t* st = &c->steps[k * STEP_W];
     int64_t macs = 1;  // H M N K, every factor checked before it enters the product
     bool over = false;
-    for (int q = 10; q <= 13 && !over; ++q) {
+    for (int q = ST_H; q <= ST_K && !over; ++q) {
       over = st[q] > MAX_PATH_STEP_MACS / macs;
       macs *= over ? 1 : st[q];
     }
@@ -2397,19 +2392,19 @@ int tnco_hip_contract_set_indirect(tnco_hip_contract c, const int64_t* ind_steps
   bool any = false;
   for (int64_t k = 0; k < S; ++k) {
     const int64_t* st = &c->steps[k * STEP_W];
-    const int64_t H = st[10], M = st[11], N = st[12], K = st[13];
+    const auto [H, M, N, K] = step_shape(st);
     const std::string at = "step " + std::to_string(k) + ": ";
     for (int side = 0; side < 2; ++side) {
-      const int64_t* o = ind_steps + k * IND_W + 3 * side;
+      const int64_t* o = ind_steps + k * IND_W + IX_SIDE * side;
       const int64_t ext[3] = {H, side ? K : M, side ? N : K};
-      const int64_t s0 = st[4 * side + 2], s1 = st[4 * side + 3];
+      const int64_t s0 = st[ST_SIDE * side + ST_A_M], s1 = st[ST_SIDE * side + ST_A_K];
       if (o[0] == -1 && o[1] == -1 && o[2] == -1) {
         if (s0 == 0 && s1 == 0) return fail(TNCO_HIP_EINVAL, at + "an operand with both strides 0 needs its tables.");
         fast[2 * k + side] = s1 == 1;  // (direct: A contiguous along k, B along n, as the plain kernel stages them)
         continue;
       }
       if (s0 != 0 || s1 != 0) return fail(TNCO_HIP_EINVAL, at + "both stride columns of a folded operand must be 0.");
-      const int64_t kind = st[4 * side], ref = st[4 * side + 1];
+      const int64_t kind = st[ST_SIDE * side + ST_A_KIND], ref = st[ST_SIDE * side + ST_A_REF];
       const int64_t room = kind == K_LEAF ? c->leaf_numel[ref] - leaf_slice_reach(c, ref) : c->arena_elems - ref;
       int64_t reach = 0, step1[3];
       for (int q = 0; q < 3; ++q) {
@@ -2427,7 +2422,7 @@ int tnco_hip_contract_set_indirect(tnco_hip_contract c, const int64_t* ind_steps
       }
       if (reach >= room) return fail(TNCO_HIP_EINVAL, at + "an offset table reaches beyond its operand.");
       // (the result of the step, in the arena, apart from everything a folded arena operand reaches)
-      if (kind == K_ARENA && st[8] == K_ARENA && st[9] <= ref + reach && ref < st[9] + H * M * N)
+      if (kind == K_ARENA && st[ST_C_KIND] == K_ARENA && st[ST_C_REF] <= ref + reach && ref < st[ST_C_REF] + H * M * N)
         return fail(TNCO_HIP_EINVAL, at + "step result overlaps a folded operand.");
       // tiled kernel: lanes along k of A (n of B) when that table has the smaller step, the source's innermost axis
       fast[2 * k + side] = step1[2] <= step1[1];  // (the tables of A: h, m, k; of B: h, k, n)

@@ -1,5 +1,5 @@
 // contract_path.h -- a whole slice assignment in one kernel (tnco_hip_contract_set_path_kernel); included by contract.hip
-// inside its anonymous namespace, after ct_slice_offset, ct_zero / ct_mac / ct_add and the table widths.
+// inside its anonymous namespace, after ct_slice_offset, ct_zero / ct_mac / ct_add and contract_tables.h.
 // The sliced runs are bound by launches: a width-bounded assignment is a few hundred small gathers and steps.  Here one
 // workgroup interprets the whole path for one assignment, so a group of up to MAX_PATH_GROUP assignments is one launch,
 // and a second launch folds the group's blocks into the output:
@@ -30,7 +30,7 @@ struct PathArgs {
   const int64_t* slice_place;  // place value of every slice position
   const int64_t* slice_dims;
   const int64_t* steps;        // [n_steps][STEP_W]
-  const int64_t* groups;       // [n_steps + 1][2]: first row and number of rows of permute group g at g + 1
+  const int64_t* groups;       // [n_steps + 1][GR_W]: first row and number of rows of permute group g at g + 1
   const void* const* leaves;
   void* arena;                 // a copy of arena_elems elements per member
   void* stage;                 // [members][block_numel]
@@ -42,27 +42,27 @@ struct PathArgs {
 // The kinds of member, and where a member's leaves come from beyond the plan's tables: nothing for MEMBER_PLAN.
 enum PathMember { MEMBER_PLAN, MEMBER_SETS, MEMBER_WALK };
 struct LeafFrom {
-  const int64_t* table = nullptr;   // MEMBER_SETS: [n_leaves][2]; MEMBER_WALK: [n_leaves][WALK_W]
+  const int64_t* table = nullptr;   // MEMBER_SETS: [n_leaves][SET_W]; MEMBER_WALK: [n_leaves][WALK_W]
   int64_t set = 0;                  // MEMBER_SETS: the member's set; MEMBER_WALK: the number of walkers
   const uint8_t* column = nullptr;  // MEMBER_WALK: the walker's column of the table of bits
 };
 
 // Leaf t as assignment sid reads it: at the slice offset of the assignment.  MEMBER_SETS: the leaf comes from the table,
-// [n_leaves][2]: its pointer and the elements between two sets of it (0 or the leaf's elements), and the base moves on by
+// [n_leaves][SET_W]: its pointer and the elements between two sets of it (0 or the leaf's elements), and the base moves on by
 // set times that, a 64-bit product; pointer and stride lie side by side, one read, and it is asked for before the slice
 // offset is worked out, as a MEMBER_PLAN asks for its pointer (every block of a launch reads the same entry at about the
 // same time: read after the offset loop, its latency lay open once per leaf and cost the kernel a quarter of its time).
 // MEMBER_WALK: the table is [n_leaves][WALK_W], the leaf's pointer, the qubit whose bit picks one of its two versions
 // (-1: none) and the elements between them; column[qubit * number of walkers] is the member's bit, a uniform address,
 // asked for right after the entry and before the offset too.  MEMBER_PLAN: nothing is added and nothing more is read.
-constexpr int WALK_W = 3;
 template <class T, PathMember MODE>
 __device__ inline const T* ct_path_leaf(const PathArgs& p, int64_t t, int64_t sid, const LeafFrom& from) {
   if constexpr (MODE == MEMBER_SETS) {
-    const int64_t base = from.table[2 * t], step = from.table[2 * t + 1];  // (asked for before the offset is worked out)
+    // (asked for before the offset is worked out)
+    const int64_t base = from.table[SET_W * t + SET_PTR], step = from.table[SET_W * t + SET_STRIDE];
     return (const T*)base + (ct_slice_offset(p.leaf_sl + t * LEAF_SL_W, p.slice_place, p.slice_dims, sid) + from.set * step);
   } else if constexpr (MODE == MEMBER_WALK) {
-    const int64_t base = from.table[WALK_W * t], qubit = from.table[WALK_W * t + 1], step = from.table[WALK_W * t + 2];
+    const int64_t base = from.table[WALK_W * t + WK_PTR], qubit = from.table[WALK_W * t + WK_QUBIT], step = from.table[WALK_W * t + WK_STRIDE];
     const int64_t version = qubit < 0 ? 0 : from.column[qubit * from.set] & 1;  // (both before the offset is worked out)
     return (const T*)base + (ct_slice_offset(p.leaf_sl + t * LEAF_SL_W, p.slice_place, p.slice_dims, sid) + version * step);
   } else {
@@ -74,23 +74,23 @@ __device__ inline const T* ct_path_leaf(const PathArgs& p, int64_t t, int64_t si
 // loop): ct_gather_body's element loop, strided over the block.  A permute feeds a step, so numel < 2^24.
 template <class T, PathMember MODE>
 __device__ inline void ct_path_permutes(const PathArgs& p, int64_t group, T* arena, int64_t sid, const LeafFrom& from) {
-  const int64_t first = p.groups[2 * (group + 1)], count = p.groups[2 * (group + 1) + 1];
+  const int64_t first = p.groups[GR_W * (group + 1) + GR_FIRST], count = p.groups[GR_W * (group + 1) + GR_COUNT];
   for (int64_t r = first; r < first + count; ++r) {
     const int64_t* row = p.perms + r * PERM_W;
-    const uint32_t numel = (uint32_t)row[5];
-    const int nd = (int)row[4];
+    const uint32_t numel = (uint32_t)row[PM_NUMEL];
+    const int nd = (int)row[PM_NDIM];
     const T* src;
-    if (row[0] == K_LEAF)
-      src = ct_path_leaf<T, MODE>(p, row[1], sid, from);
+    if (row[PM_SRC_KIND] == K_LEAF)
+      src = ct_path_leaf<T, MODE>(p, row[PM_SRC_REF], sid, from);
     else
-      src = arena + row[1];
-    T* dst = arena + row[3];
+      src = arena + row[PM_SRC_REF];
+    T* dst = arena + row[PM_DST_REF];
     for (uint32_t e = threadIdx.x; e < numel; e += PATH_LANES) {
       uint32_t rem = e;
       int64_t off = 0;  // (a stride of a leaf's axis may be beyond 32 bits: the sliced axes lie between the kept ones)
       for (int k = nd - 1; k >= 0; --k) {
-        const uint32_t d = (uint32_t)row[8 + k], q = rem / d;
-        off += (int64_t)(rem - q * d) * row[8 + CT_MAX_AXES + k];
+        const uint32_t d = (uint32_t)row[PM_DIMS + k], q = rem / d;
+        off += (int64_t)(rem - q * d) * row[PM_STRIDES + k];
         rem = q;
       }
       dst[e] = src[off];
@@ -107,8 +107,8 @@ __device__ inline void ct_path_permutes(const PathArgs& p, int64_t group, T* are
 // stores nothing and passes the barriers.  H M N K <= 2^24: every offset inside an operand fits 32 bits.
 template <class T>
 __device__ inline void ct_path_step(const int64_t* st, const T* A, const T* B, T* C, T* part) {
-  const uint32_t a_m = (uint32_t)st[2], a_k = (uint32_t)st[3], b_k = (uint32_t)st[6], b_n = (uint32_t)st[7];
-  const uint32_t H = (uint32_t)st[10], M = (uint32_t)st[11], N = (uint32_t)st[12], K = (uint32_t)st[13];
+  const uint32_t a_m = (uint32_t)st[ST_A_M], a_k = (uint32_t)st[ST_A_K], b_k = (uint32_t)st[ST_B_K], b_n = (uint32_t)st[ST_B_N];
+  const uint32_t H = (uint32_t)st[ST_H], M = (uint32_t)st[ST_M], N = (uint32_t)st[ST_N], K = (uint32_t)st[ST_K];
   const uint32_t total = H * M * N;
   const bool tiled = M >= 64 && N >= 64 && K > 32;
   if (!tiled && K >= 512 && total <= 8192) {
@@ -161,11 +161,11 @@ __device__ inline void ct_path_member(const PathArgs& p, int64_t b, int64_t sid,
     const int64_t* st = p.steps + (int64_t)k * STEP_W;
     const T* opnd[2];
     for (int side = 0; side < 2; ++side) {
-      const int64_t kind = st[4 * side], ref = st[4 * side + 1];
+      const int64_t kind = st[ST_SIDE * side + ST_A_KIND], ref = st[ST_SIDE * side + ST_A_REF];
       // (a leaf read in place: at the slice offset of this member's assignment, as ct_member has it)
       opnd[side] = kind == K_LEAF ? ct_path_leaf<T, MODE>(p, ref, sid, from) : arena + ref;
     }
-    T* C = st[8] == K_OUT ? (T*)p.stage + b * p.block_numel : arena + st[9];
+    T* C = st[ST_C_KIND] == K_OUT ? (T*)p.stage + b * p.block_numel : arena + st[ST_C_REF];
     ct_path_step<T>(st, opnd[0], opnd[1], C, part);
     __syncthreads();
   }

@@ -19,7 +19,7 @@
 
 struct SetsArgs {
   PathArgs p;                 // leaves and sid0 are not read
-  const int64_t* set_leaves;  // [n_leaves][2]: the leaf's pointer (its stack, or its single buffer) and the elements between
+  const int64_t* set_leaves;  // [n_leaves][SET_W]: the leaf's pointer (its stack, or its single buffer) and the elements between
                               // two sets of it (leaf_numel[t], or 0), side by side: one read per leaf
   int64_t m0;                 // the member of block 0
   int64_t n_assign, start;    // A and the first assignment of the plan's slice range
